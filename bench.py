@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the HippoMM hot path on MI355X (contract: see the round brief).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step, ...).  Everything else
+the benchmark measures or checks -- the count read-back variant of the step, the roofline and per-kernel table, the
+all-gather alone, the scan and the other N = 1 legs, the CPU baselines and every comparison with the oracle -- runs only
+with --full.  --dump-outputs DIR writes what the last timed step computed (see dump_outputs) before anything else runs.
 
 `--gpus N` with N > 1 and no torchrun environment launches the N ranks itself: the parent process never touches the
 GPU, starts `python -m torch.distributed.run` as a child, exits non-zero when fewer than N GPUs are visible and
@@ -20,7 +25,7 @@ Workloads
 The frames are synthetic "scenes": a low-frequency random pattern per scene (6 consecutive frames) plus pixel noise,
 so that the random-init tower yields distinct embeddings per scene and the timed selection really drops frames.
 
-At N = 1 (cfg2) the same JSON line carries the second half of BASELINE's metric under "scan" (the feature_search scan
+With --full, at N = 1 (cfg2) the same JSON line carries the second half of BASELINE's metric under "scan" (the feature_search scan
 over a resident 1M x 1024 fp32 store, k = 32, GB/s of algorithmic bytes), BASELINE cfg 3 under "joint_vision_audio",
 the encoder's latency at the reference's own call sizes (32-frame buffer, one frame, one segment, one question) under
 "reference_call_sizes", the consolidation timings and the CPU baselines of BASELINE.md section 4.
@@ -193,6 +198,29 @@ def timed_steps(step, steps: int, warmup: int, sync, barrier, reduce_max):
         last = step()
     sync(); barrier(); sync()
     return reduce_max(time.perf_counter() - t0), last
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(folder: str, feats: torch.Tensor, kept: torch.Tensor, limit_bytes: int = DUMP_LIMIT_BYTES) -> None:
+    """--dump-outputs: what a caller of the timed path receives from its last step, as .npy files in `folder`:
+    embeddings.npy (the gathered (n, 1024) fp32 matrix that the selection ran on) and kept_indices.npy (the kept frame
+    indices, float64).  Should the matrix not fit in `limit_bytes` with the indices, a fixed, seeded sample of its rows is
+    written instead, increasing, and embedding_rows.npy (float64) names them."""
+    import numpy as np
+    os.makedirs(folder, exist_ok=True)
+    emb = feats.detach().float().cpu().numpy()
+    out = {"kept_indices": kept.detach().cpu().numpy().astype(np.float64)}
+    row_bytes = emb.shape[1] * 4 + 8
+    budget = (limit_bytes - out["kept_indices"].nbytes - 4096) // row_bytes
+    if emb.shape[0] > budget:
+        rows = np.sort(np.random.default_rng(0).choice(emb.shape[0], size=budget, replace=False))
+        emb = emb[rows]
+        out["embedding_rows"] = rows.astype(np.float64)
+    out["embeddings"] = np.ascontiguousarray(emb, dtype=np.float32)
+    for name, arr in out.items():
+        np.save(os.path.join(folder, f"{name}.npy"), arr)
 
 
 def host_threads() -> int:
@@ -1070,12 +1098,20 @@ def main():
                     help="cfg5: frames of the synthetic video (default 3600 = BASELINE cfg 5; other values exercise ragged shards)")
     ap.add_argument("--scan-strong", action="store_true",
                     help="N > 1: also time the scan with 1M rows in ALL (strong scaling); default is the weak leg only")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the count read-back step, roofline and kernel table, all-gather alone, scan and "
+                         "the other N = 1 legs, CPU baselines and the oracle checks (--no-scan / --no-cpu-baseline / "
+                         "--scan-strong shape this part)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (see dump_outputs)")
     args = ap.parse_args()
     t_start = time.perf_counter()
     if args.steps is None:
         args.steps = 10 if args.workload == "cfg2" else 2
     if args.warmup is None:
         args.warmup = 3 if args.workload == "cfg2" else 1
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:          # self-launch; this process never initialises the GPU
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -1106,7 +1142,7 @@ def main():
 
     sd = synthetic_state_dict(("vision",), seed=1234)
     tower = HipTower("vision", sd)
-    extras = rank == 0 and n_gpus == 1 and args.workload == "cfg2"
+    extras = args.full and rank == 0 and n_gpus == 1 and args.workload == "cfg2"
     if not (extras and not args.no_cpu_baseline):
         sd = None
     torch.cuda.empty_cache()
@@ -1141,19 +1177,23 @@ def main():
     elapsed, (feats, (kept_buf, n_kept)) = timed_steps(step, args.steps, args.warmup, torch.cuda.synchronize,
                                                        (dist.barrier if world > 1 else (lambda: None)), reduce_max)
     kept = kept_buf[: int(n_kept.item())].clone()
-    # The timed step is launch-only (selection result left on the device; the last step's list is read after the timer).
-    # Rounds 1-2 read the kept count back inside every step: the same K steps with that read-back, for comparison.
-    def step_with_readback():
-        f, (kb, nk) = step()
-        return f, kb[: int(nk.item())]
-    elapsed_rb, _ = timed_steps(step_with_readback, args.steps, 1, torch.cuda.synchronize,
-                                (dist.barrier if world > 1 else (lambda: None)), reduce_max)
+    if rank == 0 and args.dump_outputs:                        # before anything else reuses the step's buffers
+        dump_outputs(args.dump_outputs, feats, kept)
+    elapsed_rb = None
+    if args.full:
+        # The timed step is launch-only (selection result left on the device; the last step's list is read after the timer).
+        # Rounds 1-2 read the kept count back inside every step: the same K steps with that read-back, for comparison.
+        def step_with_readback():
+            f, (kb, nk) = step()
+            return f, kb[: int(nk.item())]
+        elapsed_rb, _ = timed_steps(step_with_readback, args.steps, 1, torch.cuda.synchronize,
+                                    (dist.barrier if world > 1 else (lambda: None)), reduce_max)
 
     proof = rank_proof(world, rank, local_rank, hi - lo) if world > 1 else None
 
     gather_ms = None
     sharded_scan = None
-    if world > 1:                                              # the exchange step alone
+    if world > 1 and args.full:                                # the exchange step alone
         gather_ms = reduce_max(event_time_ms(lambda: all_gather_embeddings(emb, counts), 20, warmup=3))
         if not args.no_scan:
             # rank-local failures are agreed on inside (all_ranks_ok) before any collective; what still raises here raises on
@@ -1163,9 +1203,6 @@ def main():
             except Exception as exc:                           # noqa: BLE001
                 sharded_scan = {"error": f"{type(exc).__name__}: {exc}"}
 
-    if rank == 0 and os.environ.get("HMM_BENCH_DUMP"):         # debugging aid: the gathered embedding matrix of the last step
-        import numpy as np
-        np.save(os.environ["HMM_BENCH_DUMP"], feats.cpu().numpy())
     if rank == 0:
         value = n_total * args.steps / elapsed
         ms_step = elapsed / args.steps * 1e3
@@ -1178,10 +1215,11 @@ def main():
             "scaling": "weak" if args.workload == "cfg2" else "strong", "vs_baseline": None, "dtype": "bf16",
             "data": "synthetic",
             "timed_step": "launch-only: encode -> (all-gather) -> selection, result left on the device, one sync after K steps",
-            "ms_per_step_with_count_readback": round(elapsed_rb / args.steps * 1e3, 3),
-            "value_with_count_readback": round(n_total * args.steps / elapsed_rb, 1),
             "startup_s": round(startup_s, 2),
         }
+        if elapsed_rb is not None:
+            line["ms_per_step_with_count_readback"] = round(elapsed_rb / args.steps * 1e3, 3)
+            line["value_with_count_readback"] = round(n_total * args.steps / elapsed_rb, 1)
         if args.workload == "cfg2":
             line["config"] = {"workload": "BASELINE cfg2: ViT-H/14 vision encoder (32 blocks, 257 tokens, D=1280), 256 "
                                           "synthetic 224x224 frames per GPU per step (scenes of 6 frames), random-init "
@@ -1190,19 +1228,21 @@ def main():
                               "frames_per_gpu": FRAMES_PER_GPU, "sharding": f"frames x{n_gpus}",
                               "kept_key_frames": int(kept.numel()), "of_frames": int(feats.shape[0])}
         else:
-            from oracle.consolidation_oracle import select_key_frames_oracle
-            want = select_key_frames_oracle(feats.cpu().numpy(), None, 0.9)
             line["config"] = {"workload": f"BASELINE cfg5: 1-hour video at 1 fps = {n_total} synthetic frames (scenes of 6), "
                                           "contiguous time shards of ceil(3600/N) frames per rank -> encode -> ONE RCCL "
                                           "all-gather of the (n_local,1024) fp32 embeddings -> global cosine key-frame "
                                           "selection on every rank",
                               "frames_total": n_total, "frames_per_rank": counts, "sharding": f"time shards x{n_gpus}",
                               "kept_key_frames": int(kept.numel()),
-                              "kept_equal_cpu_oracle_on_gathered_matrix": kept.cpu().tolist() == want.tolist(),
-                              # fingerprints: the same at every N (time shards + bitwise batch invariance of the tower)
-                              "gathered_embeddings_sha256": hashlib.sha256(feats.cpu().numpy().tobytes()).hexdigest(),
-                              "kept_indices_sha256": hashlib.sha256(kept.cpu().numpy().tobytes()).hexdigest(),
                               "all_gather_bytes_per_rank": max(counts) * 4096}
+            if args.full:
+                from oracle.consolidation_oracle import select_key_frames_oracle
+                want = select_key_frames_oracle(feats.cpu().numpy(), None, 0.9)
+                line["config"].update({
+                    "kept_equal_cpu_oracle_on_gathered_matrix": kept.cpu().tolist() == want.tolist(),
+                    # fingerprints: the same at every N (time shards + bitwise batch invariance of the tower)
+                    "gathered_embeddings_sha256": hashlib.sha256(feats.cpu().numpy().tobytes()).hexdigest(),
+                    "kept_indices_sha256": hashlib.sha256(kept.cpu().numpy().tobytes()).hexdigest()})
         if gather_ms is not None:
             line["config"]["all_gather_ms"] = round(gather_ms, 4)
         if proof is not None:
@@ -1230,11 +1270,12 @@ def main():
         line["step_mfma_frac_note"] = ("step_mfma_frac credits the reference's nominal FLOPs (SURVEY 8d: un-folded patch conv, full last "
                                        "block); step_mfma_frac_executed counts only what this build runs; roofline.frac is ONE kernel "
                                        "(the dominant GEMM) on its own 2MNK")
-        roof, table = gemm_roofline(FRAMES_PER_GPU)
-        line["roofline"], line["kernels"] = roof, table
-        line["kernels_note"] = ("NOT additive: each kernel of one block is timed between its own HIP events in ONE full-batch chain "
-                                "(event gaps included), while the timed step runs two half-batch chains that overlap on the chip; "
-                                "32 x the column sums to more than ms_per_step")
+        if args.full:
+            roof, table = gemm_roofline(FRAMES_PER_GPU)
+            line["roofline"], line["kernels"] = roof, table
+            line["kernels_note"] = ("NOT additive: each kernel of one block is timed between its own HIP events in ONE full-batch "
+                                    "chain (event gaps included), while the timed step runs two half-batch chains that overlap on "
+                                    "the chip; 32 x the column sums to more than ms_per_step")
         if sharded_scan is not None:
             line["scan"] = sharded_scan
         if REHEARSAL:
@@ -1260,7 +1301,7 @@ def main():
         bad = [k for k in ("parity_vs_oracle",) if k in line and not line[k].get("ok", True)]
         if "scan" in line and "error" in line["scan"]:      # a missing second metric is a failed run, not a shorter line
             bad.append("scan.error")
-        if args.workload == "cfg5" and not line["config"]["kept_equal_cpu_oracle_on_gathered_matrix"]:
+        if args.workload == "cfg5" and not line["config"].get("kept_equal_cpu_oracle_on_gathered_matrix", True):
             bad.append("cfg5.kept_equal_cpu_oracle_on_gathered_matrix")
         if proof is not None and proof["all_reduced_rank_count"] != world:
             bad.append("all_reduced_rank_count")

@@ -215,3 +215,27 @@ def test_self_launch_takes_the_ranks_along_when_the_parent_is_terminated(tmp_pat
         time.sleep(0.1)
     else:
         raise AssertionError("the rank outlived its terminated parent")
+
+
+def test_dump_outputs_writes_the_step_result_and_samples_rows_beyond_the_limit(tmp_path):
+    """--dump-outputs: embeddings as float32, kept indices as float64; a matrix over the size limit is replaced by the same
+    seeded sample of rows every time, named in embedding_rows.npy, and the files stay under the limit."""
+    bench = _bench()
+    feats = torch.randn(300, 1024, generator=torch.Generator().manual_seed(5))
+    kept = torch.tensor([0, 7, 120, 299], dtype=torch.int64)
+    bench.dump_outputs(str(tmp_path / "all"), feats, kept)
+    assert sorted(f.name for f in (tmp_path / "all").iterdir()) == ["embeddings.npy", "kept_indices.npy"]
+    emb = np.load(tmp_path / "all" / "embeddings.npy")
+    idx = np.load(tmp_path / "all" / "kept_indices.npy")
+    assert emb.dtype == np.float32 and np.array_equal(emb, feats.numpy())
+    assert idx.dtype == np.float64 and idx.tolist() == [0, 7, 120, 299]
+
+    limit = 100 * 4096
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), feats, kept, limit_bytes=limit)
+        assert sum(f.stat().st_size for f in (tmp_path / name).iterdir()) <= limit
+    rows = np.load(tmp_path / "a" / "embedding_rows.npy")
+    assert 50 < len(rows) < 100 and np.array_equal(np.load(tmp_path / "a" / "kept_indices.npy"), idx)
+    assert rows.dtype == np.float64 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "embedding_rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "embeddings.npy"), feats.numpy()[rows.astype(np.int64)])

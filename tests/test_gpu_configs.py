@@ -33,9 +33,27 @@ def _bench(args, env=None):
     return json.loads(lines[0])
 
 
+def test_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run times exactly --steps steps and prints the headline alone (the legs and checks of --full stay out);
+    --dump-outputs holds what the last timed step computed: the 256 embeddings and the kept indices selected on them."""
+    from oracle.consolidation_oracle import evaluated_margin, select_key_frames_oracle
+    d = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert d["steps"] == 3 and d["warmup"] == 1
+    assert d["unit"] == "frame-embeddings/s" and d["higher_is_better"] is True and d["dtype"] == "bf16" and "metric" in d
+    assert abs(d["value"] - 256 * 1e3 / d["ms_per_step"]) < 1e-3 * d["value"]
+    assert not {"roofline", "kernels", "scan", "cpu_baseline", "parity_vs_oracle", "ms_per_step_with_count_readback"} & set(d)
+    emb = np.load(tmp_path / "embeddings.npy")
+    kept = np.load(tmp_path / "kept_indices.npy")
+    assert emb.dtype == np.float32 and emb.shape == (256, 1024) and np.isfinite(emb).all()
+    assert kept.dtype == np.float64 and len(kept) == d["config"]["kept_key_frames"] and kept[0] == 0
+    assert 1 < len(kept) < 256 and np.all(np.diff(kept) > 0)
+    if evaluated_margin(emb, 0.9) > 1e-6:                                    # outside the sgemm-order band
+        assert kept.tolist() == select_key_frames_oracle(emb, None, 0.9).tolist()
+
+
 @pytest.fixture(scope="module")
 def cfg5_one_gpu():
-    return _bench(["--workload", "cfg5", "--gpus", "1", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"])
+    return _bench(["--workload", "cfg5", "--gpus", "1", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--full"])
 
 
 def test_cfg5_on_one_gpu(cfg5_one_gpu):
@@ -50,7 +68,7 @@ def test_cfg5_on_one_gpu(cfg5_one_gpu):
 
 
 def test_cfg5_two_rank_rehearsal_reproduces_the_one_gpu_result_bitwise(cfg5_one_gpu):
-    d = _bench(["--workload", "cfg5", "--gpus", "2", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-scan"],
+    d = _bench(["--workload", "cfg5", "--gpus", "2", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--full", "--no-scan"],
                env={"HMM_BENCH_REHEARSAL": "1"})
     c, c1 = d["config"], cfg5_one_gpu["config"]
     assert d["n_gpus"] == 2 and "rehearsal" in d and c["frames_per_rank"] == [1800, 1800] and "all_gather_ms" in c
@@ -65,7 +83,7 @@ def test_cfg5_two_rank_rehearsal_reproduces_the_one_gpu_result_bitwise(cfg5_one_
 def test_cfg5_eight_rank_rehearsal_reproduces_the_one_gpu_result_bitwise(cfg5_one_gpu):
     """The shape the driver's 8-GPU run has: 8 ranks x 450 frames (256 + 194 per rank through the tower), one all-gather of
     (450,1024) per rank, selection on (3600,1024) on every rank.  Eight processes on one GPU over gloo."""
-    d = _bench(["--workload", "cfg5", "--gpus", "8", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-scan"],
+    d = _bench(["--workload", "cfg5", "--gpus", "8", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--full", "--no-scan"],
                env={"HMM_BENCH_REHEARSAL": "1"})
     c, c1 = d["config"], cfg5_one_gpu["config"]
     assert d["n_gpus"] == 8 and "rehearsal" in d and c["frames_per_rank"] == [450] * 8 and c["all_gather_bytes_per_rank"] == 450 * 4096
@@ -78,9 +96,10 @@ def test_cfg5_eight_rank_rehearsal_reproduces_the_one_gpu_result_bitwise(cfg5_on
 
 def test_cfg5_ragged_shards_eight_ranks_equal_one_gpu_bitwise():
     """3601 frames do not divide by 8: shard_bounds gives 7 x 451 + 444, the all-gather pads to 451 rows and trims."""
-    one = _bench(["--workload", "cfg5", "--cfg5-frames", "3601", "--gpus", "1", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"])
+    one = _bench(["--workload", "cfg5", "--cfg5-frames", "3601", "--gpus", "1", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
+                  "--full"])
     d = _bench(["--workload", "cfg5", "--cfg5-frames", "3601", "--gpus", "8", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
-                "--no-scan"], env={"HMM_BENCH_REHEARSAL": "1"})
+                "--full", "--no-scan"], env={"HMM_BENCH_REHEARSAL": "1"})
     c, c1 = d["config"], one["config"]
     assert c["frames_per_rank"] == [451] * 7 + [444] and c["all_gather_bytes_per_rank"] == 451 * 4096
     assert c["kept_equal_cpu_oracle_on_gathered_matrix"] is True and c1["kept_equal_cpu_oracle_on_gathered_matrix"] is True

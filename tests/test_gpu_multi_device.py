@@ -35,7 +35,7 @@ def _bench(args, env=None):
 
 
 def test_cfg5_two_gpus_over_rccl_equals_one_gpu_bitwise():
-    common = ["--workload", "cfg5", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"]
+    common = ["--workload", "cfg5", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--full"]
     one = _bench(common + ["--gpus", "1"])
     two = _bench(common + ["--gpus", "2", "--no-scan"])
     c, c1 = two["config"], one["config"]
@@ -49,7 +49,7 @@ def test_cfg5_two_gpus_over_rccl_equals_one_gpu_bitwise():
 
 
 def test_cfg2_two_gpus_with_the_sharded_scan_leg():
-    d = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+    d = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"])
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["rccl_ranks"] == 2
     assert d["config"]["frames_per_gpu"] == 256 and d["value"] > 0
     assert d["scan"]["weak_1M_rows_per_gpu"]["indices_match_torch_where_separated"] is True

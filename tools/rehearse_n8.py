@@ -12,12 +12,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 out = []
 for wl in ("cfg2", "cfg5"):
     t0 = time.perf_counter()
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--workload", wl],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--workload", wl, "--full"],
                        capture_output=True, text=True, env=dict(os.environ, HMM_BENCH_REHEARSAL="1"), cwd=ROOT)
     wall = time.perf_counter() - t0
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     d = json.loads(lines[-1]) if lines else {}
-    rec = {"command": f"HMM_BENCH_REHEARSAL=1 python bench.py --gpus 8 --steps 2 --warmup 1 --workload {wl}", "rc": r.returncode,
+    rec = {"command": f"HMM_BENCH_REHEARSAL=1 python bench.py --gpus 8 --steps 2 --warmup 1 --workload {wl} --full", "rc": r.returncode,
            "wall_s": round(wall, 1), "json_lines": len(lines), "n_gpus": d.get("n_gpus"), "startup_s_rank0": d.get("startup_s"),
            "ms_per_step_eight_ranks_on_one_gpu": d.get("ms_per_step"), "all_reduced_rank_count": d.get("all_reduced_rank_count"),
            "collective_backend": d.get("collective_backend"), "frames_per_rank": [x.get("frames") for x in d.get("ranks", [])],
