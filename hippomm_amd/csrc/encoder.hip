@@ -27,7 +27,7 @@ namespace hmm {
 HMM_TUNABLE(int, g_enc_side_priority, 0) // probe build: HIP priority of the second chain's stream (0 normal, 1 low, -1 high), read at create
 HMM_TUNABLE(int, g_enc_split_min, 13)    // frames of a vision forward from which it runs as two chains on two streams (round 5, tools/mid_batch_probe.py, profiles/r5_mid_batch.log: 13 / 14 / 15 frames 7.39 / 7.92 / 8.02 -> 6.78 / 6.92 / 6.93 ms, 8 ... 12 frames faster as one chain, 16 ... 56 frames 0 ... -14 %)
 HMM_TUNABLE(int, g_enc_split_min_text, 54)  // the same for the text tower: 54 questions = 4158 rows is where one chain's launches cross 16 row tiles of 256 (54 ... 62 questions 4.76 ... 5.28 -> 4.14 ... 4.50 ms as two chains; 24 ... 52 questions 8 ... 13 % slower as two; profiles/r5_split_min_text_ab.json)
-HMM_TUNABLE(int, g_enc_two_chain_small_tiles, 64)  // gemm_set_small_tiles of a two-chain forward
+HMM_TUNABLE(int, g_enc_two_chain_small_tiles, 64)  // small_tiles (gemm_bf16) of a two-chain forward
 HMM_TUNABLE(int, g_enc_split_min_audio, 12) // the audio tower's smaller kernels overlap from 4 segments on (-7 .. -11 %; tools/split_min_probe.py)
 HMM_TUNABLE(int, g_enc_audio_one_round, 1) // see split_point
 HMM_TUNABLE(int, g_enc_split_num, 128)   // frames of 256 that go to the first of the two chains
@@ -386,6 +386,7 @@ struct Chain {                 // one (half-)batch travelling through the tower 
     const void* input; float* out; char* ws; WsPlan p; hipStream_t st; int batch;
     hipStream_t cls_st; hipEvent_t ev_x, ev_cls;      // fork for the cls-row projection of the fused attention path
     int tile;                  // GEMM dispatch of this forward: HMM_GEMM_TILE_AUTO, or AUTO_TILED when the forward is large
+    int small_tiles;           // gemm_bf16's small_tiles: kGemmSmallTiles, g_enc_two_chain_small_tiles when the forward runs as two chains
     bool fuse;                 // in_proj + attention as one kernel (large enough forwards only, see hmm_encoder_forward)
     int sk_mode;               // splitk_mode() of the forward: fc2 as a split-K launch reduced by the LayerNorm behind it
     mutable const float* pending_bias;   // fc2 of the previous block left partial slabs: the next LayerNorm adds them (+ this bias)
@@ -408,7 +409,7 @@ static int chain_tokens(hmm_encoder* e, const Chain& c) {
     }
     if (e->tower == HMM_TOWER_VISION) HMM_TRY(launch_im2col_vision(static_cast<const float*>(c.input), im2col, n_img, c.st));
     else                              HMM_TRY(launch_im2col_audio(static_cast<const float*>(c.input), im2col, n_img, c.st));
-    HMM_TRY(gemm_bf16(im2col, e->patch_w, nullptr, patch, n_img * e->n_patches, D, e->patch_k_pad, HMM_EPI_F32, c.tile, c.st));
+    HMM_TRY(gemm_bf16(im2col, e->patch_w, nullptr, patch, n_img * e->n_patches, D, e->patch_k_pad, HMM_EPI_F32, c.tile, c.small_tiles, c.st));
     HMM_TRY(launch_assemble_tokens(patch, e->cls, e->pos, e->stem_g, e->stem_b, 1e-5f, e->pre_g, e->pre_b, 1e-6f,
                                    x, n_img, e->T, D, c.st));
     return HMM_OK;
@@ -421,9 +422,9 @@ static int mlp_pair(hmm_encoder* e, const Chain& c, const BlockW& w, const bf16_
     const int chunk = g_enc_mlp_chunk_rows > 0 && g_enc_mlp_chunk_rows < R ? g_enc_mlp_chunk_rows : R;
     for (int r0 = 0; r0 < R; r0 += chunk) {
         const int rows = R - r0 < chunk ? R - r0 : chunk;
-        int rc = gemm_bf16(a + (size_t)r0 * D, w.fc1_w, w.fc1_b, big, rows, e->mlp, D, HMM_EPI_BIAS_GELU_BF16, c.tile, c.st);
+        int rc = gemm_bf16(a + (size_t)r0 * D, w.fc1_w, w.fc1_b, big, rows, e->mlp, D, HMM_EPI_BIAS_GELU_BF16, c.tile, c.small_tiles, c.st);
         if (rc != HMM_OK) return rc;
-        rc = gemm_bf16(big, w.fc2_w, w.fc2_b, x + (size_t)r0 * D, rows, D, e->mlp, HMM_EPI_BIAS_RESID_F32, c.tile, c.st);
+        rc = gemm_bf16(big, w.fc2_w, w.fc2_b, x + (size_t)r0 * D, rows, D, e->mlp, HMM_EPI_BIAS_RESID_F32, c.tile, c.small_tiles, c.st);
         if (rc != HMM_OK) return rc;
     }
     return HMM_OK;
@@ -464,12 +465,12 @@ static int chain_block(hmm_encoder* e, const Chain& c, int i) {
             HMM_HIP_CHECK(hipStreamWaitEvent(cst, c.ev_x, 0));
         }
         HMM_TRY(launch_layernorm_bf16(x, (size_t)T * D, w.ln1_g, w.ln1_b, ac, n_img, D, 1e-6f, cst));     // token 0 of every image
-        HMM_TRY(gemm_bf16(ac, w.qkv_w, w.qkv_b, hc, n_img, 3 * D, D, HMM_EPI_BIAS_BF16, c.tile, cst));
+        HMM_TRY(gemm_bf16(ac, w.qkv_w, w.qkv_b, hc, n_img, 3 * D, D, HMM_EPI_BIAS_BF16, c.tile, c.small_tiles, cst));
         if (g_enc_cls_fork) HMM_HIP_CHECK(hipEventRecord(c.ev_cls, cst));
         HMM_TRY(launch_layernorm_bf16(x, (size_t)D, w.ln1_g, w.ln1_b, a, R, D, 1e-6f, st));
         if (g_enc_cls_fork) HMM_HIP_CHECK(hipStreamWaitEvent(st, c.ev_cls, 0));
         HMM_TRY(qkv_attention_bf16(a, w.qkv_w, w.qkv_b, hc, big, n_img, st));
-        HMM_TRY(gemm_bf16(big, w.out_w, w.out_b, x, R, D, D, HMM_EPI_BIAS_RESID_F32, c.tile, st));
+        HMM_TRY(gemm_bf16(big, w.out_w, w.out_b, x, R, D, D, HMM_EPI_BIAS_RESID_F32, c.tile, c.small_tiles, st));
         HMM_TRY(launch_layernorm_bf16(x, (size_t)D, w.ln2_g, w.ln2_b, a, R, D, 1e-6f, st));
         HMM_TRY(mlp_pair(e, c, w, a, big, x, R));
     } else if (i + 1 < e->depth && e->fused_attention && c.fuse && e->tower == HMM_TOWER_AUDIO && D == 768 && e->heads == 12 && T == 229 &&
@@ -477,40 +478,40 @@ static int chain_block(hmm_encoder* e, const Chain& c, int i) {
         // audio: in_proj + attention in one kernel per (clip, head); every row of a clip fits the 256-row tile, so there is
         // no cls side path.  Bitwise equal to the branch below.
         HMM_TRY(qkv_attention_audio_bf16(a, w.qkv_w, w.qkv_b, w.bias_k, w.bias_v, big, n_img, st));
-        HMM_TRY(gemm_bf16(big, w.out_w, w.out_b, x, R, D, D, HMM_EPI_BIAS_RESID_F32, c.tile, st));
+        HMM_TRY(gemm_bf16(big, w.out_w, w.out_b, x, R, D, D, HMM_EPI_BIAS_RESID_F32, c.tile, c.small_tiles, st));
         HMM_TRY(launch_layernorm_bf16(x, (size_t)D, w.ln2_g, w.ln2_b, a, R, D, 1e-6f, st));
-        HMM_TRY(gemm_bf16(a, w.fc1_w, w.fc1_b, big, R, e->mlp, D, HMM_EPI_BIAS_GELU_BF16, c.tile, st));
-        HMM_TRY(gemm_bf16(big, w.fc2_w, w.fc2_b, x, R, D, e->mlp, HMM_EPI_BIAS_RESID_F32, c.tile, st));
+        HMM_TRY(gemm_bf16(a, w.fc1_w, w.fc1_b, big, R, e->mlp, D, HMM_EPI_BIAS_GELU_BF16, c.tile, c.small_tiles, st));
+        HMM_TRY(gemm_bf16(big, w.fc2_w, w.fc2_b, x, R, D, e->mlp, HMM_EPI_BIAS_RESID_F32, c.tile, c.small_tiles, st));
     } else if (i + 1 < e->depth || text) {
-        HMM_TRY(gemm_bf16(a, w.qkv_w, w.qkv_b, big, R, 3 * D, D, HMM_EPI_BIAS_BF16, c.tile, st));
+        HMM_TRY(gemm_bf16(a, w.qkv_w, w.qkv_b, big, R, 3 * D, D, HMM_EPI_BIAS_BF16, c.tile, c.small_tiles, st));
         HMM_TRY(attention_bf16(big, a, n_img, T, e->heads, D / e->heads, w.bias_k, w.bias_v, st, text));
         if (c.sk_mode == 1 && g_enc_splitk_out > 1) {
             HMM_TRY(gemm_bf16_splitk(a, w.out_w, part, R, D, D, g_enc_splitk_out, -1, st));
             HMM_TRY(launch_layernorm_reduce_bf16(x, part, part_stride, g_enc_splitk_out, w.out_b, w.ln2_g, w.ln2_b, a, R, D, 1e-6f, st));
         } else {
-            HMM_TRY(gemm_bf16(a, w.out_w, w.out_b, x, R, D, D, HMM_EPI_BIAS_RESID_F32, c.tile, st));
+            HMM_TRY(gemm_bf16(a, w.out_w, w.out_b, x, R, D, D, HMM_EPI_BIAS_RESID_F32, c.tile, c.small_tiles, st));
             HMM_TRY(launch_layernorm_bf16(x, (size_t)D, w.ln2_g, w.ln2_b, a, R, D, 1e-6f, st));
         }
-        HMM_TRY(gemm_bf16(a, w.fc1_w, w.fc1_b, big, R, e->mlp, D, HMM_EPI_BIAS_GELU_BF16, c.tile, st));
+        HMM_TRY(gemm_bf16(a, w.fc1_w, w.fc1_b, big, R, e->mlp, D, HMM_EPI_BIAS_GELU_BF16, c.tile, c.small_tiles, st));
         if (c.sk_mode && n_splits > 1 && i + 1 < e->depth) {        // the next block's norm_1 reduces (text: the last block has none)
             HMM_TRY(gemm_bf16_splitk(big, w.fc2_w, part, R, D, e->mlp, n_splits, -1, st));
             c.pending_bias = w.fc2_b;
         } else {
-            HMM_TRY(gemm_bf16(big, w.fc2_w, w.fc2_b, x, R, D, e->mlp, HMM_EPI_BIAS_RESID_F32, c.tile, st));
+            HMM_TRY(gemm_bf16(big, w.fc2_w, w.fc2_b, x, R, D, e->mlp, HMM_EPI_BIAS_RESID_F32, c.tile, c.small_tiles, st));
         }
     } else {
         // The head reads only token 0 (SelectElement(index=0)), so the LAST block needs K/V for every
         // token but Q, attention output, out-proj and the MLP for the cls row of each image only.
         // K|V projection of all rows (in_proj rows D..3D), Q projection of the cls rows (rows 0..D).
-        HMM_TRY(gemm_bf16(a, w.qkv_w + (size_t)D * D, w.qkv_b + D, big, R, 2 * D, D, HMM_EPI_BIAS_BF16, c.tile, st));
+        HMM_TRY(gemm_bf16(a, w.qkv_w + (size_t)D * D, w.qkv_b + D, big, R, 2 * D, D, HMM_EPI_BIAS_BF16, c.tile, c.small_tiles, st));
         HMM_TRY(launch_gather_rows(a, (size_t)T * D * 2, ac, n_img, D * 2, st));
-        HMM_TRY(gemm_bf16(ac, w.qkv_w, w.qkv_b, qc, n_img, D, D, HMM_EPI_BIAS_BF16, c.tile, st));
+        HMM_TRY(gemm_bf16(ac, w.qkv_w, w.qkv_b, qc, n_img, D, D, HMM_EPI_BIAS_BF16, c.tile, c.small_tiles, st));
         HMM_TRY(attention_cls_bf16(qc, big, ac, n_img, T, e->heads, D / e->heads, w.bias_k, w.bias_v, st));
         HMM_TRY(launch_gather_rows(x, (size_t)T * D * 4, xc, n_img, D * 4, st));
-        HMM_TRY(gemm_bf16(ac, w.out_w, w.out_b, xc, n_img, D, D, HMM_EPI_BIAS_RESID_F32, c.tile, st));
+        HMM_TRY(gemm_bf16(ac, w.out_w, w.out_b, xc, n_img, D, D, HMM_EPI_BIAS_RESID_F32, c.tile, c.small_tiles, st));
         HMM_TRY(launch_layernorm_bf16(xc, (size_t)D, w.ln2_g, w.ln2_b, ac, n_img, D, 1e-6f, st));
-        HMM_TRY(gemm_bf16(ac, w.fc1_w, w.fc1_b, hc, n_img, e->mlp, D, HMM_EPI_BIAS_GELU_BF16, c.tile, st));
-        HMM_TRY(gemm_bf16(hc, w.fc2_w, w.fc2_b, xc, n_img, D, e->mlp, HMM_EPI_BIAS_RESID_F32, c.tile, st));
+        HMM_TRY(gemm_bf16(ac, w.fc1_w, w.fc1_b, hc, n_img, e->mlp, D, HMM_EPI_BIAS_GELU_BF16, c.tile, c.small_tiles, st));
+        HMM_TRY(gemm_bf16(hc, w.fc2_w, w.fc2_b, xc, n_img, D, e->mlp, HMM_EPI_BIAS_RESID_F32, c.tile, c.small_tiles, st));
     }
     return HMM_OK;
 }
@@ -531,7 +532,7 @@ static int chain_head(hmm_encoder* e, const Chain& c) {
                                                 p.n_img, e->D * 4, c.st));
         HMM_TRY(launch_layernorm_bf16(xc, (size_t)e->D, e->head_g, e->head_b, hl, p.n_img, e->D, 1e-6f, c.st));
     }
-    HMM_TRY(gemm_bf16(hl, e->head_w, nullptr, hv, p.n_img, HMM_FEATURE_DIM, e->D, HMM_EPI_F32, c.tile, c.st));
+    HMM_TRY(gemm_bf16(hl, e->head_w, nullptr, hv, p.n_img, HMM_FEATURE_DIM, e->D, HMM_EPI_F32, c.tile, c.small_tiles, c.st));
     HMM_TRY(launch_l2norm_rows(hv, c.out, c.batch, e->clips, e->log_scale, c.st));
     return HMM_OK;
 }
@@ -581,25 +582,25 @@ extern "C" int hmm_encoder_forward(hmm_encoder* e, const void* input_dev, int ba
         if (cap != hipStreamCaptureStatusNone) b0 = 0;
     }
     if (b0 == 0) {
-        chains[0] = Chain{input_dev, out_dev, ws, ws_plan(e, batch, sk), st, batch, e->cls_stream[0], e->ev_x[0], e->ev_cls[0], tile, fuse, sk, nullptr};
+        chains[0] = Chain{input_dev, out_dev, ws, ws_plan(e, batch, sk), st, batch, e->cls_stream[0], e->ev_x[0], e->ev_cls[0], tile,
+                          kGemmSmallTiles, fuse, sk, nullptr};
     } else {
         const WsPlan p0 = ws_plan(e, b0, sk);
-        chains[0] = Chain{input_dev, out_dev, ws, p0, st, b0, e->cls_stream[0], e->ev_x[0], e->ev_cls[0], tile, fuse, sk, nullptr};
+        chains[0] = Chain{input_dev, out_dev, ws, p0, st, b0, e->cls_stream[0], e->ev_x[0], e->ev_cls[0], tile,
+                          g_enc_two_chain_small_tiles, fuse, sk, nullptr};
         chains[1] = Chain{static_cast<const char*>(input_dev) + (size_t)b0 * in_bytes_per_sample, out_dev + (size_t)b0 * HMM_FEATURE_DIM,
                           ws + p0.total, ws_plan(e, batch - b0, sk), e->side_stream, batch - b0,
-                          e->cls_stream[1], e->ev_x[1], e->ev_cls[1], tile, fuse, sk, nullptr};
+                          e->cls_stream[1], e->ev_x[1], e->ev_cls[1], tile, g_enc_two_chain_small_tiles, fuse, sk, nullptr};
         n_chains = 2;
         HMM_HIP_CHECK(hipEventRecord(e->ev_fork, st));                       // fork
         HMM_HIP_CHECK(hipStreamWaitEvent(e->side_stream, e->ev_fork, 0));
     }
     // launches are interleaved block by block so that both streams always have work queued
-    const int prev_small = gemm_set_small_tiles(n_chains == 2 ? g_enc_two_chain_small_tiles : 128);
     int rc = HMM_OK;
     for (int c = 0; c < n_chains && rc == HMM_OK; ++c) rc = chain_tokens(e, chains[c]);
     for (int i = 0; i < e->depth && rc == HMM_OK; ++i)
         for (int c = 0; c < n_chains && rc == HMM_OK; ++c) rc = chain_block(e, chains[c], i);
     for (int c = 0; c < n_chains && rc == HMM_OK; ++c) rc = chain_head(e, chains[c]);
-    gemm_set_small_tiles(prev_small);
     if (rc != HMM_OK)                                                        // a failed chain may have left its cls fork un-joined
         for (int c = 0; c < 2; ++c) (void)hipStreamSynchronize(e->cls_stream[c]);
     if (n_chains == 2) {

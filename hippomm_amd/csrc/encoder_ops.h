@@ -4,12 +4,12 @@
 
 namespace hmm {
 
+// tile: an HMM_GEMM_TILE_* id.  small_tiles: under the automatic dispatch, launches of fewer 256x256 tiles than this leave the
+// ping-pong kernel for the small-tile kernels.  kGemmSmallTiles unless the forward runs as two chains: then its launches share
+// the chip with the other chain's, so half-full ping-pong launches pack well and it passes 64 (tools/mid_batch_probe.py).
+constexpr int kGemmSmallTiles = 128;
 int gemm_bf16(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K, int epi,
-              int variant, hipStream_t st);
-// Launches of fewer 256x256 tiles than this leave the ping-pong kernel for the small-tile kernels (default 128).  A forward
-// that runs as two chains sets 64 for its duration: its launches share the chip with the other chain's, so half-full
-// ping-pong launches pack well (tools/mid_batch_probe.py).  Per host thread; returns the previous value.
-int gemm_set_small_tiles(int tiles);
+              int tile, int small_tiles, hipStream_t st);
 
 // Split-K for few-row launches with a long K: `splits` fp32 partial products part[split][M][N] (no bias), added up in split
 // order by launch_layernorm_reduce_bf16 -- the LayerNorm that follows every residual GEMM -- together with the bias and the

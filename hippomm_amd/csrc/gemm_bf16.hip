@@ -115,11 +115,10 @@ __device__ __forceinline__ void gemm_epilogue(f32x4 (&acc)[MI][NI], const float*
 // (A staggered loop for the eight-wave tiles -- waves 4-7 half a K-tile behind waves 0-3, the ping-pong kernel's schedule at ring
 // size -- was built in round 5: bit-equal, 0 ... +4 % slower on the 128-row tiles; -14 % on a 256 x 128 tile, which is 25-30 % faster
 // alone than anything else on 13-16 frames' fc2 / out-proj and buys nothing in the forwards; profiles/LABNOTES_r5.md 13, 18.)
-// ABL (probe build, timing only -- results are wrong): 1 = no MFMAs, 2 = no fragment reads and no MFMAs, 3 = no LDS-DMA.
-template <int BM, int BN, int WM, int WN, int EPI, int STAGES = 2, int KSUB = 1, int ABL = 0>
+template <int BM, int BN, int WM, int WN, int EPI, int STAGES, int KSUB>
 __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_kernel(
     const bf16_t* __restrict__ A, const bf16_t* __restrict__ W, const float* __restrict__ bias,
-    void* __restrict__ Cout, int M, int N, int K, int tiles_n, int tiles_m, int col_major, int k_len) {
+    void* __restrict__ Cout, int M, int N, int K, int tiles_n, int tiles_m, int k_len) {
     constexpr int NW = WM * WN;
     constexpr int TM = BM / WM, TN = BN / WN;
     constexpr int MI = TM / 16, NI = TN / 16;
@@ -133,15 +132,13 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_kernel(
     const int wm = wave / WN, wn = wave % WN;
 
     // bijective XCD-aware remap of the linear block id: XCD x (= blockIdx % 8) takes a contiguous run of the work list.
-    // The list is [K split][tile]; tiles row-major (a row tile's column tiles are neighbours: an XCD shares A panels) or
-    // column-major (a column tile's row tiles are neighbours: an XCD shares W panels, and with few row tiles every weight
-    // byte leaves HBM / the Infinity Cache once instead of once per row tile -- see launch_gemm).
+    // The list is [K split][tile], tiles row-major: a row tile's column tiles are neighbours, so an XCD shares A panels.
     const int nb = gridDim.x, bid = blockIdx.x;
     const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7;
     const int swz = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
     const int tiles = tiles_m * tiles_n;
     const int split = swz / tiles, tl = swz - split * tiles;      // split > 0 only in a split-K launch (grid = splits x tiles)
-    const int m0 = (col_major ? tl % tiles_m : tl / tiles_n) * BM, n0 = (col_major ? tl / tiles_m : tl % tiles_n) * BN;
+    const int m0 = (tl / tiles_n) * BM, n0 = (tl % tiles_n) * BN;
     A += (size_t)split * k_len;                                   // this workgroup's K range: columns [split k_len, + k_len)
     W += (size_t)split * k_len;
     if (nb > tiles) Cout = static_cast<float*>(Cout) + (size_t)split * M * N;   // split-K: fp32 partial slab of this split
@@ -165,7 +162,6 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_kernel(
     }
 
     auto stage = [&](int kg, int buf) {                  // the KSUB K-tiles of group kg into ring buffer `buf`
-        if constexpr (ABL == 3) return;
 #pragma unroll
         for (int sub = 0; sub < KSUB; ++sub) {
             char* base = smem + buf * STAGE + sub * SUB;
@@ -202,7 +198,6 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_kernel(
     // loads are arranged; the empty asm statements tie each fragment to the wait in front of it (volatile asm keeps its order).
     const uint32_t lds0 = (uint32_t)(uintptr_t)HMM_LDS_PTR(smem);
     auto compute_sub = [&](int stage_off) {
-        if constexpr (ABL == 2) return;
         bf16x8 af[2][MI], wf[2][NI];
 #pragma unroll
         for (int kh = 0; kh < 2; ++kh) {
@@ -227,13 +222,11 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_kernel(
             for (int mi = 0; mi < MI; ++mi) asm volatile("" : "+v"(af[kh][mi]));
 #pragma unroll
             for (int ni = 0; ni < NI; ++ni) asm volatile("" : "+v"(wf[kh][ni]));
-            if constexpr (ABL != 1) {
 #pragma unroll
-                for (int mi = 0; mi < MI; ++mi)
+            for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-                    for (int ni = 0; ni < NI; ++ni)
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[kh][ni], af[kh][mi], acc[mi][ni], 0, 0, 0);
-            }
+                for (int ni = 0; ni < NI; ++ni)
+                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[kh][ni], af[kh][mi], acc[mi][ni], 0, 0, 0);
         }
     };
     auto compute = [&](int stage_off) {
@@ -523,28 +516,11 @@ static int pick_walk(int tiles_m, int tiles_n) {
     if (g_gemm_walk >= 0) return g_gemm_walk;
     return (tiles_n >= 10 && tiles_n % 5 == 0 && tiles_m >= 48) ? ((6 << 8) | 5) : 0;
 }
-#ifdef HMM_PROBE
-// in-kernel stamps (s_memrealtime, 100 MHz): per workgroup {start, -, main loop done, stores retired, XCC id, HW id};
-// written to a buffer of their own that nothing else reads
-unsigned long long* g_gemm_stamps = nullptr;
-extern "C" void hmm_probe_set_gemm_stamps(unsigned long long* p) { g_gemm_stamps = p; }
-#define HMM_PROBE_ARG , unsigned long long* stamps
-#define HMM_PROBE_VAL , g_gemm_stamps
-#define HMM_STAMP(slot)                                                                              \
-    if (stamps && threadIdx.x == 0) stamps[(size_t)blockIdx.x * 8 + (slot)] = __builtin_amdgcn_s_memrealtime();
-#else
-#define HMM_PROBE_ARG
-#define HMM_PROBE_VAL
-#define HMM_STAMP(slot)
-#endif
-
-HMM_TUNABLE(int, g_gemm_trunc_rounds, 0) // probe build: 1 = drop the tiles of a partly filled last round (quantisation-cost experiment; results wrong)
-HMM_TUNABLE(int, g_gemm_skip_tail, 0)   // probe build: 1 = do not launch the peeled tail (what the tails cost in the forward)
 
 template <int EPI>
 __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(
     const bf16_t* __restrict__ A, const bf16_t* __restrict__ W, const float* __restrict__ bias,
-    void* __restrict__ Cout, int M, int N, int K, int tiles_n, int walk HMM_PROBE_ARG) {
+    void* __restrict__ Cout, int M, int N, int K, int tiles_n, int walk) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int lane = threadIdx.x & 63;
@@ -564,14 +540,6 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(
         m0 = (rg * R + rem2 / wc) * 256;
         n0 = (cg * C + rem2 % wc) * 256;
     }
-    HMM_STAMP(0)
-#ifdef HMM_PROBE
-    if (stamps && threadIdx.x == 0) stamps[(size_t)bid * 8 + 6] = __builtin_amdgcn_s_memtime();
-    if (stamps && threadIdx.x == 0) {
-        stamps[(size_t)bid * 8 + 4] = __builtin_amdgcn_s_getreg((20) | (0 << 6) | (31 << 11));   // HW_REG_XCC_ID
-        stamps[(size_t)bid * 8 + 5] = __builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));    // HW_REG_HW_ID
-    }
-#endif
 
     // staging sources as 32-bit element offsets from A / W (launcher guarantees M*K, N*K < 2^31):
     // half-tile local row lr = (wave + 8j)*8 + (lane>>3), 16-B chunk (lane&7) un-swizzled
@@ -600,19 +568,11 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(
     pp_mainloop(A, W, src, K >> 6, smem, lane, wave, acc);   // K/64 even, >= 2 (checked by the launcher)
 
     // every wave is past its last LDS read and every DMA has landed: the LDS is free
-    HMM_STAMP(2)
-#ifdef HMM_PROBE
-    if (stamps && threadIdx.x == 0) stamps[(size_t)bid * 8 + 7] = __builtin_amdgcn_s_memtime();     // shader-clock ticks
-#endif
     // the epilogue's lane-derived indices (lane >> 4, lane & 15, ...) are recomputed HERE from an opaque copy of the lane id:
     // hoisted in front of the main loop they were carried across it and two of them spilled to scratch in the fp32 epilogues
     int lane_e = lane;
     asm volatile("" : "+v"(lane_e));
     gemm_epilogue_lds<EPI>(acc, bias, Cout, M, N, m0 + wm * 128, n0 + wn * 64, smem + wave * kEpiSlab, lane_e);
-#ifdef HMM_PROBE
-    if (stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-    HMM_STAMP(3)
-#endif
 }
 
 template <int EPI>
@@ -622,45 +582,29 @@ static int launch_gemm_pp(const bf16_t* A, const bf16_t* W, const float* bias, v
     const int tiles_m = (M + 255) / 256, tiles_n = N / 256;
     auto kern = gemm_bf16_pp_kernel<EPI>;
     HMM_ENSURE_DYN_LDS(kern, LDS);
-    int grid = tiles_m * tiles_n;
-    if (g_gemm_trunc_rounds && grid > 256 && grid % 256 > 64) grid = grid / 256 * 256;   // probe build, timing only: whole rounds
-    kern<<<grid, 512, LDS, st>>>(A, W, bias, C, M, N, K, tiles_n, pick_walk(tiles_m, tiles_n) HMM_PROBE_VAL);
+    kern<<<tiles_m * tiles_n, 512, LDS, st>>>(A, W, bias, C, M, N, K, tiles_n, pick_walk(tiles_m, tiles_n));
     HMM_LAUNCH_CHECK();
     return HMM_OK;
 }
 
-// Tile order of the tiled kernels (which workgroup computes a tile does not change the tile: same bits).  With fewer row
-// tiles than column tiles -- few-row launches: one frame's qkv GEMM is 5 x 60 tiles of 64 x 64 -- the row-major list hands
-// every XCD a run of column tiles of ONE row tile, so each W panel is pulled through the fabric by five different XCDs
-// (49 MB for 9.8 MB of weights) while the tiny A panels are what gets shared; column-major hands an XCD whole columns.
-// Built and measured in round 5 (profiles/r5_splitk_probe.json, r5_splitk_forward.json): alone with cold weights one
-// frame's qkv / fc1 13.8 -> 13.3 / 15.3 -> 14.3 us, but IN the forwards 0 ... +4 % (one / two / four questions +1.5 / +2.8 /
-// +4.3 %, one frame +0.9 %): the fabric is not what these launches wait for.  Row-major stays; 1 = column-major in the
-// probe build only.
-HMM_TUNABLE(int, g_gemm_col_major, 0)
-static thread_local int t_gemm_tail_launch = 0;       // the peeled tail of a big launch keeps the row-major list (set by gemm_bf16)
-static thread_local int t_gemm_splits = 1;            // > 1: the next launch_gemm is a split-K launch (set by gemm_bf16_splitk)
-
-template <int BM, int BN, int WM, int WN, int EPI, int STAGES = 2, int KSUB = 1, int ABL = 0>
-static int launch_gemm(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K,
+// splits > 1: a split-K launch (gemm_bf16_splitk: HMM_EPI_F32, no bias), fp32 partial slabs part[split][M][N]
+template <int BM, int BN, int WM, int WN, int EPI, int STAGES, int KSUB>
+static int launch_gemm(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K, int splits,
                        hipStream_t st) {
     constexpr int LDS = STAGES * KSUB * (BM + BN) * 128;
     static_assert(LDS <= 160 * 1024, "ring of the tiled GEMM: LDS");
-    const int splits = t_gemm_splits;
     HMM_REQUIRE(K % splits == 0 && ((K / splits) / 64) % KSUB == 0 && (K / splits) % 64 == 0, HMM_E_INVALID,
                 "gemm: K = %d / %d splits is not a multiple of %d", K, splits, 64 * KSUB);
-    HMM_REQUIRE(splits == 1 || (EPI == HMM_EPI_F32 && bias == nullptr), HMM_E_INVALID, "gemm: split-K writes fp32 partials only");
-    auto kern = gemm_bf16_kernel<BM, BN, WM, WN, EPI, STAGES, KSUB, ABL>;
+    auto kern = gemm_bf16_kernel<BM, BN, WM, WN, EPI, STAGES, KSUB>;
     HMM_ENSURE_DYN_LDS(kern, LDS);
     const int tiles_m = (M + BM - 1) / BM, tiles_n = N / BN;
-    const int col_major = g_gemm_col_major > 0 && !t_gemm_tail_launch && 2 * tiles_m <= tiles_n;
-    kern<<<tiles_m * tiles_n * splits, WM * WN * 64, LDS, st>>>(A, W, bias, C, M, N, K, tiles_n, tiles_m, col_major, K / splits);
+    kern<<<tiles_m * tiles_n * splits, WM * WN * 64, LDS, st>>>(A, W, bias, C, M, N, K, tiles_n, tiles_m, K / splits);
     HMM_LAUNCH_CHECK();
     return HMM_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// The few-row dispatcher's rules, as data.  Every threshold of launch_gemm_small_epi / gemm_bf16 below is one row here: the
+// The few-row dispatcher's rules, as data.  Every threshold of small_tile / gemm_bf16 below is one row here: the
 // constant's name (probe build: the run-time knob hmm_probe_set_<name>), the shipped limit, the value that switches the rule
 // OFF, what it decides, the forwards on which it fires ("tower:batch,batch;...") and the measurement it came from.  FROZEN in
 // round 6: no new rules.  `python tools/dispatch_audit_probe.py --check` re-times every row (rule on / off on its own forwards,
@@ -721,7 +665,6 @@ extern "C" const char* hmm_probe_dispatch_rules() {
 // 0.225 us (64x64 tiles) or 0.19 us (32x32 tiles, when the launch fits them) per 64 columns of K.  The sliver kernel wins for
 // one or two dozen rows and for the text tower's fc2 at 77 rows (13 vs 15 us).
 HMM_TUNABLE(int, g_gemm_sliver_mt, 0)    // probe build: force 16 / 32 / 64 rows per wave (1 / 2 / 4)
-HMM_TUNABLE(int, g_gemm_sliver_auto, 1)  // probe build: 0 = the dispatcher never picks the sliver kernel
 HMM_RULE(g_gemm_small_64)
 HMM_RULE(g_gemm_small_32)
 HMM_RULE(g_gemm_deepk)
@@ -739,11 +682,11 @@ static int sliver_mt(int M, int N, int K) {
     return best;
 }
 static bool sliver_wins(int M, int N, int K, int epi) {
-    if (!g_gemm_sliver_auto || epi > HMM_EPI_F32) return false;
+    if (epi > HMM_EPI_F32) return false;
     if ((long)((M + 63) / 64) * (N / 64) > 512) return false;               // that many rows: never
     const long t32 = (long)((M + 31) / 32) * (N / 32);
     float per_ktile = ring32_fits(M, N) ? 0.19f : 0.225f;                     // what the launch would use instead
-    if (g_gemm_deepk && ring32_fits(M, N)) {                                  // the deep-K rings (launch_gemm_small_epi)
+    if (g_gemm_deepk && ring32_fits(M, N)) {                                  // the deep-K rings (small_tile)
         if (K >= 2048 && (K >> 6) % 4 == 0 && t32 <= 256) per_ktile = 0.13f;
         else if (K >= 1024 && (K >> 6) % 2 == 0 && t32 <= 192) per_ktile = 0.155f;
     }
@@ -762,173 +705,96 @@ static int launch_gemm_sliver(const bf16_t* A, const bf16_t* W, const float* bia
     return HMM_OK;
 }
 
-static int launch_gemm_sliver_epi(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K,
-                                  int epi, hipStream_t st) {
+// ---------------------------------------------------------------------------------------------------------------------------
+// The geometry table.  launch_tile is the only place where an HMM_GEMM_TILE_* id becomes a kernel and its template arguments,
+// and dispatch_epi the only switch from an epilogue id to a template argument.  Every geometry gives an output element the same
+// bits (same instruction, operand roles, fragment layout and K order), so what the table decides is speed only.
+//   - 64x64 ring: four buffers (64 KiB of LDS: two workgroups per CU).  Measured and not kept, both bitwise equal: eight buffers
+//     (seven K-tiles in flight, one workgroup per CU) 0.29 us per K-tile instead of 0.225; five buffers with the fragments of the
+//     next K-tile read under the MFMAs of the current one 0.25 -- the step is the barrier, the DMA issue and the dependent
+//     read -> MFMA chain, not bytes in flight; eight waves of 32x16 per tile (two per SIMD) 0.25 (profiles/LABNOTES.md 4.8).
+//   - rectangular ring tiles (round 5): with few rows the chip is filled by COLUMN tiles, and what a launch then costs is its K
+//     walk times the workgroups a CU has to run one after (or beside) the other.  One frame's qkv GEMM is 300 tiles of 64 x 64
+//     on 256 CUs -- 44 CUs run two workgroups and the launch takes their time, 13.3 us; as 128 x 64 tiles it is 180 workgroups,
+//     one per CU, and the tile's 16 MFMAs per wave and K-tile hide the ring's latencies better than the 8 of a 64 x 64 tile.
+//   - RING8: the eight-wave instantiations (two waves per SIMD): one wave's LDS reads and DMA issue run under its partner's
+//     MFMAs.  Alone with cold weights (profiles/r5_rect_tile_probe2.json) 128 x 128: 17.1 -> 15.2 us (one frame's qkv), 13.3 ->
+//     11.9 (one audio segment's fc1), 53.4 -> 46.8 (eight frames' fc2); 128 x 64: 12.2 -> 11.5, 13.0 -> 11.9.
+template <class F>
+static int dispatch_epi(int epi, F&& launch) {
     switch (epi) {
-        case HMM_EPI_BIAS_BF16:      return launch_gemm_sliver<HMM_EPI_BIAS_BF16>(A, W, bias, C, M, N, K, st);
-        case HMM_EPI_BIAS_GELU_BF16: return launch_gemm_sliver<HMM_EPI_BIAS_GELU_BF16>(A, W, bias, C, M, N, K, st);
-        case HMM_EPI_BIAS_RESID_F32: return launch_gemm_sliver<HMM_EPI_BIAS_RESID_F32>(A, W, bias, C, M, N, K, st);
-        case HMM_EPI_F32:            return launch_gemm_sliver<HMM_EPI_F32>(A, W, bias, C, M, N, K, st);
+        case HMM_EPI_BIAS_BF16:      return launch(std::integral_constant<int, HMM_EPI_BIAS_BF16>());
+        case HMM_EPI_BIAS_GELU_BF16: return launch(std::integral_constant<int, HMM_EPI_BIAS_GELU_BF16>());
+        case HMM_EPI_BIAS_RESID_F32: return launch(std::integral_constant<int, HMM_EPI_BIAS_RESID_F32>());
+        case HMM_EPI_F32:            return launch(std::integral_constant<int, HMM_EPI_F32>());
     }
-    set_error("gemm: the sliver kernel has no epilogue %d", epi);
+    set_error("gemm: unknown epilogue %d", epi);
     return HMM_E_INVALID;
 }
 
-#define HMM_EPI_SWITCH(CALL)                                                              \
-    switch (epi) {                                                                        \
-        case HMM_EPI_BIAS_BF16:      return CALL(HMM_EPI_BIAS_BF16);                      \
-        case HMM_EPI_BIAS_GELU_BF16: return CALL(HMM_EPI_BIAS_GELU_BF16);                 \
-        case HMM_EPI_BIAS_RESID_F32: return CALL(HMM_EPI_BIAS_RESID_F32);                 \
-        case HMM_EPI_F32:            return CALL(HMM_EPI_F32);                            \
-    }                                                                                     \
-    set_error("gemm: unknown epilogue %d", epi);                                          \
-    return HMM_E_INVALID;
-
-template <int BM, int BN, int WM, int WN>
-static int launch_gemm_epi(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K,
-                           int epi, hipStream_t st) {
-#define HMM_CALL(E) launch_gemm<BM, BN, WM, WN, E>(A, W, bias, C, M, N, K, st)
-    HMM_EPI_SWITCH(HMM_CALL)
-#undef HMM_CALL
+// splits > 1 for the tiled geometries only (gemm_bf16_splitk)
+static int launch_tile(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K, int epi, int tile,
+                       int splits, hipStream_t st) {
+    if (tile == HMM_GEMM_TILE_256x256_PP && ((size_t)M * K >= (1ull << 31) || (size_t)N * K >= (1ull << 31)))
+        tile = HMM_GEMM_TILE_256x256;                   // the ping-pong kernel's staging offsets are 32-bit
+    return dispatch_epi(epi, [&](auto epi_c) {
+        constexpr int E = decltype(epi_c)::value;
+        switch (tile) {                                                          // BM   BN  WM WN   STAGES KSUB
+            case HMM_GEMM_TILE_SLIVER:        return launch_gemm_sliver<E>(A, W, bias, C, M, N, K, st);
+            case HMM_GEMM_TILE_256x256_PP:    return launch_gemm_pp<E>(A, W, bias, C, M, N, K, st);
+            case HMM_GEMM_TILE_128x128:       return launch_gemm<128, 128, 2, 2, E, 2, 1>(A, W, bias, C, M, N, K, splits, st);
+            case HMM_GEMM_TILE_256x128:       return launch_gemm<256, 128, 2, 2, E, 2, 1>(A, W, bias, C, M, N, K, splits, st);
+            case HMM_GEMM_TILE_256x256:       return launch_gemm<256, 256, 2, 4, E, 2, 1>(A, W, bias, C, M, N, K, splits, st);
+            case HMM_GEMM_TILE_128x128_RING:  return launch_gemm<128, 128, 2, 2, E, 4, 1>(A, W, bias, C, M, N, K, splits, st);
+            case HMM_GEMM_TILE_64x64_RING:    return launch_gemm< 64,  64, 2, 2, E, 4, 1>(A, W, bias, C, M, N, K, splits, st);
+            case HMM_GEMM_TILE_32x32_RING:    return launch_gemm< 32,  32, 2, 2, E, 4, 1>(A, W, bias, C, M, N, K, splits, st);
+            case HMM_GEMM_TILE_32x32_RING_K2: return launch_gemm< 32,  32, 2, 2, E, 4, 2>(A, W, bias, C, M, N, K, splits, st);
+            case HMM_GEMM_TILE_32x32_RING_K4: return launch_gemm< 32,  32, 2, 2, E, 4, 4>(A, W, bias, C, M, N, K, splits, st);
+            case HMM_GEMM_TILE_64x64_RING_K2: return launch_gemm< 64,  64, 2, 2, E, 3, 2>(A, W, bias, C, M, N, K, splits, st);
+            case HMM_GEMM_TILE_128x64_RING:   return launch_gemm<128,  64, 2, 2, E, 4, 1>(A, W, bias, C, M, N, K, splits, st);
+            case HMM_GEMM_TILE_64x128_RING:   return launch_gemm< 64, 128, 2, 2, E, 4, 1>(A, W, bias, C, M, N, K, splits, st);
+            case HMM_GEMM_TILE_128x128_RING8: return launch_gemm<128, 128, 2, 4, E, 4, 1>(A, W, bias, C, M, N, K, splits, st);
+            case HMM_GEMM_TILE_128x64_RING8:  return launch_gemm<128,  64, 4, 2, E, 4, 1>(A, W, bias, C, M, N, K, splits, st);
+            case HMM_GEMM_TILE_64x128_RING8:  return launch_gemm< 64, 128, 2, 4, E, 4, 1>(A, W, bias, C, M, N, K, splits, st);
+        }
+        set_error("gemm: unknown tile geometry %d", tile);
+        return HMM_E_INVALID;
+    });
 }
 
-// 64x64 tiles behind the four-buffer ring (64 KiB of LDS: two workgroups per CU).  Measured and not kept, both bitwise equal:
-// eight buffers (seven K-tiles in flight, one workgroup per CU) 0.29 us per K-tile instead of 0.225; five buffers with the
-// fragments of the next K-tile read under the MFMAs of the current one 0.25 -- the step is the barrier, the DMA issue and the
-// dependent read -> MFMA chain, not bytes in flight; eight waves of 32x16 per tile (two per SIMD) 0.25 (profiles/LABNOTES.md 4.8).
-static int launch_gemm_ring64_epi(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K,
-                                  int epi, hipStream_t st) {
-#define HMM_CALL(E) launch_gemm<64, 64, 2, 2, E, 4>(A, W, bias, C, M, N, K, st)
-    switch (epi) {
-        case HMM_EPI_BIAS_BF16:      return HMM_CALL(HMM_EPI_BIAS_BF16);
-        case HMM_EPI_BIAS_GELU_BF16: return HMM_CALL(HMM_EPI_BIAS_GELU_BF16);
-        case HMM_EPI_BIAS_RESID_F32: return HMM_CALL(HMM_EPI_BIAS_RESID_F32);
-        case HMM_EPI_F32:            return HMM_CALL(HMM_EPI_F32);
-    }
-#undef HMM_CALL
-    set_error("gemm: 64x64 tiles have no epilogue %d", epi);
-    return HMM_E_INVALID;
-}
-
-static int launch_gemm_ring32_epi(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K,
-                                  int epi, hipStream_t st) {
-#define HMM_CALL(E) launch_gemm<32, 32, 2, 2, E, 4>(A, W, bias, C, M, N, K, st)
-    switch (epi) {
-        case HMM_EPI_BIAS_BF16:      return HMM_CALL(HMM_EPI_BIAS_BF16);
-        case HMM_EPI_BIAS_GELU_BF16: return HMM_CALL(HMM_EPI_BIAS_GELU_BF16);
-        case HMM_EPI_BIAS_RESID_F32: return HMM_CALL(HMM_EPI_BIAS_RESID_F32);
-        case HMM_EPI_F32:            return HMM_CALL(HMM_EPI_F32);
-    }
-#undef HMM_CALL
-    set_error("gemm: 32x32 tiles have no epilogue %d", epi);
-    return HMM_E_INVALID;
-}
-
-// Deep-K rings (KSUB K-tiles per stage): the epilogues of the plain rings
-template <int BM, int STAGES, int KSUB>
-static int launch_gemm_ringk_epi(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K,
-                                 int epi, hipStream_t st) {
-#define HMM_CALL(E) launch_gemm<BM, BM, 2, 2, E, STAGES, KSUB>(A, W, bias, C, M, N, K, st)
-    switch (epi) {
-        case HMM_EPI_BIAS_BF16:      return HMM_CALL(HMM_EPI_BIAS_BF16);
-        case HMM_EPI_BIAS_GELU_BF16: return HMM_CALL(HMM_EPI_BIAS_GELU_BF16);
-        case HMM_EPI_BIAS_RESID_F32: return HMM_CALL(HMM_EPI_BIAS_RESID_F32);
-        case HMM_EPI_F32:            return HMM_CALL(HMM_EPI_F32);
-    }
-#undef HMM_CALL
-    set_error("gemm: deep-K tiles have no epilogue %d", epi);
-    return HMM_E_INVALID;
-}
-
-// Rectangular tiles behind the ring (round 5): with few rows the chip is filled by COLUMN tiles, and what a launch then costs is
-// its K walk times the workgroups a CU has to run one after (or beside) the other.  One frame's qkv GEMM is 300 tiles of 64 x 64
-// on 256 CUs -- 44 CUs run two workgroups and the launch takes their time, 13.3 us; as 128 x 64 tiles it is 180 workgroups, one per
-// CU, and the tile's 16 MFMAs per wave and K-tile hide the ring's latencies better than the 8 of a 64 x 64 tile.
-template <int BM, int BN, int WM = 2, int WN = 2>
-static int launch_gemm_ring_rect_epi(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K,
-                                     int epi, hipStream_t st) {
-#define HMM_CALL(E) launch_gemm<BM, BN, WM, WN, E, 4>(A, W, bias, C, M, N, K, st)
-    switch (epi) {
-        case HMM_EPI_BIAS_BF16:      return HMM_CALL(HMM_EPI_BIAS_BF16);
-        case HMM_EPI_BIAS_GELU_BF16: return HMM_CALL(HMM_EPI_BIAS_GELU_BF16);
-        case HMM_EPI_BIAS_RESID_F32: return HMM_CALL(HMM_EPI_BIAS_RESID_F32);
-        case HMM_EPI_F32:            return HMM_CALL(HMM_EPI_F32);
-    }
-#undef HMM_CALL
-    set_error("gemm: rectangular ring tiles have no epilogue %d", epi);
-    return HMM_E_INVALID;
-}
-
-static int launch_gemm_ring128_epi(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K,
-                                   int epi, hipStream_t st) {
-#define HMM_CALL(E) launch_gemm<128, 128, 2, 2, E, 4>(A, W, bias, C, M, N, K, st)
-    HMM_EPI_SWITCH(HMM_CALL)
-#undef HMM_CALL
-}
-
-// What the dispatcher uses where it says "128 x 128 ring" / "128 x 64 ring": the EIGHT-wave instantiations (wave tiles 64 x 32 /
-// 32 x 32, two waves per SIMD): one wave's LDS reads and DMA issue run under its partner's MFMAs.  Alone with cold weights
-// (profiles/r5_rect_tile_probe2.json) 128 x 128: 17.1 -> 15.2 us (one frame's qkv), 13.3 -> 11.9 (one audio segment's fc1),
-// 53.4 -> 46.8 (eight frames' fc2); 128 x 64: 12.2 -> 11.5, 13.0 -> 11.9.  Same MFMA sequence per output element: same bits.
-HMM_RULE(g_gemm_ring8)
-static int launch_gemm_ring128_auto_epi(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K,
-                                        int epi, hipStream_t st) {
-    return g_gemm_ring8 ? launch_gemm_ring_rect_epi<128, 128, 2, 4>(A, W, bias, C, M, N, K, epi, st)
-                        : launch_gemm_ring128_epi(A, W, bias, C, M, N, K, epi, st);
-}
-
+// ---------------------------------------------------------------------------------------------------------------------------
 // Launches of few tiles (small batches, cls rows, the head, the peeled last row tile of the big launches): a workgroup is alone
 // on its CU, so what counts is the latency of its own K walk.  64x64 tiles behind the 4-deep ring while there are at most 512 of
 // them (64 KiB of LDS, two per CU: ~0.225 us per K-tile, and four times the workgroups of 128x128 tiles), 32x32 tiles (one
 // 16x16 block per wave, ~0.19 us per K-tile) while there are at most 400 of those; 128x128 tiles behind
 // the ring up to 256 tiles (128 KiB, one per CU); beyond that the double-buffered 128x128 kernel (two per CU).
-HMM_TUNABLE(int, g_gemm_small_stages, 4)   // probe build: 2 = the double-buffered kernel only
-static thread_local int t_gemm_small_tiles = 128;     // see gemm_set_small_tiles (encoder_ops.h)
-int gemm_set_small_tiles(int tiles) {
-    const int prev = t_gemm_small_tiles;
-    t_gemm_small_tiles = tiles;
-    return prev;
-}
+// "128 x 128 ring" / "128 x 64 ring" are the eight-wave tiles (RING8, see the geometry table) under g_gemm_ring8.
+HMM_RULE(g_gemm_ring8)
 HMM_RULE(g_gemm_rect)
 HMM_RULE(g_gemm_rect64_min_t64)
 HMM_RULE(g_gemm_rect_rows)
 HMM_RULE(g_gemm_rect_rows_longk)
 HMM_RULE(g_gemm_ring_peel_rows)
-static int launch_gemm_small_epi(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K,
-                                 int epi, hipStream_t st, bool tail = false) {
-    if (g_gemm_small_stages != 2 && !tail && g_gemm_ring_peel_rows > 0) {
-        // A frame is 257 token rows = two 128-row tiles + ONE row: k frames end in a row tile of k rows.  When that sliver of a tile
-        // is what pushes the launch past one 128 x 128 ring tile per CU (three frames' fc1: 7 x 40 = 280 tiles for 6 x 40 + 3 rows;
-        // four frames' qkv: 9 x 30 = 270), peel it: the full row tiles in one round of the ring, the last rows through the
-        // one-wave sliver kernel.  Same MFMA sequence per output element: same bits.
-        const int tm = (M + 127) / 128, tail_rows = M - (tm - 1) * 128;
-        const long cols = N / 128;
-        if (tm > 1 && tail_rows <= g_gemm_ring_peel_rows && tm * cols > kNumCU && (tm - 1) * cols <= kNumCU) {
-            const int m_main = (tm - 1) * 128;
-            int rc = launch_gemm_small_epi(A, W, bias, C, m_main, N, K, epi, st, false);
-            if (rc != HMM_OK) return rc;
-            const bool c_bf16 = epi == HMM_EPI_BIAS_BF16 || epi == HMM_EPI_BIAS_GELU_BF16;
-            return launch_gemm_sliver_epi(A + (size_t)m_main * K, W, bias, static_cast<char*>(C) + (size_t)m_main * N * (c_bf16 ? 2 : 4),
-                                          tail_rows, N, K, epi, st);
-        }
-    }
-    if (g_gemm_small_stages == 2 || (long)((M + 127) / 128) * (N / 128) > 256) {
+// The geometry of such a launch (tail: the peeled last row tiles of a big ping-pong launch).  Peels are launch_gemm_small's.
+static int small_tile(int M, int N, int K, int epi, bool tail) {
+    const long t64 = (long)((M + 63) / 64) * (N / 64);
+    if ((long)((M + 127) / 128) * (N / 128) > 256) {
         // past one ring tile per CU: the double-buffered 128 x 128 kernel, two per CU.  (Round 5 sent bias -> bf16 launches of at least
         // 80 ping-pong tiles to the 256 x 256 kernel here: +0.3 ... 0.5 % on five to seven frames in round 6's recheck, below the 2 % a
         // rule has to buy -- removed, profiles/r6_dispatch_recheck_midround.json.)
-        return launch_gemm_epi<128, 128, 2, 2>(A, W, bias, C, M, N, K, epi, st);
+        return HMM_GEMM_TILE_128x128;
     }
     if (!tail && epi <= HMM_EPI_F32 && ring32_fits(M, N)) {
         // deep-K rings while the launch leaves most CUs a workgroup of their own (tools/deepk_probe.py, cold weights): one
         // question's fc2 (96 tiles, K = 4096) 16.4 -> 10.5 us with four K-tiles per stage, its out-proj 6.3 -> 5.3 with two
         const long t32 = (long)((M + 31) / 32) * (N / 32);
-        if (g_gemm_deepk && K >= 2048 && (K >> 6) % 4 == 0 && t32 <= 256) return launch_gemm_ringk_epi<32, 4, 4>(A, W, bias, C, M, N, K, epi, st);
-        if (g_gemm_deepk && K >= 1024 && (K >> 6) % 2 == 0 && t32 <= 192) return launch_gemm_ringk_epi<32, 4, 2>(A, W, bias, C, M, N, K, epi, st);
-        return launch_gemm_ring32_epi(A, W, bias, C, M, N, K, epi, st);
+        if (g_gemm_deepk && K >= 2048 && (K >> 6) % 4 == 0 && t32 <= 256) return HMM_GEMM_TILE_32x32_RING_K4;
+        if (g_gemm_deepk && K >= 1024 && (K >> 6) % 2 == 0 && t32 <= 192) return HMM_GEMM_TILE_32x32_RING_K2;
+        return HMM_GEMM_TILE_32x32_RING;
     }
     // (the peeled last row tile of a big launch used to take 64 x 64 tiles up to 128 of them: 0.0 % at 128 / 256 frames in round 6's
     // recheck -- removed; it runs on the 128 x 128 ring like any launch of few tiles)
-    if (g_gemm_small_64 && !tail && (long)((M + 63) / 64) * (N / 64) <= g_gemm_small_64) {
+    if (g_gemm_small_64 && !tail && t64 <= g_gemm_small_64) {
         // a few hundred rows with more 64 x 64 tiles than CUs, but at most one 128 x 64 tile per CU: nobody runs two workgroups one
         // after (or beside) the other -- one frame's qkv / fc1 (300 / 400 tiles -> 180 / 240) 13.9 -> 12.1 us / 15.0 -> 13.0 us
         // alone with cold weights (profiles/r5_rect_tile_probe.json), one frame's forward 2.24 -> 2.12 ms, four questions
@@ -939,37 +805,50 @@ static int launch_gemm_small_epi(const bf16_t* A, const bf16_t* W, const float* 
         // segment -1.7 %, profiles/r5_rect700_ab.json; 771 rows = three frames' out-proj is where it starts to lose.)  For K = 5120
         // up to 1536 rows: three / four / five frames -3.8 / -2.6 / -4.1 % (profiles/r5_rect_longk_ab.json); the text tower's fc2
         // (K = 4096, 16 column tiles) loses 2-3 % at 14-18 questions with the same rule, so the limit is by K.
-        if (g_gemm_rect && !tail && (M <= g_gemm_rect_rows || (M <= g_gemm_rect_rows_longk && K >= 5120)) && (long)((M + 63) / 64) * (N / 64) > kNumCU &&
+        if (g_gemm_rect && (M <= g_gemm_rect_rows || (M <= g_gemm_rect_rows_longk && K >= 5120)) && t64 > kNumCU &&
             (long)((M + 127) / 128) * (N / 64) <= kNumCU)
-            return g_gemm_ring8 ? launch_gemm_ring_rect_epi<128, 64, 4, 2>(A, W, bias, C, M, N, K, epi, st)
-                                : launch_gemm_ring_rect_epi<128, 64>(A, W, bias, C, M, N, K, epi, st);
+            return g_gemm_ring8 ? HMM_GEMM_TILE_128x64_RING8 : HMM_GEMM_TILE_128x64_RING;
         // well past one 64 x 64 tile per CU (two workgroups side by side on most CUs) but at most one 64 x 128 tile per CU: the
         // 64-row x 128-column ring tile (four waves of 32 x 64) -- six frames' out-proj / fc2 (forward -6.3 %), 24-26 questions' (-2.4 /
         // -4 %); from 450 tiles on: at 432 (22 questions) it loses 3 % (profiles/r5_dispatch_audit_ab.json, LABNOTES_r5 17)
-        if (g_gemm_rect64_min_t64 > 0 && !tail && (long)((M + 63) / 64) * (N / 64) >= g_gemm_rect64_min_t64 &&
-            (long)((M + 63) / 64) * (N / 128) <= kNumCU)
-            return launch_gemm_ring_rect_epi<64, 128>(A, W, bias, C, M, N, K, epi, st);
+        if (g_gemm_rect64_min_t64 > 0 && t64 >= g_gemm_rect64_min_t64 && (long)((M + 63) / 64) * (N / 128) <= kNumCU)
+            return HMM_GEMM_TILE_64x128_RING;
         // at most one 64x64 tile per CU: the deep-K ring (96 KiB, one workgroup per CU anyway) -- one frame's fc2 24.5 -> 21.9 us,
         // its out-proj 8.6 -> 8.0 (cold weights, tools/deepk_probe.py); with more tiles than CUs two plain-ring workgroups per CU win
-        if (g_gemm_deepk && !tail && epi <= HMM_EPI_F32 && (K >> 6) % 2 == 0 && K >= 1024 && (long)((M + 63) / 64) * (N / 64) <= kNumCU)
-            return launch_gemm_ringk_epi<64, 3, 2>(A, W, bias, C, M, N, K, epi, st);
-        return launch_gemm_ring64_epi(A, W, bias, C, M, N, K, epi, st);
+        if (g_gemm_deepk && epi <= HMM_EPI_F32 && (K >> 6) % 2 == 0 && K >= 1024 && t64 <= kNumCU)
+            return HMM_GEMM_TILE_64x64_RING_K2;
+        return HMM_GEMM_TILE_64x64_RING;
     }
-    return launch_gemm_ring128_auto_epi(A, W, bias, C, M, N, K, epi, st);
+    return g_gemm_ring8 ? HMM_GEMM_TILE_128x128_RING8 : HMM_GEMM_TILE_128x128_RING;
 }
 
-static int launch_gemm_pp_epi(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K,
-                              int epi, hipStream_t st) {
-    if ((size_t)M * K >= (1ull << 31) || (size_t)N * K >= (1ull << 31))       // 32-bit staging offsets
-        return launch_gemm_epi<256, 256, 2, 4>(A, W, bias, C, M, N, K, epi, st);
-#define HMM_CALL(E) launch_gemm_pp<E>(A, W, bias, C, M, N, K, st)
-    HMM_EPI_SWITCH(HMM_CALL)
-#undef HMM_CALL
+static void* c_row(void* C, int m, int N, int epi) {     // row m of the output
+    const bool c_bf16 = epi == HMM_EPI_BIAS_BF16 || epi == HMM_EPI_BIAS_GELU_BF16;
+    return static_cast<char*>(C) + (size_t)m * N * (c_bf16 ? 2 : 4);
 }
-#undef HMM_EPI_SWITCH
 
-int gemm_bf16(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K, int epi,
-              int tile, hipStream_t st) {
+static int launch_gemm_small(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K, int epi,
+                             bool tail, hipStream_t st) {
+    if (!tail && g_gemm_ring_peel_rows > 0) {
+        // A frame is 257 token rows = two 128-row tiles + ONE row: k frames end in a row tile of k rows.  When that sliver of a tile
+        // is what pushes the launch past one 128 x 128 ring tile per CU (three frames' fc1: 7 x 40 = 280 tiles for 6 x 40 + 3 rows;
+        // four frames' qkv: 9 x 30 = 270), peel it: the full row tiles in one round of the ring, the last rows through the
+        // one-wave sliver kernel.  Same MFMA sequence per output element: same bits.
+        const int tm = (M + 127) / 128, tail_rows = M - (tm - 1) * 128;
+        const long cols = N / 128;
+        if (tm > 1 && tail_rows <= g_gemm_ring_peel_rows && tm * cols > kNumCU && (tm - 1) * cols <= kNumCU) {
+            const int m_main = (tm - 1) * 128;
+            const int rc = launch_gemm_small(A, W, bias, C, m_main, N, K, epi, false, st);
+            if (rc != HMM_OK) return rc;
+            return launch_tile(A + (size_t)m_main * K, W, bias, c_row(C, m_main, N, epi), tail_rows, N, K, epi, HMM_GEMM_TILE_SLIVER,
+                               1, st);
+        }
+    }
+    return launch_tile(A, W, bias, C, M, N, K, epi, small_tile(M, N, K, epi, tail), 1, st);
+}
+
+int gemm_bf16(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K, int epi, int tile,
+              int small_tiles, hipStream_t st) {
     HMM_REQUIRE(A && W && C, HMM_E_INVALID, "gemm: null pointer");
     HMM_REQUIRE(M >= 1 && N >= 128 && K >= 64 && K % 64 == 0 && N % 128 == 0, HMM_E_INVALID,
                 "gemm: unsupported shape M=%d N=%d K=%d (need K%%64==0, N%%128==0)", M, N, K);
@@ -979,71 +858,34 @@ int gemm_bf16(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int 
     const bool pp_ok = N % 256 == 0 && K % 128 == 0;
     if ((tile == HMM_GEMM_TILE_PP_PEELED || tile == HMM_GEMM_TILE_256x256_PP) && !pp_ok) tile = HMM_GEMM_TILE_256x256;
     if (tile == HMM_GEMM_TILE_256x256 && N % 256 != 0) tile = HMM_GEMM_TILE_256x128;
-    if (tile == HMM_GEMM_TILE_PP_PEELED) {
-        // Tile quantisation: with 256 CUs and one 256x256 tile per CU, T tiles take ceil(T/256) rounds.
-        // ViT-H at batch 256 has 257 M-tiles (257 = 256 patches + cls per image), i.e. 5..20 tiles left
-        // over for a whole extra round.  Peel the last M-tile(s) off into a small-tile launch when that
-        // makes the main launch an exact number of rounds.
-        const int tiles_m = (M + 255) / 256, tiles_n = N / 256;
-        const long tiles = (long)tiles_m * tiles_n;
-        // few 256x256 tiles (cls-only last block, head, small and mid-size batches): smaller tiles put more CUs to work.
-        // (Round 5 also sent every launch of at most one 128 x 128 tile per CU here, whatever its count of 256-row tiles -- 24 frames on
-        // two chains -4.8 ... -6.2 % in five rechecks, -1.9 % in the one at round 6's final commit: under the 2 % a rule has to buy
-        // ON THAT RUN, so it went, profiles/r6_dispatch_recheck.json.)
-        if (tiles < t_gemm_small_tiles)
-            return sliver_ok && sliver_wins(M, N, K, epi) ? launch_gemm_sliver_epi(A, W, bias, C, M, N, K, epi, st)
-                                             : launch_gemm_small_epi(A, W, bias, C, M, N, K, epi, st);
-        // peel p <= 2 row tiles when that leaves the main launch with a last round that is full or nearly full (>= 240 of 256
-        // CUs) instead of a nearly empty one
-        int peel = 0;
-        if (tiles > 256 && tiles % 256 != 0 && tiles % 256 <= 64)
-            for (int p = 1; p <= 2 && !peel; ++p) {
-                const long r = ((long)(tiles_m - p) * tiles_n) % 256;
-                if (r == 0 || r >= 240) peel = p;
-            }
-        if (!peel) return launch_gemm_pp_epi(A, W, bias, C, M, N, K, epi, st);
-        const int m_main = (tiles_m - peel) * 256;
-        int rc = launch_gemm_pp_epi(A, W, bias, C, m_main, N, K, epi, st);
-        if (rc != HMM_OK) return rc;
-        if (g_gemm_skip_tail) return rc;                         // probe build only (timing upper bound; results are wrong)
-        const bool c_bf16 = epi == HMM_EPI_BIAS_BF16 || epi == HMM_EPI_BIAS_GELU_BF16;
-        t_gemm_tail_launch = 1;
-        rc = launch_gemm_small_epi(A + (size_t)m_main * K, W, bias,
-                                   static_cast<char*>(C) + (size_t)m_main * N * (c_bf16 ? 2 : 4), M - m_main, N, K, epi, st, true);
-        t_gemm_tail_launch = 0;
-        return rc;
-    }
-    switch (tile) {
-        case HMM_GEMM_TILE_SLIVER:     return launch_gemm_sliver_epi(A, W, bias, C, M, N, K, epi, st);
-        case HMM_GEMM_TILE_128x128_RING: return launch_gemm_ring128_epi(A, W, bias, C, M, N, K, epi, st);
-        case HMM_GEMM_TILE_64x64_RING:   return launch_gemm_ring64_epi(A, W, bias, C, M, N, K, epi, st);
-        case HMM_GEMM_TILE_32x32_RING:   return launch_gemm_ring32_epi(A, W, bias, C, M, N, K, epi, st);
-        case HMM_GEMM_TILE_64x64_RING_K2: return launch_gemm_ringk_epi<64, 3, 2>(A, W, bias, C, M, N, K, epi, st);
-        case HMM_GEMM_TILE_32x32_RING_K2: return launch_gemm_ringk_epi<32, 4, 2>(A, W, bias, C, M, N, K, epi, st);
-        case HMM_GEMM_TILE_32x32_RING_K4: return launch_gemm_ringk_epi<32, 4, 4>(A, W, bias, C, M, N, K, epi, st);
-        case HMM_GEMM_TILE_128x64_RING:   return launch_gemm_ring_rect_epi<128, 64>(A, W, bias, C, M, N, K, epi, st);
-        case HMM_GEMM_TILE_64x128_RING:   return launch_gemm_ring_rect_epi<64, 128>(A, W, bias, C, M, N, K, epi, st);
-        case HMM_GEMM_TILE_128x128_RING8: return launch_gemm_ring_rect_epi<128, 128, 2, 4>(A, W, bias, C, M, N, K, epi, st);
-        case HMM_GEMM_TILE_128x64_RING8:  return launch_gemm_ring_rect_epi<128, 64, 4, 2>(A, W, bias, C, M, N, K, epi, st);
-        case HMM_GEMM_TILE_64x128_RING8:  return launch_gemm_ring_rect_epi<64, 128, 2, 4>(A, W, bias, C, M, N, K, epi, st);
-#ifdef HMM_PROBE
-        // timing-only ablations of the eight-wave 128 x 128 ring (bias -> bf16 epilogue), five ring stages, and of the 64 x 64 ring
-        case 101: return launch_gemm<128, 128, 2, 4, HMM_EPI_BIAS_BF16, 4, 1, 1>(A, W, bias, C, M, N, K, st);
-        case 102: return launch_gemm<128, 128, 2, 4, HMM_EPI_BIAS_BF16, 4, 1, 2>(A, W, bias, C, M, N, K, st);
-        case 103: return launch_gemm<128, 128, 2, 4, HMM_EPI_BIAS_BF16, 4, 1, 3>(A, W, bias, C, M, N, K, st);
-        case 105: return launch_gemm<128, 128, 2, 4, HMM_EPI_BIAS_BF16, 5>(A, W, bias, C, M, N, K, st);
-        case 106: return launch_gemm<128, 128, 2, 4, HMM_EPI_BIAS_BF16, 3>(A, W, bias, C, M, N, K, st);
-        case 111: return launch_gemm<64, 64, 2, 2, HMM_EPI_BIAS_BF16, 4, 1, 1>(A, W, bias, C, M, N, K, st);
-        case 112: return launch_gemm<64, 64, 2, 2, HMM_EPI_BIAS_BF16, 4, 1, 2>(A, W, bias, C, M, N, K, st);
-        case 113: return launch_gemm<64, 64, 2, 2, HMM_EPI_BIAS_BF16, 4, 1, 3>(A, W, bias, C, M, N, K, st);
-#endif
-        case HMM_GEMM_TILE_256x256_PP: return launch_gemm_pp_epi(A, W, bias, C, M, N, K, epi, st);
-        case HMM_GEMM_TILE_128x128:    return launch_gemm_epi<128, 128, 2, 2>(A, W, bias, C, M, N, K, epi, st);
-        case HMM_GEMM_TILE_256x128:    return launch_gemm_epi<256, 128, 2, 2>(A, W, bias, C, M, N, K, epi, st);
-        case HMM_GEMM_TILE_256x256:    return launch_gemm_epi<256, 256, 2, 4>(A, W, bias, C, M, N, K, epi, st);
-    }
-    set_error("gemm: unknown tile geometry %d", tile);
-    return HMM_E_INVALID;
+    if (tile != HMM_GEMM_TILE_PP_PEELED) return launch_tile(A, W, bias, C, M, N, K, epi, tile, 1, st);
+
+    // Tile quantisation: with 256 CUs and one 256x256 tile per CU, T tiles take ceil(T/256) rounds.
+    // ViT-H at batch 256 has 257 M-tiles (257 = 256 patches + cls per image), i.e. 5..20 tiles left
+    // over for a whole extra round.  Peel the last M-tile(s) off into a small-tile launch when that
+    // makes the main launch an exact number of rounds.
+    const int tiles_m = (M + 255) / 256, tiles_n = N / 256;
+    const long tiles = (long)tiles_m * tiles_n;
+    // few 256x256 tiles (cls-only last block, head, small and mid-size batches): smaller tiles put more CUs to work.
+    // (Round 5 also sent every launch of at most one 128 x 128 tile per CU here, whatever its count of 256-row tiles -- 24 frames on
+    // two chains -4.8 ... -6.2 % in five rechecks, -1.9 % in the one at round 6's final commit: under the 2 % a rule has to buy
+    // ON THAT RUN, so it went, profiles/r6_dispatch_recheck.json.)
+    if (tiles < small_tiles)
+        return sliver_ok && sliver_wins(M, N, K, epi) ? launch_tile(A, W, bias, C, M, N, K, epi, HMM_GEMM_TILE_SLIVER, 1, st)
+                                                      : launch_gemm_small(A, W, bias, C, M, N, K, epi, false, st);
+    // peel p <= 2 row tiles when that leaves the main launch with a last round that is full or nearly full (>= 240 of 256
+    // CUs) instead of a nearly empty one
+    int peel = 0;
+    if (tiles > 256 && tiles % 256 != 0 && tiles % 256 <= 64)
+        for (int p = 1; p <= 2 && !peel; ++p) {
+            const long r = ((long)(tiles_m - p) * tiles_n) % 256;
+            if (r == 0 || r >= 240) peel = p;
+        }
+    if (!peel) return launch_tile(A, W, bias, C, M, N, K, epi, HMM_GEMM_TILE_256x256_PP, 1, st);
+    const int m_main = (tiles_m - peel) * 256;
+    const int rc = launch_tile(A, W, bias, C, m_main, N, K, epi, HMM_GEMM_TILE_256x256_PP, 1, st);
+    if (rc != HMM_OK) return rc;
+    return launch_gemm_small(A + (size_t)m_main * K, W, bias, c_row(C, m_main, N, epi), M - m_main, N, K, epi, true, st);
 }
 
 // Deterministic split-K for launches of few rows x a long K (out-proj / fc2 of one frame, one question, one segment): the
@@ -1051,19 +893,16 @@ int gemm_bf16(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int 
 // workgroups per tile walk K / splits each and write their fp32 partial products to slab[split][M][N]; the consumer (the
 // LayerNorm behind every residual GEMM: launch_layernorm_reduce_bf16) adds the slabs in split order, the bias and the
 // residual, so no launch is added and an element's bits depend on (N, K, splits) only -- not on M, the tile geometry or timing.
-HMM_TUNABLE(int, g_gemm_splitk_tile, -1)     // probe build: force a ring geometry for the split launches
 int gemm_bf16_splitk(const bf16_t* A, const bf16_t* W, float* part, int M, int N, int K, int splits, int tile, hipStream_t st) {
     HMM_REQUIRE(A && W && part, HMM_E_INVALID, "gemm_splitk: null pointer");
     HMM_REQUIRE(M >= 1 && N >= 128 && N % 128 == 0 && splits >= 1 && splits <= 8 && K % (64 * splits) == 0, HMM_E_INVALID,
                 "gemm_splitk: unsupported shape M=%d N=%d K=%d splits=%d", M, N, K, splits);
-    if (g_gemm_splitk_tile >= 0) tile = g_gemm_splitk_tile;
-    const int k_len = K / splits;
     if (tile < 0) {
         // by the number of 64 x 64 workgroups (profiles/r5_splitk_probe.json, cold weights): up to half a chip of them, 32 x 32
         // tiles put four times the workgroups to work (one question's fc2: 11.2 vs 14.3 us); up to one per CU, 64 x 64 tiles with
         // two K-tiles per ring stage (one frame's fc2: 12.6 us, 22 unsplit); beyond that the plain rings;
         const long w64 = (long)((M + 63) / 64) * (N / 64) * splits;
-        const bool k2 = k_len % 128 == 0;
+        const bool k2 = (K / splits) % 128 == 0;
         // re-audited with the eight-wave tiles (profiles/r5_splitk_tile_audit.json, r5_splitk_rule2_ab.json): one question's 128 workgroups
         // belong to the 32 x 32 tiles (6.8 vs 7.2 us; the question 0.982 -> 0.972 ms); past ~450 workgroups of 64 x 64 one round of
         // 128 x 64 tiles (six questions 12.0 -> 10.9 us, -1.8 % in the forward; seven / eight questions would need two rounds: they keep
@@ -1074,26 +913,10 @@ int gemm_bf16_splitk(const bf16_t* A, const bf16_t* W, float* part, int M, int N
         else if (w64 > 640) tile = HMM_GEMM_TILE_128x128_RING8;
         else tile = HMM_GEMM_TILE_64x64_RING;
     }
-    t_gemm_splits = splits;
-    int rc;
-    switch (tile) {
-        case HMM_GEMM_TILE_128x128_RING:  rc = launch_gemm<128, 128, 2, 2, HMM_EPI_F32, 4>(A, W, nullptr, part, M, N, K, st); break;
-        case HMM_GEMM_TILE_64x64_RING:    rc = launch_gemm<64, 64, 2, 2, HMM_EPI_F32, 4>(A, W, nullptr, part, M, N, K, st); break;
-        case HMM_GEMM_TILE_32x32_RING:    rc = launch_gemm<32, 32, 2, 2, HMM_EPI_F32, 4>(A, W, nullptr, part, M, N, K, st); break;
-        case HMM_GEMM_TILE_64x64_RING_K2: rc = launch_gemm<64, 64, 2, 2, HMM_EPI_F32, 3, 2>(A, W, nullptr, part, M, N, K, st); break;
-        case HMM_GEMM_TILE_32x32_RING_K2: rc = launch_gemm<32, 32, 2, 2, HMM_EPI_F32, 4, 2>(A, W, nullptr, part, M, N, K, st); break;
-        case HMM_GEMM_TILE_32x32_RING_K4: rc = launch_gemm<32, 32, 2, 2, HMM_EPI_F32, 4, 4>(A, W, nullptr, part, M, N, K, st); break;
-        case HMM_GEMM_TILE_128x64_RING:   rc = launch_gemm<128, 64, 2, 2, HMM_EPI_F32, 4>(A, W, nullptr, part, M, N, K, st); break;
-        case HMM_GEMM_TILE_64x128_RING:   rc = launch_gemm<64, 128, 2, 2, HMM_EPI_F32, 4>(A, W, nullptr, part, M, N, K, st); break;
-        case HMM_GEMM_TILE_128x128_RING8: rc = launch_gemm<128, 128, 2, 4, HMM_EPI_F32, 4>(A, W, nullptr, part, M, N, K, st); break;
-        case HMM_GEMM_TILE_128x64_RING8:  rc = launch_gemm<128, 64, 4, 2, HMM_EPI_F32, 4>(A, W, nullptr, part, M, N, K, st); break;
-        case HMM_GEMM_TILE_64x128_RING8:  rc = launch_gemm<64, 128, 2, 4, HMM_EPI_F32, 4>(A, W, nullptr, part, M, N, K, st); break;
-        default:
-            set_error("gemm_splitk: tile geometry %d has no split-K launch", tile);
-            rc = HMM_E_INVALID;
-    }
-    t_gemm_splits = 1;
-    return rc;
+    // the ring geometries only (ids 6 ... 16), fp32 partials without a bias
+    HMM_REQUIRE(tile >= HMM_GEMM_TILE_128x128_RING && tile <= HMM_GEMM_TILE_64x128_RING8, HMM_E_INVALID,
+                "gemm_splitk: tile geometry %d has no split-K launch", tile);
+    return launch_tile(A, W, nullptr, part, M, N, K, HMM_EPI_F32, tile, splits, st);
 }
 
 }  // namespace hmm
@@ -1109,11 +932,11 @@ extern "C" int hmm_op_gemm_bf16_splitk(const uint16_t* a_dev, const uint16_t* w_
 extern "C" int hmm_op_gemm_bf16(const uint16_t* a_dev, const uint16_t* w_dev, const float* bias_dev, void* c_dev,
                                 int M, int N, int K, int epilogue, hmm_stream_t stream) {
     return gemm_bf16(reinterpret_cast<const bf16_t*>(a_dev), reinterpret_cast<const bf16_t*>(w_dev), bias_dev, c_dev,
-                     M, N, K, epilogue, HMM_GEMM_TILE_AUTO, static_cast<hipStream_t>(stream));
+                     M, N, K, epilogue, HMM_GEMM_TILE_AUTO, kGemmSmallTiles, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int hmm_op_gemm_bf16_tile(const uint16_t* a_dev, const uint16_t* w_dev, const float* bias_dev,
                                      void* c_dev, int M, int N, int K, int epilogue, int tile, hmm_stream_t stream) {
     return gemm_bf16(reinterpret_cast<const bf16_t*>(a_dev), reinterpret_cast<const bf16_t*>(w_dev), bias_dev, c_dev,
-                     M, N, K, epilogue, tile, static_cast<hipStream_t>(stream));
+                     M, N, K, epilogue, tile, kGemmSmallTiles, static_cast<hipStream_t>(stream));
 }
