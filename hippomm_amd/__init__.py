@@ -6,6 +6,12 @@ through the C ABI in include/hippomm_hip.h:
     hippomm_amd.encoder.ImageBind                    <- hippomm/models/foundation_models.py:21-151
     hippomm_amd.consolidation._select_key_frames     <- hippomm/core/hippocampal_memory.py:944-967
     hippomm_amd.vector_ops.top_k_cosine_similarity   <- hippomm/utils/vector_ops.py:151-188
+
+and the two SSIM call sites of the formation path (frame SSIM in hippomm_amd/csrc/ssim.hip):
+
+    hippomm_amd.segmentation.compute_frame_difference   <- hippomm/core/batch_process.py:32-69
+    hippomm_amd.segmentation._compute_frame_similarity  <- hippomm/core/hippocampal_memory.py:980-991
+    hippomm_amd.segmentation._segment_sequence          <- hippomm/core/hippocampal_memory.py:1002-1114
     hippomm_amd.sharding                             one-process-per-GPU sharding (RCCL all-gather)
 """
 __version__ = "0.1.0"

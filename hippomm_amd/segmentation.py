@@ -1,0 +1,492 @@
+"""Frame SSIM and sequence segmentation on MI355X -- drop-ins for the reference's two SSIM call sites:
+
+    compute_frame_difference      <- hippomm/core/batch_process.py:32-69
+    _compute_frame_similarity     <- hippomm/core/hippocampal_memory.py:980-991
+    _segment_sequence             <- hippomm/core/hippocampal_memory.py:1002-1114 (segment_sequence: the same as a function)
+
+The SSIM is skimage 0.18.3 ``structural_similarity`` with its defaults, computed by ``hmm_ssim_pairs`` (exact integer 7x7 box sums,
+fp64 formula, fixed-order mean; include/hippomm_hip.h), on gray frames made by ``hmm_gray_u8`` with OpenCV's 8-bit BGR2GRAY rule.
+
+The window walk of ``_segment_sequence`` is a pure host function of the scores (``walk_segments``).  The GPU scorer behind it
+decodes a frame only when the walk first consults a pair that needs it, keeps decoded gray frames in a byte-bounded device cache
+keyed by path (boundary frames are shared between windows), scores the last pair of a window on its own and, when that one does
+not break, the rest of the window in one launch.  Errors -- an unreadable file, frames of different shapes, a side under 7 pixels
+-- are raised only when the walk consults the pair they belong to, which is where the reference raises them.
+
+Deliberate deviations from the reference, all documented on the functions: ``compute_frame_difference`` takes uint8 frames only
+(``TypeError`` otherwise); ``_segment_sequence`` raises ``ValueError`` where the reference would loop forever; an unreadable image
+raises ``OSError`` naming the path where the reference raises ``cv2.error``; the audio-level scan stays on the host (numpy).
+There is no CPU fallback for the SSIM: without a GPU these calls raise ``HippoMMHipError``.
+"""
+from __future__ import annotations
+
+import os
+import threading
+from collections import OrderedDict
+from dataclasses import dataclass
+from typing import Callable, Iterable, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+
+WIN = 7                                   # skimage's default win_size
+CACHE_BYTES = 512 << 20                   # device cache of gray frames (1080p: 2 MiB per frame)
+UPLOAD_FRAMES = 32                        # frames per pinned staging round
+
+# the reference's __init__ defaults (hippocampal_memory.py:263-266)
+MAX_SEGMENT_DURATION = 10.0
+MIN_SEGMENT_DURATION = 5.0
+FRAME_SIMILARITY_THRESHOLD = 0.95
+AUDIO_SILENCE_THRESHOLD = -40
+
+
+@dataclass
+class SequenceSegment:
+    """The fields of the reference's SequenceSegment (hippocampal_memory.py:36-42)."""
+    start_time: float
+    end_time: float
+    frames: Optional[List[str]] = None
+    audio_data: Optional[np.ndarray] = None
+    frame_times: Optional[List[float]] = None
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# tensor-in kernels
+# ---------------------------------------------------------------------------------------------------------------------------------
+_ORDER = {"RGB": 0, "BGR": 1}
+
+
+def _gray_into(frames: torch.Tensor, order: int, gray: Optional[torch.Tensor], minmax: torch.Tensor) -> None:
+    n, h, w = frames.shape[:3]
+    _lib.check(_lib.load().hmm_gray_u8(frames.data_ptr(), n, h, w, order, 0 if gray is None else gray.data_ptr(),
+                                       minmax.data_ptr(), _lib.stream_ptr()), "hmm_gray_u8")
+
+
+def _check_u8_cuda(t: torch.Tensor, ndim: int, what: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != ndim:
+        raise TypeError(f"{what} must be a uint8 tensor with {ndim} dimensions")
+    dev = _lib.require_gpu()
+    return t.to(dev).contiguous()
+
+
+def gray_frames(frames_u8: torch.Tensor, channel_order: str = "RGB", return_minmax: bool = False):
+    """(n, H, W, 3) uint8 frames -> (n, H, W) uint8 gray by OpenCV's 8-bit BGR2GRAY rule,
+    g = (1868 B + 9617 G + 4899 R + 8192) >> 14, on the GPU.  ``channel_order`` "RGB" (Pillow) or "BGR" (OpenCV).
+    ``return_minmax``: also return the (n, 2) int32 (min, max) of each gray frame, computed in the same pass."""
+    if channel_order not in _ORDER:
+        raise ValueError(f"channel_order must be 'RGB' or 'BGR', got {channel_order!r}")
+    f = _check_u8_cuda(frames_u8, 4, "frames_u8")
+    if f.shape[3] != 3:
+        raise ValueError(f"frames_u8 must be (n, H, W, 3), got {tuple(f.shape)}")
+    n, h, w = f.shape[:3]
+    gray = torch.empty((n, h, w), dtype=torch.uint8, device=f.device)
+    minmax = torch.empty((max(n, 1), 2), dtype=torch.int32, device=f.device)
+    if n:
+        _gray_into(f, _ORDER[channel_order], gray, minmax)
+    return (gray, minmax[:n]) if return_minmax else gray
+
+
+def _ssim_launch(gray: torch.Tensor, pairs: np.ndarray, data_range: float, minmax: Optional[torch.Tensor]) -> torch.Tensor:
+    """gray (n, H, W) uint8 CUDA, pairs (m, 2) int32 host -> (m,) float64 CUDA.  data_range < 0: R of frame a from minmax."""
+    lib = _lib.load()
+    n, h, w = gray.shape
+    m = len(pairs)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+    ws = torch.empty(max(lib.hmm_ssim_pairs_workspace_bytes(h, w, m), 256), dtype=torch.uint8, device=gray.device)
+    out = torch.empty(m, dtype=torch.float64, device=gray.device)
+    _lib.check(lib.hmm_ssim_pairs(gray.data_ptr(), n, h, w, pairs.ctypes.data, m, float(data_range),
+                                  0 if minmax is None else minmax.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                  _lib.stream_ptr()), "hmm_ssim_pairs")
+    return out
+
+
+def ssim_pairs(gray: torch.Tensor, pairs, data_range: Optional[float] = None) -> torch.Tensor:
+    """SSIM of gray frames, one float64 score per pair.  gray: (n, H, W) uint8; pairs: (m, 2) integer indices (a, b), where a
+    plays skimage's im1.  data_range None: R = max(a) - min(a) (what ``_compute_frame_similarity`` passes); a number: that R on the
+    0..255 scale (``data_range=1.0`` on frames / 255 is 255 here).  Same scores as skimage 0.18.3 ``structural_similarity(a, b,
+    data_range=R)`` to ~1e-15 relative; NaN where skimage gives NaN."""
+    g = _check_u8_cuda(gray, 3, "gray")
+    p = np.asarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs).reshape(-1, 2)
+    if len(p) == 0:
+        return torch.empty(0, dtype=torch.float64, device=g.device)
+    if g.shape[1] < WIN or g.shape[2] < WIN:
+        raise ValueError("win_size exceeds image extent.  Either ensure that your images are at least 7x7; or pass win_size "
+                         "explicitly in the function call, with an odd value less than or equal to the smaller side of your images.")
+    if data_range is None:
+        minmax = torch.empty((g.shape[0], 2), dtype=torch.int32, device=g.device)
+        _gray_into(g, 2, None, minmax)
+        return _ssim_launch(g, p, -1.0, minmax)
+    if not data_range >= 0:
+        raise ValueError(f"data_range must be >= 0, got {data_range}")
+    return _ssim_launch(g, p, float(data_range), None)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# batch_process.compute_frame_difference
+# ---------------------------------------------------------------------------------------------------------------------------------
+_pinned = {"buf": None}
+_pinned_lock = threading.Lock()
+
+
+def _pinned_bytes(nbytes: int) -> torch.Tensor:
+    """A pinned host buffer of at least nbytes, reused across calls; every user synchronises before it returns."""
+    buf = _pinned["buf"]
+    if buf is None or buf.numel() < nbytes:
+        buf = _pinned["buf"] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, pin_memory=True)
+    return buf
+
+
+def _host_gray(frame: np.ndarray) -> np.ndarray:
+    """OpenCV's 8-bit BGR2GRAY rule on the host (the reference's MSE fallback needs the gray frames there)."""
+    if frame.ndim == 2:
+        return frame
+    b, g, r = (frame[..., c].astype(np.int32) for c in range(3))
+    return ((1868 * b + 9617 * g + 4899 * r + 8192) >> 14).astype(np.uint8)
+
+
+def _check_frame(frame, name: str) -> np.ndarray:
+    if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8:
+        raise TypeError(f"{name} must be a uint8 numpy array (H, W, 3) BGR or (H, W) gray, got "
+                        f"{type(frame).__name__} {getattr(frame, 'dtype', '')}")
+    if not (frame.ndim == 2 or (frame.ndim == 3 and frame.shape[2] == 3)):
+        raise ValueError(f"{name} must be (H, W, 3) BGR or (H, W) gray, got shape {frame.shape}")
+    return frame
+
+
+def _mse_fallback(frame1: np.ndarray, frame2: np.ndarray):
+    """The reference's own fallback expression (batch_process.py:66-69), with whatever it returns or raises."""
+    frame1_norm = _host_gray(frame1).astype(float) / 255.0
+    frame2_norm = _host_gray(frame2).astype(float) / 255.0
+    mse = np.mean((frame1_norm - frame2_norm) ** 2)
+    return min(1.0, mse)
+
+
+def compute_frame_difference(frame1: np.ndarray, frame2: np.ndarray) -> float:
+    """Drop-in for ``batch_process.compute_frame_difference``: 1 - SSIM(gray1, gray2) with data_range 1.0 on frames / 255 (R = 255
+    here), gray by OpenCV's BGR2GRAY rule.  Frames: uint8 (H, W, 3) BGR or (H, W) gray; any other dtype raises ``TypeError`` (the
+    reference would hand it to cv2 / skimage), any other shape ``ValueError``.  Where the reference's SSIM raises (frames of
+    different shapes, a side under 7) or is not finite, the reference's numpy MSE expression runs on the host instead, with
+    whatever it then returns or raises."""
+    frame1 = _check_frame(frame1, "frame1")
+    frame2 = _check_frame(frame2, "frame2")
+    dev = _lib.require_gpu()
+    h, w = frame1.shape[:2]
+    if frame2.shape[:2] != (h, w) or h < WIN or w < WIN:
+        return _mse_fallback(frame1, frame2)
+    with _pinned_lock:
+        n1, n2 = frame1.size, frame2.size
+        stage = _pinned_bytes(n1 + n2)
+        stage[:n1].numpy().reshape(frame1.shape)[...] = frame1
+        stage[n1:n1 + n2].numpy().reshape(frame2.shape)[...] = frame2
+        up = stage[:n1 + n2].to(dev, non_blocking=True)
+        gray = torch.empty((2, h, w), dtype=torch.uint8, device=dev)
+        minmax = torch.empty((1, 2), dtype=torch.int32, device=dev)
+        for k, (frame, off, nb) in enumerate(((frame1, 0, n1), (frame2, n1, n2))):
+            if frame.ndim == 3:
+                _lib.check(_lib.load().hmm_gray_u8(up.data_ptr() + off, 1, h, w, 1, gray[k].data_ptr(), minmax.data_ptr(),
+                                                   _lib.stream_ptr()), "hmm_gray_u8")
+            else:
+                gray[k].view(-1).copy_(up[off:off + nb])
+        score = _ssim_launch(gray, np.array([[0, 1]], np.int32), 255.0, None).cpu().numpy()[0]
+    if np.isfinite(score):
+        return 1.0 - score
+    return _mse_fallback(frame1, frame2)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# frames by path: decode, gray, device cache
+# ---------------------------------------------------------------------------------------------------------------------------------
+class _Slab:
+    """Gray frames of one (H, W) in device memory, LRU over slots."""
+
+    def __init__(self, h: int, w: int, capacity: int, dev):
+        self.h, self.w, self.capacity = h, w, capacity
+        self.gray = torch.empty((capacity, h, w), dtype=torch.uint8, device=dev)
+        self.minmax = torch.empty((capacity, 2), dtype=torch.int32, device=dev)
+        self.slots: "OrderedDict[tuple, int]" = OrderedDict()
+        self.free = list(range(capacity - 1, -1, -1))
+
+    def take(self, key) -> int:
+        if not self.free:
+            _, slot = self.slots.popitem(last=False)
+            self.free.append(slot)
+        slot = self.free.pop()
+        self.slots[key] = slot
+        return slot
+
+
+class FrameCache:
+    """Gray frames decoded from image files, on the device, keyed by (path, size, mtime); at most ``cache_bytes`` of frames per
+    frame size (and always room for the frames of one launch).  Decoding runs on the package's decode thread pool and goes
+    through pinned staging; the gray kernel writes the frame's min and max alongside (the data range of
+    ``_compute_frame_similarity``)."""
+
+    def __init__(self, cache_bytes: int = CACHE_BYTES):
+        self.cache_bytes = cache_bytes
+        self.slabs = {}
+        self.decodes = 0
+        self.lock = threading.Lock()
+
+    @staticmethod
+    def key(path):
+        st = os.stat(path)
+        return (str(path), st.st_size, st.st_mtime_ns)
+
+    def _slab(self, h: int, w: int, need: int, dev) -> _Slab:
+        slab = self.slabs.get((h, w))
+        if slab is None or slab.capacity < need:
+            grown = _Slab(h, w, max(need, self.cache_bytes // max(h * w, 1), 4), dev)
+            if slab is not None:                       # more frames in one call than the budget holds: keep every slot
+                grown.gray[:slab.capacity].copy_(slab.gray)
+                grown.minmax[:slab.capacity].copy_(slab.minmax)
+                grown.slots = slab.slots
+                grown.free = list(range(grown.capacity - 1, slab.capacity - 1, -1)) + slab.free
+            slab = self.slabs[(h, w)] = grown
+        return slab
+
+    def lookup(self, path):
+        """-> (slab, slot) of a cached frame, or None."""
+        try:
+            k = self.key(path)
+        except OSError:
+            return None
+        for slab in self.slabs.values():
+            slot = slab.slots.get(k)
+            if slot is not None:
+                slab.slots.move_to_end(k)
+                return slab, slot
+        return None
+
+    def load(self, paths: Sequence[str], dev) -> dict:
+        """Decode the paths that are not cached; -> {path: (slab, slot) or the exception its decode raised}.  The frames of one
+        call are never evicted by that call."""
+        from . import preprocess as pp
+        out, todo = {}, []
+        for p in dict.fromkeys(paths):
+            hit = self.lookup(p)
+            if hit is None:
+                todo.append(p)
+            else:
+                out[p] = hit
+        lib = _lib.load()
+
+        def open_one(path):
+            try:
+                k = self.key(path)
+                with open(path, "rb") as fh:
+                    return k, pp._open_rgb(fh)
+            except Exception as exc:                   # noqa: BLE001 - raised later, when the walk consults this frame
+                return None, OSError(f"cannot read image file {path!r}: {exc}")
+
+        workers = pp.decode_workers()
+        for c0 in range(0, len(todo), UPLOAD_FRAMES):
+            chunk = todo[c0:c0 + UPLOAD_FRAMES]
+            opened = list(pp._decode_pool(workers).map(open_one, chunk)) if len(chunk) > 1 else [open_one(chunk[0])]
+            self.decodes += len(chunk)
+            groups = {}
+            for p, (k, im) in zip(chunk, opened):
+                if k is None:
+                    out[p] = im
+                else:
+                    groups.setdefault((im.size[1], im.size[0]), []).append((p, k, im))
+            for (h, w), items in groups.items():
+                protect = sum(1 for v in out.values() if isinstance(v, tuple) and v[0].h == h and v[0].w == w)
+                slab = self._slab(h, w, protect + len(items), dev)
+                with _pinned_lock:
+                    stage = _pinned_bytes(len(items) * h * w * 3)[:len(items) * h * w * 3].view(len(items), h, w, 3)
+                    arrs = stage.numpy()
+                    list(pp._decode_pool(workers).map(lambda it: pp._pack_into(it[1][2], arrs[it[0]], lib), enumerate(items)))
+                    up = stage.to(dev, non_blocking=True)
+                    gray = torch.empty((len(items), h, w), dtype=torch.uint8, device=dev)
+                    minmax = torch.empty((len(items), 2), dtype=torch.int32, device=dev)
+                    _gray_into(up, 0, gray, minmax)
+                    slots = [slab.take(k) for _, k, _ in items]
+                    idx = torch.tensor(slots, dtype=torch.int64).to(dev)
+                    slab.gray.index_copy_(0, idx, gray)
+                    slab.minmax.index_copy_(0, idx, minmax)
+                    torch.cuda.current_stream().synchronize()      # the staging buffer is free again
+                for (p, _, _), slot in zip(items, slots):
+                    out[p] = (slab, slot)
+        return out
+
+
+_default_cache = None
+
+
+def default_cache() -> FrameCache:
+    global _default_cache
+    if _default_cache is None:
+        _default_cache = FrameCache()
+    return _default_cache
+
+
+_SHAPE_MSG = "Input images must have the same dimensions."
+_EXTENT_MSG = "win_size exceeds image extent."
+
+
+class PathScorer:
+    """SSIM of (later, earlier) image-file pairs as ``_compute_frame_similarity`` computes it (R from the first frame), with the
+    errors of a pair raised only when its score is asked for.  ``pairs_scored`` counts the pairs sent to the GPU."""
+
+    def __init__(self, cache: Optional[FrameCache] = None):
+        self.cache = cache if cache is not None else default_cache()
+        self.pairs_scored = 0
+        self.dev = _lib.require_gpu()
+
+    def _problem(self, loaded: dict, p1: str, p2: str) -> Optional[Exception]:
+        for p in (p1, p2):
+            if isinstance(loaded[p], Exception):
+                return loaded[p]
+        (s1, _), (s2, _) = loaded[p1], loaded[p2]
+        if (s1.h, s1.w) != (s2.h, s2.w):
+            return ValueError(f"{_SHAPE_MSG} {p1!r} is {s1.h}x{s1.w}, {p2!r} is {s2.h}x{s2.w}")
+        if s1.h < WIN or s1.w < WIN:
+            return ValueError(f"{_EXTENT_MSG} {p1!r} and {p2!r} are {s1.h}x{s1.w}; the window is {WIN}x{WIN}")
+        return None
+
+    def score(self, pairs: Sequence[Tuple[str, str]]) -> Iterable[float]:
+        """Yield the scores of the pairs in order; raise a pair's error when its turn comes.  Every pair before the first
+        problem is scored in one launch per frame size (one in practice)."""
+        with self.cache.lock:
+            loaded = self.cache.load([p for pair in pairs for p in pair], self.dev)
+            good, err = [], None
+            for p1, p2 in pairs:
+                err = self._problem(loaded, p1, p2)
+                if err is not None:
+                    break
+                good.append((p1, p2))
+            scores = np.empty(0)
+            if good:
+                first = loaded[good[0][0]][0]
+                slab = self.cache.slabs[(first.h, first.w)]    # the current slab of that size (it may have grown meanwhile)
+                idx = np.array([[loaded[p1][1], loaded[p2][1]] for p1, p2 in good], dtype=np.int32)
+                scores = _ssim_launch(slab.gray, idx, -1.0, slab.minmax).cpu().numpy()
+                self.pairs_scored += len(good)
+        yield from (np.float64(s) for s in scores)
+        if err is not None:
+            raise err
+
+
+def _compute_frame_similarity(self, frame1_path: str, frame2_path: str) -> float:
+    """Drop-in for ``HippocampalMemory._compute_frame_similarity`` (assign it on the class; ``self`` is unused): SSIM of the two
+    files' gray frames with data_range = max - min of the first.  Pillow decodes (the reference uses cv2.imread); an unreadable
+    file raises ``OSError`` naming its path, frames of different shapes or under 7x7 raise ``ValueError`` as skimage does."""
+    return next(iter(PathScorer().score([(frame1_path, frame2_path)])))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# HippocampalMemory._segment_sequence
+# ---------------------------------------------------------------------------------------------------------------------------------
+def audio_level(audio_data: np.ndarray, sample_rate: int):
+    """RMS level in dB with the reference's numpy expression (hippocampal_memory.py:993-1000), so levels are bit-identical."""
+    if len(audio_data.shape) > 1:
+        audio_data = audio_data.mean(axis=1)
+    rms = np.sqrt(np.mean(np.square(audio_data)))
+    return 20 * np.log10(rms) if rms > 0 else -100
+
+
+def walk_segments(video_frames, frame_times, audio_data, audio_sample_rate,
+                  score_window: Callable[[List[Tuple[int, int]]], Iterable[float]],
+                  max_segment_duration: float = MAX_SEGMENT_DURATION, min_segment_duration: float = MIN_SEGMENT_DURATION,
+                  frame_similarity_threshold: float = FRAME_SIMILARITY_THRESHOLD,
+                  audio_silence_threshold: float = AUDIO_SILENCE_THRESHOLD) -> List[SequenceSegment]:
+    """The window walk of ``_segment_sequence`` as a host function of the scores.  ``score_window(pairs)`` gets one window's pairs
+    of frame indices (later, earlier) -- adjacent entries of the window's frame list, scanned from the end -- and yields their
+    similarities in that order; the walk stops reading at the first score below the threshold (NaN never breaks).
+
+    Behaviour of the reference kept: the walk starts at 0.0 whatever frame_times[0] is; a frame is in a window when
+    start <= t <= end; the audio scan (500 ms windows, from the end backwards, excluding offset 0) runs after the video scan and
+    overrides it; then the minimum-duration clamp; segment contents take inclusive time bounds and audio samples
+    int(start * sr):int(end * sr).  One deviation: where the reference would loop forever (a start it has already been at, which
+    only happens with min_segment_duration <= 0), this raises ValueError."""
+    segments: List[SequenceSegment] = []
+    if video_frames is None and audio_data is None:
+        return segments
+    has_video = bool(video_frames and frame_times)
+    has_audio = audio_data is not None and bool(audio_sample_rate)
+    if has_video:
+        total_duration = frame_times[-1] - frame_times[0]
+    elif has_audio:
+        total_duration = len(audio_data) / audio_sample_rate
+    else:
+        return segments
+
+    current_start = 0.0
+    seen = set()
+    while current_start < total_duration:
+        if current_start in seen:
+            raise ValueError(f"segmentation makes no progress at t = {current_start} (min_segment_duration = "
+                             f"{min_segment_duration}); the reference would loop forever here")
+        seen.add(current_start)
+        current_end = min(current_start + max_segment_duration, total_duration)
+        optimal_end = current_end
+
+        if has_video:
+            inside = [i for i, t in enumerate(frame_times) if current_start <= t <= current_end]
+            if len(inside) > 1:
+                pairs = [(inside[k], inside[k - 1]) for k in range(len(inside) - 1, 0, -1)]
+                for (later, _), similarity in zip(pairs, score_window(pairs)):
+                    if similarity < frame_similarity_threshold:
+                        optimal_end = frame_times[later]
+                        break
+
+        if has_audio:
+            start_sample = int(current_start * audio_sample_rate)
+            end_sample = int(current_end * audio_sample_rate)
+            window = int(0.5 * audio_sample_rate)
+            for off in range(end_sample - start_sample - window, 0, -window):
+                lo = start_sample + off
+                if audio_level(audio_data[lo:lo + window], audio_sample_rate) < audio_silence_threshold:
+                    optimal_end = lo / audio_sample_rate
+                    break
+
+        if optimal_end - current_start < min_segment_duration:
+            optimal_end = min(current_start + min_segment_duration, total_duration)
+
+        seg = SequenceSegment(start_time=current_start, end_time=optimal_end)
+        if has_video:
+            seg.frames = [f for f, t in zip(video_frames, frame_times) if current_start <= t <= optimal_end]
+            seg.frame_times = [t for t in frame_times if current_start <= t <= optimal_end]
+        if has_audio:
+            seg.audio_data = audio_data[int(current_start * audio_sample_rate):int(optimal_end * audio_sample_rate)]
+        segments.append(seg)
+        current_start = optimal_end
+    return segments
+
+
+def _window_scorer(video_frames, scorer: PathScorer):
+    """score_window for walk_segments on the GPU: the window's last pair alone first (at threshold 0.95 it usually breaks), then,
+    if it did not, the rest of the window in one launch."""
+    def score_window(pairs):
+        paths = [(video_frames[a], video_frames[b]) for a, b in pairs]
+        yield from scorer.score(paths[:1])
+        if len(paths) > 1:
+            yield from scorer.score(paths[1:])
+    return score_window
+
+
+def segment_sequence(video_frames: Optional[List[str]] = None, frame_times: Optional[List[float]] = None,
+                     audio_data: Optional[np.ndarray] = None, audio_sample_rate: Optional[int] = None, *,
+                     max_segment_duration: float = MAX_SEGMENT_DURATION, min_segment_duration: float = MIN_SEGMENT_DURATION,
+                     frame_similarity_threshold: float = FRAME_SIMILARITY_THRESHOLD,
+                     audio_silence_threshold: float = AUDIO_SILENCE_THRESHOLD,
+                     scorer: Optional[PathScorer] = None) -> List[SequenceSegment]:
+    """``_segment_sequence`` as a function; the four parameters default to the reference's __init__ defaults.  Frame similarities
+    come from the GPU (``PathScorer``); an audio-only call needs no GPU (the audio scan is host numpy, as in the reference)."""
+    if video_frames and frame_times and scorer is None:
+        scorer = PathScorer()
+    score_window = _window_scorer(video_frames, scorer) if scorer is not None else None
+    return walk_segments(video_frames, frame_times, audio_data, audio_sample_rate, score_window,
+                         max_segment_duration, min_segment_duration, frame_similarity_threshold, audio_silence_threshold)
+
+
+def _segment_sequence(self, video_frames: Optional[List[str]] = None, frame_times: Optional[List[float]] = None,
+                      audio_data: Optional[np.ndarray] = None, audio_sample_rate: Optional[int] = None) -> List[SequenceSegment]:
+    """Drop-in for ``HippocampalMemory._segment_sequence`` (assign it on the class): reads self.max_segment_duration,
+    self.min_segment_duration, self.frame_similarity_threshold and self.audio_silence_threshold."""
+    return segment_sequence(video_frames, frame_times, audio_data, audio_sample_rate,
+                            max_segment_duration=self.max_segment_duration, min_segment_duration=self.min_segment_duration,
+                            frame_similarity_threshold=self.frame_similarity_threshold,
+                            audio_silence_threshold=self.audio_silence_threshold)

@@ -273,6 +273,36 @@ int    hmm_audio_fbank(const float* clips_dev, int n_clips, int clip_len, int64_
                        void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Frame SSIM (structural similarity) for sequence segmentation and frame differences.  Replaces skimage 0.18.3
+ * structural_similarity as hippomm/core/hippocampal_memory.py:980-991 (_compute_frame_similarity, consulted by
+ * _segment_sequence :1002-1114) and hippomm/core/batch_process.py:32-69 (compute_frame_difference) call it on gray frames.
+ *
+ * hmm_gray_u8: frames_dev (n, H, W, 3) u8 interleaved -> gray_out_dev (n, H, W) u8 by OpenCV's 8-bit BGR2GRAY rule,
+ *   g = (1868 B + 9617 G + 4899 R + 8192) >> 14, and minmax_out_dev int32[n][2] = (min, max) of each gray frame.
+ *   channel_order: HMM_GRAY_FROM_RGB / _BGR give the byte order of the input; HMM_GRAY_FROM_GRAY takes frames_dev as
+ *   (n, H, W) gray frames and only writes minmax_out_dev (gray_out_dev may be null).  n <= 65535.
+ *
+ * hmm_ssim_pairs: scores_out_dev[p] = SSIM(gray[a_p], gray[b_p]) in fp64 for pairs_host[p] = (a_p, b_p), a HOST int32 array
+ *   of n_pairs pairs (validated, then passed to the kernels by value: nothing is copied, the call stays capturable).  a plays
+ *   skimage's im1.  gray_dev (n_frames, H, W) u8.  data_range >= 0: R = data_range (data_range=1.0 on frames / 255 is R = 255
+ *   here); data_range < 0: R = max(a) - min(a) from minmax_dev (hmm_gray_u8's output for the same frames).
+ *   Arithmetic: the five 7x7 box sums of the (H-6) x (W-6) window positions inside the image, exact in int32; then in fp64
+ *   ux = sum_x / 49 (and likewise uy, uxx, uyy, uxy), v* = 49/48 (u** - u* u*), C1 = (0.01 R)^2, C2 = (0.03 R)^2,
+ *   S = ((2 ux uy + C1)(2 vxy + C2)) / ((ux^2 + uy^2 + C1)(vx + vy + C2)), score = fixed-order fp64 sum of S / count.  No
+ *   float atomics: a rerun gives the same bits, and a pair's score does not depend on the other pairs of the call.  R = 0 and a
+ *   flat frame give NaN, as in skimage.  H < 7 or W < 7 is refused (skimage: "win_size exceeds image extent").
+ * ---------------------------------------------------------------------------------------- */
+#define HMM_GRAY_FROM_RGB   0
+#define HMM_GRAY_FROM_BGR   1
+#define HMM_GRAY_FROM_GRAY  2
+int    hmm_gray_u8(const uint8_t* frames_dev, int n, int H, int W, int channel_order, uint8_t* gray_out_dev,
+                   int32_t* minmax_out_dev, hmm_stream_t stream);
+size_t hmm_ssim_pairs_workspace_bytes(int H, int W, int n_pairs);
+int    hmm_ssim_pairs(const uint8_t* gray_dev, int n_frames, int H, int W, const int32_t* pairs_host, int n_pairs,
+                      double data_range, const int32_t* minmax_dev, double* scores_out_dev,
+                      void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Building blocks of the encoder, exported so that each kernel is parity-tested on its own
  * against a torch fp32 reference of the same op (tests/test_gpu_ops.py) and timed on its own
  * (bench.py roofline).  bf16 tensors are raw uint16 bit patterns in device memory.
