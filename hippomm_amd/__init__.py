@@ -13,5 +13,11 @@ and the two SSIM call sites of the formation path (frame SSIM in hippomm_amd/csr
     hippomm_amd.segmentation._compute_frame_similarity  <- hippomm/core/hippocampal_memory.py:980-991
     hippomm_amd.segmentation._segment_sequence          <- hippomm/core/hippocampal_memory.py:1002-1114
     hippomm_amd.sharding                             one-process-per-GPU sharding (RCCL all-gather)
+
+and a baseline JPEG decoder with the pixel work on the GPU, bit-exact with Pillow (hippomm_amd/csrc/jpeg.hip):
+
+    hippomm_amd.decode_jpeg                          <- Image.open(path).convert("RGB") of the reference's frame reads
 """
 __version__ = "0.1.0"
+
+from .jpeg import decode_jpeg  # noqa: E402,F401

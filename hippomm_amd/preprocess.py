@@ -15,7 +15,7 @@ from typing import List, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, jpeg
 
 OUT = 224
 PRECISION_BITS = 32 - 8 - 2
@@ -306,6 +306,11 @@ def _decode_file(path: str, w: int, h: int, dst: np.ndarray, lib, window=None):
     """One image file -> dst (its `window` (x0, y0, w, h) when given) when it is w x h (returns None), else -> its own (H,W,3) array."""
     with open(path, "rb") as fh:
         data = fh.read()
+    return _decode_bytes(data, w, h, dst, lib, window)
+
+
+def _decode_bytes(data: bytes, w: int, h: int, dst: np.ndarray, lib, window=None):
+    """_decode_file on the file's bytes."""
     if _jpeg_geometry(data) == (w, h) and _decode_jpeg_direct(data, w, h, dst, lib, window):
         return None
     im = _open_rgb_bytes(data)
@@ -383,6 +388,30 @@ def _get_staging(h: int, w: int, need: int, dev) -> _Staging:
     return st
 
 
+class _CoefStaging:
+    """Pinned ring of `capacity` coefficient slots (hmm_jpeg_decode_coefs) for one frame geometry and window."""
+
+    def __init__(self, slot_bytes: int, capacity: int):
+        self.capacity = capacity
+        self.pinned = torch.empty(capacity, slot_bytes, dtype=torch.uint8, pin_memory=True)
+        self.host = self.pinned.numpy()
+        self.last_upload = None
+
+
+_coef_staging = {}
+
+
+def _get_coef_staging(key, slot_bytes: int, capacity: int) -> _CoefStaging:
+    st = _coef_staging.get(key)
+    if st is None or st.capacity < capacity:
+        for k in list(_coef_staging):
+            if _coef_staging[k].last_upload is not None:
+                _coef_staging[k].last_upload.synchronize()
+            del _coef_staging[k]                                             # one ring: the last geometry's
+        st = _coef_staging[key] = _CoefStaging(slot_bytes, capacity)
+    return st
+
+
 def _side_stream(dev):
     key = str(dev)
     if key not in _side_streams:
@@ -427,6 +456,8 @@ def vision_pipeline(image_paths: Sequence[str], device=None, consume=None, worke
     with _pipeline_lock, torch.cuda.device(dev):
         with open(paths[0], "rb") as fh:
             W, H = Image.open(fh).size                                    # header only
+            fh.seek(0)
+            head = fh.read()
         window = needed_window(H, W)                                      # only these pixels are kept, uploaded and read
         WW, WH = window[2], window[3]
         cap = min(n, max(STAGING_BYTES // (WH * WW * 3), workers + 2 * max(first_chunk, upload_min)))
@@ -434,6 +465,15 @@ def vision_pipeline(image_paths: Sequence[str], device=None, consume=None, worke
         cap = st.capacity
         if st.last_upload is not None:
             st.last_upload.synchronize()                                  # the previous call's uploads have left the ring
+        # the JPEG device route (hippomm_amd/jpeg.py): the first file decides; a file it does not take uses the route above
+        geom = jpeg.parse(head)
+        coef = None
+        if geom is not None and geom[:2] == (W, H) and jpeg.takes(geom) and jpeg.route_ok(head, dev):
+            coef = _get_coef_staging((geom[:5], window, str(dev)), jpeg.slot_bytes(geom, window), cap)
+            if coef.last_upload is not None:
+                coef.last_upload.synchronize()
+        del head
+        on_dev = [False] * n                                              # frame -> its coefficients are in the coefficient ring
         side, cur = _side_stream(dev), torch.cuda.current_stream(dev)
         side.wait_stream(cur)                                             # x (and whatever memory it reuses) is ours from here
 
@@ -456,7 +496,15 @@ def vision_pipeline(image_paths: Sequence[str], device=None, consume=None, worke
                         ev.synchronize()
                 if state["abort"]:
                     return
-                arr = _decode_file(paths[i], W, H, st.host[i % cap], lib, window)
+                if coef is not None:
+                    with open(paths[i], "rb") as fh:
+                        data = fh.read()
+                    if jpeg.decode_coefs(data, geom, window, coef.host[i % cap]) == jpeg.DECODED:
+                        arr, on_dev[i] = None, True
+                    else:
+                        arr = _decode_bytes(data, W, H, st.host[i % cap], lib, window)
+                else:
+                    arr = _decode_file(paths[i], W, H, st.host[i % cap], lib, window)
                 with cond:
                     if arr is not None:
                         odd[i] = arr
@@ -484,15 +532,19 @@ def vision_pipeline(image_paths: Sequence[str], device=None, consume=None, worke
                         ev, b = True, a + 1
                     else:
                         b = a + 1
-                        while b < hi and b not in odd and b % cap != 0:
+                        while b < hi and b not in odd and b % cap != 0 and on_dev[b] == on_dev[a]:
                             b += 1
                         d = torch.empty(b - a, WH, WW, 3, dtype=torch.uint8, device=dev)
-                        d.copy_(st.pinned[a % cap:a % cap + (b - a)], non_blocking=True)
+                        ring = coef if on_dev[a] else st
+                        src = torch.empty((b - a,) + tuple(ring.pinned.shape[1:]), dtype=torch.uint8, device=dev) if on_dev[a] else d
+                        src.copy_(ring.pinned[a % cap:a % cap + (b - a)], non_blocking=True)
                         ev = torch.cuda.Event()
                         ev.record(side)
-                        st.last_upload = ev
+                        ring.last_upload = ev
+                        if on_dev[a]:
+                            jpeg.reconstruct(src, geom, window, d)                # coefficients -> the window's RGB
                         _preprocess_into(d, x[a:b], (H, W))
-                        del d
+                        del d, src
                     with cond:
                         for i in range(a, b):
                             slot_free[i] = ev
@@ -587,6 +639,7 @@ def vision_pipeline(image_paths: Sequence[str], device=None, consume=None, worke
                         f.result()                                        # work() never raises: errors are in state["error"]
         if stats is not None:
             stats.update(chunks=chunks, workers=workers, ring_frames=cap, frame_hw=(H, W), window=window, odd_sized=state["odd"],
+                         device_decoded=sum(on_dev),
                          uploads=len(batches) if consume is None else None)
             if trace is not None and trace:                               # diagnostic: synchronises
                 torch.cuda.synchronize(dev)

@@ -29,7 +29,7 @@ from typing import Callable, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, jpeg
 
 WIN = 7                                   # skimage's default win_size
 CACHE_BYTES = 512 << 20                   # device cache of gray frames (1080p: 2 MiB per frame)
@@ -227,6 +227,7 @@ class FrameCache:
         self.cache_bytes = cache_bytes
         self.slabs = {}
         self.decodes = 0
+        self.device_decodes = 0                        # of them, frames the JPEG device route decoded
         self.lock = threading.Lock()
 
     @staticmethod
@@ -272,43 +273,77 @@ class FrameCache:
                 out[p] = hit
         lib = _lib.load()
 
-        def open_one(path):
+        def read_one(path):
             try:
                 k = self.key(path)
                 with open(path, "rb") as fh:
-                    return k, pp._open_rgb(fh)
+                    return k, fh.read()
             except Exception as exc:                   # noqa: BLE001 - raised later, when the walk consults this frame
                 return None, OSError(f"cannot read image file {path!r}: {exc}")
+
+        def open_one(item):
+            path, data = item
+            try:
+                return pp._open_rgb_bytes(data)
+            except Exception as exc:                   # noqa: BLE001 - raised later, when the walk consults this frame
+                return OSError(f"cannot read image file {path!r}: {exc}")
+
+        def store(h, w, items, up):
+            """items [(path, key)] of frames (n, h, w, 3) u8 `up` on the device -> gray + min / max into the slab."""
+            protect = sum(1 for v in out.values() if isinstance(v, tuple) and v[0].h == h and v[0].w == w)
+            slab = self._slab(h, w, protect + len(items), dev)
+            gray = torch.empty((len(items), h, w), dtype=torch.uint8, device=dev)
+            minmax = torch.empty((len(items), 2), dtype=torch.int32, device=dev)
+            _gray_into(up, 0, gray, minmax)
+            slots = [slab.take(k) for _, k in items]
+            idx = torch.tensor(slots, dtype=torch.int64).to(dev)
+            slab.gray.index_copy_(0, idx, gray)
+            slab.minmax.index_copy_(0, idx, minmax)
+            for (p, _), slot in zip(items, slots):
+                out[p] = (slab, slot)
 
         workers = pp.decode_workers()
         for c0 in range(0, len(todo), UPLOAD_FRAMES):
             chunk = todo[c0:c0 + UPLOAD_FRAMES]
-            opened = list(pp._decode_pool(workers).map(open_one, chunk)) if len(chunk) > 1 else [open_one(chunk[0])]
+            read = list(pp._decode_pool(workers).map(read_one, chunk)) if len(chunk) > 1 else [read_one(chunk[0])]
             self.decodes += len(chunk)
-            groups = {}
-            for p, (k, im) in zip(chunk, opened):
+            on_host = []
+            # the JPEG device route (hippomm_amd/jpeg.py) for the files it takes; Pillow for the rest, as before
+            jpegs = [(p, k, data) for p, (k, data) in zip(chunk, read) if k is not None and jpeg.takes(jpeg.parse(data))]
+            if jpegs and jpeg.route_ok(jpegs[0][2], dev):
+                frames, errors, n_dev = jpeg._decode_many([d for _, _, d in jpegs], dev)
+                self.device_decodes += n_dev
+                sizes = {}
+                for (p, k, _), frame, exc in zip(jpegs, frames, errors):
+                    if exc is not None:
+                        out[p] = OSError(f"cannot read image file {p!r}: {exc}")
+                    else:
+                        sizes.setdefault((frame.shape[0], frame.shape[1]), []).append((p, k, frame))
+                for (h, w), items in sizes.items():
+                    store(h, w, [(p, k) for p, k, _ in items], torch.stack([f for _, _, f in items]))
+                taken = {p for p, _, _ in jpegs}
+            else:
+                taken = set()
+            for p, (k, data) in zip(chunk, read):
                 if k is None:
+                    out[p] = data
+                elif p not in taken:
+                    on_host.append((p, k, data))
+            opened = list(pp._decode_pool(workers).map(open_one, [(p, d) for p, _, d in on_host])) if len(on_host) > 1 else \
+                [open_one((p, d)) for p, _, d in on_host]
+            groups = {}
+            for (p, k, _), im in zip(on_host, opened):
+                if isinstance(im, Exception):
                     out[p] = im
                 else:
                     groups.setdefault((im.size[1], im.size[0]), []).append((p, k, im))
             for (h, w), items in groups.items():
-                protect = sum(1 for v in out.values() if isinstance(v, tuple) and v[0].h == h and v[0].w == w)
-                slab = self._slab(h, w, protect + len(items), dev)
                 with _pinned_lock:
                     stage = _pinned_bytes(len(items) * h * w * 3)[:len(items) * h * w * 3].view(len(items), h, w, 3)
                     arrs = stage.numpy()
                     list(pp._decode_pool(workers).map(lambda it: pp._pack_into(it[1][2], arrs[it[0]], lib), enumerate(items)))
-                    up = stage.to(dev, non_blocking=True)
-                    gray = torch.empty((len(items), h, w), dtype=torch.uint8, device=dev)
-                    minmax = torch.empty((len(items), 2), dtype=torch.int32, device=dev)
-                    _gray_into(up, 0, gray, minmax)
-                    slots = [slab.take(k) for _, k, _ in items]
-                    idx = torch.tensor(slots, dtype=torch.int64).to(dev)
-                    slab.gray.index_copy_(0, idx, gray)
-                    slab.minmax.index_copy_(0, idx, minmax)
+                    store(h, w, [(p, k) for p, k, _ in items], stage.to(dev, non_blocking=True))
                     torch.cuda.current_stream().synchronize()      # the staging buffer is free again
-                for (p, _, _), slot in zip(items, slots):
-                    out[p] = (slab, slot)
         return out
 
 

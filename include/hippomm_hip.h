@@ -303,6 +303,40 @@ int    hmm_ssim_pairs(const uint8_t* gray_dev, int n_frames, int H, int W, const
                       void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Baseline JPEG decoding, split between host and GPU.  Replaces the libjpeg decode inside Image.open(path).convert("RGB") of
+ * imagebind.data.load_and_transform_vision_data [upstream, recalled] (hippomm/models/foundation_models.py:87-90) and of the
+ * frame reads of _segment_sequence (hippomm/core/hippocampal_memory.py:1002-1114), with Pillow's pixels to the bit: libjpeg-turbo's
+ * defaults (islow IDCT, fancy upsampling, its fixed-point YCbCr -> RGB).
+ *
+ * Supported: 8-bit Huffman sequential (SOF0 / SOF1) files with one interleaved scan of one component (grey) or three (YCbCr;
+ * not Adobe, not component ids R, G, B) with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1; restart intervals.  Everything else,
+ * and every anomaly in the data, is HMM_JPEG_UNSUPPORTED: the caller decodes such a file with Pillow.
+ *
+ * geometry: int32[HMM_JPEG_GEOMETRY_INTS] = (width, height, components, luma h sampling, luma v sampling, restart interval);
+ *   sampling is 1 x 1 for grey.  The first five define the coefficient layout; frames that share them share slots.
+ * hmm_jpeg_parse: markers only -> HMM_JPEG_DECODED (geometry filled) or HMM_JPEG_UNSUPPORTED.  Host, no GPU call.
+ * hmm_jpeg_slot_bytes: bytes of one coefficient slot for frames of `geometry` cut to the window [x0, x0 + w) x [y0, y0 + h)
+ *   (the blocks the window and the upsampling halo touch, plus the quantisation tables; a multiple of 256); 0 for a bad window.
+ * hmm_jpeg_decode_coefs: the entropy pass of one file into a host slot -> HMM_JPEG_DECODED; HMM_JPEG_OTHER_GEOMETRY (a supported
+ *   file whose first five geometry values differ); HMM_JPEG_UNSUPPORTED; HMM_E_* for bad arguments.  Host, no GPU call, no
+ *   interpreter state: safe on any number of threads.
+ * hmm_jpeg_reconstruct: n slots at slots_dev + i * slot_stride (device) -> rgb_out_dev (n, h, w, 3) u8, the window of each frame;
+ *   grey frames come out with R = G = B.  Two kernels (dequantise + IDCT into u8 planes in the workspace; upsample + colour) on
+ *   `stream`; no synchronisation, no allocation.
+ * ---------------------------------------------------------------------------------------- */
+#define HMM_JPEG_GEOMETRY_INTS   6
+#define HMM_JPEG_DECODED         0
+#define HMM_JPEG_UNSUPPORTED     1
+#define HMM_JPEG_OTHER_GEOMETRY  2
+int     hmm_jpeg_parse(const uint8_t* data, size_t n, int32_t* geometry);
+int64_t hmm_jpeg_slot_bytes(const int32_t* geometry, int x0, int y0, int w, int h);
+int     hmm_jpeg_decode_coefs(const uint8_t* data, size_t n, const int32_t* geometry, int x0, int y0, int w, int h, void* slot,
+                              size_t slot_bytes);
+size_t  hmm_jpeg_workspace_bytes(const int32_t* geometry, int n, int x0, int y0, int w, int h);
+int     hmm_jpeg_reconstruct(const void* slots_dev, int n, size_t slot_stride, const int32_t* geometry, int x0, int y0, int w, int h,
+                             uint8_t* rgb_out_dev, void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Building blocks of the encoder, exported so that each kernel is parity-tested on its own
  * against a torch fp32 reference of the same op (tests/test_gpu_ops.py) and timed on its own
  * (bench.py roofline).  bf16 tensors are raw uint16 bit patterns in device memory.

@@ -1,0 +1,136 @@
+"""GPU: the JPEG device route inside the paths that start from files -- preprocess.vision_pipeline (extract_features) and
+segmentation.FrameCache (segment_sequence) -- gives the host route's bits, with the route taken; damaged files the host pass
+still accepts reach the real kernels and equal Pillow; a self-check mismatch turns the route off."""
+import logging
+
+import numpy as np
+import pytest
+import torch
+from PIL import Image
+
+from test_cpu_jpeg import encode, frame, pillow
+
+pytestmark = pytest.mark.gpu
+
+
+def _scene_frames(tmp_path, n, size=(320, 240), seed=0, cut_every=6):
+    """n frames of scenes with sensor noise, a cut every `cut_every` frames, saved with Pillow at quality 90 (4:2:0)."""
+    rng = np.random.default_rng(seed)
+    w, h = size
+    paths = []
+    for i in range(n):
+        base = np.random.default_rng(100 + i // cut_every).uniform(0, 255, (6, 8, 3)).astype(np.uint8)
+        scene = np.asarray(Image.fromarray(base).resize((w, h), Image.BICUBIC)).astype(np.float32)
+        img = np.clip(scene + rng.normal(0, 4, (h, w, 3)), 0, 255).astype(np.uint8)
+        p = tmp_path / f"video_00_{i:05d}.jpg"
+        Image.fromarray(img).save(p, quality=90)
+        paths.append(str(p))
+    return paths
+
+
+def test_vision_pipeline_from_files_equals_host_chain_bitwise(tmp_path):
+    """40 paths: supported frames of the call's size, frames of another size (the odd route), a progressive and a grey file of
+    the call's size (the host route inside the ring).  Preprocessed tensors and embeddings equal the host chain's bits."""
+    from host_vision_pipeline import load_and_transform_vision_data
+    from oracle import imagebind_oracle as ib
+    from hippomm_amd import preprocess
+    from hippomm_amd.encoder import ImageBind
+    paths = _scene_frames(tmp_path, 40)
+    for i in (5, 17, 29):                                               # another size
+        Image.open(paths[i]).resize((288, 360)).save(paths[i], quality=88)
+    Image.open(paths[11]).save(paths[11], quality=90, progressive=True)
+    Image.open(paths[23]).convert("L").save(paths[23], quality=90)
+    Image.open(paths[31]).save(paths[31], quality=75, subsampling=0)      # same size, another sampling
+    want = load_and_transform_vision_data(paths, "cpu")
+    stats = {}
+    got = preprocess.vision_pipeline(paths, "cuda", stats=stats, workers=4, upload_min=3)
+    torch.cuda.synchronize()
+    assert torch.equal(got.cpu(), want)
+    assert stats["device_decoded"] == 40 - 6 and stats["odd_sized"] == 3
+
+    vspec = ib.reduced(ib.VISION_HUGE, 2)
+    model = ImageBind(state_dict=ib.synthetic_state(vspec, seed=77, init="rich"), towers=("vision",), depth={"vision": 2})
+    fused = model.extract_features({"vision": paths}, ["vision"])["vision"]
+    direct = model.forward({"vision": want.cuda()})["vision"]
+    assert torch.equal(fused, direct)
+
+
+def test_segment_sequence_on_jpeg_frames_equals_the_oracle(tmp_path):
+    """segment_sequence through the device route: the segments the window walk makes from the SSIM numpy oracle on
+    Pillow-decoded gray frames."""
+    import ssim_oracle
+    from hippomm_amd.segmentation import default_cache, segment_sequence, walk_segments
+    paths = _scene_frames(tmp_path, 48, size=(640, 360), seed=3, cut_every=7)
+    times = [float(i) for i in range(48)]
+    gray = [ssim_oracle.gray_from_bgr(pillow(open(p, "rb").read())[..., ::-1]) for p in paths]
+
+    def oracle_window(pairs):
+        for a, b in pairs:
+            yield ssim_oracle.ssim(gray[a], gray[b])
+
+    kw = dict(max_segment_duration=10.0, min_segment_duration=2.0, frame_similarity_threshold=0.7)
+    want = walk_segments(paths, times, None, None, oracle_window, **kw)
+    before = default_cache().device_decodes
+    got = segment_sequence(paths, times, None, None, **kw)
+    assert default_cache().device_decodes > before
+    assert [(s.start_time, s.end_time, s.frames) for s in got] == [(s.start_time, s.end_time, s.frames) for s in want]
+    assert len(want) > 4
+
+
+def test_damaged_files_the_host_pass_takes_equal_pillow_on_the_gpu():
+    """The seeded damage sweep of the CPU test, through decode_jpeg: the accepted cases include IDCT outputs far outside
+    [-128, 127], where the kernel's range limit must saturate as Pillow's libjpeg-turbo does."""
+    from hippomm_amd import decode_jpeg, jpeg
+    rng = np.random.default_rng(1234)
+    sources = [encode(frame(130, 90, seed=s), quality=q, subsampling=sub) for s, q, sub in ((1, 90, 2), (2, 30, 0), (4, 95, 1))]
+    taken = []
+    for data in sources:
+        g = jpeg.parse(data)
+        slot = np.zeros(jpeg.slot_bytes(g, (0, 0, g[0], g[1])), dtype=np.uint8)
+        for _ in range(200):
+            b = bytearray(data)
+            for pos in rng.integers(0, len(b), int(rng.integers(1, 4))):
+                b[pos] = int(rng.integers(0, 256))
+            case = bytes(b)
+            if jpeg.decode_coefs(case, g, (0, 0, g[0], g[1]), slot) == jpeg.DECODED:
+                taken.append(case)
+    assert len(taken) > 20
+    stats = {}
+    got = decode_jpeg(taken, device="cuda", stats=stats)
+    assert stats["device"] == len(taken)
+    for k, case in enumerate(taken):
+        np.testing.assert_array_equal(got[k].cpu().numpy(), pillow(case), err_msg=f"case {k}")
+
+
+def test_self_check_mismatch_turns_the_route_off(monkeypatch, caplog):
+    from hippomm_amd import decode_jpeg, jpeg
+    real = jpeg._pillow_rgb
+    calls = {"n": 0}
+
+    def disagree_once(source):
+        calls["n"] += 1
+        arr = real(source)
+        return arr ^ 1 if calls["n"] == 1 else arr
+
+    monkeypatch.setitem(jpeg._check, "ok", None)
+    monkeypatch.setattr(jpeg, "_pillow_rgb", disagree_once)
+    sources = [encode(frame(130, 90, seed=s), quality=90, subsampling=2) for s in range(4)]
+    stats = {}
+    with caplog.at_level(logging.WARNING, logger="hippomm_amd.jpeg"):
+        got = decode_jpeg(sources, device="cuda", stats=stats)
+    assert jpeg._check["ok"] is False
+    assert "disagrees" in caplog.text
+    assert stats == {"device": 0, "host": 4}
+    for g, s in zip(got, sources):
+        np.testing.assert_array_equal(g.cpu().numpy(), pillow(s))
+
+
+def test_frames_beyond_the_decompression_bomb_limit_take_pillow(monkeypatch):
+    from hippomm_amd import decode_jpeg
+    data = encode(frame(130, 90, seed=1), quality=90)
+    monkeypatch.setattr(Image, "MAX_IMAGE_PIXELS", 130 * 90 - 1)                # Pillow warns above it
+    stats = {}
+    with pytest.warns(Image.DecompressionBombWarning):
+        got = decode_jpeg([data], device="cuda", stats=stats)
+    assert stats == {"device": 0, "host": 1}
+    np.testing.assert_array_equal(got[0].cpu().numpy(), pillow(data))
