@@ -138,6 +138,8 @@ using namespace hmm;
 
 extern "C" size_t hmm_audio_fbank_workspace_bytes(int n_clips) {
     if (n_clips < 1) return 0;
+    // + 64 floats behind the means, and the 64 between BANKS and MEANS: margin only, no kernel touches them
+    // (tests/test_gpu_memory_contract.py, profiles/memory_contract.json)
     return ((size_t)FbankTables::MEANS + (size_t)n_clips + 64) * sizeof(float);
 }
 

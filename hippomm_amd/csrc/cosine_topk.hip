@@ -637,7 +637,7 @@ static ScanPlan make_plan(int64_t n, int k) {
     p.off_sims = 0;
     p.off_a = sims;
     p.off_b = p.off_a + align_up(a, 256);
-    p.total = p.off_b + align_up(b, 256) + 256;
+    p.total = p.off_b + align_up(b, 256) + 256;  // + 256: margin only -- no kernel touches it (tests/test_gpu_memory_contract.py, profiles/memory_contract.json)
     return p;
 }
 
@@ -830,7 +830,7 @@ extern "C" int hmm_op_scan_topk_only(const float* store_dev, int64_t n_rows, con
 
 extern "C" size_t hmm_cosine_topk_segmented_workspace_bytes(int64_t n_rows, int n_segments, int k) {
     if (n_rows < 0 || n_segments < 1 || k < 1) return 0;
-    return align_up((size_t)(n_rows > 0 ? n_rows : 1) * sizeof(float), 256) + 256;
+    return align_up((size_t)(n_rows > 0 ? n_rows : 1) * sizeof(float), 256) + 256;  // + 256: margin only -- no kernel touches it (tests/test_gpu_memory_contract.py, profiles/memory_contract.json)
 }
 
 extern "C" int hmm_cosine_topk_segmented(const float* store_dev, int64_t n_rows, int dim, const float* query_dev,

@@ -325,7 +325,7 @@ extern "C" size_t hmm_cosine_topk_multi_workspace_bytes(int64_t n_rows, int n_qu
     if (n_rows < 1 || n_queries < 1 || k < 1) return 0;
     const int64_t k_eff = k < n_rows ? k : n_rows;
     if (k_eff > kMMaxK) return hmm_cosine_topk_workspace_bytes(n_rows, k);           // per-query fallback
-    return align_up((size_t)kMQ * multi_grid(n_rows) * (size_t)k_eff * 8, 256) + 256;
+    return align_up((size_t)kMQ * multi_grid(n_rows) * (size_t)k_eff * 8, 256) + 256;  // + 256: margin only -- no kernel touches it (tests/test_gpu_memory_contract.py, profiles/memory_contract.json)
 }
 
 extern "C" int hmm_cosine_topk_multi(const float* store_dev, int64_t n_rows, int dim, const float* queries_dev,

@@ -539,7 +539,7 @@ static PrefilterPlan prefilter_plan(int64_t n, int k) {
     p.blocks = blocks > g_prefilter_blocks ? g_prefilter_blocks : blocks;
     p.off_maxima = p.off_lists + align_up((size_t)kScanBlocks * (size_t)kPrefilterMaxK * 8, 256);
     p.off_flag = p.off_maxima + align_up((size_t)kScanBlocks * 8, 256);          // int flag, then the fallback's unsigned ticket
-    p.total = p.off_flag + 256;
+    p.total = p.off_flag + 256;                                                  // the flag and the ticket use 8 of these 256 bytes; the rest is margin
     return p;
 }
 

@@ -207,7 +207,7 @@ static WsPlan ws_plan(const hmm_encoder* e, int batch, int sk_mode) {
     // split-K partial slabs [splits][R][D] fp32 (few-row forwards only)
     const int max_splits = mode_splits(e, sk_mode) > g_enc_splitk_out ? mode_splits(e, sk_mode) : g_enc_splitk_out;
     p.off_part = cur; cur = align_up(cur + (sk_mode ? (size_t)max_splits * p.R * D * 4 : 0), 256);
-    p.total = cur + 256;
+    p.total = cur + 256;  // + 256: margin only -- no kernel touches it (tests/test_gpu_memory_contract.py, profiles/memory_contract.json)
     return p;
 }
 
@@ -553,7 +553,9 @@ extern "C" int hmm_encoder_forward(hmm_encoder* e, const void* input_dev, int ba
         e->ready = true;
     }
     HMM_REQUIRE((int64_t)batch * e->clips * e->T < (1ll << 31) / 8, HMM_E_INVALID, "encoder_forward: batch too large");
-    const size_t need = workspace_bytes_exact(e, batch);
+    // what the size query answers, not the (sometimes smaller) layout of this very batch: one rule for callers, "at least
+    // hmm_encoder_workspace_bytes(batch)", and a workspace one byte short of it is refused at every batch
+    const size_t need = hmm_encoder_workspace_bytes(e, batch);
     HMM_REQUIRE(workspace_bytes >= need, HMM_E_WORKSPACE, "encoder_forward: workspace %zu < required %zu",
                 workspace_bytes, need);
     hipStream_t st = static_cast<hipStream_t>(stream);

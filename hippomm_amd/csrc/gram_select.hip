@@ -170,7 +170,7 @@ static GramPlan gram_plan(int n) {
     p.n_pad = (n + kGT - 1) / kGT * kGT;
     p.off_fn = 0;
     p.off_adj = align_up((size_t)p.n_pad * HMM_FEATURE_DIM * sizeof(float), 256);
-    p.total = p.off_adj + align_up((size_t)p.n_pad * (p.n_pad / 32) * sizeof(uint32_t), 256) + 256;
+    p.total = p.off_adj + align_up((size_t)p.n_pad * (p.n_pad / 32) * sizeof(uint32_t), 256) + 256;  // + 256: margin only -- no kernel touches it (tests/test_gpu_memory_contract.py, profiles/memory_contract.json)
     return p;
 }
 

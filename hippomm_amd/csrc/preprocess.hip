@@ -80,7 +80,7 @@ using namespace hmm;
 
 extern "C" size_t hmm_preprocess_vision_workspace_bytes(int batch, int rows_needed) {
     if (batch < 1 || rows_needed < 1) return 0;
-    return align_up((size_t)batch * rows_needed * kOut * 3, 256) + 256;
+    return align_up((size_t)batch * rows_needed * kOut * 3, 256) + 256;  // + 256: margin only -- no kernel touches it (tests/test_gpu_memory_contract.py, profiles/memory_contract.json)
 }
 
 extern "C" int hmm_preprocess_vision_u8(const uint8_t* frames_dev, int batch, int in_h, int in_w,

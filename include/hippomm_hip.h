@@ -43,7 +43,12 @@ extern "C" {
 typedef void* hmm_stream_t;   /* hipStream_t */
 
 /* Alignment: stores, queries and workspaces (*_dev) must be 16-byte aligned -- anything hipMalloc or a torch allocation returns is
- * 256-byte aligned; a pointer into the middle of such a buffer must keep the 16 bytes.  Refused with HMM_E_INVALID otherwise. */
+ * 256-byte aligned; a pointer into the middle of such a buffer must keep the 16 bytes.  Refused with HMM_E_INVALID otherwise.
+ * Workspaces: exactly the bytes a *_workspace_bytes query answers suffice (one byte fewer is refused with HMM_E_WORKSPACE before
+ * anything is launched or written); their contents need no initialisation; and one workspace may be reused across calls, shapes
+ * and entry points on one stream -- no call depends on what an earlier one left there.  No call reads or writes a byte outside
+ * the documented extent of its buffers (tests/test_gpu_memory_contract.py).  hmm_encoder_workspace_bytes answers for the
+ * handle's current hmm_encoder_set_streams setting: ask again after changing it. */
 
 int         hmm_abi_version(void);
 const char* hmm_last_error(void);
