@@ -505,13 +505,17 @@ __global__ __launch_bounds__(256) void merge_keys_kernel(const uint64_t* __restr
 // chain of dependent steps whatever the thread count, and eight small workgroups fit a CU where two large ones do (2000 events of
 // 500 rows: one round of workgroups instead of four).  Same result: keys are unique and totally ordered.
 // ------------------------------------------------------------------------------------------------------
+// Batched questions (hmm_cosine_topk_segmented_multi): the grid's y dimension is the query; its similarities start at
+// sims + y * sims_stride and its outputs are slot (y, event) of the query-major (Q, E, k) arrays.  A single question is y = 0.
 template <int CHUNK, int THREADS>
-__global__ __launch_bounds__(THREADS) void segment_topk_kernel(const float* __restrict__ sims,
+__global__ __launch_bounds__(THREADS) void segment_topk_kernel(const float* __restrict__ sims, int64_t sims_stride,
                                                             const int64_t* __restrict__ seg_off, int k,
                                                             int64_t* __restrict__ idx_out, float* __restrict__ sim_out,
                                                             int32_t* __restrict__ n_out) {
     __shared__ uint64_t s[CHUNK];
     const int e = blockIdx.x, tid = threadIdx.x;
+    const int64_t slot = (int64_t)blockIdx.y * gridDim.x + e;
+    sims += (int64_t)blockIdx.y * sims_stride;
     const int64_t lo = seg_off[e], hi = seg_off[e + 1];
     const int64_t n = hi - lo;
     const int k_out = (int)(n < k ? (n > 0 ? n : 0) : k);
@@ -536,12 +540,22 @@ __global__ __launch_bounds__(THREADS) void segment_topk_kernel(const float* __re
         have = total < k ? total : k;
         base += take;
     } while (base < n);
-    if (tid == 0) n_out[e] = k_out;
+    if (tid == 0) n_out[slot] = k_out;
     for (int t = tid; t < k; t += THREADS) {
         const bool ok = t < k_out;
-        idx_out[(int64_t)e * k + t] = ok ? (int64_t)(s[t] & 0xFFFFFFFFull) : -1;
-        sim_out[(int64_t)e * k + t] = ok ? order_bits_inverse((uint32_t)(s[t] >> 32)) : 0.0f;
+        idx_out[slot * k + t] = ok ? (int64_t)(s[t] & 0xFFFFFFFFull) : -1;
+        sim_out[slot * k + t] = ok ? order_bits_inverse((uint32_t)(s[t] >> 32)) : 0.0f;
     }
+}
+
+// The selection launch of the per-event calls: n_queries x n_segments workgroups of the shape that fits the mean event.
+void launch_segment_topk(const float* sims, int64_t sims_stride, int n_queries, int64_t n_rows, const int64_t* seg_off, int n_segments,
+                         int k, int64_t* idx_out, float* sim_out, int32_t* n_out, hipStream_t st) {
+    const dim3 grid(n_segments, n_queries);
+    if (segments_are_small(n_rows, n_segments, k))
+        segment_topk_kernel<kSmallSegChunk, 256><<<grid, 256, 0, st>>>(sims, sims_stride, seg_off, k, idx_out, sim_out, n_out);
+    else
+        segment_topk_kernel<kChunk, 1024><<<grid, 1024, 0, st>>>(sims, sims_stride, seg_off, k, idx_out, sim_out, n_out);
 }
 
 struct ScanPlan {
@@ -561,6 +575,10 @@ __global__ __launch_bounds__(1024) void rank_segment_hits_kernel(const int64_t* 
     __shared__ uint64_t w[kChunk];
     __shared__ int n_cand;
     const int64_t total = (int64_t)n_segments * k;
+    // one workgroup per question (hmm_rank_segment_hits_multi): inputs (Q, E, k) / (Q, E), outputs (Q, keep) / (Q); one question is block 0
+    idx += blockIdx.x * total; sims += blockIdx.x * total; counts += (int64_t)blockIdx.x * n_segments;
+    event_out += (int64_t)blockIdx.x * keep; row_out += (int64_t)blockIdx.x * keep; sim_out += (int64_t)blockIdx.x * keep;
+    n_out += blockIdx.x;
     auto key_at = [&](int64_t pos) -> uint64_t {
         if (pos < total && (int)(pos % k) < counts[pos / k])
             return ((uint64_t)order_bits(sims[pos]) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)pos);
@@ -853,10 +871,7 @@ extern "C" int hmm_cosine_topk_segmented(const float* store_dev, int64_t n_rows,
         launch_scan_sims(store_dev, n_rows, query_dev, sims, st);
         HMM_LAUNCH_CHECK();
     }
-    if (segments_are_small(n_rows, n_segments, k))
-        segment_topk_kernel<kSmallSegChunk, 256><<<n_segments, 256, 0, st>>>(sims, seg_offsets_dev, k, idx_out_dev, sim_out_dev, n_out_dev);
-    else
-        segment_topk_kernel<kChunk, 1024><<<n_segments, 1024, 0, st>>>(sims, seg_offsets_dev, k, idx_out_dev, sim_out_dev, n_out_dev);
+    launch_segment_topk(sims, 0, 1, n_rows, seg_offsets_dev, n_segments, k, idx_out_dev, sim_out_dev, n_out_dev, st);
     HMM_LAUNCH_CHECK();
     return HMM_OK;
 }
@@ -871,6 +886,22 @@ extern "C" int hmm_rank_segment_hits(const int64_t* idx_dev, const float* sims_d
                 n_segments, k, keep);
     rank_segment_hits_kernel<<<1, 1024, 0, static_cast<hipStream_t>(stream)>>>(idx_dev, sims_dev, counts_dev, n_segments, k, keep,
                                                                               event_out_dev, row_out_dev, sim_out_dev, n_out_dev);
+    HMM_LAUNCH_CHECK();
+    return HMM_OK;
+}
+
+extern "C" int hmm_rank_segment_hits_multi(const int64_t* idx_dev, const float* sims_dev, const int32_t* counts_dev, int n_queries,
+                                           int n_segments, int k, int keep, int64_t* event_out_dev, int64_t* row_out_dev,
+                                           float* sim_out_dev, int32_t* n_out_dev, hmm_stream_t stream) {
+    HMM_REQUIRE(idx_dev && sims_dev && counts_dev && event_out_dev && row_out_dev && sim_out_dev && n_out_dev, HMM_E_INVALID,
+                "rank_segment_hits_multi: null pointer");
+    HMM_REQUIRE(n_queries >= 1 && n_segments >= 1 && k >= 1 && keep >= 1 && keep <= 64 &&
+                    (int64_t)n_segments * k < (int64_t)0xFFFFFFFFll, HMM_E_INVALID,
+                "rank_segment_hits_multi: need n_queries >= 1, n_segments >= 1, k >= 1, 1 <= keep <= 64 and fewer than 2^32 hits per "
+                "query (got %d x %d x %d, keep %d)", n_queries, n_segments, k, keep);
+    rank_segment_hits_kernel<<<n_queries, 1024, 0, static_cast<hipStream_t>(stream)>>>(idx_dev, sims_dev, counts_dev, n_segments, k,
+                                                                                      keep, event_out_dev, row_out_dev, sim_out_dev,
+                                                                                      n_out_dev);
     HMM_LAUNCH_CHECK();
     return HMM_OK;
 }

@@ -27,7 +27,7 @@
 // sit in the in-order VMEM queue in front of the slice waits.  Not kept.)  A second kernel (one workgroup per query) finishes
 // exactly as topk_final_kernel does: the global top-k lies in the lists of the k workgroups with the largest maxima.
 // Keys, total order (NaN first, higher row first on ties) and outputs are those of hmm_cosine_topk.
-#include "hmm_common.h"
+#include "cosine_topk_shared.h"
 #include "topk_tournament.h"
 
 namespace hmm {
@@ -92,9 +92,15 @@ __device__ __forceinline__ void multi_barrier() {
     __builtin_amdgcn_sched_barrier(0);
 }
 
+// SIMS_OUT (hmm_cosine_topk_segmented_multi): the same pass, the same similarities bit for bit, but nothing is selected here --
+// the similarity of (query q, row r) goes to sims_out[q * sims_stride + r] (sims_stride = rows rounded up to whole tiles, so a lane
+// stores its four rows with one 16-byte store; the entries of the rows past the end are never read) and a per-event selection
+// follows in its own launch.  No candidate lists, so the waves of a workgroup never meet after the prologue.
+template <bool SIMS_OUT>
 __global__ __launch_bounds__(kMWaves * 64) void scan_multi_kernel(const float* __restrict__ store, int64_t n_rows,
                                                                   const float* __restrict__ queries, int n_q, int k,
-                                                                  uint64_t* __restrict__ out) {
+                                                                  uint64_t* __restrict__ out, float* __restrict__ sims_out,
+                                                                  int64_t sims_stride) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     MultiLds& L = *reinterpret_cast<MultiLds*>(smem_raw);
     const int tid = threadIdx.x, lane = tid & 63;
@@ -202,6 +208,18 @@ __global__ __launch_bounds__(kMWaves * 64) void scan_multi_kernel(const float* _
         ss += __shfl_xor(ss, 32, 64);
         const float norm = sqrtf(ss);                             // row r16 of the tile
         const f32x4 acc = acc0 + acc1;                            // D layout: query r16, rows 4 g + j
+        if constexpr (SIMS_OUT) {
+            if (tile < n_tiles) {
+                f32x4 sim4;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float rn = __shfl(norm, 4 * g + j, 64);
+                    sim4[j] = acc[j] / (rn * my_qlen);
+                }
+                if (r16 < n_q) *reinterpret_cast<f32x4*>(sims_out + r16 * sims_stride + tile * kMTileRows + 4 * g) = sim4;
+            }
+            continue;
+        }
         if (tile < n_tiles) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -260,6 +278,7 @@ __global__ __launch_bounds__(kMWaves * 64) void scan_multi_kernel(const float* _
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // the look-ahead slices past the end
+    if constexpr (SIMS_OUT) return;
     __syncthreads();
     // this workgroup's best k per query (sorted, 0-padded); a workgroup with no tile leaves zeros
     for (int i = tid; i < n_q * k; i += kMWaves * 64) {
@@ -352,16 +371,77 @@ extern "C" int hmm_cosine_topk_multi(const float* store_dev, int64_t n_rows, int
         }
         return HMM_OK;
     }
-    HMM_ENSURE_DYN_LDS(scan_multi_kernel, (int)sizeof(MultiLds));
+    HMM_ENSURE_DYN_LDS(scan_multi_kernel<false>, (int)sizeof(MultiLds));
     const int grid = multi_grid(n_rows);
     uint64_t* cand = static_cast<uint64_t*>(workspace_dev);
     for (int q0 = 0; q0 < n_queries; q0 += kMQ) {                  // 16 queries per pass over the store
         const int nq = n_queries - q0 < kMQ ? n_queries - q0 : kMQ;
-        scan_multi_kernel<<<grid, kMWaves * 64, sizeof(MultiLds), st>>>(store_dev, n_rows, queries_dev + (size_t)q0 * dim,
-                                                                       nq, k_eff, cand);
+        scan_multi_kernel<false><<<grid, kMWaves * 64, sizeof(MultiLds), st>>>(store_dev, n_rows, queries_dev + (size_t)q0 * dim,
+                                                                              nq, k_eff, cand, nullptr, 0);
         HMM_LAUNCH_CHECK();
         topk_final_multi_kernel<<<nq, 1024, 0, st>>>(cand, grid, k_eff, k_eff, idx_out_dev + (size_t)q0 * k,
                                                      sim_out_dev + (size_t)q0 * k, n_out_dev ? n_out_dev + q0 : nullptr, k);
+        HMM_LAUNCH_CHECK();
+    }
+    return HMM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// Per-event top-k for a batch of questions: the pass above with SIMS_OUT, then segment_topk_kernel over an (event, query) grid
+// (cosine_topk.hip).  The similarities of 16 questions are 64 B per 4096-B row read.
+// ------------------------------------------------------------------------------------------------------
+extern "C" int hmm_cosine_topk_segmented(const float* store_dev, int64_t n_rows, int dim, const float* query_dev,
+                                         const int64_t* seg_offsets_dev, int n_segments, int k,
+                                         int64_t* idx_out_dev, float* sim_out_dev, int32_t* n_out_dev,
+                                         void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
+
+static int64_t multi_sims_stride(int64_t n_rows) { return (n_rows + kMTileRows - 1) / kMTileRows * kMTileRows; }
+
+// The same for every n_queries and every k: one pass of 16 questions, which also covers the one-question scans behind k > 64.
+extern "C" size_t hmm_cosine_topk_segmented_multi_workspace_bytes(int64_t n_rows, int n_segments, int n_queries, int k) {
+    if (n_rows < 1 || n_segments < 1 || n_queries < 1 || k < 1) return 0;
+    return align_up((size_t)kMQ * multi_sims_stride(n_rows) * sizeof(float), 256) + 256;  // + 256: margin only -- no kernel touches it
+}
+
+extern "C" int hmm_cosine_topk_segmented_multi(const float* store_dev, int64_t n_rows, int dim, const float* queries_dev,
+                                               int n_queries, const int64_t* seg_offsets_dev, int n_segments, int k,
+                                               int64_t* idx_out_dev, float* sim_out_dev, int32_t* n_out_dev,
+                                               void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream) {
+    HMM_REQUIRE(dim == HMM_FEATURE_DIM, HMM_E_INVALID, "cosine_topk_segmented_multi: dim must be %d, got %d", HMM_FEATURE_DIM, dim);
+    HMM_REQUIRE(n_rows >= 1 && n_rows < (int64_t)0xFFFFFFFFll, HMM_E_INVALID, "cosine_topk_segmented_multi: n_rows=%lld out of range",
+                (long long)n_rows);
+    HMM_REQUIRE(n_queries >= 1 && n_segments >= 1 && k >= 1 && k <= 1024, HMM_E_INVALID,
+                "cosine_topk_segmented_multi: need n_queries >= 1, n_segments >= 1 and 1 <= k <= 1024 (got %d, %d, k=%d)", n_queries,
+                n_segments, k);
+    HMM_REQUIRE(store_dev && queries_dev && seg_offsets_dev && idx_out_dev && sim_out_dev && n_out_dev && workspace_dev, HMM_E_INVALID,
+                "cosine_topk_segmented_multi: null pointer");
+    HMM_REQUIRE(((uintptr_t)store_dev & 15) == 0 && ((uintptr_t)queries_dev & 15) == 0 && ((uintptr_t)workspace_dev & 15) == 0,
+                HMM_E_INVALID, "cosine_topk_segmented_multi: store/queries/workspace must be 16-byte aligned");
+    const size_t need = hmm_cosine_topk_segmented_multi_workspace_bytes(n_rows, n_segments, n_queries, k);
+    HMM_REQUIRE(workspace_bytes >= need, HMM_E_WORKSPACE, "cosine_topk_segmented_multi: workspace %zu < required %zu", workspace_bytes,
+                need);
+    const size_t per_query = (size_t)n_segments * k;
+    if (k > kMMaxK) {                                              // large k: one ordinary per-event scan per query
+        for (int qi = 0; qi < n_queries; ++qi) {
+            const int rc = hmm_cosine_topk_segmented(store_dev, n_rows, dim, queries_dev + (size_t)qi * dim, seg_offsets_dev, n_segments,
+                                                     k, idx_out_dev + qi * per_query, sim_out_dev + qi * per_query,
+                                                     n_out_dev + (size_t)qi * n_segments, workspace_dev, workspace_bytes, stream);
+            if (rc != HMM_OK) return rc;
+        }
+        return HMM_OK;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HMM_ENSURE_DYN_LDS(scan_multi_kernel<true>, (int)sizeof(MultiLds));
+    const int grid = multi_grid(n_rows);
+    const int64_t stride = multi_sims_stride(n_rows);
+    float* sims = static_cast<float*>(workspace_dev);
+    for (int q0 = 0; q0 < n_queries; q0 += kMQ) {                  // 16 queries per pass over the store
+        const int nq = n_queries - q0 < kMQ ? n_queries - q0 : kMQ;
+        scan_multi_kernel<true><<<grid, kMWaves * 64, sizeof(MultiLds), st>>>(store_dev, n_rows, queries_dev + (size_t)q0 * dim, nq, k,
+                                                                             nullptr, sims, stride);
+        HMM_LAUNCH_CHECK();
+        launch_segment_topk(sims, stride, nq, n_rows, seg_offsets_dev, n_segments, k, idx_out_dev + q0 * per_query,
+                            sim_out_dev + q0 * per_query, n_out_dev + (size_t)q0 * n_segments, st);
         HMM_LAUNCH_CHECK();
     }
     return HMM_OK;

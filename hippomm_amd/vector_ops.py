@@ -186,6 +186,46 @@ class FeatureStore:
                                                  _lib.stream_ptr()), "hmm_cosine_topk_segmented")
         return packed, idx, sims, counts
 
+    def search_segments_multi_device(self, queries, seg_offsets: torch.Tensor, k: int):
+        """``search_segments_device`` for a batch of questions in one pass over the store per 16 of them
+        (hmm_cosine_topk_segmented_multi).  queries: (Q,1024) numpy or torch, any device, fp32 or fp64.  Returns CUDA tensors
+        idx (Q,E,k) int64 rows within each event (-1 padded), sims (Q,E,k) fp32, counts (Q,E) int32 = min(k, n_e), without
+        synchronising."""
+        return self._search_segments_multi_packed(queries, seg_offsets, k)[1:]
+
+    def _search_segments_multi_packed(self, queries, seg_offsets: torch.Tensor, k: int):
+        """search_segments_multi_device, returning (packed, idx, sims, counts): the three outputs are views of `packed`."""
+        dev = self.rows.device
+        q = queries if isinstance(queries, torch.Tensor) else torch.from_numpy(np.asarray(queries))
+        if q.dim() != 2 or q.shape[1] != FEATURE_DIM:
+            raise ValueError(f"queries must be (Q,{FEATURE_DIM}), got {tuple(q.shape)}")
+        q = q.detach().to(device=dev, dtype=torch.float32).contiguous()
+        Q, E, k = q.shape[0], seg_offsets.numel() - 1, int(k)
+        if Q == 0:
+            raise ValueError("no queries")
+        if k < 1:
+            raise ValueError("k must be >= 1")
+        packed = torch.empty(Q * E * (k * 12 + 4), dtype=torch.uint8, device=dev)      # idx | sims | counts, as one read-back
+        idx = packed[: Q * E * k * 8].view(torch.int64).view(Q, E, k)
+        sims = packed[Q * E * k * 8: Q * E * k * 12].view(torch.float32).view(Q, E, k)
+        counts = packed[Q * E * k * 12:].view(torch.int32).view(Q, E)
+        if E == 0:
+            return packed, idx, sims, counts
+        if len(self) == 0:                                       # events without a row: nothing to scan, the padding is the answer
+            idx.fill_(-1)
+            sims.zero_()
+            counts.zero_()
+            return packed, idx, sims, counts
+        lib = _lib.load()
+        need = lib.hmm_cosine_topk_segmented_multi_workspace_bytes(len(self), E, Q, k)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _lib.check(lib.hmm_cosine_topk_segmented_multi(self.rows.data_ptr(), len(self), FEATURE_DIM, q.data_ptr(), Q,
+                                                       seg_offsets.data_ptr(), E, k, idx.data_ptr(), sims.data_ptr(),
+                                                       counts.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
+                                                       _lib.stream_ptr()), "hmm_cosine_topk_segmented_multi")
+        return packed, idx, sims, counts
+
     def search_multi_device(self, queries: torch.Tensor, k: int):
         """queries (Q,1024) fp32 on the store's device -> (idx (Q,k') int64, sims (Q,k') fp32) device tensors,
         k' = min(k, N).  One pass over the store per 16 queries (hmm_cosine_topk_multi)."""
@@ -445,6 +485,64 @@ class EventStore(FeatureStore):
         if int(counts_h.min()) == k:                             # every event has k rows: plain row views, no slicing
             return list(zip(idx_h, sims_h))
         return [(idx_h[e, :counts_h[e]], sims_h[e, :counts_h[e]]) for e in range(E)]
+
+    def _queries_2d(self, queries):
+        q = queries if isinstance(queries, torch.Tensor) else torch.from_numpy(np.asarray(queries))
+        if q.dim() != 2 or q.shape[1] != FEATURE_DIM:
+            raise ValueError(f"queries must be (Q,{FEATURE_DIM}), got {tuple(q.shape)}")
+        if q.shape[0] == 0:
+            raise ValueError("no queries")
+        return q
+
+    def _read_back(self, packed: torch.Tensor) -> np.ndarray:
+        """One copy of a packed device buffer into pinned memory; the bytes are valid until the next read-back."""
+        host = self._readback_buffer(packed.numel())
+        host.copy_(packed, non_blocking=True)
+        torch.cuda.current_stream(packed.device).synchronize()
+        return host.numpy()
+
+    def top_k_per_event_multi(self, queries, k: int = 5):
+        """``top_k_per_event`` for a batch of questions: per query the list that ``top_k_per_event(query, k)`` returns, from one
+        pass over the store per 16 questions and one read-back."""
+        q = self._queries_2d(queries)
+        Q, E, k = q.shape[0], len(self.lengths), int(k)
+        if E == 0 or len(self) == 0:
+            return [[(np.zeros(0, np.int64), np.zeros(0, np.float32)) for _ in range(E)] for _ in range(Q)]
+        packed = self._search_segments_multi_packed(q, self.offsets, k)[0]
+        raw = self._read_back(packed)
+        idx_h = raw[: Q * E * k * 8].view(np.int64).reshape(Q, E, k).copy()
+        sims_h = raw[Q * E * k * 8: Q * E * k * 12].view(np.float32).reshape(Q, E, k).copy()
+        counts_h = raw[Q * E * k * 12:].view(np.int32).reshape(Q, E)[0].copy()     # min(k, n_e): the same for every query
+        if int(counts_h.min()) == k:
+            return [list(zip(idx_h[qi], sims_h[qi])) for qi in range(Q)]
+        return [[(idx_h[qi, e, :counts_h[e]], sims_h[qi, e, :counts_h[e]]) for e in range(E)] for qi in range(Q)]
+
+    def top_hits_multi(self, queries, k: int = 5, keep: int = 5):
+        """``top_hits`` for a batch of questions: per query the list that ``top_hits(query, k, keep)`` returns.  One pass over the
+        store per 16 questions, one ranking launch for all of them (hmm_rank_segment_hits_multi), one read-back of Q x `keep`
+        hits.  keep > 64 is served by ``top_hits`` per query."""
+        q = self._queries_2d(queries)
+        Q, E, k, keep = q.shape[0], len(self.lengths), int(k), int(keep)
+        if E == 0 or len(self) == 0 or keep < 1:
+            return [[] for _ in range(Q)]
+        if keep > 64:
+            return [self.top_hits(q[qi], k, keep) for qi in range(Q)]
+        idx, sims, counts = self.search_segments_multi_device(q, self.offsets, k)
+        lib = _lib.load()
+        packed = torch.empty(Q * (keep * 20 + 4), dtype=torch.uint8, device=idx.device)      # event | row | sim | count
+        ev = packed[: Q * keep * 8].view(torch.int64)
+        row = packed[Q * keep * 8: Q * keep * 16].view(torch.int64)
+        val = packed[Q * keep * 16: Q * keep * 20].view(torch.float32)
+        n_out = packed[Q * keep * 20:].view(torch.int32)
+        _lib.check(lib.hmm_rank_segment_hits_multi(idx.data_ptr(), sims.data_ptr(), counts.data_ptr(), Q, E, k, keep, ev.data_ptr(),
+                                                   row.data_ptr(), val.data_ptr(), n_out.data_ptr(), _lib.stream_ptr()),
+                   "hmm_rank_segment_hits_multi")
+        raw = self._read_back(packed)
+        ev_h = raw[: Q * keep * 8].view(np.int64).reshape(Q, keep)
+        row_h = raw[Q * keep * 8: Q * keep * 16].view(np.int64).reshape(Q, keep)
+        val_h = raw[Q * keep * 16: Q * keep * 20].view(np.float32).reshape(Q, keep)
+        n_h = raw[Q * keep * 20:].view(np.int32)
+        return [[(int(ev_h[qi, t]), int(row_h[qi, t]), float(val_h[qi, t])) for t in range(int(n_h[qi]))] for qi in range(Q)]
 
     def _readback_buffer(self, nbytes: int) -> torch.Tensor:
         buf = getattr(self, "_pinned", None)

@@ -154,6 +154,31 @@ int    hmm_rank_segment_hits(const int64_t* idx_dev, const float* sims_dev, cons
                              int keep, int64_t* event_out_dev, int64_t* row_out_dev, float* sim_out_dev, int32_t* n_out_dev,
                              hmm_stream_t stream);
 
+/* Per-event feature_search for a BATCH of questions: what n_queries calls of hmm_cosine_topk_segmented return, for one
+ * read of the store per 16 questions instead of one per question -- the similarity block of 16 questions x rows runs on the fp32
+ * matrix cores exactly as in hmm_cosine_topk_multi, the per-event selection is hmm_cosine_topk_segmented's.  queries_dev
+ * (n_queries,1024) fp32 row-major; store_dev / seg_offsets_dev as in hmm_cosine_topk_segmented, n_rows >= 1.  Outputs are
+ * query-major: idx_out[(q*n_segments + e)*k ..] rows WITHIN event e (best first, -1 padded), sim_out likewise (0 padded),
+ * n_out[q*n_segments + e] = min(k, n_e).  The similarity of (row, query) has the bits hmm_cosine_topk_multi gives it, whatever the
+ * row's place in the store and the query's place in the batch: slice (q, e) equals hmm_cosine_topk_multi on event e's rows alone.
+ * k > 64: one hmm_cosine_topk_segmented per query inside the call (that function's bits).  k <= 1024.  The workspace does not
+ * depend on n_queries or k: it holds the similarities of one pass, 16 x 4 B per row. */
+size_t hmm_cosine_topk_segmented_multi_workspace_bytes(int64_t n_rows, int n_segments, int n_queries, int k);
+int    hmm_cosine_topk_segmented_multi(const float* store_dev, int64_t n_rows, int dim,
+                                       const float* queries_dev, int n_queries,
+                                       const int64_t* seg_offsets_dev, int n_segments, int k,
+                                       int64_t* idx_out_dev, float* sim_out_dev, int32_t* n_out_dev,
+                                       void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
+
+/* hmm_rank_segment_hits for every question of a batch in one launch: inputs are the three outputs of
+ * hmm_cosine_topk_segmented_multi, (n_queries, n_segments, k) / (n_queries, n_segments); per question q the best
+ * keep' = min(keep, its number of hits) hits at event_out[q*keep ..], row_out[q*keep ..], sim_out[q*keep ..] (-1 / -1 / 0 padded to
+ * `keep`), n_out[q] = keep'.  Same key and stable order as hmm_rank_segment_hits.  keep <= 64. */
+int    hmm_rank_segment_hits_multi(const int64_t* idx_dev, const float* sims_dev, const int32_t* counts_dev,
+                                   int n_queries, int n_segments, int k, int keep,
+                                   int64_t* event_out_dev, int64_t* row_out_dev, float* sim_out_dev, int32_t* n_out_dev,
+                                   hmm_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Consolidation similarity.  Replaces HippocampalMemory._select_key_frames(features, times,
  * similarity_threshold=0.9) (hippomm/core/hippocampal_memory.py:944-967; caller :855).

@@ -1,0 +1,262 @@
+"""GPU: per-event top-k for a batch of questions (hmm_cosine_topk_segmented_multi, hmm_rank_segment_hits_multi).
+
+  * bit identity with the batched whole-store scan: slice (q, e) == row q of hmm_cosine_topk_multi on event e's rows alone;
+  * every (q, e) result against the reference's per-event call (the oracle), with a cap on how many ranks may hide in a near-tie;
+  * the batched calls against Q single-question calls, k > 64, keep > 64, stable order of equal similarities across events.
+"""
+import numpy as np
+import pytest
+import torch
+
+from oracle.vector_ops_oracle import top_k_cosine_similarity_oracle
+
+pytestmark = pytest.mark.gpu
+SIM_ATOL = 2e-6          # the scan tolerance of tests/test_gpu_scan.py
+BAND = 1e-6              # assert_topk_matches' near-tie band (tests/test_gpu_scan.py)
+EXACT_SHARE = 0.99       # of all ranks checked against the oracle, at least this share must be outside a near-tie: index-exact
+
+SIZE_LISTS = [([300, 1, 0, 57, 5, 4096, 4097, 2], 5),                   # the lists of tests/test_gpu_segments.py
+              ([9000, 3, 12000], 32),
+              ([40] * 200, 5),
+              ([1500, 2, 0, 700, 1025, 64, 3000, 1], 5),
+              ([200] * 50, 64)]
+QS = [1, 3, 16, 17, 33]
+
+
+def _events(sizes, seed, plant=True):
+    rng = np.random.default_rng(seed)
+    events = [rng.standard_normal((n, 1024), dtype=np.float32) for n in sizes]
+    if plant and len(events) > 3 and events[3].shape[0] > 10:             # as tests/test_gpu_segments.py plants them
+        events[3][7] = events[3][2]                                       # a tie inside an event
+        events[3][9] = 0.0                                                # a zero row: NaN, ranked first
+    return events
+
+
+def _queries(nq, seed):
+    return np.random.default_rng(seed).standard_normal((nq, 1024), dtype=np.float32)
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+def _assert_slice_is_whole_store_scan(idx, sims, counts, events, queries, k):
+    """(q, e) slice of the per-event outputs == FeatureStore(event e).search_multi_device(queries, k), indices, similarity bits, count."""
+    from hippomm_amd.vector_ops import FeatureStore
+    nq = queries.shape[0]
+    for e, ev in enumerate(events):
+        n = ev.shape[0]
+        kk = min(k, n)
+        assert counts[:, e].tolist() == [kk] * nq
+        assert bool((idx[:, e, kk:] == -1).all()) and bool((_bits(sims[:, e, kk:]) == 0).all())
+        if n == 0:
+            continue
+        want_idx, want_sims = FeatureStore(ev).search_multi_device(queries, k)
+        assert want_idx.shape == (nq, kk)
+        assert torch.equal(idx[:, e, :kk], want_idx), f"event {e} ({n} rows): indices differ"
+        assert torch.equal(_bits(sims[:, e, :kk]), _bits(want_sims)), f"event {e} ({n} rows): similarity bits differ"
+
+
+@pytest.mark.parametrize("nq", QS)
+@pytest.mark.parametrize("case", range(len(SIZE_LISTS)))
+def test_slices_are_bit_identical_with_the_batched_whole_store_scan(case, nq):
+    from hippomm_amd.vector_ops import EventStore
+    sizes, k = SIZE_LISTS[case]
+    events = _events(sizes, seed=len(sizes) * 7 + k)
+    queries = torch.from_numpy(_queries(nq, 100 + nq)).cuda()
+    es = EventStore(events)
+    idx, sims, counts = es.search_segments_multi_device(queries, es.offsets, k)
+    assert idx.shape == (nq, len(sizes), k) and idx.dtype == torch.int64
+    assert sims.shape == (nq, len(sizes), k) and sims.dtype == torch.float32
+    assert counts.shape == (nq, len(sizes)) and counts.dtype == torch.int32
+    _assert_slice_is_whole_store_scan(idx, sims, counts, events, queries, k)
+    if len(events) > 3 and events[3].shape[0] > 10:                       # the planted rows: NaN first, then the higher row of the tie
+        assert bool((idx[:, 3, 0] == 9).all()) and bool(torch.isnan(sims[:, 3, 0]).all())
+        pos7, pos2 = (idx[:, 3, :] == 7).nonzero(), (idx[:, 3, :] == 2).nonzero()
+        for (q7, r7) in pos7.tolist():
+            assert [q7, r7 + 1] in pos2.tolist() or r7 == k - 1         # row 2 follows row 7 directly, with the same bits
+        for (q2, r2) in pos2.tolist():
+            assert [q2, r2 - 1] in pos7.tolist()
+            assert int(_bits(sims[q2, 3, r2])) == int(_bits(sims[q2, 3, r2 - 1]))
+
+
+def test_bits_do_not_depend_on_the_events_offset_or_the_querys_slot():
+    from hippomm_amd.vector_ops import EventStore
+    rng = np.random.default_rng(77)
+    a = rng.standard_normal((333, 1024), dtype=np.float32)
+    a[100] = a[50]
+    a[200] = 0.0
+    fill = [rng.standard_normal((n, 1024), dtype=np.float32) for n in (7, 1001, 64)]
+    events = [a, fill[0], fill[1], a, fill[2], a]                         # the same event at rows 0, 1341 (odd: another place in its tile), 1738
+    q = _queries(20, 5)
+    q[11] = q[2]                                                          # the same question in slots 2 and 11 of the first pass ...
+    q[19] = q[2]                                                          # ... and in slot 3 of the second
+    es = EventStore(events)
+    idx, sims, counts = es.search_segments_multi_device(torch.from_numpy(q).cuda(), es.offsets, 8)
+    for e in (3, 5):
+        assert torch.equal(idx[:, 0], idx[:, e]) and torch.equal(_bits(sims[:, 0]), _bits(sims[:, e]))
+    for s in (11, 19):
+        assert torch.equal(idx[2], idx[s]) and torch.equal(_bits(sims[2]), _bits(sims[s])) and torch.equal(counts[2], counts[s])
+    assert bool((idx[:, 0, 0] == 200).all()) and bool(torch.isnan(sims[:, 0, 0]).all())
+    _assert_slice_is_whole_store_scan(idx, sims, counts, events, torch.from_numpy(q).cuda(), 8)
+
+
+# ---- against the reference's per-event call -----------------------------------------------------------------------------------
+ORACLE_CASES = [(sizes, k, nq) for (sizes, k), nq in zip(SIZE_LISTS, (17, 3, 1, 33, 16))] + [([5000, 70, 300], 100, 3)]
+
+
+def oracle_case_inputs(i):
+    sizes, k, nq = ORACLE_CASES[i]
+    return _events(sizes, seed=1000 + i, plant=False), _queries(nq, 2000 + i), k
+
+
+def separated_ranks(all_sims, kk):
+    """assert_topk_matches' rule: rank i is index-exact when the oracle's similarity there is further than BAND from both neighbours."""
+    ordered = np.sort(all_sims[~np.isnan(all_sims)])[::-1][: kk + 1].astype(np.float64)
+    gaps = np.full(kk + 1, np.inf)
+    gaps[1: len(ordered)] = ordered[:-1] - ordered[1:]
+    return (gaps[:kk] > BAND) & (gaps[1: kk + 1] > BAND)
+
+
+def test_every_query_and_event_matches_the_reference_per_event_call():
+    """Similarities within 2e-6 of the oracle's; indices exact wherever the oracle's neighbouring similarities are more than BAND apart,
+    by value inside a near-tie -- and at least 99 % of all ranks checked here must be on the exact side."""
+    from hippomm_amd.vector_ops import EventStore
+    exact = checked = 0
+    for i in range(len(ORACLE_CASES)):
+        events, queries, k = oracle_case_inputs(i)
+        got = EventStore(events).top_k_per_event_multi(queries, k)
+        assert len(got) == queries.shape[0]
+        for q, per_event in zip(queries, got):
+            assert len(per_event) == len(events)
+            for ev, (idx, sims) in zip(events, per_event):
+                n = ev.shape[0]
+                kk = min(k, n)
+                assert idx.dtype == np.int64 and sims.dtype == np.float32 and len(idx) == kk and len(sims) == kk
+                if n == 0:
+                    continue
+                want_idx, want_sims = top_k_cosine_similarity_oracle(q, ev, k)
+                all_sims = (ev @ q) / (np.linalg.norm(ev, axis=1) * np.linalg.norm(q))
+                assert len(set(idx.tolist())) == kk
+                np.testing.assert_allclose(sims, want_sims, rtol=0, atol=SIM_ATOL)
+                np.testing.assert_allclose(all_sims[idx], want_sims, rtol=0, atol=SIM_ATOL)
+                sep = separated_ranks(all_sims, kk)
+                assert np.array_equal(idx[sep], want_idx[sep])
+                exact += int(sep.sum())
+                checked += kk
+        print(f"case {i}: {exact} of {checked} ranks index-exact so far")
+    share = exact / checked
+    print(f"index-exact share: {exact} / {checked} = {share:.5f}")
+    assert share >= EXACT_SHARE, f"only {exact} of {checked} ranks ({share:.4f}) were outside a near-tie"
+
+
+# ---- against Q single-question calls ------------------------------------------------------------------------------------------
+def _separated_store(sizes, nq, seed):
+    """Unit rows; every query sits next to a stored row of its own, so the best similarities are far apart."""
+    rng = np.random.default_rng(seed)
+    events = []
+    for n in sizes:
+        x = rng.standard_normal((n, 1024)).astype(np.float32)
+        events.append(x / np.linalg.norm(x, axis=1, keepdims=True))
+    rows = np.concatenate(events)
+    picks = rng.choice(rows.shape[0], size=nq, replace=False)
+    queries = np.stack([rows[p] + 0.05 * rng.standard_normal(1024).astype(np.float32) / 32 for p in picks])
+    return events, queries.astype(np.float32), picks
+
+
+def test_top_hits_multi_equals_single_question_top_hits():
+    from hippomm_amd.vector_ops import EventStore
+    sizes = [500] * 40 + [3, 0, 1200, 64]
+    events, queries, picks = _separated_store(sizes, 19, 21)
+    es = EventStore(events)
+    offsets = np.concatenate([[0], np.cumsum(sizes)])
+    multi = es.top_hits_multi(queries, 5, 5)
+    assert len(multi) == 19
+    for qi in range(19):
+        single = es.top_hits(queries[qi], 5, 5)
+        assert [(e, r) for e, r, _ in multi[qi]] == [(e, r) for e, r, _ in single]
+        np.testing.assert_allclose([v for _, _, v in multi[qi]], [v for _, _, v in single], rtol=0, atol=SIM_ATOL)
+        e0, r0, _ = multi[qi][0]
+        assert offsets[e0] + r0 == picks[qi]                              # the planted neighbour is the best hit
+    # torch queries, fp64, on the host: the same answer
+    again = es.top_hits_multi(torch.from_numpy(queries.astype(np.float64)), 5, 5)
+    assert again == multi
+    # per-event lists for all questions against the single-question ones
+    per_event = es.top_k_per_event_multi(queries[:3], 5)
+    for qi in range(3):
+        single = es.top_k_per_event(queries[qi], 5)
+        assert len(per_event[qi]) == len(single) == len(sizes)
+        for (mi, ms), (si, ss) in zip(per_event[qi], single):
+            assert len(mi) == len(si)
+            np.testing.assert_allclose(ms, ss, rtol=0, atol=SIM_ATOL)
+    e0, r0, _ = multi[0][0]
+    assert per_event[0][e0][0][0] == r0
+
+
+def test_k_above_64_is_the_single_question_scan_bit_for_bit():
+    from hippomm_amd.vector_ops import EventStore
+    events = _events([300, 1, 0, 5000, 99, 4097], seed=31)
+    queries = torch.from_numpy(_queries(3, 32)).cuda()
+    es = EventStore(events)
+    idx, sims, counts = es.search_segments_multi_device(queries, es.offsets, 100)
+    assert idx.shape == (3, 6, 100)
+    for qi in range(3):
+        i1, s1, c1 = es.search_segments_device(queries[qi], es.offsets, 100)
+        assert torch.equal(idx[qi], i1) and torch.equal(_bits(sims[qi]), _bits(s1)) and torch.equal(counts[qi], c1)
+
+
+def test_keep_beyond_the_ranking_kernel_returns_every_hit_ranked():
+    from hippomm_amd.vector_ops import EventStore
+    sizes = [30, 2, 0, 7, 100]
+    events, queries, _ = _separated_store(sizes, 4, 8)
+    es = EventStore(events)
+    multi = es.top_hits_multi(queries, 5, 100000)
+    for qi in range(4):
+        assert len(multi[qi]) == sum(min(5, n) for n in sizes)
+        vals = [v for _, _, v in multi[qi]]
+        assert vals == sorted(vals, reverse=True)
+        assert multi[qi] == es.top_hits(queries[qi], 5, 100000)
+    full = es.top_hits_multi(queries, 5, 64)                              # the widest device ranking: also every hit here (24 < 64)
+    for qi in range(4):
+        assert [(e, r) for e, r, _ in full[qi]] == [(e, r) for e, r, _ in multi[qi]]
+
+
+def test_equal_similarities_across_events_keep_event_order():
+    from hippomm_amd.vector_ops import EventStore
+    rng = np.random.default_rng(5)
+    events = [rng.standard_normal((n, 1024), dtype=np.float32) for n in (20, 33, 5, 40)]
+    queries = _queries(18, 6)
+    twin = (queries[0] + queries[17]).astype(np.float32)                  # one row, stored in events 3, 1 and 2: the same similarity bits
+    events[3][4] = twin
+    events[1][30] = twin
+    events[2][0] = twin
+    es = EventStore(events)
+    hits = es.top_hits_multi(queries, 3, 5)
+    for qi in (0, 17):
+        assert [(e, r) for e, r, _ in hits[qi][:3]] == [(1, 30), (2, 0), (3, 4)]
+        assert hits[qi][0][2] == hits[qi][1][2] == hits[qi][2][2]
+        ranked = sorted(((e, r, v) for e, (idx, sims) in enumerate(es.top_k_per_event_multi(queries, 3)[qi])
+                         for r, v in zip(idx.tolist(), sims.tolist())), key=lambda h: h[2], reverse=True)      # Python's stable sort
+        assert [(e, r) for e, r, _ in ranked[:5]] == [(e, r) for e, r, _ in hits[qi]]
+
+
+def test_arguments_and_empty_stores():
+    from hippomm_amd.vector_ops import EventStore
+    es = EventStore(_events([10, 0, 3], seed=1, plant=False))
+    with pytest.raises(ValueError):
+        es.top_hits_multi(np.zeros((0, 1024), np.float32))
+    with pytest.raises(ValueError):
+        es.top_k_per_event_multi(np.zeros((2, 512), np.float32))
+    with pytest.raises(ValueError):
+        es.search_segments_multi_device(torch.zeros(0, 1024), es.offsets, 5)
+    q = _queries(3, 2)
+    none = EventStore([])
+    assert none.top_hits_multi(q) == [[], [], []] and none.top_k_per_event_multi(q) == [[], [], []]
+    hollow = EventStore([np.zeros((0, 1024), np.float32)] * 2)
+    assert hollow.top_hits_multi(q) == [[], [], []]
+    got = hollow.top_k_per_event_multi(q)
+    assert [len(g) for g in got] == [2, 2, 2] and all(len(i) == 0 and len(s) == 0 for g in got for i, s in g)
+    idx, sims, counts = hollow.search_segments_multi_device(q, hollow.offsets, 5)
+    assert idx.shape == (3, 2, 5) and bool((idx == -1).all()) and bool((sims == 0).all()) and bool((counts == 0).all())
+    got = es.top_k_per_event_multi(q, 5)
+    assert [[len(i) for i, _ in g] for g in got] == [[5, 0, 3]] * 3
