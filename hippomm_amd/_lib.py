@@ -45,6 +45,12 @@ _SIGNATURES = {
     "hmm_cosine_topk_multi_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "hmm_cosine_topk_multi": (C.c_int, [c_ptr, C.c_int64, C.c_int, c_ptr, C.c_int, C.c_int, c_ptr, c_ptr, c_ptr, c_ptr,
                                         C.c_size_t, c_ptr]),
+    "hmm_cosine_topk_multi_prefilter_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    "hmm_cosine_topk_multi_prefilter": (C.c_int, [c_ptr, c_ptr, C.c_int64, C.c_int, c_ptr, C.c_int, C.c_int, c_ptr, c_ptr, c_ptr,
+                                                  c_ptr, c_ptr, C.c_size_t, c_ptr]),
+    "hmm_cosine_topk_segmented_multi_prefilter_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "hmm_cosine_topk_segmented_multi_prefilter": (C.c_int, [c_ptr, c_ptr, C.c_int64, C.c_int, c_ptr, C.c_int, c_ptr, C.c_int, C.c_int,
+                                                            c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, C.c_size_t, c_ptr]),
     "hmm_gram_select_workspace_bytes": (C.c_size_t, [C.c_int]),
     "hmm_gram_select": (C.c_int, [c_ptr, C.c_int, C.c_int, C.c_float, c_ptr, c_ptr, c_ptr, C.c_size_t, c_ptr]),
     "hmm_preprocess_vision_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),

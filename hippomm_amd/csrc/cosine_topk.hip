@@ -659,6 +659,19 @@ static ScanPlan make_plan(int64_t n, int k) {
     return p;
 }
 
+// Monotone envelope of make_plan(n, k).total: the similarities, and the larger of the two candidate layouts -- the full sort's padded
+// keys, or the lists of max(kScanBlocks, chunks) blocks and their merge -- whichever branch the plan takes at (n, k).
+size_t cosine_topk_workspace_envelope(int64_t n, int k) {
+    if (n < 1 || k < 1) return 0;
+    const int64_t kk = (int64_t)k < n ? k : n;
+    const int64_t chunks = (n + kChunk - 1) / kChunk, blocks = chunks > kScanBlocks ? chunks : kScanBlocks;
+    const size_t lists = align_up((size_t)blocks * kk * 8, 256) + align_up((size_t)((blocks * kk + kChunk - 1) / kChunk) * kk * 8, 256);
+    const size_t sorted = align_up((size_t)next_pow2(n) * 8, 256);
+    const size_t bound = align_up((size_t)n * sizeof(float), 256) + (lists > sorted ? lists : sorted) + 256;
+    const size_t plan = make_plan(n, k).total;
+    return bound > plan ? bound : plan;
+}
+
 struct ScanOut {                 // where the result of run_scan lives
     const uint64_t* best;         // sorted best keys (>= k_eff entries), or nullptr when `fused` is set
     int k_eff;

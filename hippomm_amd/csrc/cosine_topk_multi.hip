@@ -92,6 +92,43 @@ __device__ __forceinline__ void multi_barrier() {
     __builtin_amdgcn_sched_barrier(0);
 }
 
+// ---- the arithmetic that DEFINES the bits of a batched similarity ------------------------------------------------------------
+// Shared by scan_multi_kernel and the re-scoring of the shadow route (multi_rescore_tile): a (row, query) pair gets the same
+// bits from both because both run exactly this sequence.  Lane (r16, g) of a wave holds, for K slice sl and step j, the floats
+// 128 sl + 32 g + 4 j + 0..3 of row r16 (A fragment x[j]) and of query r16 (B fragment b[j]).
+__device__ __forceinline__ void multi_sumsq4(float& ss, const f32x4& v) {
+    ss = fmaf(v[0], v[0], ss); ss = fmaf(v[1], v[1], ss); ss = fmaf(v[2], v[2], ss); ss = fmaf(v[3], v[3], ss);
+}
+// one K slice: 32 MFMA steps alternating two accumulators, and the row's partial sum of squares
+__device__ __forceinline__ void multi_slice_mac(const f32x4 (&x)[8], const f32x4 (&b)[8], f32x4& acc0, f32x4& acc1, float& ss) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j][0], b[j][0], acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j][1], b[j][1], acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j][2], b[j][2], acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j][3], b[j][3], acc1, 0, 0, 0);
+        multi_sumsq4(ss, x[j]);
+    }
+}
+// the length of row / query r16: its four lanes (r16, g = 0..3) hold the partial sums
+__device__ __forceinline__ float multi_len(float ss) {
+    ss += __shfl_xor(ss, 16, 64);
+    ss += __shfl_xor(ss, 32, 64);
+    return sqrtf(ss);
+}
+// after the eight slices: the similarities of query r16 with rows 4 g + 0..3 of the tile (the D layout of the MFMA)
+__device__ __forceinline__ f32x4 multi_tile_sims(const f32x4& acc0, const f32x4& acc1, float ss, float my_qlen, int g) {
+    const float norm = multi_len(ss);                             // row r16 of the tile
+    const f32x4 acc = acc0 + acc1;
+    f32x4 sim4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float rn = __shfl(norm, 4 * g + j, 64);
+        sim4[j] = acc[j] / (rn * my_qlen);
+    }
+    return sim4;
+}
+
 // SIMS_OUT (hmm_cosine_topk_segmented_multi): the same pass, the same similarities bit for bit, but nothing is selected here --
 // the similarity of (query q, row r) goes to sims_out[q * sims_stride + r] (sims_stride = rows rounded up to whole tiles, so a lane
 // stores its four rows with one 16-byte store; the entries of the rows past the end are never read) and a per-event selection
@@ -100,7 +137,8 @@ template <bool SIMS_OUT>
 __global__ __launch_bounds__(kMWaves * 64) void scan_multi_kernel(const float* __restrict__ store, int64_t n_rows,
                                                                   const float* __restrict__ queries, int n_q, int k,
                                                                   uint64_t* __restrict__ out, float* __restrict__ sims_out,
-                                                                  int64_t sims_stride) {
+                                                                  int64_t sims_stride, const int* __restrict__ run_if) {
+    if (run_if != nullptr && *run_if == 0) return;                // the conditional exact pass behind the shadow route: flag down
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     MultiLds& L = *reinterpret_cast<MultiLds*>(smem_raw);
     const int tid = threadIdx.x, lane = tid & 63;
@@ -133,12 +171,10 @@ __global__ __launch_bounds__(kMWaves * 64) void scan_multi_kernel(const float* _
             for (int j = 0; j < 8; ++j) {
                 const f32x4 v = *reinterpret_cast<const f32x4*>(qs + 128 * sl + 4 * j);
                 bq[sl][j] = v;
-                qss = fmaf(v[0], v[0], qss); qss = fmaf(v[1], v[1], qss); qss = fmaf(v[2], v[2], qss); qss = fmaf(v[3], v[3], qss);
+                multi_sumsq4(qss, v);
             }
     }
-    qss += __shfl_xor(qss, 16, 64);
-    qss += __shfl_xor(qss, 32, 64);
-    const float my_qlen = sqrtf(qss);                             // |query r16|, in all four lanes that hold a part of it
+    const float my_qlen = multi_len(qss);                         // |query r16|, in all four lanes that hold a part of it
     if (tid < kMQ) { L.cnt[tid] = 0; L.tau[tid] = 0ull; }
     if (tid == 0) L.need = 0;
     __syncthreads();                                              // fragments are in registers: the ring may be overwritten
@@ -191,41 +227,20 @@ __global__ __launch_bounds__(kMWaves * 64) void scan_multi_kernel(const float* _
             f32x4 x[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) x[j] = *reinterpret_cast<const f32x4*>(ap + j * 32);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const f32x4 b = bq[sl][j];
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j][0], b[0], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j][1], b[1], acc1, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j][2], b[2], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j][3], b[3], acc1, 0, 0, 0);
-                ss = fmaf(x[j][0], x[j][0], ss); ss = fmaf(x[j][1], x[j][1], ss);
-                ss = fmaf(x[j][2], x[j][2], ss); ss = fmaf(x[j][3], x[j][3], ss);
-            }
+            multi_slice_mac(x, bq[sl], acc0, acc1, ss);
             slot = slot == kMRing - 1 ? 0 : slot + 1;
         }
-        // row norms: the four lanes (r16, g = 0..3) of a row hold its partial sums
-        ss += __shfl_xor(ss, 16, 64);
-        ss += __shfl_xor(ss, 32, 64);
-        const float norm = sqrtf(ss);                             // row r16 of the tile
-        const f32x4 acc = acc0 + acc1;                            // D layout: query r16, rows 4 g + j
+        const f32x4 sim4 = multi_tile_sims(acc0, acc1, ss, my_qlen, g);     // D layout: query r16, rows 4 g + j
         if constexpr (SIMS_OUT) {
-            if (tile < n_tiles) {
-                f32x4 sim4;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float rn = __shfl(norm, 4 * g + j, 64);
-                    sim4[j] = acc[j] / (rn * my_qlen);
-                }
-                if (r16 < n_q) *reinterpret_cast<f32x4*>(sims_out + r16 * sims_stride + tile * kMTileRows + 4 * g) = sim4;
-            }
+            if (tile < n_tiles && r16 < n_q)
+                *reinterpret_cast<f32x4*>(sims_out + r16 * sims_stride + tile * kMTileRows + 4 * g) = sim4;
             continue;
         }
         if (tile < n_tiles) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const float rn = __shfl(norm, 4 * g + j, 64);
                 const int64_t row = tile * kMTileRows + 4 * g + j;
-                const float sim = acc[j] / (rn * my_qlen);
+                const float sim = sim4[j];
                 const uint64_t key = ((uint64_t)order_bits(sim) << 32) | (uint64_t)(uint32_t)row;
                 if (r16 < n_q && row < n_rows && key > L.tau[r16]) {
                     const int pos = atomicAdd(&L.cnt[r16], 1);
@@ -292,9 +307,10 @@ __global__ __launch_bounds__(kMWaves * 64) void scan_multi_kernel(const float* _
 __global__ __launch_bounds__(1024) void topk_final_multi_kernel(const uint64_t* __restrict__ cand, int n_blocks, int k,
                                                                 int k_eff, int64_t* __restrict__ idx_out,
                                                                 float* __restrict__ sim_out, int32_t* __restrict__ n_out,
-                                                                int k_stride) {
+                                                                int k_stride, const int* __restrict__ run_if) {
     __shared__ uint64_t mx[kMMaxBlocks];
     __shared__ uint64_t s[4096];
+    if (run_if != nullptr && *run_if == 0) return;                // see scan_multi_kernel
     const int tid = threadIdx.x, qi = blockIdx.x;
     const uint64_t* c = cand + (size_t)qi * n_blocks * k;
     int n2 = 64;
@@ -377,10 +393,10 @@ extern "C" int hmm_cosine_topk_multi(const float* store_dev, int64_t n_rows, int
     for (int q0 = 0; q0 < n_queries; q0 += kMQ) {                  // 16 queries per pass over the store
         const int nq = n_queries - q0 < kMQ ? n_queries - q0 : kMQ;
         scan_multi_kernel<false><<<grid, kMWaves * 64, sizeof(MultiLds), st>>>(store_dev, n_rows, queries_dev + (size_t)q0 * dim,
-                                                                              nq, k_eff, cand, nullptr, 0);
+                                                                              nq, k_eff, cand, nullptr, 0, nullptr);
         HMM_LAUNCH_CHECK();
         topk_final_multi_kernel<<<nq, 1024, 0, st>>>(cand, grid, k_eff, k_eff, idx_out_dev + (size_t)q0 * k,
-                                                     sim_out_dev + (size_t)q0 * k, n_out_dev ? n_out_dev + q0 : nullptr, k);
+                                                     sim_out_dev + (size_t)q0 * k, n_out_dev ? n_out_dev + q0 : nullptr, k, nullptr);
         HMM_LAUNCH_CHECK();
     }
     return HMM_OK;
@@ -438,10 +454,582 @@ extern "C" int hmm_cosine_topk_segmented_multi(const float* store_dev, int64_t n
     for (int q0 = 0; q0 < n_queries; q0 += kMQ) {                  // 16 queries per pass over the store
         const int nq = n_queries - q0 < kMQ ? n_queries - q0 : kMQ;
         scan_multi_kernel<true><<<grid, kMWaves * 64, sizeof(MultiLds), st>>>(store_dev, n_rows, queries_dev + (size_t)q0 * dim, nq, k,
-                                                                             nullptr, sims, stride);
+                                                                             nullptr, sims, stride, nullptr);
         HMM_LAUNCH_CHECK();
         launch_segment_topk(sims, stride, nq, n_rows, seg_offsets_dev, n_segments, k, idx_out_dev + q0 * per_query,
                             sim_out_dev + q0 * per_query, n_out_dev + (size_t)q0 * n_segments, st);
+        HMM_LAUNCH_CHECK();
+    }
+    return HMM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// The batched scans through the bf16 shadow (hmm_cosine_topk_multi_prefilter, hmm_cosine_topk_segmented_multi_prefilter): the
+// scheme of cosine_topk_prefilter.hip for 16 questions per pass, 2048 B per row streamed instead of 4096.
+//
+//   pass 1   shadow_multi_kernel: s~(r, q) = dot(shadow_r, q) / ||q|| on v_mfma_f32_16x16x32_bf16.  The shadow rows are the A
+//            operand, read straight into registers: lane (r16, g) of a wave holds, for step t of 32, the 16 bytes (8 bf16)
+//            32 t + 8 g .. + 7 of row r16; one load instruction covers 16 rows x 64 B, two consecutive ones whole 128-B lines.  A
+//            wave keeps one tile (16 rows, 128 registers) and refills register t for the next tile as soon as step t has used
+//            it: 31 loads (31 KiB) per wave stay in flight behind a counted vmcnt, 8 waves per CU.  The questions are the B
+//            operand, each split into bf16 hi = bf16(q) and lo = bf16(q - hi), two MFMAs per step; the 64 KiB of fragments live
+//            in LDS in fragment order ([step][lane] x 16 B: a wave's read is one contiguous KiB, conflict-free) -- two
+//            ds_read_b128 per KiB of rows streamed, a fifth of the LDS bandwidth at the HBM row rate -- which leaves the registers
+//            to the row stream.  Selection (or the similarities-out mode) is scan_multi_kernel's.
+//   pass 2   flat: multi_prefilter_final_kernel, one workgroup per question: threshold t = the k-th largest s~, candidates = the
+//            rows with s~ >= t - 2 eps, re-scored by multi_rescore_tile and ranked.  A saturated list or more candidates than
+//            the buffer holds raises ONE flag for the pass, and the exact pass (scan_multi_kernel<false> +
+//            topk_final_multi_kernel, both conditional on that flag) answers for all its questions.
+//            per event: segment_multi_prefilter_kernel over (event, question): threshold inside the event, candidates re-scored,
+//            every row of the event when the candidates do not fit.
+//   Re-scoring.  multi_rescore_tile gathers up to 16 candidate rows of the fp32 store into the A layout of scan_multi_kernel and
+//            runs its sequence (multi_slice_mac / multi_tile_sims above) with the question in its own slot of the B operand and
+//            zeros elsewhere: the bits of hmm_cosine_topk_multi, which depend neither on the row's place nor on the slot
+//            (tests/test_gpu_segments_multi.py).
+//   Error bound.  Shadow element x~ = (x / ||x||)(1 + d), |d| <= 2^-8 (as cosine_topk_prefilter.hip takes it; round to nearest
+//            gives 2^-9): |dot(x~, q) - dot(x / ||x||, q)| <= 2^-8 (1 + 2^-8) ||q||                          -> 0.003922
+//            question: hi + lo = q (1 + e), |e| <= 2^-9 * 2^-9 (+ one fp32 rounding of q - hi, exact here) -> 2^-16 = 0.000016
+//            the bf16 x bf16 products are exact in fp32; they are summed in fp32 inside the MFMA and along 32 steps, K = 1024
+//            terms per chain: at most 1024 * 2^-23 * sum |x~_i q_i| / ||q|| (truncating adds assumed)   -> 0.000123
+//            1 / ||q|| in fp32 and the final product: 3 * 2^-24                                             -> 0.0000002
+//            total |s~ - s| < 0.004061 < eps = 0.0042.  The candidate argument is that of cosine_topk_prefilter.hip:14-17.
+// ------------------------------------------------------------------------------------------------------
+namespace hmm {
+
+constexpr float kMPEps = 0.0042f;
+constexpr int kSWaves = 8;                          // two waves per SIMD: ~150 registers each (128 of them one tile of rows)
+constexpr int kSRows = kSWaves * kMTileRows;        // rows per workgroup per round
+constexpr int kSSteps = 32;                         // MFMA steps per tile: 32 bf16 of K each
+constexpr int kSCap = 256;                          // candidate keys per query and workgroup (>= 64 + kSRows, power of two)
+constexpr int kMPCandCap = 1024;                    // candidate rows a question re-scores itself
+constexpr int kMPFinalThreads = 512;
+constexpr int kMPMinRows = 16384;                   // flat dispatch limit: hmm_cosine_topk_prefilter's, NOT yet measured for a batch
+constexpr int kMPMinSegRows = 128;                  // per-event dispatch limit, rows per event on average: inherited likewise, NOT yet measured
+
+struct ShadowLds {
+    uint4 bhi[kSSteps][64];                         // 32768 B
+    uint4 blo[kSSteps][64];                         // 32768 B
+    uint64_t keys[kMQ][kSCap];                      // 32768 B
+    uint64_t tau[kMQ];
+    float inv_qlen[kMQ];
+    int cnt[kMQ];
+    int need;
+};
+
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+static int mp_list_len(int k) {                                       // prefilter_list_len of cosine_topk_prefilter.hip
+    const int kk = 2 * k < 32 ? 32 : 2 * k;
+    return kk > kMMaxK ? kMMaxK : kk;
+}
+
+template <bool SIMS_OUT>
+__global__ __launch_bounds__(kSWaves * 64) void shadow_multi_kernel(const uint4* __restrict__ shadow, int64_t n_rows,
+                                                                    const float* __restrict__ queries, int n_q, int kk,
+                                                                    uint64_t* __restrict__ out, float* __restrict__ sims_out,
+                                                                    int64_t sims_stride, int* __restrict__ flag) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    ShadowLds& L = *reinterpret_cast<ShadowLds*>(smem_raw);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r16 = lane & 15, g = lane >> 4;
+    if (flag != nullptr && blockIdx.x == 0 && tid == 0) *flag = 0;            // the pass's fallback flag (raised by the finish)
+
+    // 1 / ||q||: wave w takes questions w and w + 8, lane l the floats 4 (64 j + l)
+    for (int qi = wave; qi < kMQ; qi += kSWaves) {
+        float qs = 0.f;
+        if (qi < n_q) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) multi_sumsq4(qs, *reinterpret_cast<const f32x4*>(queries + (size_t)qi * 1024 + 4 * (64 * j + lane)));
+        }
+        qs = wave_sum(qs);
+        if (lane == 0) L.inv_qlen[qi] = 1.0f / sqrtf(qs);
+    }
+    // B fragments: entry (t, lane (q, g)) = bf16 hi / lo of q[32 t + 8 g .. + 7] (zeros past n_q)
+    for (int i = tid; i < kSSteps * 64; i += kSWaves * 64) {
+        const int t = i >> 6, l = i & 63, qi = l & 15, gg = l >> 4;
+        bf16x8 hi, lo;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { hi[e] = (bf16_t)0.f; lo[e] = (bf16_t)0.f; }
+        if (qi < n_q) {
+            const float* p = queries + (size_t)qi * 1024 + 32 * t + 8 * gg;
+            const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float v = e < 4 ? a[e & 3] : b[e & 3];
+                hi[e] = (bf16_t)v;
+                lo[e] = (bf16_t)(v - (float)hi[e]);
+            }
+        }
+        L.bhi[t][l] = __builtin_bit_cast(uint4, hi);
+        L.blo[t][l] = __builtin_bit_cast(uint4, lo);
+    }
+    if (tid < kMQ) { L.cnt[tid] = 0; L.tau[tid] = 0ull; }
+    if (tid == 0) L.need = 0;
+    __syncthreads();
+    const float my_inv_qlen = L.inv_qlen[r16];
+
+    const int64_t n_tiles = (n_rows + kMTileRows - 1) / kMTileRows;
+    const int64_t n_waves = (int64_t)gridDim.x * kSWaves;
+    const int64_t wave_gid = (int64_t)blockIdx.x * kSWaves + wave;
+    const int64_t n_rounds = (n_tiles + n_waves - 1) / n_waves;   // same for every wave of the grid
+    auto src_of = [&](int64_t round) {                            // lane's 16 B of step 0; step t is + 4 t (rows past the end: clamped)
+        int64_t row = (wave_gid + round * n_waves) * kMTileRows + r16;
+        row = row < n_rows ? row : n_rows - 1;
+        return reinterpret_cast<const u32x4*>(shadow) + row * 128 + g;
+    };
+    u32x4 x[kSSteps];
+    {
+        const u32x4* p = src_of(0);
+#pragma unroll
+        for (int t = 0; t < kSSteps; ++t) x[t] = __builtin_nontemporal_load(p + 4 * t);
+    }
+    for (int64_t round = 0; round < n_rounds; ++round) {
+        const int64_t tile = wave_gid + round * n_waves;
+        const u32x4* pn = src_of(round + 1);                      // next tile (clamped past the end, never used then)
+        asm volatile("" ::: "memory");                            // the B fragments are re-read from LDS every round: hoisted out of the
+                                                                  // loop they would take 256 registers and spill the row stream
+        f32x4 acc0 = f32x4{0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
+#pragma unroll
+        for (int t = 0; t < kSSteps; ++t) {
+            const bf16x8 a = __builtin_bit_cast(bf16x8, x[t]);
+            const bf16x8 bh = __builtin_bit_cast(bf16x8, L.bhi[t][lane]);
+            const bf16x8 bl = __builtin_bit_cast(bf16x8, L.blo[t][lane]);
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bh, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bl, acc1, 0, 0, 0);
+            x[t] = __builtin_nontemporal_load(pn + 4 * t);        // register t is free: the same step of the next tile
+            __builtin_amdgcn_sched_barrier(0);                    // keep the load HERE: gathered behind the MFMAs, all 32 are waited for at once
+        }
+        const f32x4 acc = acc0 + acc1;                            // D layout: query r16, rows 4 g + j
+        f32x4 sim4;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sim4[j] = acc[j] * my_inv_qlen;
+        if constexpr (SIMS_OUT) {
+            if (tile < n_tiles && r16 < n_q)
+                *reinterpret_cast<f32x4*>(sims_out + r16 * sims_stride + tile * kMTileRows + 4 * g) = sim4;
+            continue;
+        }
+        if (tile < n_tiles) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int64_t row = tile * kMTileRows + 4 * g + j;
+                const uint64_t key = ((uint64_t)order_bits(sim4[j]) << 32) | (uint64_t)(uint32_t)row;
+                if (r16 < n_q && row < n_rows && key > L.tau[r16]) {
+                    const int pos = atomicAdd(&L.cnt[r16], 1);
+                    L.keys[r16][pos] = key;
+                }
+            }
+        }
+        // lists sorted down to kk exactly as scan_multi_kernel sorts its lists down to k (see there)
+        multi_barrier();
+        if (wave == 0) {
+            bool need = round + 1 >= n_rounds || round == 0;
+            if (lane < kMQ) need |= L.cnt[lane] > kSCap - kSRows;
+            need = __any(need);
+            if (lane == 0) L.need = need ? 1 : 0;
+        }
+        multi_barrier();
+        if (L.need) {
+            constexpr int NL = kMQ / kSWaves;                     // lists per wave: wave w owns queries w, w + 8
+            uint64_t* lists[NL];
+            int n[NL], nmax = 0;
+#pragma unroll
+            for (int q = 0; q < NL; ++q) {
+                lists[q] = L.keys[wave + q * kSWaves];
+                n[q] = L.cnt[wave + q * kSWaves];
+                nmax = n[q] > nmax ? n[q] : nmax;
+            }
+            int n2 = 64;
+            while (n2 < nmax) n2 <<= 1;
+#pragma unroll
+            for (int q = 0; q < NL; ++q)
+                for (int t = n[q] + lane; t < n2; t += 64) lists[q][t] = 0ull;
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
+            wave_bitonic_desc<NL>(lists, n2, lane);
+            if (lane == 0) {
+#pragma unroll
+                for (int q = 0; q < NL; ++q) {
+                    const int qi = wave + q * kSWaves;
+                    L.cnt[qi] = n[q] < kk ? n[q] : kk;
+                    L.tau[qi] = n[q] >= kk ? lists[q][kk - 1] : 0ull;
+                }
+            }
+            multi_barrier();
+        }
+    }
+    if constexpr (SIMS_OUT) return;
+    __syncthreads();
+    // this workgroup's best kk per query (sorted, 0-padded); a workgroup with no tile leaves zeros
+    for (int i = tid; i < n_q * kk; i += kSWaves * 64) {
+        const int qi = i / kk, t = i - qi * kk;
+        out[((size_t)qi * gridDim.x + blockIdx.x) * kk + t] = t < L.cnt[qi] ? L.keys[qi][t] : 0ull;
+    }
+}
+
+// Up to 16 rows of the fp32 store against the question in B slot `slot`, with the bits of scan_multi_kernel: lane (r16, g) passes
+// row r16 of the gathered tile (nullptr: no row, zeros) and gets, where r16 == slot, the similarities of rows 4 g + 0..3.
+// q_lds: the question's 1024 floats in LDS.  Two K slices per memory latency; not a bandwidth path.
+__device__ __forceinline__ f32x4 multi_rescore_tile(const float* row, const float* q_lds, int slot, int lane) {
+    const int r16 = lane & 15, g = lane >> 4;
+    const bool mine = r16 == slot;
+    const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 acc0 = zero, acc1 = zero;
+    float ss = 0.f, qss = 0.f;
+#pragma unroll 1
+    for (int sp = 0; sp < kMSlices / 2; ++sp) {
+        f32x4 xa[8], xb[8], ba[8], bb[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            xa[j] = row ? *reinterpret_cast<const f32x4*>(row + 256 * sp + 32 * g + 4 * j) : zero;
+            xb[j] = row ? *reinterpret_cast<const f32x4*>(row + 256 * sp + 128 + 32 * g + 4 * j) : zero;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            ba[j] = mine ? *reinterpret_cast<const f32x4*>(q_lds + 256 * sp + 32 * g + 4 * j) : zero;
+            multi_sumsq4(qss, ba[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            bb[j] = mine ? *reinterpret_cast<const f32x4*>(q_lds + 256 * sp + 128 + 32 * g + 4 * j) : zero;
+            multi_sumsq4(qss, bb[j]);
+        }
+        multi_slice_mac(xa, ba, acc0, acc1, ss);
+        multi_slice_mac(xb, bb, acc0, acc1, ss);
+    }
+    return multi_tile_sims(acc0, acc1, ss, multi_len(qss), g);
+}
+
+__device__ __forceinline__ uint32_t mp_threshold_below(uint32_t key_hi) {    // NaN -> 0xFFFFFFFF: only NaN rows pass
+    return order_bits(order_bits_inverse(key_hi) - 2.0f * kMPEps);
+}
+
+// Flat finish, one workgroup per question of the pass.  lists: [question][n_blocks][kk] keys of shadow_multi_kernel.
+__global__ __launch_bounds__(kMPFinalThreads) void multi_prefilter_final_kernel(const uint64_t* __restrict__ lists, int n_blocks, int k,
+                                                                                int kk, const float* __restrict__ store,
+                                                                                const float* __restrict__ queries,
+                                                                                int64_t* __restrict__ idx_out, float* __restrict__ sim_out,
+                                                                                int32_t* __restrict__ n_out, int k_stride,
+                                                                                int* __restrict__ flag, int32_t* __restrict__ stats) {
+    __shared__ uint64_t mx[kNumCU];
+    __shared__ uint64_t s[kChunk];
+    __shared__ uint32_t cand_row[kMPCandCap];
+    __shared__ __attribute__((aligned(16))) float qs[1024];
+    __shared__ int n_cand, n_sat;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, qi = blockIdx.x;
+    const uint64_t* c = lists + (size_t)qi * n_blocks * kk;
+    if (tid == 0) { n_cand = 0; n_sat = 0; }
+    for (int t = tid; t < 256; t += kMPFinalThreads)
+        *reinterpret_cast<f32x4*>(qs + 4 * t) = *reinterpret_cast<const f32x4*>(queries + (size_t)qi * 1024 + 4 * t);
+    const int n2 = pow2_at_least(n_blocks, 64);
+    for (int t = tid; t < n2; t += kMPFinalThreads) mx[t] = t < n_blocks ? c[(size_t)t * kk] : 0ull;
+    __syncthreads();
+    top64_desc(mx, n2);
+    // the k lists with the largest maxima hold the k largest keys (every list keeps kk >= k entries): rank them
+    const int n_win = n_blocks < k ? n_blocks : k;
+    const int m2 = pow2_at_least(n_win * kk, 64);
+    for (int t = tid; t < m2; t += kMPFinalThreads) {
+        uint64_t key = 0ull;
+        if (t < n_win * kk) {
+            const uint64_t top = mx[t / kk];
+            if (top != 0ull) {
+                const int64_t row = (int64_t)(top & 0xFFFFFFFFull);
+                const int blk = (int)(((row / kMTileRows) % ((int64_t)n_blocks * kSWaves)) / kSWaves);
+                key = c[(size_t)blk * kk + (t % kk)];
+            }
+        }
+        s[t] = key;
+    }
+    __syncthreads();
+    top64_desc(s, m2);
+    const uint64_t kth = s[k - 1];                                // 0 = fewer than k rows in all (the launcher excludes it)
+    __syncthreads();
+    const uint32_t thr = mp_threshold_below((uint32_t)(kth >> 32));
+    // candidates: every entry at or above the threshold; a list whose LAST entry passes may have dropped some (saturated)
+    for (int t = tid; t < n_blocks * kk; t += kMPFinalThreads) {
+        const uint64_t key = c[t];
+        if (key != 0ull && (uint32_t)(key >> 32) >= thr) {
+            const int pos = atomicAdd(&n_cand, 1);
+            if (pos < kMPCandCap) cand_row[pos] = (uint32_t)(key & 0xFFFFFFFFull);
+            if (t % kk == kk - 1) atomicAdd(&n_sat, 1);
+        }
+    }
+    __syncthreads();
+    const int m = n_cand;
+    const bool fall = kth == 0ull || n_sat > 0 || m > kMPCandCap;
+    if (tid == 0) {
+        if (fall) *flag = 1;                                      // one flag for the pass: the exact pass answers every question of it
+        if (stats) { stats[2 * qi] = m; stats[2 * qi + 1] = n_sat; }
+    }
+    if (fall) return;                                             // block-uniform
+    const int m_pad = pow2_at_least(m, 64);
+    for (int t = m + tid; t < m_pad; t += kMPFinalThreads) s[t] = 0ull;
+    const int r16 = lane & 15, g = lane >> 4;
+    for (int tile = wave; tile * kMTileRows < m; tile += kMPFinalThreads / 64) {       // wave-uniform
+        const int cc = tile * kMTileRows + r16;
+        const float* row = cc < m ? store + (int64_t)cand_row[cc] * 1024 : nullptr;
+        const f32x4 sim4 = multi_rescore_tile(row, qs, qi, lane);
+        if (r16 == qi) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int cj = tile * kMTileRows + 4 * g + j;
+                if (cj < m) s[cj] = ((uint64_t)order_bits(sim4[j]) << 32) | (uint64_t)cand_row[cj];
+            }
+        }
+    }
+    __syncthreads();
+    top64_desc(s, m_pad);
+    if (tid == 0 && n_out) n_out[qi] = k;
+    for (int t = tid; t < k; t += kMPFinalThreads) {
+        idx_out[(size_t)qi * k_stride + t] = (int64_t)(s[t] & 0xFFFFFFFFull);
+        sim_out[(size_t)qi * k_stride + t] = order_bits_inverse((uint32_t)(s[t] >> 32));
+    }
+}
+
+// Per-event finish over an (event, question) grid: segment_prefilter_kernel (cosine_topk_prefilter.hip) with multi_rescore_tile as
+// the re-scorer.  sims: s~ of question y at sims + y * sims_stride.  stats (nullable): [0] += 1 when the whole event was re-scored,
+// [1] += rows re-scored.
+template <int CHUNK, int THREADS>
+__global__ __launch_bounds__(THREADS) void segment_multi_prefilter_kernel(const float* __restrict__ sims, int64_t sims_stride,
+                                                                          const int64_t* __restrict__ seg_off, int k,
+                                                                          const float* __restrict__ store, const float* __restrict__ queries,
+                                                                          int64_t* __restrict__ idx_out, float* __restrict__ sim_out,
+                                                                          int32_t* __restrict__ n_out, int32_t* __restrict__ stats) {
+    __shared__ uint64_t s[CHUNK];
+    __shared__ uint32_t cand[kMPCandCap];
+    __shared__ __attribute__((aligned(16))) float qs[1024];
+    __shared__ int n_cand;
+    const int e = blockIdx.x, y = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t slot = (int64_t)y * gridDim.x + e;              // query-major outputs
+    sims += (int64_t)y * sims_stride;
+    const int64_t lo = seg_off[e], hi = seg_off[e + 1];
+    const int64_t n = hi - lo;
+    const int k_out = (int)(n < k ? (n > 0 ? n : 0) : k);
+    if (tid == 0) n_cand = 0;
+    if (n <= 0) {                                                  // block-uniform
+        if (tid == 0) n_out[slot] = 0;
+        for (int t = tid; t < k; t += THREADS) { idx_out[slot * k + t] = -1; sim_out[slot * k + t] = 0.0f; }
+        return;
+    }
+    for (int t = tid; t < 256; t += THREADS)
+        *reinterpret_cast<f32x4*>(qs + 4 * t) = *reinterpret_cast<const f32x4*>(queries + (size_t)y * 1024 + 4 * t);
+    // ---- the k-th largest approximate key of the event (pieces of a chunk, carrying the running best k) ---------------------
+    uint32_t thr = 0u;                                             // n <= k: every row is a candidate
+    if (n > k) {
+        int have = 0;
+        int64_t base = 0;
+        do {
+            const int64_t left = n - base;
+            const int take = (int)(left < (int64_t)(CHUNK - have) ? left : (int64_t)(CHUNK - have));
+            const int total = have + take;
+            const int n2 = pow2_at_least(total, 64);
+            for (int t = have + tid; t < n2; t += THREADS) {
+                uint64_t key = 0ull;
+                if (t < total) {
+                    const int64_t r = base + (t - have);
+                    key = ((uint64_t)order_bits(sims[lo + r]) << 32) | (uint64_t)(uint32_t)r;
+                }
+                s[t] = key;
+            }
+            __syncthreads();
+            top64_desc(s, n2);
+            have = total < k ? total : k;
+            base += take;
+        } while (base < n);
+        thr = mp_threshold_below((uint32_t)(s[k - 1] >> 32));
+    }
+    __syncthreads();
+    // ---- candidates ---------------------------------------------------------------------------------------------------------
+    for (int64_t r = tid; r < n; r += THREADS) {
+        if (order_bits(sims[lo + r]) >= thr) {
+            const int pos = atomicAdd(&n_cand, 1);
+            if (pos < kMPCandCap) cand[pos] = (uint32_t)r;
+        }
+    }
+    __syncthreads();
+    const bool all_rows = n_cand > kMPCandCap;                     // block-uniform
+    const int64_t m = all_rows ? n : (int64_t)n_cand;
+    if (tid == 0 && stats) {                                       // a diagnostic: an int32 sum over all pairs and passes, it may wrap
+        if (all_rows) atomicAdd(&stats[0], 1);
+        atomicAdd(&stats[1], (int)m);
+    }
+    // ---- exact re-score in tiles of 16 rows, k best (pieces of a chunk with carry, as above) ---------------------------------
+    const int r16 = lane & 15, g = lane >> 4;
+    int have = 0;
+    int64_t base = 0;
+    do {
+        const int64_t left = m - base;
+        const int take = (int)(left < (int64_t)(CHUNK - have) ? left : (int64_t)(CHUNK - have));
+        const int total = have + take;
+        const int n2 = pow2_at_least(total, 64);
+        for (int t = total + tid; t < n2; t += THREADS) s[t] = 0ull;
+        for (int tile = wave; tile * kMTileRows < take; tile += THREADS / 64) {        // wave-uniform trip count per wave
+            const int cc = tile * kMTileRows + r16;
+            const float* row = nullptr;
+            if (cc < take) row = store + (lo + (all_rows ? base + cc : (int64_t)cand[base + cc])) * 1024;
+            const f32x4 sim4 = multi_rescore_tile(row, qs, y, lane);
+            if (r16 == y) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int cj = tile * kMTileRows + 4 * g + j;
+                    if (cj < take) {
+                        const int64_t r = all_rows ? base + cj : (int64_t)cand[base + cj];
+                        s[have + cj] = ((uint64_t)order_bits(sim4[j]) << 32) | (uint64_t)(uint32_t)r;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        top64_desc(s, n2);
+        have = total < k ? total : k;
+        base += take;
+    } while (base < m);
+    if (tid == 0) n_out[slot] = k_out;
+    for (int t = tid; t < k; t += THREADS) {
+        const bool ok = t < k_out;
+        idx_out[slot * k + t] = ok ? (int64_t)(s[t] & 0xFFFFFFFFull) : -1;
+        sim_out[slot * k + t] = ok ? order_bits_inverse((uint32_t)(s[t] >> 32)) : 0.0f;
+    }
+}
+
+static int shadow_multi_grid(int64_t n_rows) {                 // one workgroup per CU (its LDS fills the CU), 128 rows per round
+    const int64_t chunks = (n_rows + kSRows - 1) / kSRows;
+    return (int)(chunks < kNumCU ? chunks : kNumCU);
+}
+
+struct MultiPrefilterPlan { size_t exact, off_lists, off_flag, total; };
+
+static MultiPrefilterPlan multi_prefilter_plan(int64_t n_rows, int n_queries, int k) {
+    MultiPrefilterPlan p{};
+    // The exact function runs inside the first part.  Its own query is not monotone in n_rows beyond k = 64 (the one-question scan's
+    // plan changes shape with min(k, n_rows)), so this part is an envelope of it that is: the batched pass's lists, and beyond 64 the
+    // one-question scan's own envelope (cosine_topk_workspace_envelope, beside its plan in cosine_topk.hip).
+    const int64_t k_eff = k < n_rows ? k : n_rows;
+    size_t part = align_up((size_t)kMQ * multi_grid(n_rows) * (size_t)(k_eff < kMMaxK ? k_eff : kMMaxK) * 8, 256) + 256;
+    if (k_eff > kMMaxK) {
+        const size_t one = cosine_topk_workspace_envelope(n_rows, k);
+        part = part > one ? part : one;
+    }
+    const size_t exact = hmm_cosine_topk_multi_workspace_bytes(n_rows, n_queries, k);
+    p.exact = part > exact ? part : exact;
+    p.off_lists = align_up(p.exact, 256);
+    p.off_flag = p.off_lists + (size_t)kMQ * kNumCU * kMMaxK * 8;                         // [16][<= 256 workgroups][<= 64] keys
+    p.total = p.off_flag + 256;                                                          // the flag uses 4 of these 256 bytes
+    return p;
+}
+
+}  // namespace hmm
+
+extern "C" size_t hmm_cosine_topk_multi_prefilter_workspace_bytes(int64_t n_rows, int n_queries, int k) {
+    if (n_rows < 1 || n_queries < 1 || k < 1) return 0;
+    return multi_prefilter_plan(n_rows, n_queries, k).total;
+}
+
+extern "C" int hmm_cosine_topk_multi_prefilter(const float* store_dev, const void* shadow_dev, int64_t n_rows, int dim,
+                                               const float* queries_dev, int n_queries, int k, int64_t* idx_out_dev, float* sim_out_dev,
+                                               int32_t* n_out_dev, int32_t* stats_out_dev, void* workspace_dev, size_t workspace_bytes,
+                                               hmm_stream_t stream) {
+    HMM_REQUIRE(dim == HMM_FEATURE_DIM, HMM_E_INVALID, "cosine_topk_multi_prefilter: dim must be %d, got %d", HMM_FEATURE_DIM, dim);
+    HMM_REQUIRE(n_rows >= 1 && n_rows < (int64_t)0xFFFFFFFFll, HMM_E_INVALID, "cosine_topk_multi_prefilter: n_rows=%lld out of range",
+                (long long)n_rows);
+    HMM_REQUIRE(n_queries >= 1 && k >= 1, HMM_E_INVALID, "cosine_topk_multi_prefilter: n_queries=%d k=%d", n_queries, k);
+    HMM_REQUIRE(store_dev && shadow_dev && queries_dev && idx_out_dev && sim_out_dev && workspace_dev, HMM_E_INVALID,
+                "cosine_topk_multi_prefilter: null pointer");
+    HMM_REQUIRE(((uintptr_t)store_dev & 15) == 0 && ((uintptr_t)shadow_dev & 15) == 0 && ((uintptr_t)queries_dev & 15) == 0 &&
+                    ((uintptr_t)workspace_dev & 15) == 0,
+                HMM_E_INVALID, "cosine_topk_multi_prefilter: store / shadow / queries / workspace must be 16-byte aligned");
+    const MultiPrefilterPlan p = multi_prefilter_plan(n_rows, n_queries, k);
+    HMM_REQUIRE(workspace_bytes >= p.total, HMM_E_WORKSPACE, "cosine_topk_multi_prefilter: workspace %zu < required %zu", workspace_bytes,
+                p.total);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace_dev);
+    // small stores, large k: nothing to win (or no list machinery): the exact pass is the whole call
+    if (k > kMMaxK || n_rows < kMPMinRows || n_rows <= k) {
+        if (stats_out_dev) HMM_HIP_CHECK(hipMemsetAsync(stats_out_dev, 0xFF, (size_t)n_queries * 2 * sizeof(int32_t), st));  // -1, -1
+        return hmm_cosine_topk_multi(store_dev, n_rows, dim, queries_dev, n_queries, k, idx_out_dev, sim_out_dev, n_out_dev, ws, p.exact,
+                                     stream);
+    }
+    HMM_ENSURE_DYN_LDS(shadow_multi_kernel<false>, (int)sizeof(ShadowLds));
+    HMM_ENSURE_DYN_LDS(scan_multi_kernel<false>, (int)sizeof(MultiLds));
+    const int kk = mp_list_len(k);
+    const int grid = shadow_multi_grid(n_rows), exact_grid = multi_grid(n_rows);
+    uint64_t* lists = reinterpret_cast<uint64_t*>(ws + p.off_lists);
+    uint64_t* cand = reinterpret_cast<uint64_t*>(ws);
+    int* flag = reinterpret_cast<int*>(ws + p.off_flag);
+    for (int q0 = 0; q0 < n_queries; q0 += kMQ) {                  // 16 queries per pass over the shadow
+        const int nq = n_queries - q0 < kMQ ? n_queries - q0 : kMQ;
+        const float* qp = queries_dev + (size_t)q0 * dim;
+        int64_t* io = idx_out_dev + (size_t)q0 * k;
+        float* so = sim_out_dev + (size_t)q0 * k;
+        int32_t* no = n_out_dev ? n_out_dev + q0 : nullptr;
+        shadow_multi_kernel<false><<<grid, kSWaves * 64, sizeof(ShadowLds), st>>>(static_cast<const uint4*>(shadow_dev), n_rows, qp, nq, kk,
+                                                                                 lists, nullptr, 0, flag);
+        HMM_LAUNCH_CHECK();
+        multi_prefilter_final_kernel<<<nq, kMPFinalThreads, 0, st>>>(lists, grid, k, kk, store_dev, qp, io, so, no, k, flag,
+                                                                     stats_out_dev ? stats_out_dev + 2 * q0 : nullptr);
+        HMM_LAUNCH_CHECK();
+        // the exact pass, conditional on the flag (its workgroups return at once otherwise)
+        scan_multi_kernel<false><<<exact_grid, kMWaves * 64, sizeof(MultiLds), st>>>(store_dev, n_rows, qp, nq, k, cand, nullptr, 0, flag);
+        HMM_LAUNCH_CHECK();
+        topk_final_multi_kernel<<<nq, 1024, 0, st>>>(cand, exact_grid, k, k, io, so, no, k, flag);
+        HMM_LAUNCH_CHECK();
+    }
+    return HMM_OK;
+}
+
+extern "C" size_t hmm_cosine_topk_segmented_multi_prefilter_workspace_bytes(int64_t n_rows, int n_segments, int n_queries, int k) {
+    return hmm_cosine_topk_segmented_multi_workspace_bytes(n_rows, n_segments, n_queries, k);      // s~ of one pass, 16 x 4 B per row
+}
+
+extern "C" int hmm_cosine_topk_segmented_multi_prefilter(const float* store_dev, const void* shadow_dev, int64_t n_rows, int dim,
+                                                         const float* queries_dev, int n_queries, const int64_t* seg_offsets_dev,
+                                                         int n_segments, int k, int64_t* idx_out_dev, float* sim_out_dev,
+                                                         int32_t* n_out_dev, int32_t* stats_out_dev, void* workspace_dev,
+                                                         size_t workspace_bytes, hmm_stream_t stream) {
+    HMM_REQUIRE(dim == HMM_FEATURE_DIM, HMM_E_INVALID, "cosine_topk_segmented_multi_prefilter: dim must be %d, got %d", HMM_FEATURE_DIM,
+                dim);
+    HMM_REQUIRE(n_rows >= 1 && n_rows < (int64_t)0xFFFFFFFFll, HMM_E_INVALID,
+                "cosine_topk_segmented_multi_prefilter: n_rows=%lld out of range", (long long)n_rows);
+    HMM_REQUIRE(n_queries >= 1 && n_segments >= 1 && k >= 1 && k <= 1024, HMM_E_INVALID,
+                "cosine_topk_segmented_multi_prefilter: need n_queries >= 1, n_segments >= 1 and 1 <= k <= 1024 (got %d, %d, k=%d)",
+                n_queries, n_segments, k);
+    HMM_REQUIRE(store_dev && shadow_dev && queries_dev && seg_offsets_dev && idx_out_dev && sim_out_dev && n_out_dev && workspace_dev,
+                HMM_E_INVALID, "cosine_topk_segmented_multi_prefilter: null pointer");
+    HMM_REQUIRE(((uintptr_t)store_dev & 15) == 0 && ((uintptr_t)shadow_dev & 15) == 0 && ((uintptr_t)queries_dev & 15) == 0 &&
+                    ((uintptr_t)workspace_dev & 15) == 0,
+                HMM_E_INVALID, "cosine_topk_segmented_multi_prefilter: store / shadow / queries / workspace must be 16-byte aligned");
+    const size_t need = hmm_cosine_topk_segmented_multi_prefilter_workspace_bytes(n_rows, n_segments, n_queries, k);
+    HMM_REQUIRE(workspace_bytes >= need, HMM_E_WORKSPACE, "cosine_topk_segmented_multi_prefilter: workspace %zu < required %zu",
+                workspace_bytes, need);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // no tournament beyond 64 keys, and nothing to win on events of a few dozen rows: the exact function is the whole call
+    if (k > kMMaxK || n_rows / n_segments < kMPMinSegRows) {
+        if (stats_out_dev) HMM_HIP_CHECK(hipMemsetAsync(stats_out_dev, 0xFF, 2 * sizeof(int32_t), st));                        // -1, -1
+        return hmm_cosine_topk_segmented_multi(store_dev, n_rows, dim, queries_dev, n_queries, seg_offsets_dev, n_segments, k, idx_out_dev,
+                                               sim_out_dev, n_out_dev, workspace_dev, workspace_bytes, stream);
+    }
+    if (stats_out_dev) HMM_HIP_CHECK(hipMemsetAsync(stats_out_dev, 0, 2 * sizeof(int32_t), st));
+    HMM_ENSURE_DYN_LDS(shadow_multi_kernel<true>, (int)sizeof(ShadowLds));
+    const int grid = shadow_multi_grid(n_rows);
+    const int64_t stride = multi_sims_stride(n_rows);
+    float* sims = static_cast<float*>(workspace_dev);
+    const size_t per_query = (size_t)n_segments * k;
+    const bool small = segments_are_small(n_rows, n_segments, k);  // the two shapes of segment_topk_kernel, for the same reason
+    for (int q0 = 0; q0 < n_queries; q0 += kMQ) {                  // 16 queries per pass over the shadow
+        const int nq = n_queries - q0 < kMQ ? n_queries - q0 : kMQ;
+        const float* qp = queries_dev + (size_t)q0 * dim;
+        shadow_multi_kernel<true><<<grid, kSWaves * 64, sizeof(ShadowLds), st>>>(static_cast<const uint4*>(shadow_dev), n_rows, qp, nq, 0,
+                                                                                nullptr, sims, stride, nullptr);
+        HMM_LAUNCH_CHECK();
+        const dim3 sgrid(n_segments, nq);
+        if (small)
+            segment_multi_prefilter_kernel<kSmallSegChunk, 256><<<sgrid, 256, 0, st>>>(
+                sims, stride, seg_offsets_dev, k, store_dev, qp, idx_out_dev + q0 * per_query, sim_out_dev + q0 * per_query,
+                n_out_dev + (size_t)q0 * n_segments, stats_out_dev);
+        else
+            segment_multi_prefilter_kernel<kChunk, 512><<<sgrid, 512, 0, st>>>(
+                sims, stride, seg_offsets_dev, k, store_dev, qp, idx_out_dev + q0 * per_query, sim_out_dev + q0 * per_query,
+                n_out_dev + (size_t)q0 * n_segments, stats_out_dev);
         HMM_LAUNCH_CHECK();
     }
     return HMM_OK;

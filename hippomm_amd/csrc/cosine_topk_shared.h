@@ -80,6 +80,10 @@ bool segments_are_small(int64_t n_rows, int n_segments, int k);
 void launch_segment_topk(const float* sims, int64_t sims_stride, int n_queries, int64_t n_rows, const int64_t* seg_off, int n_segments,
                          int k, int64_t* idx_out, float* sim_out, int32_t* n_out, hipStream_t st);
 
+// An upper bound of hmm_cosine_topk_workspace_bytes(n, k) that is monotone in n and in k (the plan itself is not: it changes shape
+// with min(k, n)); kept beside the plan in cosine_topk.hip so that the two change together.
+size_t cosine_topk_workspace_envelope(int64_t n, int k);
+
 int cosine_topk_if(const int* run_if, unsigned* ticket, const float* store, int64_t n, const float* query, int k, int64_t* idx_out,
                    float* sim_out, int32_t* n_out, void* ws, size_t ws_bytes, hipStream_t st);
 

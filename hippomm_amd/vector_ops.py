@@ -186,14 +186,19 @@ class FeatureStore:
                                                  _lib.stream_ptr()), "hmm_cosine_topk_segmented")
         return packed, idx, sims, counts
 
-    def search_segments_multi_device(self, queries, seg_offsets: torch.Tensor, k: int):
+    def search_segments_multi_device(self, queries, seg_offsets: torch.Tensor, k: int, prefilter: bool = False,
+                                     stats: torch.Tensor = None):
         """``search_segments_device`` for a batch of questions in one pass over the store per 16 of them
         (hmm_cosine_topk_segmented_multi).  queries: (Q,1024) numpy or torch, any device, fp32 or fp64.  Returns CUDA tensors
         idx (Q,E,k) int64 rows within each event (-1 padded), sims (Q,E,k) fp32, counts (Q,E) int32 = min(k, n_e), without
-        synchronising."""
-        return self._search_segments_multi_packed(queries, seg_offsets, k)[1:]
+        synchronising.  ``prefilter``: stream the bf16 shadow (built on first use) and re-score each event's candidates on the
+        fp32 rows -- the same outputs, bit for bit (hmm_cosine_topk_segmented_multi_prefilter); ``stats``: optional int32[2]
+        CUDA tensor receiving ((event, question) pairs that re-scored the whole event, rows re-scored), -1 / -1 when the exact
+        function was the whole call."""
+        return self._search_segments_multi_packed(queries, seg_offsets, k, prefilter, stats)[1:]
 
-    def _search_segments_multi_packed(self, queries, seg_offsets: torch.Tensor, k: int):
+    def _search_segments_multi_packed(self, queries, seg_offsets: torch.Tensor, k: int, prefilter: bool = False,
+                                      stats: torch.Tensor = None):
         """search_segments_multi_device, returning (packed, idx, sims, counts): the three outputs are views of `packed`."""
         dev = self.rows.device
         q = queries if isinstance(queries, torch.Tensor) else torch.from_numpy(np.asarray(queries))
@@ -217,6 +222,16 @@ class FeatureStore:
             counts.zero_()
             return packed, idx, sims, counts
         lib = _lib.load()
+        if prefilter:
+            self.build_shadow()
+            need = lib.hmm_cosine_topk_segmented_multi_prefilter_workspace_bytes(len(self), E, Q, k)
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            _lib.check(lib.hmm_cosine_topk_segmented_multi_prefilter(
+                self.rows.data_ptr(), self._shadow.data_ptr(), len(self), FEATURE_DIM, q.data_ptr(), Q, seg_offsets.data_ptr(), E, k,
+                idx.data_ptr(), sims.data_ptr(), counts.data_ptr(), stats.data_ptr() if stats is not None else None,
+                self._ws.data_ptr(), self._ws.numel(), _lib.stream_ptr()), "hmm_cosine_topk_segmented_multi_prefilter")
+            return packed, idx, sims, counts
         need = lib.hmm_cosine_topk_segmented_multi_workspace_bytes(len(self), E, Q, k)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
@@ -226,9 +241,13 @@ class FeatureStore:
                                                        _lib.stream_ptr()), "hmm_cosine_topk_segmented_multi")
         return packed, idx, sims, counts
 
-    def search_multi_device(self, queries: torch.Tensor, k: int):
+    def search_multi_device(self, queries: torch.Tensor, k: int, prefilter: bool = None, stats: torch.Tensor = None):
         """queries (Q,1024) fp32 on the store's device -> (idx (Q,k') int64, sims (Q,k') fp32) device tensors,
-        k' = min(k, N).  One pass over the store per 16 queries (hmm_cosine_topk_multi)."""
+        k' = min(k, N).  One pass over the store per 16 queries (hmm_cosine_topk_multi).  ``prefilter=True``: one pass over the
+        bf16 shadow instead, candidates re-scored on the fp32 rows -- the same outputs, bit for bit
+        (hmm_cosine_topk_multi_prefilter).  ``None`` is the exact pass even on a store built with ``shadow=True``: the shadow
+        route has not been timed against it yet, and the results are the same either way; ``stats``: optional int32 (Q,2) CUDA tensor receiving per
+        question (candidates re-scored, saturated lists), -1 / -1 when the exact function was the whole call."""
         if queries.dim() != 2 or queries.shape[1] != FEATURE_DIM:
             raise ValueError(f"queries must be (Q,{FEATURE_DIM}), got {tuple(queries.shape)}")
         queries = queries.to(device=self.rows.device, dtype=torch.float32).contiguous()
@@ -236,23 +255,37 @@ class FeatureStore:
         if nq == 0:
             raise ValueError("no queries")
         lib = _lib.load()
+        if prefilter is None:                                   # not self.use_shadow until tools/multi_prefilter_probe.py has placed the limits
+            prefilter = False
+        idx = torch.empty(nq, k, dtype=torch.int64, device=self.rows.device)
+        sims = torch.empty(nq, k, dtype=torch.float32, device=self.rows.device)
+        n_out = torch.empty(nq, dtype=torch.int32, device=self.rows.device)
+        if prefilter and n > 0:
+            self.build_shadow()
+            need = lib.hmm_cosine_topk_multi_prefilter_workspace_bytes(n, nq, k)
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=self.rows.device)
+            _lib.check(lib.hmm_cosine_topk_multi_prefilter(
+                self.rows.data_ptr(), self._shadow.data_ptr(), n, FEATURE_DIM, queries.data_ptr(), nq, k, idx.data_ptr(),
+                sims.data_ptr(), n_out.data_ptr(), stats.data_ptr() if stats is not None else None, self._ws.data_ptr(),
+                self._ws.numel(), _lib.stream_ptr()), "hmm_cosine_topk_multi_prefilter")
+            kk = min(k, n)
+            return idx[:, :kk], sims[:, :kk]
         need = lib.hmm_cosine_topk_multi_workspace_bytes(n, nq, k)
         if self._ws is None or self._ws.numel() < need:      # kept between calls, like the single-query workspace
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.rows.device)
         ws = self._ws
-        idx = torch.empty(nq, k, dtype=torch.int64, device=self.rows.device)
-        sims = torch.empty(nq, k, dtype=torch.float32, device=self.rows.device)
-        n_out = torch.empty(nq, dtype=torch.int32, device=self.rows.device)
         _lib.check(lib.hmm_cosine_topk_multi(self.rows.data_ptr(), n, FEATURE_DIM, queries.data_ptr(), nq, k,
                                                    idx.data_ptr(), sims.data_ptr(), n_out.data_ptr(), ws.data_ptr(),
                                                    ws.numel(), _lib.stream_ptr()), "hmm_cosine_topk_multi")
         kk = min(k, n)
         return idx[:, :kk], sims[:, :kk]
 
-    def search_multi(self, queries, k: int) -> List[Tuple[np.ndarray, np.ndarray]]:
-        """Per query the (indices int64, similarities) pair top_k_cosine_similarity would return."""
+    def search_multi(self, queries, k: int, prefilter: bool = None) -> List[Tuple[np.ndarray, np.ndarray]]:
+        """Per query the (indices int64, similarities) pair top_k_cosine_similarity would return.  ``prefilter``: see
+        ``search_multi_device``."""
         q = queries if isinstance(queries, torch.Tensor) else torch.from_numpy(np.asarray(queries, dtype=np.float32))
-        idx, sims = self.search_multi_device(q.reshape(-1, FEATURE_DIM), k)
+        idx, sims = self.search_multi_device(q.reshape(-1, FEATURE_DIM), k, prefilter)
         idx, sims = idx.cpu().numpy(), sims.cpu().numpy()
         return [(idx[i], sims[i]) for i in range(idx.shape[0])]
 
@@ -501,14 +534,15 @@ class EventStore(FeatureStore):
         torch.cuda.current_stream(packed.device).synchronize()
         return host.numpy()
 
-    def top_k_per_event_multi(self, queries, k: int = 5):
+    def top_k_per_event_multi(self, queries, k: int = 5, prefilter: bool = False):
         """``top_k_per_event`` for a batch of questions: per query the list that ``top_k_per_event(query, k)`` returns, from one
-        pass over the store per 16 questions and one read-back."""
+        pass over the store per 16 questions and one read-back.  ``prefilter``: through the bf16 shadow, the same results
+        (``search_segments_multi_device``)."""
         q = self._queries_2d(queries)
         Q, E, k = q.shape[0], len(self.lengths), int(k)
         if E == 0 or len(self) == 0:
             return [[(np.zeros(0, np.int64), np.zeros(0, np.float32)) for _ in range(E)] for _ in range(Q)]
-        packed = self._search_segments_multi_packed(q, self.offsets, k)[0]
+        packed = self._search_segments_multi_packed(q, self.offsets, k, prefilter)[0]
         raw = self._read_back(packed)
         idx_h = raw[: Q * E * k * 8].view(np.int64).reshape(Q, E, k).copy()
         sims_h = raw[Q * E * k * 8: Q * E * k * 12].view(np.float32).reshape(Q, E, k).copy()
@@ -517,17 +551,18 @@ class EventStore(FeatureStore):
             return [list(zip(idx_h[qi], sims_h[qi])) for qi in range(Q)]
         return [[(idx_h[qi, e, :counts_h[e]], sims_h[qi, e, :counts_h[e]]) for e in range(E)] for qi in range(Q)]
 
-    def top_hits_multi(self, queries, k: int = 5, keep: int = 5):
+    def top_hits_multi(self, queries, k: int = 5, keep: int = 5, prefilter: bool = False):
         """``top_hits`` for a batch of questions: per query the list that ``top_hits(query, k, keep)`` returns.  One pass over the
         store per 16 questions, one ranking launch for all of them (hmm_rank_segment_hits_multi), one read-back of Q x `keep`
-        hits.  keep > 64 is served by ``top_hits`` per query."""
+        hits.  keep > 64 is served by ``top_hits`` per query.  ``prefilter``: the pass streams the bf16 shadow, the same results
+        (``search_segments_multi_device``)."""
         q = self._queries_2d(queries)
         Q, E, k, keep = q.shape[0], len(self.lengths), int(k), int(keep)
         if E == 0 or len(self) == 0 or keep < 1:
             return [[] for _ in range(Q)]
         if keep > 64:
-            return [self.top_hits(q[qi], k, keep) for qi in range(Q)]
-        idx, sims, counts = self.search_segments_multi_device(q, self.offsets, k)
+            return [self.top_hits(q[qi], k, keep, prefilter) for qi in range(Q)]
+        idx, sims, counts = self.search_segments_multi_device(q, self.offsets, k, prefilter)
         lib = _lib.load()
         packed = torch.empty(Q * (keep * 20 + 4), dtype=torch.uint8, device=idx.device)      # event | row | sim | count
         ev = packed[: Q * keep * 8].view(torch.int64)

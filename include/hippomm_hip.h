@@ -170,6 +170,40 @@ int    hmm_cosine_topk_segmented_multi(const float* store_dev, int64_t n_rows, i
                                        int64_t* idx_out_dev, float* sim_out_dev, int32_t* n_out_dev,
                                        void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
 
+/* hmm_cosine_topk_multi through the bf16 shadow (hmm_shadow_store_build; the shadow's format is unchanged): one pass over 2048 B per
+ * row per 16 questions on the bf16 matrix cores (each question split into bf16 hi + lo), per question every row that can be among
+ * its k best under a proven error bound (|s~ - s| < 0.0042) re-scored on the fp32 store with the arithmetic of hmm_cosine_topk_multi,
+ * the k best returned: the SAME indices, similarity bits and counts as hmm_cosine_topk_multi.  When a question's candidate set is
+ * not provably complete (thousands of near-ties, a zero or NaN question) the exact pass answers for the 16 questions of that pass,
+ * inside the same call, decided on the device.  k > 64, fewer than 16384 rows or n_rows <= k: the call IS hmm_cosine_topk_multi.
+ * stats_out_dev (may be null) int32[n_queries][2]: per question, candidates re-scored and saturated workgroup lists (-1, -1 in every
+ * slot when the call was the exact function); a non-zero second entry or more than 1024 candidates means the exact pass answered
+ * for that question's pass.  Layouts, the precondition on the rows' norms and the snapshot rule are those of hmm_cosine_topk_multi and
+ * hmm_cosine_topk_prefilter.  The workspace holds the exact function's and must be 16-byte aligned. */
+size_t hmm_cosine_topk_multi_prefilter_workspace_bytes(int64_t n_rows, int n_queries, int k);
+int    hmm_cosine_topk_multi_prefilter(const float* store_dev, const void* shadow_dev, int64_t n_rows, int dim,
+                                       const float* queries_dev, int n_queries, int k,
+                                       int64_t* idx_out_dev, float* sim_out_dev, int32_t* n_out_dev,
+                                       int32_t* stats_out_dev /* nullable, int32[n_queries][2] */,
+                                       void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
+
+/* hmm_cosine_topk_segmented_multi through the shadow: the same pass writes the approximate similarities of 16 questions (64 B per
+ * row, the exact function's workspace), then per (event, question) the rows that can be among the event's k best (same bound) are
+ * re-scored on the fp32 store -- every row of an event whose candidates do not fit (an event of near-identical rows).  Same
+ * outputs as hmm_cosine_topk_segmented_multi, bit for bit.  k > 64, or events of fewer than 128 rows on average: the call IS
+ * hmm_cosine_topk_segmented_multi.  stats_out_dev (may be null) int32[2]: (event, question) pairs that re-scored the whole event,
+ * and rows re-scored in all (-1, -1 when the call was the exact function); a diagnostic: the second is an int32 sum over all pairs
+ * and passes and may wrap on millions of near-identical rows.  Both dispatch limits (here and in hmm_cosine_topk_multi_prefilter)
+ * are those of the single-question functions and have not been timed for a batch yet: tools/multi_prefilter_probe.py places them,
+ * and until it has run no Python call takes these two routes unless asked to (prefilter=True). */
+size_t hmm_cosine_topk_segmented_multi_prefilter_workspace_bytes(int64_t n_rows, int n_segments, int n_queries, int k);
+int    hmm_cosine_topk_segmented_multi_prefilter(const float* store_dev, const void* shadow_dev, int64_t n_rows, int dim,
+                                                 const float* queries_dev, int n_queries,
+                                                 const int64_t* seg_offsets_dev, int n_segments, int k,
+                                                 int64_t* idx_out_dev, float* sim_out_dev, int32_t* n_out_dev,
+                                                 int32_t* stats_out_dev /* nullable, int32[2] */,
+                                                 void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
+
 /* hmm_rank_segment_hits for every question of a batch in one launch: inputs are the three outputs of
  * hmm_cosine_topk_segmented_multi, (n_queries, n_segments, k) / (n_queries, n_segments); per question q the best
  * keep' = min(keep, its number of hits) hits at event_out[q*keep ..], row_out[q*keep ..], sim_out[q*keep ..] (-1 / -1 / 0 padded to
