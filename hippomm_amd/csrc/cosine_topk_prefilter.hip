@@ -45,27 +45,8 @@ __global__ __launch_bounds__(256) void shadow_build_kernel(const float4* __restr
     for (int64_t r = wave; r < n_rows; r += n_waves) {
         // lane l owns elements 8 l .. 8 l + 7 and 512 + 8 l .. + 7 (two 32-B pieces in, two 16-B pieces out)
         const float4* p = store + r * 256;
-        float4 v[4] = {p[2 * lane], p[2 * lane + 1], p[128 + 2 * lane], p[128 + 2 * lane + 1]};
-        float ss = 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            ss = fmaf(v[i].x, v[i].x, ss); ss = fmaf(v[i].y, v[i].y, ss);
-            ss = fmaf(v[i].z, v[i].z, ss); ss = fmaf(v[i].w, v[i].w, ss);
-        }
-        ss = wave_sum(ss);
-        float inv = 1.0f / sqrtf(ss);
-        if (!(ss > 0.f) || !(ss < INFINITY)) inv = __uint_as_float(0x7FC00000u);      // zero / non-finite norm: the row is NaN
-        uint4 o[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const float4 a = v[2 * h], b = v[2 * h + 1];
-            bf16x8 t = {(bf16_t)(a.x * inv), (bf16_t)(a.y * inv), (bf16_t)(a.z * inv), (bf16_t)(a.w * inv),
-                        (bf16_t)(b.x * inv), (bf16_t)(b.y * inv), (bf16_t)(b.z * inv), (bf16_t)(b.w * inv)};
-            o[h] = __builtin_bit_cast(uint4, t);
-        }
-        uint4* q = shadow + r * 128;
-        q[lane] = o[0];
-        q[64 + lane] = o[1];
+        const float4 v[4] = {p[2 * lane], p[2 * lane + 1], p[128 + 2 * lane], p[128 + 2 * lane + 1]};
+        shadow_row_store(v, lane, shadow + r * 128);          // the row's arithmetic: cosine_topk_shared.h (shared with the ingest)
     }
 }
 

@@ -72,6 +72,32 @@ __device__ __forceinline__ void exact_row_sim4(const float4* const (&row_lane)[4
     }
 }
 
+// One row of the bf16 shadow, as hmm_shadow_store_build DEFINES its bits, from the registers of one wave: lane l holds elements
+// 8 l .. 8 l + 7 (v[0], v[1]) and 512 + 8 l .. + 7 (v[2], v[3]) of the fp32 row -- two 32-B pieces in, two 16-B pieces out.
+// shadow_row_out: the row's 2048 bytes.  shadow_build_kernel (cosine_topk_prefilter.hip) and store_ingest_kernel
+// (store_ingest.hip) both call it: a row ingested into a store gets the shadow row a whole build would give it.
+__device__ __forceinline__ void shadow_row_store(const float4 (&v)[4], int lane, uint4* __restrict__ shadow_row_out) {
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        ss = fmaf(v[i].x, v[i].x, ss); ss = fmaf(v[i].y, v[i].y, ss);
+        ss = fmaf(v[i].z, v[i].z, ss); ss = fmaf(v[i].w, v[i].w, ss);
+    }
+    ss = wave_sum(ss);
+    float inv = 1.0f / sqrtf(ss);
+    if (!(ss > 0.f) || !(ss < INFINITY)) inv = __uint_as_float(0x7FC00000u);      // zero / non-finite norm: the row is NaN
+    uint4 o[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const float4 a = v[2 * h], b = v[2 * h + 1];
+        bf16x8 t = {(bf16_t)(a.x * inv), (bf16_t)(a.y * inv), (bf16_t)(a.z * inv), (bf16_t)(a.w * inv),
+                    (bf16_t)(b.x * inv), (bf16_t)(b.y * inv), (bf16_t)(b.z * inv), (bf16_t)(b.w * inv)};
+        o[h] = __builtin_bit_cast(uint4, t);
+    }
+    shadow_row_out[lane] = o[0];
+    shadow_row_out[64 + lane] = o[1];
+}
+
 // The per-event selection kernels come in two shapes (see segment_topk_kernel): true when the small one serves this call.
 constexpr int kSmallSegChunk = 1024;
 bool segments_are_small(int64_t n_rows, int n_segments, int k);

@@ -13,9 +13,10 @@ stored fp32, float64 arrays after loading.  That file format is the contract wit
                      identical either way: the JSON holds fp32 values printed as doubles, and
                      ``float32(float64(text))`` round-trips them exactly (SURVEY 5.4b);
 * ``build_event_store``  reads ``event_index.json`` (:338-346) and returns an ``EventStore`` with one modality's
-                     matrices of all events resident in HBM, ready for ``top_k_per_event``.
+                     matrices of all events resident in HBM, ready for ``top_k_per_event``;
+* ``refresh_event_store``  appends the events the index gained since to that resident store, and drops the ones it lost.
 
-Nothing here touches the GPU except ``build_event_store``.
+Nothing here touches the GPU except ``build_event_store`` and ``refresh_event_store``.
 """
 from __future__ import annotations
 
@@ -323,11 +324,39 @@ def build_event_store(memory_store_dir, modality: str = "vision", device=None, w
         loaded = [load_event_features(path) for _, path in files]
     ids, mats = [], []
     for (event_id, path), feats in zip(files, loaded):
-        a = feats.get(modality)
-        if a is not None and a.ndim == 1 and a.shape[0] == 1024:
-            a = a.reshape(1, 1024)                   # top_k_cosine_similarity treats a 1-D feature as one row (vector_ops.py:173-174)
-        if a is None or a.ndim != 2 or a.shape[1] != 1024:
-            a = np.zeros((0, 1024), np.float32)
         ids.append(event_id)
-        mats.append(a)
+        mats.append(_modality_matrix(feats, modality))
     return EventStore(mats, device), ids
+
+
+def _modality_matrix(feats: Mapping[str, np.ndarray], modality: str) -> np.ndarray:
+    """One event's segment of an EventStore: its ``modality`` matrix, a 1-D feature as one row, and an empty segment when the
+    modality is missing or its width is not 1024."""
+    a = feats.get(modality)
+    if a is not None and a.ndim == 1 and a.shape[0] == 1024:
+        a = a.reshape(1, 1024)                       # top_k_cosine_similarity treats a 1-D feature as one row (vector_ops.py:173-174)
+    if a is None or a.ndim != 2 or a.shape[1] != 1024:
+        a = np.zeros((0, 1024), np.float32)
+    return a
+
+
+def refresh_event_store(store, ids, memory_store_dir, modality: str = "vision"):
+    """Bring a resident EventStore up to date with ``event_index.json`` after ``save_theta_event`` wrote new events: the events
+    of the index that are not in ``ids`` yet are appended on the device (``EventStore.extend``: the rows already resident are
+    neither re-read nor re-uploaded, a shadow is kept current), events that vanished from the index are removed
+    (``EventStore.remove_events``).  Returns the new id list; ``store`` and the list equal what ``build_event_store`` returns
+    for the same index as long as the index only grew at its end or lost entries, which is how the reference writes it
+    (hippocampal_memory.py:338-346).  A missing modality, a 1-D feature and a wrong width are handled as there.  An event whose
+    file changed under an id that stays is not noticed: use ``EventStore.replace_event``."""
+    files = list(iter_event_files(memory_store_dir))
+    in_index = {event_id for event_id, _ in files}
+    gone = [pos for pos, event_id in enumerate(ids) if event_id not in in_index]
+    if gone:
+        store.remove_events(gone)
+    new_ids = [event_id for event_id in ids if event_id in in_index]
+    have = set(new_ids)
+    fresh = [(event_id, path) for event_id, path in files if event_id not in have]
+    if fresh:
+        store.extend([_modality_matrix(load_event_features(path), modality) for _, path in fresh])
+        new_ids += [event_id for event_id, _ in fresh]
+    return new_ids

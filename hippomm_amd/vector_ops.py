@@ -584,3 +584,225 @@ class EventStore(FeatureStore):
         if buf is None or buf.numel() < nbytes:
             buf = self._pinned = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, pin_memory=True)
         return buf[:nbytes]
+
+    # ---- a store that grows: append, replace and drop events on the device ----------------------------------------------------
+    # The constructor and from_device_rows leave `rows` as they always did (an exact-size upload, or the caller's tensor).  The
+    # first mutating call moves the store into buffers it owns: `_buf`, (capacity, 1024) fp32, and -- once a shadow exists --
+    # `_shadow_buf`, capacity * 2048 bytes.  `rows` stays a contiguous view of the first n rows and `_shadow` of the first
+    # n * 2048 bytes, `offsets` and `lengths` keep their meaning, so every search method above works unchanged on a grown store and
+    # returns what a fresh EventStore of the same events returns, bit for bit.  New rows are written by hmm_store_ingest_rows
+    # (fp32 rows and their shadow rows in one launch), events are moved by hmm_store_gather_segments.  Everything is enqueued on
+    # the current stream and nothing synchronises the device; a mutating call makes one small host-to-device copy (the offsets,
+    # from pinned memory) plus the upload of a source that lives on the host.  Single-threaded use, like the rest of the class.
+
+    @property
+    def capacity(self) -> int:
+        """Rows the store holds without moving (its row count while it still aliases the tensor it was built from)."""
+        buf = getattr(self, "_buf", None)
+        return len(self) if buf is None else buf.shape[0]
+
+    def _rows_version(self) -> int:
+        try:
+            return self.rows._version
+        except (RuntimeError, AttributeError):       # an inference tensor tracks no version (see FeatureStore.build_shadow)
+            return 0
+
+    def _shadow_is_current(self) -> bool:
+        """True when a shadow exists and matches the rows.  A stale one (the rows were edited through torch since) is dropped:
+        the next prefiltered search rebuilds it whole, as it would have anyway."""
+        if getattr(self, "_shadow", None) is None:
+            return False
+        version = self._rows_version()
+        if getattr(self, "_shadow_version", version) != version:
+            self._shadow = None
+            return False
+        return True
+
+    def build_shadow(self, force: bool = False):
+        """FeatureStore.build_shadow; on a store that owns its buffers the shadow is built into the capacity-sized buffer, where
+        later appends keep it current row by row (an append never rebuilds it).  The ingest and the gather write rows behind
+        torch's back AND their shadow rows with them, so the version the shadow was built at stays the one it is checked
+        against; edits of ``rows`` made through torch still bump it and cause a rebuild."""
+        buf = getattr(self, "_buf", None)
+        if buf is None:
+            return super().build_shadow(force)
+        version = self._rows_version()
+        if force or getattr(self, "_shadow", None) is None or getattr(self, "_shadow_version", version) != version:
+            n = len(self)
+            if getattr(self, "_shadow_buf", None) is None or self._shadow_buf.numel() != buf.shape[0] * 2048:
+                self._shadow_buf = torch.empty(buf.shape[0] * 2048, dtype=torch.uint8, device=buf.device)
+            if n > 0:
+                _lib.check(_lib.load().hmm_shadow_store_build(buf.data_ptr(), n, FEATURE_DIM, self._shadow_buf.data_ptr(), n * 2048,
+                                                              _lib.stream_ptr()), "hmm_shadow_store_build")
+            self._shadow = self._shadow_buf[: n * 2048]
+            self._shadow_version = version
+        return self
+
+    def _set_buffers(self, buf: torch.Tensor, shadow_buf, n: int, shadow: bool):
+        self._buf, self._shadow_buf = buf, shadow_buf
+        self.rows = buf[:n]
+        self._shadow = shadow_buf[: n * 2048] if shadow else None
+        if shadow:
+            self._shadow_version = self._rows_version()
+
+    def _new_buffers(self, capacity: int, shadow: bool):
+        dev = self.rows.device
+        return (torch.empty(capacity, FEATURE_DIM, dtype=torch.float32, device=dev),
+                torch.empty(capacity * 2048, dtype=torch.uint8, device=dev) if shadow else None)
+
+    def _move_to(self, capacity: int, shadow: bool):
+        """Owned buffers of `capacity` rows holding the present rows (and shadow): two device-to-device copies."""
+        n = len(self)
+        buf, shadow_buf = self._new_buffers(capacity, shadow)
+        if n > 0:
+            buf[:n].copy_(self.rows)
+            if shadow:
+                shadow_buf[: n * 2048].copy_(self._shadow[: n * 2048])
+        self._set_buffers(buf, shadow_buf, n, shadow)
+
+    def _grown(self, needed: int) -> int:
+        return max(int(needed), 2 * self.capacity, 1)
+
+    def reserve(self, rows: int):
+        """Grow the capacity to at least `rows` rows now (existing rows and shadow are copied device to device; both buffers exist
+        side by side until the old one is released), so that later appends up to that size write nothing but their own rows and
+        ``rows.data_ptr()`` stays put.  A store built by the constructor or by ``from_device_rows`` moves into buffers of its own."""
+        rows = int(rows)
+        if rows < 0:
+            raise ValueError("rows must be >= 0")
+        if rows > self.capacity:
+            self._move_to(rows, self._shadow_is_current())
+        return self
+
+    def _source_rows(self, features) -> torch.Tensor:
+        """The rows of one event as a contiguous (n,1024) fp32 or fp64 tensor on the store's device: a device tensor stays where
+        it lies, a host array is uploaded as it is (fp64 is narrowed by the ingest kernel, not by numpy), any other dtype is
+        converted to fp32 first, as the constructor converts it."""
+        if isinstance(features, torch.Tensor):
+            t = features.detach()
+            if t.dtype not in (torch.float32, torch.float64):
+                t = t.to(torch.float32)
+        else:
+            a = np.asarray(features)
+            if a.dtype not in (np.float32, np.float64):
+                a = a.astype(np.float32)
+            t = torch.from_numpy(np.ascontiguousarray(a))
+        if t.numel() == 0:
+            return torch.empty(0, FEATURE_DIM, dtype=torch.float32, device=self.rows.device)
+        if t.dim() == 1 and t.shape[0] == FEATURE_DIM:
+            t = t.reshape(1, FEATURE_DIM)
+        if t.dim() != 2 or t.shape[1] != FEATURE_DIM:
+            raise ValueError(f"event features must be (n,{FEATURE_DIM}) or ({FEATURE_DIM},), got {tuple(t.shape)}")
+        t = t.to(self.rows.device).contiguous()
+        buf = getattr(self, "_buf", None)
+        for mine in (self.rows if buf is None else buf, getattr(self, "_shadow_buf", None)):
+            if mine is not None and mine.numel() > 0:
+                a0, b0 = t.data_ptr(), mine.data_ptr()
+                if a0 < b0 + mine.numel() * mine.element_size() and b0 < a0 + t.numel() * t.element_size():
+                    raise ValueError("the source overlaps the store's own buffer: clone it first")
+        return t
+
+    def _upload_tables(self, lengths, src_segment=None):
+        """offsets (int64, E + 1) and, for a gather, the source segment of every destination segment (int32, E): one pinned
+        buffer, one asynchronous copy."""
+        off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+        seg = np.asarray(src_segment if src_segment is not None else [], dtype=np.int32)
+        host = torch.from_numpy(np.concatenate([off.view(np.uint8), seg.view(np.uint8)])).pin_memory()
+        dev = host.to(self.rows.device, non_blocking=True)
+        return dev[: off.nbytes].view(torch.int64), dev[off.nbytes:].view(torch.int32)
+
+    def _ingest(self, src: torch.Tensor, at: int, shadow: bool):
+        if src.shape[0] == 0:
+            return
+        _lib.check(_lib.load().hmm_store_ingest_rows(src.data_ptr(), 1 if src.dtype == torch.float64 else 0, src.shape[0], FEATURE_DIM,
+                                                     self._buf.data_ptr(), self._shadow_buf.data_ptr() if shadow else None,
+                                                     self._buf.shape[0], at, _lib.stream_ptr()), "hmm_store_ingest_rows")
+
+    def append_event(self, features) -> int:
+        """Append one event and return its index.  ``features``: numpy or torch, host or device, (n,1024), a 1-D (1024,) row or
+        an empty matrix, float32 or float64 (another dtype is converted to float32 first; another width is a ValueError).  A
+        device tensor is ingested where it lies -- no host trip -- and float64 is narrowed on the device, to the bits
+        ``astype(np.float32)`` gives.  While the rows fit the capacity nothing but the new rows (and their shadow rows, when the
+        store has a shadow) is written and ``rows.data_ptr()`` does not change; otherwise the capacity becomes
+        max(needed, 2 x capacity) and the store moves (see ``reserve``).  The result is the store -- rows, offsets, shadow --
+        that ``EventStore(all events)`` builds."""
+        return self.extend([features])[0]
+
+    def extend(self, list_of_features):
+        """``append_event`` for several events: at most one move, one ingest launch per event, one offsets update.  Returns the
+        new events' indices."""
+        srcs = [self._source_rows(f) for f in list_of_features]
+        first = len(self.lengths)
+        if not srcs:
+            return []
+        n = len(self)
+        needed = n + sum(s.shape[0] for s in srcs)
+        shadow = self._shadow_is_current()
+        if getattr(self, "_buf", None) is None or needed > self._buf.shape[0]:
+            self._move_to(self._grown(needed), shadow)
+        at = n
+        for s in srcs:
+            self._ingest(s, at, shadow)
+            at += s.shape[0]
+        self.lengths = list(self.lengths) + [int(s.shape[0]) for s in srcs]
+        self.offsets = self._upload_tables(self.lengths)[0]
+        self._set_buffers(self._buf, self._shadow_buf, needed, shadow)
+        return list(range(first, first + len(srcs)))
+
+    def _regather(self, src_segment, new_lengths):
+        """Rebuild the store out of place: destination event j takes the rows of present event src_segment[j], or stays a hole
+        of new_lengths[j] rows (-1)."""
+        needed = int(sum(new_lengths))
+        shadow = self._shadow_is_current()
+        owned = getattr(self, "_buf", None) is not None
+        capacity = max(self.capacity, 1) if needed <= self.capacity else self._grown(needed)
+        offsets, seg = self._upload_tables(new_lengths, src_segment)
+        copies = any(s >= 0 and n > 0 for s, n in zip(src_segment, new_lengths))
+        if copies or not owned or capacity != self.capacity:
+            buf, shadow_buf = self._new_buffers(capacity, shadow)
+        else:                                                    # nothing survives and the buffers fit: they are reused
+            buf, shadow_buf = self._buf, self._shadow_buf
+        if copies:
+            _lib.check(_lib.load().hmm_store_gather_segments(
+                self.rows.data_ptr(), self._shadow.data_ptr() if shadow else None, len(self), self.offsets.data_ptr(),
+                len(self.lengths), seg.data_ptr(), offsets.data_ptr(), len(new_lengths), FEATURE_DIM, buf.data_ptr(),
+                shadow_buf.data_ptr() if shadow else None, needed, capacity, _lib.stream_ptr()), "hmm_store_gather_segments")
+        self.lengths = [int(n) for n in new_lengths]
+        self.offsets = offsets
+        self._set_buffers(buf, shadow_buf, needed, shadow)
+
+    def remove_events(self, indices):
+        """Drop the events at ``indices`` (negative ones count from the end); later events shift down, as ``del`` on the list
+        would.  The survivors are gathered out of place into a second buffer of the same capacity and the old one is released,
+        so for the length of the call the store takes twice its memory (no workgroup ever waits for another one's copy).  An
+        index out of range (IndexError) or named twice (ValueError) raises before anything is launched."""
+        E = len(self.lengths)
+        drop = set()
+        for i in indices:
+            j = int(i)
+            if j != i or not -E <= j < E:
+                raise IndexError(f"event index {i!r} out of range for {E} events")
+            j += E if j < 0 else 0
+            if j in drop:
+                raise ValueError(f"event {j} is named twice")
+            drop.add(j)
+        if not drop:
+            return self
+        keep = [j for j in range(E) if j not in drop]
+        self._regather(keep, [self.lengths[j] for j in keep])
+        return self
+
+    def replace_event(self, i: int, features):
+        """Event ``i`` gets new rows, of any length, and keeps its index: a gather with a hole at ``i`` (out of place, transient
+        2 x memory as in ``remove_events``), then an ingest into the hole."""
+        E = len(self.lengths)
+        j = int(i)
+        if j != i or not -E <= j < E:
+            raise IndexError(f"event index {i!r} out of range for {E} events")
+        j += E if j < 0 else 0
+        src = self._source_rows(features)
+        lengths = list(self.lengths)
+        lengths[j] = int(src.shape[0])
+        self._regather([-1 if e == j else e for e in range(E)], lengths)
+        self._ingest(src, int(sum(lengths[:j])), self._shadow is not None)
+        return self

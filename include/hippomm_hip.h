@@ -122,6 +122,34 @@ int    hmm_cosine_topk_segmented_prefilter(const float* store_dev, const void* s
                                            int64_t* idx_out_dev, float* sim_out_dev, int32_t* n_out_dev,
                                            void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
 
+/* A store that grows on the device (EventStore.append_event / remove_events / replace_event): the caller owns a buffer of
+ * capacity_rows fp32 rows and, optionally, one of capacity_rows * 2048 bytes for the shadow; these two calls fill them.
+ *
+ * hmm_store_ingest_rows: src_dtype: 0 = fp32, 1 = fp64.  Writes rows [row_offset, row_offset + n_new) of store_dev and, when
+ * shadow_dev is not null, the same rows of the shadow.  Touches no other byte of either buffer.  An fp32 source is copied bit
+ * for bit; an fp64 source is narrowed with round-to-nearest-even (ndarray.astype(float32)); the shadow rows have the bits
+ * hmm_shadow_store_build gives those rows.  One pass: 4 KB (8 KB) read, 4 KB + 2 KB written per row.
+ *
+ * hmm_store_gather_segments: out of place.  Destination segment j (rows dst_offsets[j] .. dst_offsets[j+1]) receives source
+ * segment src_segment[j] (rows src_offsets[s] .. src_offsets[s+1]), or is left untouched when src_segment[j] == -1 (a hole the
+ * caller fills with hmm_store_ingest_rows).  Shadow rows travel with their fp32 rows when both shadow pointers are given; both
+ * null is allowed, one null is an error.  Segments of equal length are the caller's precondition; a segment copies
+ * min(destination length, source length) rows, reads nothing outside its source segment or beyond src_rows and writes nothing
+ * outside its destination segment or at or beyond dst_rows.
+ *
+ * Both: n_new == 0, n_dst == 0 or dst_rows == 0 return HMM_OK without a launch and without looking at a pointer.  Otherwise
+ * HMM_E_INVALID, before anything is launched, for dim != 1024, an unknown src_dtype, a negative count, row_offset + n_new >
+ * capacity_rows, dst_rows > dst_capacity_rows, a null pointer, a row pointer that is not 16-byte aligned, or a source byte range
+ * that overlaps the bytes to be written.  No workspace; nothing is allocated, copied or synchronised. */
+int    hmm_store_ingest_rows(const void* src_dev, int src_dtype, int64_t n_new, int dim,
+                             float* store_dev, void* shadow_dev /* nullable */,
+                             int64_t capacity_rows, int64_t row_offset, hmm_stream_t stream);
+int    hmm_store_gather_segments(const float* src_store_dev, const void* src_shadow_dev, int64_t src_rows,
+                                 const int64_t* src_offsets_dev, int n_src_segments,
+                                 const int32_t* src_segment_dev /* [n_dst] */, const int64_t* dst_offsets_dev /* [n_dst+1] */,
+                                 int n_dst, int dim, float* dst_store_dev, void* dst_shadow_dev, int64_t dst_rows,
+                                 int64_t dst_capacity_rows, hmm_stream_t stream);
+
 /* Batched feature_search: the top-k of n_queries queries against the same store in ONE pass over it
  * (16 queries per pass; the Q x rows similarity block runs on the fp32 matrix cores, so a row is still read once from
  * HBM).  The reference calls top_k_cosine_similarity once per question (hippomm/utils/vector_ops.py:151-188 via
