@@ -18,6 +18,7 @@
 #include "hmm_common.h"
 #include "topk_tournament.h"
 #include "cosine_topk_shared.h"
+#include "topk_select.h"
 
 namespace hmm {
 
@@ -53,14 +54,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 6))) voi
     const int64_t n_waves = (int64_t)gridDim.x * 4;
 
     float4 q[4];
-    float qs = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        q[j] = query[j * 64 + lane];
-        qs = fmaf(q[j].x, q[j].x, qs); qs = fmaf(q[j].y, q[j].y, qs);
-        qs = fmaf(q[j].z, q[j].z, qs); qs = fmaf(q[j].w, q[j].w, qs);
-    }
-    const float q_len = sqrtf(wave_sum(qs));
+    const float q_len = load_query_frags(query, lane, q);
 
     // A wave takes 32 consecutive rows at a time (16 pairs) and writes their 32 similarities as ONE 128-byte line: with
     // rows dealt pair by pair, every line of `sims` was assembled from 4-byte stores of 16 different waves (partial-line
@@ -99,7 +93,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 6))) voi
 #endif  // HMM_PROBE
 
 // sims[r] = dot(store[r], q) / (||store[r]|| * ||q||)     (vector_ops.py:178-182)
-// scan_topk_kernel's row dealing (pair p belongs to wave p % n_waves: at any moment the waves of the chip read one contiguous window
+// scan_topk_kernel's row dealing (ScanDealing: pair p belongs to wave p % n_waves: at any moment the waves of the chip read one contiguous window
 // of the store; at most six waves per SIMD, all eight loads of a row pair in flight) and NO store inside the loop: lane l of two registers keeps the results of iteration
 // 64 j + l, and the wave writes everything it computed when it has read its last row.  Stores mixed into the read stream are what
 // scan_sims_kernel pays for: groups of 32 rows with one 128-B line of results each 0.606 ms per pass, the same without its stores
@@ -113,23 +107,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 6))) voi
     const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int64_t n_waves = (int64_t)gridDim.x * 4;
     float4 q[4];
-    float qs = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        q[j] = query[j * 64 + lane];
-        qs = fmaf(q[j].x, q[j].x, qs); qs = fmaf(q[j].y, q[j].y, qs);
-        qs = fmaf(q[j].z, q[j].z, qs); qs = fmaf(q[j].w, q[j].w, qs);
-    }
-    const float q_len = sqrtf(wave_sum(qs));
+    const float q_len = load_query_frags(query, lane, q);
     // an epoch = 64 kSimsHeld iterations (1M rows on the scan's grid: one epoch of 326); larger stores write once per epoch
-    for (int64_t it0 = 0; (wave + it0 * n_waves) * 2 < n_rows; it0 += 64 * kSimsHeld) {
+    for (int64_t it0 = 0; ScanDealing::first_row(wave, it0, n_waves) < n_rows; it0 += 64 * kSimsHeld) {
     float h0[kSimsHeld], h1[kSimsHeld];
 #pragma unroll
     for (int j = 0; j < kSimsHeld; ++j) { h0[j] = 0.f; h1[j] = 0.f; }
 #pragma unroll
     for (int j = 0; j < kSimsHeld; ++j) {
         for (int l = 0; l < 64; ++l) {
-            const int64_t r = (wave + (it0 + j * 64 + l) * n_waves) * 2;
+            const int64_t r = ScanDealing::first_row(wave, it0 + j * 64 + l, n_waves);
             if (r >= n_rows) break;                                          // wave-uniform; every later iteration is past the end too
             const bool two = (r + 1) < n_rows;
             const float4* p0 = store + r * 256 + lane;
@@ -154,7 +141,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 6))) voi
     }
 #pragma unroll
     for (int j = 0; j < kSimsHeld; ++j) {
-        const int64_t r = (wave + (it0 + j * 64 + lane) * n_waves) * 2;
+        const int64_t r = ScanDealing::first_row(wave, it0 + j * 64 + lane, n_waves);
         if (r + 1 < n_rows)  *reinterpret_cast<float2*>(sims + r) = make_float2(h0[j], h1[j]);
         else if (r < n_rows) sims[r] = h0[j];
     }
@@ -163,17 +150,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 6))) voi
 
 // All similarities of a store into sims[].
 static void launch_scan_sims(const float* store, int64_t n, const float* query, float* sims, hipStream_t st) {
-    int64_t waves_needed = (n + 1) / 2;
-    int blocks = (int)((waves_needed + 3) / 4);
 #ifdef HMM_PROBE
     if (!g_sims_deferred) {
-        if (blocks > g_sims_blocks) blocks = g_sims_blocks;
-        scan_sims_kernel<true><<<blocks, 256, 0, st>>>(reinterpret_cast<const float4*>(store), n, reinterpret_cast<const float4*>(query), sims);
+        scan_sims_kernel<true><<<ScanDealing::grid(n, g_sims_blocks), 256, 0, st>>>(reinterpret_cast<const float4*>(store), n, reinterpret_cast<const float4*>(query), sims);
         return;
     }
 #endif
-    if (blocks > g_scan_blocks) blocks = g_scan_blocks;
-    scan_sims_deferred_kernel<true><<<blocks, 256, 0, st>>>(reinterpret_cast<const float4*>(store), n,
+    scan_sims_deferred_kernel<true><<<ScanDealing::grid(n, g_scan_blocks), 256, 0, st>>>(reinterpret_cast<const float4*>(store), n,
                                                             reinterpret_cast<const float4*>(query), sims);
 }
 
@@ -183,22 +166,6 @@ __device__ __forceinline__ void bitonic_sort_desc(uint64_t* s) {
     for (int k = 2; k <= N; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
             for (int t = threadIdx.x; t < N / 2; t += NT) {
-                const int i = 2 * t - (t & (j - 1));
-                const int l = i + j;
-                const bool desc = (i & k) == 0;
-                const uint64_t a = s[i], b = s[l];
-                if ((a < b) == desc) { s[i] = b; s[l] = a; }
-            }
-            __syncthreads();
-        }
-    }
-}
-
-// Descending bitonic sort of the first n2 (power of two) keys in LDS by the whole block.
-__device__ __forceinline__ void bitonic_sort_desc_rt(uint64_t* s, int n2) {
-    for (int k = 2; k <= n2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < (n2 >> 1); t += blockDim.x) {
                 const int i = 2 * t - (t & (j - 1));
                 const int l = i + j;
                 const bool desc = (i & k) == 0;
@@ -224,7 +191,7 @@ __global__ __launch_bounds__(1024) void topk_chunk_kernel(const void* __restrict
         if (g < n_in) {
             if constexpr (FROM_SIMS) {
                 const float v = static_cast<const float*>(in)[g];
-                key = ((uint64_t)order_bits(v) << 32) | (uint64_t)(uint32_t)g;
+                key = make_key(v, (uint32_t)g);
             } else {
                 key = static_cast<const uint64_t*>(in)[g];
             }
@@ -255,20 +222,13 @@ __device__ __forceinline__ void scan_topk_body(const float4* __restrict__ store,
     if (threadIdx.x == 0) count = 0;
 
     float4 q[4];
-    float qs = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        q[j] = query[j * 64 + lane];
-        qs = fmaf(q[j].x, q[j].x, qs); qs = fmaf(q[j].y, q[j].y, qs);
-        qs = fmaf(q[j].z, q[j].z, qs); qs = fmaf(q[j].w, q[j].w, qs);
-    }
-    const float q_len = sqrtf(wave_sum(qs));
+    const float q_len = load_query_frags(query, lane, q);
     __syncthreads();
 
-    const int64_t iters = (n_rows + n_waves * 2 - 1) / (n_waves * 2);     // same trip count for every wave
-    const int compact_every = (kFusedCap - k) / 8;                        // 8 rows per block per iteration
+    const int64_t iters = ScanDealing::iterations(n_rows, n_waves);       // same trip count for every wave
+    const int compact_every = (kFusedCap - k) / ScanDealing::kBlockRows;  // 8 rows per block per iteration
     for (int64_t it = 0; it < iters; ++it) {
-        const int64_t r = wave * 2 + it * n_waves * 2;
+        const int64_t r = ScanDealing::first_row(wave, it, n_waves);
         const bool one = r < n_rows, two = (r + 1) < n_rows;              // wave-uniform
         if (one) {
             const float4* p0 = store + r * 256 + lane;
@@ -291,25 +251,13 @@ __device__ __forceinline__ void scan_topk_body(const float4* __restrict__ store,
             d1 = wave_sum(d1); s1 = wave_sum(s1);
             if (lane == 0) {
                 const int pos = atomicAdd(&count, two ? 2 : 1);
-                cand[pos] = ((uint64_t)order_bits(d0 / (sqrtf(s0) * q_len)) << 32) | (uint64_t)(uint32_t)r;
-                if (two)
-                    cand[pos + 1] = ((uint64_t)order_bits(d1 / (sqrtf(s1) * q_len)) << 32) | (uint64_t)(uint32_t)(r + 1);
+                cand[pos] = make_key(d0 / (sqrtf(s0) * q_len), (uint32_t)r);
+                if (two) cand[pos + 1] = make_key(d1 / (sqrtf(s1) * q_len), (uint32_t)(r + 1));
             }
         }
-        if ((it + 1) % compact_every == 0 || it + 1 == iters) {          // block-uniform
-            __syncthreads();
-            const int n = count;
-            const int n2 = pow2_at_least(n, 64);
-            for (int t = n + threadIdx.x; t < n2; t += 256) cand[t] = 0ull;
-            __syncthreads();
-            if (k <= 64) top64_desc<false>(cand, n2);                   // block-uniform; leaves cand[0..63] sorted
-            else         bitonic_sort_desc_rt(cand, n2);
-            if (threadIdx.x == 0) count = n < k ? n : k;
-            __syncthreads();
-        }
+        if ((it + 1) % compact_every == 0 || it + 1 == iters) compact_block_list<true>(cand, count, k);     // block-uniform
     }
-    const int n = count;
-    for (int t = threadIdx.x; t < k; t += 256) out[(int64_t)blockIdx.x * k + t] = t < n ? cand[t] : 0ull;
+    flush_block_list(cand, count, k, out);
 }
 
 // At most SIX waves per SIMD.  The kernel is bound by HBM and wants many bytes in flight per wave (eight 16-byte loads per lane),
@@ -325,25 +273,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 6))) voi
     scan_topk_body<NT>(store, n_rows, query, k, out, cand, &count);
 }
 
-// Best 64 of n_keys keys produced by key_at(i), through a 1024-key LDS window (the best 64 so far stay at w[0..63], 960 new keys per
-// round): for the exact scan's conditional fallback below, which must not cost the streaming kernel its occupancy.
-template <class F>
-__device__ __forceinline__ void top64_of_stream(uint64_t* w, int n_keys, F key_at) {
-    int base = 0, keep = 0;
-    do {
-        const int take = kFusedCap - keep;
-        for (int t = threadIdx.x; t < take; t += blockDim.x) w[keep + t] = base + t < n_keys ? key_at(base + t) : 0ull;
-        base += take;
-        keep = 64;
-        __syncthreads();
-        top64_desc(w, kFusedCap);                                            // ends on a barrier: w[0..63] = the best so far
-    } while (base < n_keys);
-}
-
 // The exact scan as the CONDITIONAL FALLBACK of the bf16-prefilter path (cosine_topk_prefilter.hip), one launch with its own symbol:
 // returns at once unless *run_if != 0 (the usual case: the scan's 384 workgroups exit, ~4.5 us); otherwise scan_topk_kernel's streaming body,
 // and the workgroup that takes the last ticket (device-scope counter, zeroed by prefilter_final_kernel) finishes as topk_final_kernel
-// does -- the k lists with the largest maxima hold the answer -- in the 8 KB of LDS the streaming body already has.  k <= 64.
+// does -- the k lists with the largest maxima hold the answer -- in the 8 KB of LDS the streaming body already has: both rankings
+// are folded through that window (fold_topk), which must not cost the streaming body its occupancy.  k <= 64.
 __global__ __launch_bounds__(256) void exact_scan_fallback_kernel(const float4* __restrict__ store, int64_t n_rows,
                                                                   const float4* __restrict__ query, int k,
                                                                   uint64_t* __restrict__ lists, const int* __restrict__ run_if,
@@ -362,68 +296,40 @@ __global__ __launch_bounds__(256) void exact_scan_fallback_kernel(const float4* 
     if (!last) return;
     __threadfence();                                                        // every other block's list is visible here
     const int n_blocks = (int)gridDim.x;
-    const int64_t n_waves = (int64_t)n_blocks * 4;
     const volatile uint64_t* all = lists;
-    top64_of_stream(cand, n_blocks, [&](int b) { return all[(int64_t)b * k]; });          // the block maxima
+    fold_topk<kFusedCap, 256, false>(cand, n_blocks, k, [&](int64_t base, int have, int take) {       // the block maxima
+        for (int t = threadIdx.x; t < take; t += 256) cand[have + t] = all[(base + t) * k];
+    });
     if (threadIdx.x < 64) winners[threadIdx.x] = cand[threadIdx.x];
     __syncthreads();
     const int n_win = n_blocks < k ? n_blocks : k;
-    top64_of_stream(cand, n_win * k, [&](int t) {
-        const uint64_t top = winners[t / k];
-        if (top == 0ull) return (uint64_t)0;
-        const int blk = (int)((((int64_t)(top & 0xFFFFFFFFull) >> 1) % n_waves) >> 2);     // row r belongs to wave (r / 2) % n_waves
-        return (uint64_t)all[(int64_t)blk * k + (t % k)];
+    fold_topk<kFusedCap, 256, false>(cand, n_win * k, k, [&](int64_t base, int have, int take) {      // the winners' lists
+        for (int t = threadIdx.x; t < take; t += 256) {
+            const uint64_t top = winners[(base + t) / k];
+            cand[have + t] = top == 0ull ? 0ull : all[(int64_t)ScanDealing::block_of_row((uint32_t)key_row(top), n_blocks) * k + (base + t) % k];
+        }
     });
-    if (threadIdx.x == 0) { *n_out = k; *ticket = 0u; }
-    for (int t = threadIdx.x; t < k; t += 256) {
-        idx_out[t] = (int64_t)(cand[t] & 0xFFFFFFFFull);
-        sim_out[t] = order_bits_inverse((uint32_t)(cand[t] >> 32));
-    }
+    if (threadIdx.x == 0) *ticket = 0u;
+    write_hits(cand, k, k, idx_out, sim_out, n_out);
 }
 
 // Final selection for the fused path when k*k <= kChunk.  Every scan block left its best k keys, sorted,
 // at cand[b*k ..].  The global top-k can only contain keys of the k blocks with the largest maxima: a key
 // below the k-th largest block maximum has k better keys (those maxima) ahead of it.  One workgroup sorts
-// the block maxima, gathers the k*k keys of the winning blocks, sorts them and decodes the best k.
+// the block maxima, gathers the k*k keys of the winning blocks, sorts them (rank_winning_lists) and decodes the best k.
 // Replaces two chunk-sort passes and the decode launch.  Both selections are best-64 tournaments (topk_tournament.h):
 // full bitonic sorts here were 66 + 55 barrier-separated stages of 1024 threads, 36 us = 5.5 % of a 1M-row query.
 __global__ __launch_bounds__(1024) void topk_final_kernel(const uint64_t* __restrict__ cand, int n_blocks, int k,
-                                                          int64_t n_waves, uint64_t* __restrict__ keys_out, int k_pad,
+                                                          uint64_t* __restrict__ keys_out, int k_pad,
                                                           int64_t* __restrict__ idx_out, float* __restrict__ sim_out,
                                                           int32_t* __restrict__ n_out) {
     __shared__ uint64_t mx[kScanBlocks];       // block maxima
     __shared__ uint64_t s[kChunk];             // keys of the winning blocks
-    const int tid = threadIdx.x;
-    const int n2 = pow2_at_least(n_blocks, 64);
-    for (int t = tid; t < n2; t += 1024) mx[t] = t < n_blocks ? cand[(int64_t)t * k] : 0ull;
-    __syncthreads();
-    top64_desc(mx, n2);                        // k <= 64 here (k*k <= kChunk)
-    // mx[0..k) = the k largest maxima; recover their blocks from the row index (row r belongs to wave
-    // (r/2) % n_waves, 4 waves per block) and gather those blocks' lists
-    const int n_win = n_blocks < k ? n_blocks : k;
-    const int m2 = pow2_at_least(n_win * k, 64);
-    for (int t = tid; t < m2; t += 1024) {
-        uint64_t key = 0ull;
-        if (t < n_win * k) {
-            const uint64_t top = mx[t / k];
-            if (top != 0ull) {
-                const int64_t row = (int64_t)(top & 0xFFFFFFFFull);
-                const int blk = (int)(((row >> 1) % n_waves) >> 2);
-                key = cand[(int64_t)blk * k + (t % k)];
-            }
-        }
-        s[t] = key;
-    }
-    __syncthreads();
-    top64_desc(s, m2);
+    rank_winning_lists<ScanDealing, 1024>(cand, n_blocks, k, k, mx, s);      // k <= 64 here (k*k <= kChunk)
     if (keys_out != nullptr) {
-        for (int t = tid; t < k_pad; t += 1024) keys_out[t] = t < k ? s[t] : 0ull;
+        for (int t = threadIdx.x; t < k_pad; t += 1024) keys_out[t] = t < k ? s[t] : 0ull;
     } else {
-        if (tid == 0 && n_out) *n_out = k;
-        for (int t = tid; t < k; t += 1024) {
-            idx_out[t] = (int64_t)(s[t] & 0xFFFFFFFFull);
-            sim_out[t] = order_bits_inverse((uint32_t)(s[t] >> 32));
-        }
+        write_hits(s, k, k, idx_out, sim_out, n_out);
     }
 }
 
@@ -431,7 +337,7 @@ __global__ void keys_from_sims_kernel(const float* __restrict__ sims, int64_t n,
                                       uint64_t* __restrict__ keys) {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n_pad) return;
-    keys[g] = g < n ? (((uint64_t)order_bits(sims[g]) << 32) | (uint64_t)(uint32_t)g) : 0ull;
+    keys[g] = g < n ? make_key(sims[g], (uint32_t)g) : 0ull;
 }
 
 __global__ void bitonic_global_step_kernel(uint64_t* __restrict__ keys, int64_t half, int64_t j, int64_t k) {
@@ -450,9 +356,8 @@ __global__ void decode_kernel(const uint64_t* __restrict__ keys, int k_out,
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t == 0 && n_out) *n_out = k_out;
     if (t >= k_out) return;
-    const uint64_t key = keys[t];
-    idx_out[t] = (int64_t)(key & 0xFFFFFFFFull);
-    sim_out[t] = order_bits_inverse((uint32_t)(key >> 32));
+    idx_out[t] = key_row(keys[t]);
+    sim_out[t] = key_sim(keys[t]);
 }
 
 __global__ void copy_keys_kernel(const uint64_t* __restrict__ src, int n_src, uint64_t* __restrict__ dst, int k) {
@@ -477,8 +382,7 @@ __global__ __launch_bounds__(256) void merge_keys_kernel(const uint64_t* __restr
         if (t < total) {
             key = keys[t];
             if (key != 0) {
-                const uint64_t row = (key & 0xFFFFFFFFull) + (uint64_t)row_offset[t / k];
-                key = (key & 0xFFFFFFFF00000000ull) | (row & 0xFFFFFFFFull);
+                key = (key & 0xFFFFFFFF00000000ull) | (uint64_t)(uint32_t)(key_row(key) + row_offset[t / k]);
                 ++mine;
             }
         }
@@ -488,11 +392,7 @@ __global__ __launch_bounds__(256) void merge_keys_kernel(const uint64_t* __restr
     __syncthreads();
     bitonic_sort_desc<kChunk, 256>(s);
     const int k_out = n_valid < k ? n_valid : k;
-    if (threadIdx.x == 0) *n_out = k_out;
-    for (int t = threadIdx.x; t < k_out; t += 256) {
-        idx_out[t] = (int64_t)(s[t] & 0xFFFFFFFFull);
-        sim_out[t] = order_bits_inverse((uint32_t)(s[t] >> 32));
-    }
+    write_hits(s, k_out, k_out, idx_out, sim_out, n_out);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -519,33 +419,11 @@ __global__ __launch_bounds__(THREADS) void segment_topk_kernel(const float* __re
     const int64_t lo = seg_off[e], hi = seg_off[e + 1];
     const int64_t n = hi - lo;
     const int k_out = (int)(n < k ? (n > 0 ? n : 0) : k);
-    int have = 0;                                              // best keys carried from earlier pieces, at s[0..have)
-    int64_t base = 0;
-    do {
-        const int64_t left = n - base;
-        const int take = (int)(left < (int64_t)(CHUNK - have) ? left : (int64_t)(CHUNK - have));
-        const int total = have + take;
-        const int n2 = pow2_at_least(total, 64);
-        for (int t = have + tid; t < n2; t += THREADS) {
-            uint64_t key = 0ull;
-            if (t < total) {
-                const int64_t r = base + (t - have);
-                key = ((uint64_t)order_bits(sims[lo + r]) << 32) | (uint64_t)(uint32_t)r;
-            }
-            s[t] = key;
-        }
-        __syncthreads();
-        if (k <= 64) top64_desc(s, n2);                        // best-64 tournament: s[0..63] sorted, the rest clobbered
-        else         bitonic_sort_desc_rt(s, n2);
-        have = total < k ? total : k;
-        base += take;
-    } while (base < n);
-    if (tid == 0) n_out[slot] = k_out;
-    for (int t = tid; t < k; t += THREADS) {
-        const bool ok = t < k_out;
-        idx_out[slot * k + t] = ok ? (int64_t)(s[t] & 0xFFFFFFFFull) : -1;
-        sim_out[slot * k + t] = ok ? order_bits_inverse((uint32_t)(s[t] >> 32)) : 0.0f;
-    }
+    if (n > 0)                                                 // block-uniform; pieces of a chunk, carrying the running best k
+        fold_topk<CHUNK, THREADS, true>(s, n, k, [&](int64_t base, int have, int take) {
+            for (int t = tid; t < take; t += THREADS) s[have + t] = make_key(sims[lo + base + t], (uint32_t)(base + t));
+        });
+    write_hits(s, k_out, k, idx_out + slot * k, sim_out + slot * k, n_out + slot);
 }
 
 // The selection launch of the per-event calls: n_queries x n_segments workgroups of the shape that fits the mean event.
@@ -581,7 +459,7 @@ __global__ __launch_bounds__(1024) void rank_segment_hits_kernel(const int64_t* 
     n_out += blockIdx.x;
     auto key_at = [&](int64_t pos) -> uint64_t {
         if (pos < total && (int)(pos % k) < counts[pos / k])
-            return ((uint64_t)order_bits(sims[pos]) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)pos);
+            return make_key(sims[pos], 0xFFFFFFFFu - (uint32_t)pos);
         return 0ull;
     };
     if (total <= (int64_t)1024 * (kChunk / 64)) {
@@ -609,23 +487,16 @@ __global__ __launch_bounds__(1024) void rank_segment_hits_kernel(const int64_t* 
         __syncthreads();
         top64_desc(w, n2);
     } else {
-        int64_t base = 0;
-        int held = 0;
-        do {
-            const int take = kChunk - held;
-            for (int t = threadIdx.x; t < take; t += 1024) w[held + t] = key_at(base + t);
-            base += take;
-            held = 64;
-            __syncthreads();
-            top64_desc(w, kChunk);
-        } while (base < total);
+        fold_topk<kChunk, 1024, false>(w, total, keep, [&](int64_t base, int have, int take) {
+            for (int t = threadIdx.x; t < take; t += 1024) w[have + t] = key_at(base + t);
+        });
     }
     int n = 0;
     for (int t = 0; t < keep; ++t) n += w[t] != 0ull;                        // every thread the same count (keys are sorted, zeros last)
     if (threadIdx.x == 0) *n_out = n;
     for (int t = threadIdx.x; t < keep; t += 1024) {
         const bool valid = t < n;
-        const int64_t pos = valid ? (int64_t)(0xFFFFFFFFu - (uint32_t)(w[t] & 0xFFFFFFFFull)) : 0;
+        const int64_t pos = valid ? (int64_t)(0xFFFFFFFFu - (uint32_t)key_row(w[t])) : 0;
         event_out[t] = valid ? pos / k : -1;
         row_out[t] = valid ? idx[pos] : -1;
         sim_out[t] = valid ? sims[pos] : 0.0f;
@@ -676,7 +547,7 @@ struct ScanOut {                 // where the result of run_scan lives
     const uint64_t* best;         // sorted best keys (>= k_eff entries), or nullptr when `fused` is set
     int k_eff;
     bool fused;                   // candidates of the fused scan still need topk_final_kernel
-    const uint64_t* cand; int n_blocks; int64_t n_waves;
+    const uint64_t* cand; int n_blocks;
 };
 
 // Runs scan + selection up to (not including) the final decode / key copy.
@@ -698,9 +569,7 @@ static int run_scan(const float* store, int64_t n, int dim, const float* query, 
     uint64_t* buf_a = reinterpret_cast<uint64_t*>(base + p.off_a);
     uint64_t* buf_b = reinterpret_cast<uint64_t*>(base + p.off_b);
 
-    int64_t waves_needed = (n + 1) / 2;
-    int blocks = (int)((waves_needed + 3) / 4);
-    if (blocks > g_scan_blocks) blocks = g_scan_blocks;
+    const int blocks = ScanDealing::grid(n, g_scan_blocks);
     *k_eff = p.k_eff;
 
     if (!p.full_sort && n > kChunk && p.k_eff <= kFusedK) {
@@ -709,7 +578,7 @@ static int run_scan(const float* store, int64_t n, int dim, const float* query, 
                                                        reinterpret_cast<const float4*>(query), p.k_eff, buf_a);
         HMM_LAUNCH_CHECK();
         if ((int64_t)p.k_eff * p.k_eff <= kChunk && blocks <= kScanBlocks) {     // one-kernel finish
-            out->fused = true; out->cand = buf_a; out->n_blocks = blocks; out->n_waves = (int64_t)blocks * 4;
+            out->fused = true; out->cand = buf_a; out->n_blocks = blocks;
             out->best = nullptr;
             return HMM_OK;
         }
@@ -768,9 +637,7 @@ int cosine_topk_if(const int* run_if, unsigned* ticket, const float* store, int6
                 "cosine_topk_if: needs more than %d rows and k <= 64", kChunk);
     const ScanPlan p = make_plan(n, k);
     HMM_REQUIRE(ws_bytes >= p.total, HMM_E_WORKSPACE, "cosine_topk_if: workspace %zu < required %zu", ws_bytes, p.total);
-    int64_t waves_needed = (n + 1) / 2;
-    int blocks = (int)((waves_needed + 3) / 4);
-    if (blocks > g_scan_blocks) blocks = g_scan_blocks;
+    const int blocks = ScanDealing::grid(n, g_scan_blocks);
     exact_scan_fallback_kernel<<<blocks, 256, 0, st>>>(reinterpret_cast<const float4*>(store), n, reinterpret_cast<const float4*>(query),
                                                        k, reinterpret_cast<uint64_t*>(static_cast<char*>(ws) + p.off_a), run_if, ticket,
                                                        idx_out, sim_out, n_out);
@@ -796,7 +663,7 @@ extern "C" int hmm_cosine_topk(const float* store_dev, int64_t n_rows, int dim, 
     int rc = run_scan(store_dev, n_rows, dim, query_dev, k, workspace_dev, workspace_bytes, st, &r);
     if (rc != HMM_OK) return rc;
     if (r.fused) {
-        topk_final_kernel<<<1, 1024, 0, st>>>(r.cand, r.n_blocks, r.k_eff, r.n_waves, nullptr, 0, idx_out_dev, sim_out_dev,
+        topk_final_kernel<<<1, 1024, 0, st>>>(r.cand, r.n_blocks, r.k_eff, nullptr, 0, idx_out_dev, sim_out_dev,
                                               n_out_dev);
     } else {
         decode_kernel<<<(r.k_eff + 255) / 256, 256, 0, st>>>(r.best, r.k_eff, idx_out_dev, sim_out_dev, n_out_dev);
@@ -814,7 +681,7 @@ extern "C" int hmm_cosine_topk_keys(const float* store_dev, int64_t n_rows, int 
     int rc = run_scan(store_dev, n_rows, dim, query_dev, k, workspace_dev, workspace_bytes, st, &r);
     if (rc != HMM_OK) return rc;
     if (r.fused) {
-        topk_final_kernel<<<1, 1024, 0, st>>>(r.cand, r.n_blocks, r.k_eff, r.n_waves, keys_out_dev, k, nullptr, nullptr,
+        topk_final_kernel<<<1, 1024, 0, st>>>(r.cand, r.n_blocks, r.k_eff, keys_out_dev, k, nullptr, nullptr,
                                               nullptr);
     } else {
         copy_keys_kernel<<<(k + 255) / 256, 256, 0, st>>>(r.best, r.k_eff, keys_out_dev, k);
@@ -850,10 +717,7 @@ extern "C" int hmm_op_scan_sims(const float* store_dev, int64_t n_rows, const fl
 extern "C" int hmm_op_scan_topk_only(const float* store_dev, int64_t n_rows, const float* query_dev, int k,
                                       uint64_t* cand_dev /* [2048*k] */, hmm_stream_t stream) {
     HMM_REQUIRE(k >= 1 && k <= kFusedK, HMM_E_INVALID, "scan_topk_only: k out of range");
-    int64_t waves_needed = (n_rows + 1) / 2;
-    int blocks = (int)((waves_needed + 3) / 4);
-    if (blocks > g_scan_blocks) blocks = g_scan_blocks;
-    scan_topk_kernel<true><<<blocks, 256, 0, static_cast<hipStream_t>(stream)>>>(
+    scan_topk_kernel<true><<<ScanDealing::grid(n_rows, g_scan_blocks), 256, 0, static_cast<hipStream_t>(stream)>>>(
         reinterpret_cast<const float4*>(store_dev), n_rows, reinterpret_cast<const float4*>(query_dev), k, cand_dev);
     HMM_LAUNCH_CHECK();
     return HMM_OK;

@@ -29,13 +29,12 @@
 // Keys, total order (NaN first, higher row first on ties) and outputs are those of hmm_cosine_topk.
 #include "cosine_topk_shared.h"
 #include "topk_tournament.h"
+#include "topk_select.h"
 
 namespace hmm {
 
-constexpr int kMQ = 16;                 // queries per pass
 constexpr int kMWaves = 4;              // one wave per SIMD: 512 registers each (256 of them hold the queries)
-constexpr int kMTileRows = 16;          // rows per wave per round (one MFMA tile)
-constexpr int kMRows = kMWaves * kMTileRows;      // rows per workgroup per round
+using MultiDealing = RowDealing<kMTileRows, kMWaves>;       // scan_multi_kernel: one tile of kMTileRows rows per wave and round (kMQ, kMTileRows: topk_select.h)
 constexpr int kMSlices = 8;             // K slices per tile: 128 floats each
 constexpr int kMPiece = 1056;           // LDS bytes per DMA piece: 2 rows x 512 B + 32 B (bank rotation between pieces)
 constexpr int kMSliceBytes = 8 * kMPiece;
@@ -44,8 +43,8 @@ constexpr int kMRing = 4;               // slices per wave: one being read, thre
                                         // MFMAs (VALU dot products instead: 0.653) or, mostly, the 512-B pieces: the bare DMA stream of
                                         // this kernel, nothing read or computed, runs 0.613 against 0.650.  1-KiB pieces (one row x 256
                                         // floats per instruction, 16-KiB slices) leave room for only two slices per wave: 0.683
-constexpr int kMCap = 128;              // candidate keys per query and workgroup (>= k + kMRows, power of two)
-constexpr int kMMaxK = 64;              // k*k <= 4096 for the one-kernel finish
+constexpr int kMCap = 128;              // candidate keys per query and workgroup (>= k + MultiDealing::kBlockRows, power of two)
+constexpr int kMMaxK = kListMaxK;       // k*k <= 4096 for the one-kernel finish
 constexpr int kMMaxBlocks = 2048;
 constexpr int kMDmaAux = 2;             // cache policy of the row stream: 2 = non-temporal (each row is read once; 0: 0.724 ms)
 
@@ -59,38 +58,6 @@ struct MultiLds {
 
 #define HMM_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 #define HMM_GLB_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
-
-// Descending bitonic sort, by ONE wave, of the first n2 (power of two, <= kMCap) keys of NL lists at once: the lists'
-// compare-exchange steps are independent, so walking them in lockstep overlaps their LDS round trips (a single
-// list is latency-bound: ~26 us for 512 keys).
-template <int NL>
-__device__ __forceinline__ void wave_bitonic_desc(uint64_t* (&s)[NL], int n2, int lane) {
-    for (int k = 2; k <= n2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = lane; t < (n2 >> 1); t += 64) {
-                const int i = 2 * t - (t & (j - 1));
-                const int l = i + j;
-                const bool desc = (i & k) == 0;
-                uint64_t a[NL], b[NL];
-#pragma unroll
-                for (int q = 0; q < NL; ++q) { a[q] = s[q][i]; b[q] = s[q][l]; }
-#pragma unroll
-                for (int q = 0; q < NL; ++q)
-                    if ((a[q] < b[q]) == desc) { s[q][i] = b[q]; s[q][l] = a[q]; }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-        }
-    }
-}
-
-// A raw workgroup barrier that leaves LDS-DMA in flight (__syncthreads() would drain vmcnt to 0).
-__device__ __forceinline__ void multi_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-}
 
 // ---- the arithmetic that DEFINES the bits of a batched similarity ------------------------------------------------------------
 // Shared by scan_multi_kernel and the re-scoring of the shadow route (multi_rescore_tile): a (row, query) pair gets the same
@@ -207,7 +174,7 @@ __global__ __launch_bounds__(kMWaves * 64) void scan_multi_kernel(const float* _
 
     // flattened (round, slice) sequence n = 8 round + slice; slot n % kMRing; slices n + 1 .. n + LA are in flight while n is read
     constexpr int LA = kMRing - 1;
-    auto tile_of = [&](int64_t round) { return wave_gid + round * n_waves; };
+    auto tile_of = [&](int64_t round) { return MultiDealing::group(wave_gid, round, n_waves); };
 #pragma unroll
     for (int p = 0; p < LA; ++p) issue_slice(tile_of(0), p, p);
     int slot = 0;                                                 // slot of the slice being read
@@ -236,74 +203,15 @@ __global__ __launch_bounds__(kMWaves * 64) void scan_multi_kernel(const float* _
                 *reinterpret_cast<f32x4*>(sims_out + r16 * sims_stride + tile * kMTileRows + 4 * g) = sim4;
             continue;
         }
-        if (tile < n_tiles) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int64_t row = tile * kMTileRows + 4 * g + j;
-                const float sim = sim4[j];
-                const uint64_t key = ((uint64_t)order_bits(sim) << 32) | (uint64_t)(uint32_t)row;
-                if (r16 < n_q && row < n_rows && key > L.tau[r16]) {
-                    const int pos = atomicAdd(&L.cnt[r16], 1);
-                    L.keys[r16][pos] = key;
-                }
-            }
-        }
-        // Sort the lists down to k: at the end, whenever one could overflow in the next round, and once after the very
-        // first round -- that sets the thresholds early, so that from the second round on only rows that beat the
-        // current k-th best are appended at all.  The decision is taken by ONE wave between two barriers and read by
-        // the others after the second one: it is workgroup-uniform by construction (no wave can append again before
-        // every wave has read the flag, because the flag is reset only behind the third barrier).
-        multi_barrier();                                          // every append of this round is visible
-        if (wave == 0) {
-            bool need = round + 1 >= n_rounds || round == 0;
-            if (lane < kMQ) {
-                need |= L.cnt[lane] > kMCap - kMRows;
-            }
-            need = __any(need);
-            if (lane == 0) L.need = need ? 1 : 0;
-        }
-        multi_barrier();
-        if (L.need) {
-            constexpr int NL = kMQ / kMWaves;                     // lists per wave: wave w owns queries w, w + 4, ...
-            uint64_t* lists[NL];
-            int n[NL], nmax = 0;
-#pragma unroll
-            for (int q = 0; q < NL; ++q) {
-                lists[q] = L.keys[wave + q * kMWaves];
-                n[q] = L.cnt[wave + q * kMWaves];
-                nmax = n[q] > nmax ? n[q] : nmax;
-            }
-            int n2 = 64;
-            while (n2 < nmax) n2 <<= 1;
-#pragma unroll
-            for (int q = 0; q < NL; ++q)
-                for (int t = n[q] + lane; t < n2; t += 64) lists[q][t] = 0ull;
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            wave_bitonic_desc<NL>(lists, n2, lane);
-            if (lane == 0) {
-#pragma unroll
-                for (int q = 0; q < NL; ++q) {
-                    const int qi = wave + q * kMWaves;
-                    L.cnt[qi] = n[q] < k ? n[q] : k;
-                    L.tau[qi] = n[q] >= k ? lists[q][k - 1] : 0ull;
-                }
-            }
-            multi_barrier();                                      // new counts / thresholds visible before the next appends
-        }
+        // fused selection: appends above the thresholds, lists sorted down to k when they could overflow (multi_lists_round)
+        multi_lists_round<MultiDealing, kMCap>(L, sim4, tile, n_tiles, n_rows, n_q, k, round + 1 >= n_rounds || round == 0, wave, lane);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // the look-ahead slices past the end
     if constexpr (SIMS_OUT) return;
-    __syncthreads();
-    // this workgroup's best k per query (sorted, 0-padded); a workgroup with no tile leaves zeros
-    for (int i = tid; i < n_q * k; i += kMWaves * 64) {
-        const int qi = i / k, t = i - qi * k;
-        out[((size_t)qi * gridDim.x + blockIdx.x) * k + t] = t < L.cnt[qi] ? L.keys[qi][t] : 0ull;
-    }
+    multi_lists_flush<MultiDealing>(L, n_q, k, out);
 }
 
-// One workgroup per query: see topk_final_kernel.  Row r lies in tile r / 16, which wave (tile % (4 n_blocks)) of the
-// grid scanned, i.e. workgroup (tile % (4 n_blocks)) / 4.
+// One workgroup per query: see topk_final_kernel; the lists are scan_multi_kernel's (MultiDealing).
 __global__ __launch_bounds__(1024) void topk_final_multi_kernel(const uint64_t* __restrict__ cand, int n_blocks, int k,
                                                                 int k_eff, int64_t* __restrict__ idx_out,
                                                                 float* __restrict__ sim_out, int32_t* __restrict__ n_out,
@@ -311,40 +219,13 @@ __global__ __launch_bounds__(1024) void topk_final_multi_kernel(const uint64_t* 
     __shared__ uint64_t mx[kMMaxBlocks];
     __shared__ uint64_t s[4096];
     if (run_if != nullptr && *run_if == 0) return;                // see scan_multi_kernel
-    const int tid = threadIdx.x, qi = blockIdx.x;
-    const uint64_t* c = cand + (size_t)qi * n_blocks * k;
-    int n2 = 64;
-    while (n2 < n_blocks) n2 <<= 1;
-    for (int t = tid; t < n2; t += 1024) mx[t] = t < n_blocks ? c[(size_t)t * k] : 0ull;
-    __syncthreads();
-    top64_desc(mx, n2);                                      // k <= kMMaxK = 64: the best 64 maxima are enough
-    const int n_win = n_blocks < k ? n_blocks : k;
-    int m2 = 64;
-    while (m2 < n_win * k) m2 <<= 1;
-    for (int t = tid; t < m2; t += 1024) {
-        uint64_t key = 0ull;
-        if (t < n_win * k) {
-            const uint64_t top = mx[t / k];
-            if (top != 0ull) {
-                const int64_t row = (int64_t)(top & 0xFFFFFFFFull);
-                const int blk = (int)(((row / kMTileRows) % ((int64_t)n_blocks * kMWaves)) / kMWaves);
-                key = c[(size_t)blk * k + (t % k)];
-            }
-        }
-        s[t] = key;
-    }
-    __syncthreads();
-    top64_desc(s, m2);
-    if (tid == 0 && n_out) n_out[qi] = k_eff;
-    for (int t = tid; t < k_eff; t += 1024) {
-        idx_out[(size_t)qi * k_stride + t] = (int64_t)(s[t] & 0xFFFFFFFFull);
-        sim_out[(size_t)qi * k_stride + t] = order_bits_inverse((uint32_t)(s[t] >> 32));
-    }
+    const int qi = blockIdx.x;
+    rank_winning_lists<MultiDealing, 1024>(cand + (size_t)qi * n_blocks * k, n_blocks, k, k, mx, s);     // k <= kMMaxK = 64
+    write_hits(s, k_eff, k_eff, idx_out + (size_t)qi * k_stride, sim_out + (size_t)qi * k_stride, n_out ? n_out + qi : nullptr);
 }
 
 static int multi_grid(int64_t n_rows) {                        // one workgroup per CU (its LDS fills the CU), 64 rows per round
-    const int64_t chunks = (n_rows + kMRows - 1) / kMRows;
-    return (int)(chunks < kNumCU ? chunks : kNumCU);
+    return MultiDealing::grid(n_rows, kNumCU);
 }
 
 }  // namespace hmm
@@ -390,16 +271,15 @@ extern "C" int hmm_cosine_topk_multi(const float* store_dev, int64_t n_rows, int
     HMM_ENSURE_DYN_LDS(scan_multi_kernel<false>, (int)sizeof(MultiLds));
     const int grid = multi_grid(n_rows);
     uint64_t* cand = static_cast<uint64_t*>(workspace_dev);
-    for (int q0 = 0; q0 < n_queries; q0 += kMQ) {                  // 16 queries per pass over the store
-        const int nq = n_queries - q0 < kMQ ? n_queries - q0 : kMQ;
-        scan_multi_kernel<false><<<grid, kMWaves * 64, sizeof(MultiLds), st>>>(store_dev, n_rows, queries_dev + (size_t)q0 * dim,
-                                                                              nq, k_eff, cand, nullptr, 0, nullptr);
+    return for_each_pass(n_queries, [&](const QuestionPass& pass) -> int {       // 16 queries per pass over the store
+        scan_multi_kernel<false><<<grid, kMWaves * 64, sizeof(MultiLds), st>>>(store_dev, n_rows, pass.at(queries_dev, dim), pass.nq, k_eff, cand,
+                                                                              nullptr, 0, nullptr);
         HMM_LAUNCH_CHECK();
-        topk_final_multi_kernel<<<nq, 1024, 0, st>>>(cand, grid, k_eff, k_eff, idx_out_dev + (size_t)q0 * k,
-                                                     sim_out_dev + (size_t)q0 * k, n_out_dev ? n_out_dev + q0 : nullptr, k, nullptr);
+        topk_final_multi_kernel<<<pass.nq, 1024, 0, st>>>(cand, grid, k_eff, k_eff, pass.at(idx_out_dev, k), pass.at(sim_out_dev, k),
+                                                       pass.at(n_out_dev, 1), k, nullptr);
         HMM_LAUNCH_CHECK();
-    }
-    return HMM_OK;
+        return HMM_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -451,16 +331,15 @@ extern "C" int hmm_cosine_topk_segmented_multi(const float* store_dev, int64_t n
     const int grid = multi_grid(n_rows);
     const int64_t stride = multi_sims_stride(n_rows);
     float* sims = static_cast<float*>(workspace_dev);
-    for (int q0 = 0; q0 < n_queries; q0 += kMQ) {                  // 16 queries per pass over the store
-        const int nq = n_queries - q0 < kMQ ? n_queries - q0 : kMQ;
-        scan_multi_kernel<true><<<grid, kMWaves * 64, sizeof(MultiLds), st>>>(store_dev, n_rows, queries_dev + (size_t)q0 * dim, nq, k,
-                                                                             nullptr, sims, stride, nullptr);
+    return for_each_pass(n_queries, [&](const QuestionPass& pass) -> int {       // 16 queries per pass over the store
+        scan_multi_kernel<true><<<grid, kMWaves * 64, sizeof(MultiLds), st>>>(store_dev, n_rows, pass.at(queries_dev, dim), pass.nq, k, nullptr,
+                                                                             sims, stride, nullptr);
         HMM_LAUNCH_CHECK();
-        launch_segment_topk(sims, stride, nq, n_rows, seg_offsets_dev, n_segments, k, idx_out_dev + q0 * per_query,
-                            sim_out_dev + q0 * per_query, n_out_dev + (size_t)q0 * n_segments, st);
+        launch_segment_topk(sims, stride, pass.nq, n_rows, seg_offsets_dev, n_segments, k, pass.at(idx_out_dev, per_query),
+                            pass.at(sim_out_dev, per_query), pass.at(n_out_dev, n_segments), st);
         HMM_LAUNCH_CHECK();
-    }
-    return HMM_OK;
+        return HMM_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -480,7 +359,7 @@ extern "C" int hmm_cosine_topk_segmented_multi(const float* store_dev, int64_t n
 //            rows with s~ >= t - 2 eps, re-scored by multi_rescore_tile and ranked.  A saturated list or more candidates than
 //            the buffer holds raises ONE flag for the pass, and the exact pass (scan_multi_kernel<false> +
 //            topk_final_multi_kernel, both conditional on that flag) answers for all its questions.
-//            per event: segment_multi_prefilter_kernel over (event, question): threshold inside the event, candidates re-scored,
+//            per event: segment_prefilter_kernel<.., TileRescore> over (event, question): threshold inside the event, candidates re-scored,
 //            every row of the event when the candidates do not fit.
 //   Re-scoring.  multi_rescore_tile gathers up to 16 candidate rows of the fp32 store into the A layout of scan_multi_kernel and
 //            runs its sequence (multi_slice_mac / multi_tile_sims above) with the question in its own slot of the B operand and
@@ -496,12 +375,11 @@ extern "C" int hmm_cosine_topk_segmented_multi(const float* store_dev, int64_t n
 // ------------------------------------------------------------------------------------------------------
 namespace hmm {
 
-constexpr float kMPEps = 0.0042f;
+constexpr float kMPEps = 0.0042f;                   // |s~ - s| on this route: the error bound above
 constexpr int kSWaves = 8;                          // two waves per SIMD: ~150 registers each (128 of them one tile of rows)
-constexpr int kSRows = kSWaves * kMTileRows;        // rows per workgroup per round
+using ShadowMultiDealing = RowDealing<kMTileRows, kSWaves>;     // shadow_multi_kernel: one tile per wave and round
 constexpr int kSSteps = 32;                         // MFMA steps per tile: 32 bf16 of K each
-constexpr int kSCap = 256;                          // candidate keys per query and workgroup (>= 64 + kSRows, power of two)
-constexpr int kMPCandCap = 1024;                    // candidate rows a question re-scores itself
+constexpr int kSCap = 256;                          // candidate keys per query and workgroup (>= 64 + ShadowMultiDealing::kBlockRows, power of two)
 constexpr int kMPFinalThreads = 512;
 constexpr int kMPMinRows = 16384;                   // flat dispatch limit: hmm_cosine_topk_prefilter's, NOT yet measured for a batch
 constexpr int kMPMinSegRows = 128;                  // per-event dispatch limit, rows per event on average: inherited likewise, NOT yet measured
@@ -517,11 +395,6 @@ struct ShadowLds {
 };
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-static int mp_list_len(int k) {                                       // prefilter_list_len of cosine_topk_prefilter.hip
-    const int kk = 2 * k < 32 ? 32 : 2 * k;
-    return kk > kMMaxK ? kMMaxK : kk;
-}
 
 template <bool SIMS_OUT>
 __global__ __launch_bounds__(kSWaves * 64) void shadow_multi_kernel(const uint4* __restrict__ shadow, int64_t n_rows,
@@ -574,7 +447,7 @@ __global__ __launch_bounds__(kSWaves * 64) void shadow_multi_kernel(const uint4*
     const int64_t wave_gid = (int64_t)blockIdx.x * kSWaves + wave;
     const int64_t n_rounds = (n_tiles + n_waves - 1) / n_waves;   // same for every wave of the grid
     auto src_of = [&](int64_t round) {                            // lane's 16 B of step 0; step t is + 4 t (rows past the end: clamped)
-        int64_t row = (wave_gid + round * n_waves) * kMTileRows + r16;
+        int64_t row = ShadowMultiDealing::first_row(wave_gid, round, n_waves) + r16;
         row = row < n_rows ? row : n_rows - 1;
         return reinterpret_cast<const u32x4*>(shadow) + row * 128 + g;
     };
@@ -585,7 +458,7 @@ __global__ __launch_bounds__(kSWaves * 64) void shadow_multi_kernel(const uint4*
         for (int t = 0; t < kSSteps; ++t) x[t] = __builtin_nontemporal_load(p + 4 * t);
     }
     for (int64_t round = 0; round < n_rounds; ++round) {
-        const int64_t tile = wave_gid + round * n_waves;
+        const int64_t tile = ShadowMultiDealing::group(wave_gid, round, n_waves);
         const u32x4* pn = src_of(round + 1);                      // next tile (clamped past the end, never used then)
         asm volatile("" ::: "memory");                            // the B fragments are re-read from LDS every round: hoisted out of the
                                                                   // loop they would take 256 registers and spill the row stream
@@ -609,62 +482,11 @@ __global__ __launch_bounds__(kSWaves * 64) void shadow_multi_kernel(const uint4*
                 *reinterpret_cast<f32x4*>(sims_out + r16 * sims_stride + tile * kMTileRows + 4 * g) = sim4;
             continue;
         }
-        if (tile < n_tiles) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int64_t row = tile * kMTileRows + 4 * g + j;
-                const uint64_t key = ((uint64_t)order_bits(sim4[j]) << 32) | (uint64_t)(uint32_t)row;
-                if (r16 < n_q && row < n_rows && key > L.tau[r16]) {
-                    const int pos = atomicAdd(&L.cnt[r16], 1);
-                    L.keys[r16][pos] = key;
-                }
-            }
-        }
-        // lists sorted down to kk exactly as scan_multi_kernel sorts its lists down to k (see there)
-        multi_barrier();
-        if (wave == 0) {
-            bool need = round + 1 >= n_rounds || round == 0;
-            if (lane < kMQ) need |= L.cnt[lane] > kSCap - kSRows;
-            need = __any(need);
-            if (lane == 0) L.need = need ? 1 : 0;
-        }
-        multi_barrier();
-        if (L.need) {
-            constexpr int NL = kMQ / kSWaves;                     // lists per wave: wave w owns queries w, w + 8
-            uint64_t* lists[NL];
-            int n[NL], nmax = 0;
-#pragma unroll
-            for (int q = 0; q < NL; ++q) {
-                lists[q] = L.keys[wave + q * kSWaves];
-                n[q] = L.cnt[wave + q * kSWaves];
-                nmax = n[q] > nmax ? n[q] : nmax;
-            }
-            int n2 = 64;
-            while (n2 < nmax) n2 <<= 1;
-#pragma unroll
-            for (int q = 0; q < NL; ++q)
-                for (int t = n[q] + lane; t < n2; t += 64) lists[q][t] = 0ull;
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            wave_bitonic_desc<NL>(lists, n2, lane);
-            if (lane == 0) {
-#pragma unroll
-                for (int q = 0; q < NL; ++q) {
-                    const int qi = wave + q * kSWaves;
-                    L.cnt[qi] = n[q] < kk ? n[q] : kk;
-                    L.tau[qi] = n[q] >= kk ? lists[q][kk - 1] : 0ull;
-                }
-            }
-            multi_barrier();
-        }
+        // lists sorted down to kk exactly as scan_multi_kernel sorts its lists down to k (multi_lists_round)
+        multi_lists_round<ShadowMultiDealing, kSCap>(L, sim4, tile, n_tiles, n_rows, n_q, kk, round + 1 >= n_rounds || round == 0, wave, lane);
     }
     if constexpr (SIMS_OUT) return;
-    __syncthreads();
-    // this workgroup's best kk per query (sorted, 0-padded); a workgroup with no tile leaves zeros
-    for (int i = tid; i < n_q * kk; i += kSWaves * 64) {
-        const int qi = i / kk, t = i - qi * kk;
-        out[((size_t)qi * gridDim.x + blockIdx.x) * kk + t] = t < L.cnt[qi] ? L.keys[qi][t] : 0ull;
-    }
+    multi_lists_flush<ShadowMultiDealing>(L, n_q, kk, out);
 }
 
 // Up to 16 rows of the fp32 store against the question in B slot `slot`, with the bits of scan_multi_kernel: lane (r16, g) passes
@@ -700,10 +522,6 @@ __device__ __forceinline__ f32x4 multi_rescore_tile(const float* row, const floa
     return multi_tile_sims(acc0, acc1, ss, multi_len(qss), g);
 }
 
-__device__ __forceinline__ uint32_t mp_threshold_below(uint32_t key_hi) {    // NaN -> 0xFFFFFFFF: only NaN rows pass
-    return order_bits(order_bits_inverse(key_hi) - 2.0f * kMPEps);
-}
-
 // Flat finish, one workgroup per question of the pass.  lists: [question][n_blocks][kk] keys of shadow_multi_kernel.
 __global__ __launch_bounds__(kMPFinalThreads) void multi_prefilter_final_kernel(const uint64_t* __restrict__ lists, int n_blocks, int k,
                                                                                 int kk, const float* __restrict__ store,
@@ -713,7 +531,7 @@ __global__ __launch_bounds__(kMPFinalThreads) void multi_prefilter_final_kernel(
                                                                                 int* __restrict__ flag, int32_t* __restrict__ stats) {
     __shared__ uint64_t mx[kNumCU];
     __shared__ uint64_t s[kChunk];
-    __shared__ uint32_t cand_row[kMPCandCap];
+    __shared__ uint32_t cand_row[kCandCap];
     __shared__ __attribute__((aligned(16))) float qs[1024];
     __shared__ int n_cand, n_sat;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, qi = blockIdx.x;
@@ -721,42 +539,23 @@ __global__ __launch_bounds__(kMPFinalThreads) void multi_prefilter_final_kernel(
     if (tid == 0) { n_cand = 0; n_sat = 0; }
     for (int t = tid; t < 256; t += kMPFinalThreads)
         *reinterpret_cast<f32x4*>(qs + 4 * t) = *reinterpret_cast<const f32x4*>(queries + (size_t)qi * 1024 + 4 * t);
-    const int n2 = pow2_at_least(n_blocks, 64);
-    for (int t = tid; t < n2; t += kMPFinalThreads) mx[t] = t < n_blocks ? c[(size_t)t * kk] : 0ull;
-    __syncthreads();
-    top64_desc(mx, n2);
     // the k lists with the largest maxima hold the k largest keys (every list keeps kk >= k entries): rank them
-    const int n_win = n_blocks < k ? n_blocks : k;
-    const int m2 = pow2_at_least(n_win * kk, 64);
-    for (int t = tid; t < m2; t += kMPFinalThreads) {
-        uint64_t key = 0ull;
-        if (t < n_win * kk) {
-            const uint64_t top = mx[t / kk];
-            if (top != 0ull) {
-                const int64_t row = (int64_t)(top & 0xFFFFFFFFull);
-                const int blk = (int)(((row / kMTileRows) % ((int64_t)n_blocks * kSWaves)) / kSWaves);
-                key = c[(size_t)blk * kk + (t % kk)];
-            }
-        }
-        s[t] = key;
-    }
-    __syncthreads();
-    top64_desc(s, m2);
+    rank_winning_lists<ShadowMultiDealing, kMPFinalThreads>(c, n_blocks, kk, k, mx, s);
     const uint64_t kth = s[k - 1];                                // 0 = fewer than k rows in all (the launcher excludes it)
     __syncthreads();
-    const uint32_t thr = mp_threshold_below((uint32_t)(kth >> 32));
+    const uint32_t thr = threshold_below(key_order(kth), kMPEps);
     // candidates: every entry at or above the threshold; a list whose LAST entry passes may have dropped some (saturated)
     for (int t = tid; t < n_blocks * kk; t += kMPFinalThreads) {
         const uint64_t key = c[t];
-        if (key != 0ull && (uint32_t)(key >> 32) >= thr) {
+        if (key != 0ull && key_order(key) >= thr) {
             const int pos = atomicAdd(&n_cand, 1);
-            if (pos < kMPCandCap) cand_row[pos] = (uint32_t)(key & 0xFFFFFFFFull);
+            if (pos < kCandCap) cand_row[pos] = (uint32_t)key_row(key);
             if (t % kk == kk - 1) atomicAdd(&n_sat, 1);
         }
     }
     __syncthreads();
     const int m = n_cand;
-    const bool fall = kth == 0ull || n_sat > 0 || m > kMPCandCap;
+    const bool fall = kth == 0ull || n_sat > 0 || m > kCandCap;
     if (tid == 0) {
         if (fall) *flag = 1;                                      // one flag for the pass: the exact pass answers every question of it
         if (stats) { stats[2 * qi] = m; stats[2 * qi + 1] = n_sat; }
@@ -773,128 +572,47 @@ __global__ __launch_bounds__(kMPFinalThreads) void multi_prefilter_final_kernel(
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int cj = tile * kMTileRows + 4 * g + j;
-                if (cj < m) s[cj] = ((uint64_t)order_bits(sim4[j]) << 32) | (uint64_t)cand_row[cj];
+                if (cj < m) s[cj] = make_key(sim4[j], cand_row[cj]);
             }
         }
     }
     __syncthreads();
     top64_desc(s, m_pad);
-    if (tid == 0 && n_out) n_out[qi] = k;
-    for (int t = tid; t < k; t += kMPFinalThreads) {
-        idx_out[(size_t)qi * k_stride + t] = (int64_t)(s[t] & 0xFFFFFFFFull);
-        sim_out[(size_t)qi * k_stride + t] = order_bits_inverse((uint32_t)(s[t] >> 32));
-    }
+    write_hits(s, k, k, idx_out + (size_t)qi * k_stride, sim_out + (size_t)qi * k_stride, n_out ? n_out + qi : nullptr);
 }
 
-// Per-event finish over an (event, question) grid: segment_prefilter_kernel (cosine_topk_prefilter.hip) with multi_rescore_tile as
-// the re-scorer.  sims: s~ of question y at sims + y * sims_stride.  stats (nullable): [0] += 1 when the whole event was re-scored,
-// [1] += rows re-scored.
-template <int CHUNK, int THREADS>
-__global__ __launch_bounds__(THREADS) void segment_multi_prefilter_kernel(const float* __restrict__ sims, int64_t sims_stride,
-                                                                          const int64_t* __restrict__ seg_off, int k,
-                                                                          const float* __restrict__ store, const float* __restrict__ queries,
-                                                                          int64_t* __restrict__ idx_out, float* __restrict__ sim_out,
-                                                                          int32_t* __restrict__ n_out, int32_t* __restrict__ stats) {
-    __shared__ uint64_t s[CHUNK];
-    __shared__ uint32_t cand[kMPCandCap];
-    __shared__ __attribute__((aligned(16))) float qs[1024];
-    __shared__ int n_cand;
-    const int e = blockIdx.x, y = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t slot = (int64_t)y * gridDim.x + e;              // query-major outputs
-    sims += (int64_t)y * sims_stride;
-    const int64_t lo = seg_off[e], hi = seg_off[e + 1];
-    const int64_t n = hi - lo;
-    const int k_out = (int)(n < k ? (n > 0 ? n : 0) : k);
-    if (tid == 0) n_cand = 0;
-    if (n <= 0) {                                                  // block-uniform
-        if (tid == 0) n_out[slot] = 0;
-        for (int t = tid; t < k; t += THREADS) { idx_out[slot * k + t] = -1; sim_out[slot * k + t] = 0.0f; }
-        return;
+// Per-event finish over an (event, question) grid: segment_prefilter_kernel (topk_select.h) with multi_rescore_tile as the
+// re-scorer, in tiles of 16 candidate rows per wave; the question waits in LDS.
+struct TileRescore {
+    static constexpr float kEps = kMPEps;
+    struct Lds { __attribute__((aligned(16))) float qs[1024]; };
+    template <int THREADS>
+    __device__ static __forceinline__ void stage(Lds& l, const float* __restrict__ queries, int y) {
+        for (int t = threadIdx.x; t < 256; t += THREADS)
+            *reinterpret_cast<f32x4*>(l.qs + 4 * t) = *reinterpret_cast<const f32x4*>(queries + (size_t)y * 1024 + 4 * t);
     }
-    for (int t = tid; t < 256; t += THREADS)
-        *reinterpret_cast<f32x4*>(qs + 4 * t) = *reinterpret_cast<const f32x4*>(queries + (size_t)y * 1024 + 4 * t);
-    // ---- the k-th largest approximate key of the event (pieces of a chunk, carrying the running best k) ---------------------
-    uint32_t thr = 0u;                                             // n <= k: every row is a candidate
-    if (n > k) {
-        int have = 0;
-        int64_t base = 0;
-        do {
-            const int64_t left = n - base;
-            const int take = (int)(left < (int64_t)(CHUNK - have) ? left : (int64_t)(CHUNK - have));
-            const int total = have + take;
-            const int n2 = pow2_at_least(total, 64);
-            for (int t = have + tid; t < n2; t += THREADS) {
-                uint64_t key = 0ull;
-                if (t < total) {
-                    const int64_t r = base + (t - have);
-                    key = ((uint64_t)order_bits(sims[lo + r]) << 32) | (uint64_t)(uint32_t)r;
-                }
-                s[t] = key;
-            }
-            __syncthreads();
-            top64_desc(s, n2);
-            have = total < k ? total : k;
-            base += take;
-        } while (base < n);
-        thr = mp_threshold_below((uint32_t)(s[k - 1] >> 32));
-    }
-    __syncthreads();
-    // ---- candidates ---------------------------------------------------------------------------------------------------------
-    for (int64_t r = tid; r < n; r += THREADS) {
-        if (order_bits(sims[lo + r]) >= thr) {
-            const int pos = atomicAdd(&n_cand, 1);
-            if (pos < kMPCandCap) cand[pos] = (uint32_t)r;
-        }
-    }
-    __syncthreads();
-    const bool all_rows = n_cand > kMPCandCap;                     // block-uniform
-    const int64_t m = all_rows ? n : (int64_t)n_cand;
-    if (tid == 0 && stats) {                                       // a diagnostic: an int32 sum over all pairs and passes, it may wrap
-        if (all_rows) atomicAdd(&stats[0], 1);
-        atomicAdd(&stats[1], (int)m);
-    }
-    // ---- exact re-score in tiles of 16 rows, k best (pieces of a chunk with carry, as above) ---------------------------------
-    const int r16 = lane & 15, g = lane >> 4;
-    int have = 0;
-    int64_t base = 0;
-    do {
-        const int64_t left = m - base;
-        const int take = (int)(left < (int64_t)(CHUNK - have) ? left : (int64_t)(CHUNK - have));
-        const int total = have + take;
-        const int n2 = pow2_at_least(total, 64);
-        for (int t = total + tid; t < n2; t += THREADS) s[t] = 0ull;
-        for (int tile = wave; tile * kMTileRows < take; tile += THREADS / 64) {        // wave-uniform trip count per wave
+    const float* qs;
+    int y;
+    __device__ __forceinline__ TileRescore(Lds& l, const float*, int y_) : qs(l.qs), y(y_) {}
+    template <int THREADS, class RowOf>
+    __device__ __forceinline__ void score(const float* __restrict__ rows, int take, RowOf row_of, uint64_t* out) const {
+        const int lane = threadIdx.x & 63, r16 = lane & 15, g = lane >> 4;
+        for (int tile = threadIdx.x >> 6; tile * kMTileRows < take; tile += THREADS / 64) {        // wave-uniform trip count per wave
             const int cc = tile * kMTileRows + r16;
-            const float* row = nullptr;
-            if (cc < take) row = store + (lo + (all_rows ? base + cc : (int64_t)cand[base + cc])) * 1024;
-            const f32x4 sim4 = multi_rescore_tile(row, qs, y, lane);
+            const f32x4 sim4 = multi_rescore_tile(cc < take ? rows + row_of(cc) * 1024 : nullptr, qs, y, lane);
             if (r16 == y) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int cj = tile * kMTileRows + 4 * g + j;
-                    if (cj < take) {
-                        const int64_t r = all_rows ? base + cj : (int64_t)cand[base + cj];
-                        s[have + cj] = ((uint64_t)order_bits(sim4[j]) << 32) | (uint64_t)(uint32_t)r;
-                    }
+                    if (cj < take) out[cj] = make_key(sim4[j], (uint32_t)row_of(cj));
                 }
             }
         }
-        __syncthreads();
-        top64_desc(s, n2);
-        have = total < k ? total : k;
-        base += take;
-    } while (base < m);
-    if (tid == 0) n_out[slot] = k_out;
-    for (int t = tid; t < k; t += THREADS) {
-        const bool ok = t < k_out;
-        idx_out[slot * k + t] = ok ? (int64_t)(s[t] & 0xFFFFFFFFull) : -1;
-        sim_out[slot * k + t] = ok ? order_bits_inverse((uint32_t)(s[t] >> 32)) : 0.0f;
     }
-}
+};
 
 static int shadow_multi_grid(int64_t n_rows) {                 // one workgroup per CU (its LDS fills the CU), 128 rows per round
-    const int64_t chunks = (n_rows + kSRows - 1) / kSRows;
-    return (int)(chunks < kNumCU ? chunks : kNumCU);
+    return ShadowMultiDealing::grid(n_rows, kNumCU);
 }
 
 struct MultiPrefilterPlan { size_t exact, off_lists, off_flag, total; };
@@ -951,30 +669,30 @@ extern "C" int hmm_cosine_topk_multi_prefilter(const float* store_dev, const voi
     }
     HMM_ENSURE_DYN_LDS(shadow_multi_kernel<false>, (int)sizeof(ShadowLds));
     HMM_ENSURE_DYN_LDS(scan_multi_kernel<false>, (int)sizeof(MultiLds));
-    const int kk = mp_list_len(k);
+    const int kk = prefilter_list_len(k);
     const int grid = shadow_multi_grid(n_rows), exact_grid = multi_grid(n_rows);
     uint64_t* lists = reinterpret_cast<uint64_t*>(ws + p.off_lists);
     uint64_t* cand = reinterpret_cast<uint64_t*>(ws);
     int* flag = reinterpret_cast<int*>(ws + p.off_flag);
-    for (int q0 = 0; q0 < n_queries; q0 += kMQ) {                  // 16 queries per pass over the shadow
-        const int nq = n_queries - q0 < kMQ ? n_queries - q0 : kMQ;
-        const float* qp = queries_dev + (size_t)q0 * dim;
-        int64_t* io = idx_out_dev + (size_t)q0 * k;
-        float* so = sim_out_dev + (size_t)q0 * k;
-        int32_t* no = n_out_dev ? n_out_dev + q0 : nullptr;
+    return for_each_pass(n_queries, [&](const QuestionPass& pass) -> int {       // 16 queries per pass over the shadow
+        const int nq = pass.nq;
+        const float* qp = pass.at(queries_dev, dim);
+        int64_t* io = pass.at(idx_out_dev, k);
+        float* so = pass.at(sim_out_dev, k);
+        int32_t* no = pass.at(n_out_dev, 1);
         shadow_multi_kernel<false><<<grid, kSWaves * 64, sizeof(ShadowLds), st>>>(static_cast<const uint4*>(shadow_dev), n_rows, qp, nq, kk,
                                                                                  lists, nullptr, 0, flag);
         HMM_LAUNCH_CHECK();
         multi_prefilter_final_kernel<<<nq, kMPFinalThreads, 0, st>>>(lists, grid, k, kk, store_dev, qp, io, so, no, k, flag,
-                                                                     stats_out_dev ? stats_out_dev + 2 * q0 : nullptr);
+                                                                     pass.at(stats_out_dev, 2));
         HMM_LAUNCH_CHECK();
         // the exact pass, conditional on the flag (its workgroups return at once otherwise)
         scan_multi_kernel<false><<<exact_grid, kMWaves * 64, sizeof(MultiLds), st>>>(store_dev, n_rows, qp, nq, k, cand, nullptr, 0, flag);
         HMM_LAUNCH_CHECK();
         topk_final_multi_kernel<<<nq, 1024, 0, st>>>(cand, exact_grid, k, k, io, so, no, k, flag);
         HMM_LAUNCH_CHECK();
-    }
-    return HMM_OK;
+        return HMM_OK;
+    });
 }
 
 extern "C" size_t hmm_cosine_topk_segmented_multi_prefilter_workspace_bytes(int64_t n_rows, int n_segments, int n_queries, int k) {
@@ -1015,22 +733,21 @@ extern "C" int hmm_cosine_topk_segmented_multi_prefilter(const float* store_dev,
     float* sims = static_cast<float*>(workspace_dev);
     const size_t per_query = (size_t)n_segments * k;
     const bool small = segments_are_small(n_rows, n_segments, k);  // the two shapes of segment_topk_kernel, for the same reason
-    for (int q0 = 0; q0 < n_queries; q0 += kMQ) {                  // 16 queries per pass over the shadow
-        const int nq = n_queries - q0 < kMQ ? n_queries - q0 : kMQ;
-        const float* qp = queries_dev + (size_t)q0 * dim;
-        shadow_multi_kernel<true><<<grid, kSWaves * 64, sizeof(ShadowLds), st>>>(static_cast<const uint4*>(shadow_dev), n_rows, qp, nq, 0,
+    return for_each_pass(n_queries, [&](const QuestionPass& pass) -> int {       // 16 queries per pass over the shadow
+        const float* qp = pass.at(queries_dev, dim);
+        shadow_multi_kernel<true><<<grid, kSWaves * 64, sizeof(ShadowLds), st>>>(static_cast<const uint4*>(shadow_dev), n_rows, qp, pass.nq, 0,
                                                                                 nullptr, sims, stride, nullptr);
         HMM_LAUNCH_CHECK();
-        const dim3 sgrid(n_segments, nq);
+        const dim3 sgrid(n_segments, pass.nq);
         if (small)
-            segment_multi_prefilter_kernel<kSmallSegChunk, 256><<<sgrid, 256, 0, st>>>(
-                sims, stride, seg_offsets_dev, k, store_dev, qp, idx_out_dev + q0 * per_query, sim_out_dev + q0 * per_query,
-                n_out_dev + (size_t)q0 * n_segments, stats_out_dev);
+            segment_prefilter_kernel<kSmallSegChunk, 256, TileRescore><<<sgrid, 256, 0, st>>>(
+                sims, stride, seg_offsets_dev, k, store_dev, qp, pass.at(idx_out_dev, per_query), pass.at(sim_out_dev, per_query),
+                pass.at(n_out_dev, n_segments), stats_out_dev);
         else
-            segment_multi_prefilter_kernel<kChunk, 512><<<sgrid, 512, 0, st>>>(
-                sims, stride, seg_offsets_dev, k, store_dev, qp, idx_out_dev + q0 * per_query, sim_out_dev + q0 * per_query,
-                n_out_dev + (size_t)q0 * n_segments, stats_out_dev);
+            segment_prefilter_kernel<kChunk, 512, TileRescore><<<sgrid, 512, 0, st>>>(
+                sims, stride, seg_offsets_dev, k, store_dev, qp, pass.at(idx_out_dev, per_query), pass.at(sim_out_dev, per_query),
+                pass.at(n_out_dev, n_segments), stats_out_dev);
         HMM_LAUNCH_CHECK();
-    }
-    return HMM_OK;
+        return HMM_OK;
+    });
 }

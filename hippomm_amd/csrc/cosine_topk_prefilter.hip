@@ -23,6 +23,7 @@
 #include "hmm_common.h"
 #include "topk_tournament.h"
 #include "cosine_topk_shared.h"
+#include "topk_select.h"
 
 namespace hmm {
 
@@ -33,9 +34,8 @@ HMM_TUNABLE(int, g_prefilter_blocks, kNumCU * 3)       // prefilter_topk_kernel
 HMM_TUNABLE(int, g_prefilter_sims_blocks, kScanBlocks) // prefilter_sims_kernel (probe build only)
 HMM_TUNABLE(int, g_prefilter_sims_deferred, 1)         // 0: prefilter_sims_kernel instead of prefilter_sims_deferred_kernel (probe build only)
 #endif
-constexpr float kPrefilterEps = 0.0040f;
-constexpr int kPrefilterCap = 1024;           // candidate rows pass 2 re-scores itself (16 waves)
-constexpr int kPrefilterMaxK = 64;
+constexpr float kPrefilterEps = 0.0040f;       // |s~ - s| on this route: the error bound above
+constexpr int kPrefilterMaxK = kListMaxK;
 
 // ---- shadow build: one wave per row ----------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void shadow_build_kernel(const float4* __restrict__ store, int64_t n_rows,
@@ -59,8 +59,17 @@ __device__ __forceinline__ float dot8_bf16(const uint4& x, const float4& qa, con
     return acc;
 }
 
+// The query of a shadow pass in a wave's registers: this lane's elements in the shadow's piece order (shadow_row_store), and
+// 1 / ||q|| exactly as the exact kernels take ||q|| (load_query_frags).
+__device__ __forceinline__ float load_shadow_query_frags(const float4* __restrict__ query, int lane, float4 (&q)[4]) {
+    float4 t[4];
+    const float q_len = load_query_frags(query, lane, t);
+    q[0] = query[2 * lane]; q[1] = query[2 * lane + 1]; q[2] = query[128 + 2 * lane]; q[3] = query[128 + 2 * lane + 1];
+    return 1.0f / q_len;
+}
+
 // ---- pass 1: stream the shadow, block-local top-k of the approximate keys ------------------------------------------------------
-// Rows are dealt four at a time, wave after wave (row r belongs to wave (r / 4) % n_waves): a block reads 32 KiB contiguous per
+// Rows are dealt four at a time, wave after wave (PrefilterDealing: row r belongs to wave (r / 4) % n_waves): a block reads 32 KiB contiguous per
 // iteration and takes 16 consecutive rows of every band of 32 768, so a run of neighbouring rows -- the near-identical frames of
 // one scene of a video -- puts at most 16 candidates into one block's list, which keeps at least 32 entries (prefilter_list_len):
 // contiguous scenes of any length do not saturate a list.  (Spreading consecutive groups over different blocks, or dealing one
@@ -73,26 +82,14 @@ __global__ __launch_bounds__(256) void prefilter_topk_kernel(const uint4* __rest
     const int lane = threadIdx.x & 63;
     const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * 4;
     if (threadIdx.x == 0) count = 0;
-    // query elements of this lane, in the shadow's piece order, and 1 / ||q|| exactly as the exact kernels take ||q||
     float4 q[4];
-    float qs = 0.f;
-    {
-        float4 t[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            t[j] = query[j * 64 + lane];
-            qs = fmaf(t[j].x, t[j].x, qs); qs = fmaf(t[j].y, t[j].y, qs);
-            qs = fmaf(t[j].z, t[j].z, qs); qs = fmaf(t[j].w, t[j].w, qs);
-        }
-        q[0] = query[2 * lane]; q[1] = query[2 * lane + 1]; q[2] = query[128 + 2 * lane]; q[3] = query[128 + 2 * lane + 1];
-    }
-    const float inv_qlen = 1.0f / sqrtf(wave_sum(qs));
+    const float inv_qlen = load_shadow_query_frags(query, lane, q);
     __syncthreads();
 
-    const int64_t iters = (n_rows + n_waves * 4 - 1) / (n_waves * 4);
-    const int compact_every = (kFusedCap - k) / 16;                          // 16 rows per block per iteration
+    const int64_t iters = PrefilterDealing::iterations(n_rows, n_waves);
+    const int compact_every = (kFusedCap - k) / PrefilterDealing::kBlockRows;    // 16 rows per block per iteration
     for (int64_t it = 0; it < iters; ++it) {
-        const int64_t r0 = wave * 4 + it * n_waves * 4;                      // this wave's group of four rows
+        const int64_t r0 = PrefilterDealing::first_row(wave, it, n_waves);   // this wave's group of four rows
         const int have = r0 >= n_rows ? 0 : (n_rows - r0 >= 4 ? 4 : (int)(n_rows - r0));             // wave-uniform
         if (have) {
             uint4 x[4][2];
@@ -114,22 +111,13 @@ __global__ __launch_bounds__(256) void prefilter_topk_kernel(const uint4* __rest
                 const int pos = atomicAdd(&count, have);
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
-                    if (i < have) cand[pos + i] = ((uint64_t)order_bits(d[i] * inv_qlen) << 32) | (uint64_t)(uint32_t)(r0 + i);
+                    if (i < have) cand[pos + i] = make_key(d[i] * inv_qlen, (uint32_t)(r0 + i));
             }
         }
-        if ((it + 1) % compact_every == 0 || it + 1 == iters) {              // block-uniform
-            __syncthreads();
-            const int n = count;
-            const int n2 = pow2_at_least(n, 64);
-            for (int t = n + threadIdx.x; t < n2; t += 256) cand[t] = 0ull;
-            __syncthreads();
-            top64_desc<false>(cand, n2);                                     // k <= 64 on this path
-            if (threadIdx.x == 0) count = n < k ? n : k;
-            __syncthreads();
-        }
+        if ((it + 1) % compact_every == 0 || it + 1 == iters) compact_block_list<false>(cand, count, k);    // block-uniform; k <= 64 on this path
     }
     const int n = count;
-    for (int t = threadIdx.x; t < k; t += 256) out[(int64_t)blockIdx.x * k + t] = t < n ? cand[t] : 0ull;
+    flush_block_list(cand, n, k, out);
     if (threadIdx.x == 0) maxima[blockIdx.x] = n > 0 ? cand[0] : 0ull;       // the block maxima once more, contiguous: pass 2's first read
 }
 
@@ -150,7 +138,7 @@ extern "C" void hmm_probe_set_prefilter_stamps(long long* stamps_dev) { g_pf_sta
 // lists: n_blocks x kk keys (kk >= k entries per block, sorted descending, 0-padded).
 __global__ __launch_bounds__(1024) void prefilter_final_kernel(const uint64_t* __restrict__ lists, const uint64_t* __restrict__ maxima,
                                                                unsigned* __restrict__ fallback_ticket, int n_blocks, int k, int kk,
-                                                               int64_t n_waves, const float4* __restrict__ store,
+                                                               const float4* __restrict__ store,
                                                                const float4* __restrict__ query,
                                                                int64_t* __restrict__ idx_out, float* __restrict__ sim_out,
                                                                int32_t* __restrict__ n_out, int* __restrict__ fallback,
@@ -158,7 +146,7 @@ __global__ __launch_bounds__(1024) void prefilter_final_kernel(const uint64_t* _
                                                                HMM_PF_STAMP_PARAM) {
     __shared__ uint64_t mx[kScanBlocks];
     __shared__ uint64_t s[kChunk];
-    __shared__ uint32_t cand_row[kPrefilterCap];
+    __shared__ uint32_t cand_row[kCandCap];
     __shared__ uint16_t hot[kScanBlocks];
     __shared__ int n_cand, n_sat, n_hot;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -184,7 +172,7 @@ __global__ __launch_bounds__(1024) void prefilter_final_kernel(const uint64_t* _
     auto collect = [&](uint32_t thr) {
 #pragma unroll
         for (int i = 0; i < kScanBlocks / 1024; ++i)
-            if (own[i] != 0ull && (uint32_t)(own[i] >> 32) >= thr) hot[atomicAdd(&n_hot, 1)] = (uint16_t)(tid + i * 1024);
+            if (own[i] != 0ull && key_order(own[i]) >= thr) hot[atomicAdd(&n_hot, 1)] = (uint16_t)(tid + i * 1024);
         __syncthreads();
         constexpr int kHotUnroll = 8;
         for (int h0 = wave; h0 < n_hot; h0 += 16 * kHotUnroll) {
@@ -198,22 +186,19 @@ __global__ __launch_bounds__(1024) void prefilter_final_kernel(const uint64_t* _
             for (int u = 0; u < kHotUnroll; ++u) {
                 if (h0 + 16 * u >= n_hot) break;                              // wave-uniform
                 const uint64_t key = keys[u];
-                const bool pass = key != 0ull && (uint32_t)(key >> 32) >= thr;
+                const bool pass = key != 0ull && key_order(key) >= thr;
                 const unsigned long long mask = __ballot(pass);
                 int base = 0;
                 if (lane == 0) base = atomicAdd(&n_cand, __popcll(mask));
                 base = __shfl(base, 0, 64);
                 if (pass) {
                     const int pos = base + __popcll(mask & ((1ull << lane) - 1ull));
-                    if (pos < kPrefilterCap) cand_row[pos] = (uint32_t)(key & 0xFFFFFFFFull);
+                    if (pos < kCandCap) cand_row[pos] = (uint32_t)key_row(key);
                     if (lane == kk - 1) atomicAdd(&n_sat, 1);
                 }
             }
         }
         __syncthreads();
-    };
-    auto threshold_below = [](uint64_t key) {                                 // NaN key -> 0xFFFFFFFF: only NaN rows pass
-        return order_bits(order_bits_inverse((uint32_t)(key >> 32)) - 2.0f * kPrefilterEps);
     };
     // QUICK route: the k-th largest block MAXIMUM is a lower bound of the k-th largest key (k lists hold a key that large), and it
     // IS that key whenever the k best rows sit in k different lists -- the rule on a store without long runs of near-identical
@@ -223,7 +208,7 @@ __global__ __launch_bounds__(1024) void prefilter_final_kernel(const uint64_t* _
     uint64_t kth = mx[k - 1];                                                 // k <= 64: inside the ranked front of mx
     bool quick = false;
     if (kth != 0ull) {                                                        // block-uniform (mx is shared)
-        collect(threshold_below(kth));
+        collect(threshold_below(key_order(kth), kPrefilterEps));
         quick = n_sat == 0 && n_cand <= kQuickCap;
     }
     if (!quick) {
@@ -233,31 +218,17 @@ __global__ __launch_bounds__(1024) void prefilter_final_kernel(const uint64_t* _
         // exact-scan fallback on that bound alone.)
         __syncthreads();
         if (tid == 0) { n_cand = 0; n_sat = 0; n_hot = 0; }
-        const int n_win = n_blocks < k ? n_blocks : k;
-        const int m2 = pow2_at_least(n_win * kk, 64);
-        for (int t = tid; t < m2; t += 1024) {
-            uint64_t key = 0ull;
-            if (t < n_win * kk) {
-                const uint64_t top = mx[t / kk];
-                if (top != 0ull) {
-                    const int64_t row = (int64_t)(top & 0xFFFFFFFFull);
-                    const int blk = (int)(((row >> 2) % n_waves) >> 2);       // rows are dealt four per wave
-                    key = lists[(int64_t)blk * kk + (t % kk)];
-                }
-            }
-            s[t] = key;
-        }
-        __syncthreads();
+        const int m2 = gather_winning_lists<PrefilterDealing, 1024>(lists, mx, n_blocks, kk, k, s);
         HMM_PF_STAMP(3);                                                      // winners' lists gathered
         top64_desc(s, m2);
         HMM_PF_STAMP(4);                                                      // ... ranked: the k-th largest approximate key
         kth = s[k - 1];                                                       // 0 = fewer than k rows in all (launcher excludes it)
         __syncthreads();
-        collect(threshold_below(kth));
+        collect(threshold_below(key_order(kth), kPrefilterEps));
     }
     HMM_PF_STAMP(5);                                                          // hot lists read, candidates listed
     const int m = n_cand;
-    const bool fall = kth == 0ull || n_sat > 0 || m > kPrefilterCap;
+    const bool fall = kth == 0ull || n_sat > 0 || m > kCandCap;
     if (tid == 0) {
         *fallback = fall ? 1 : 0;
         if (stats) { stats[0] = m; stats[1] = n_sat; }
@@ -265,14 +236,7 @@ __global__ __launch_bounds__(1024) void prefilter_final_kernel(const uint64_t* _
     if (fall) return;                                                         // block-uniform: the exact scan answers
     // exact re-score: one wave per candidate row, the arithmetic of scan_topk_kernel
     float4 q[4];
-    float qs = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        q[j] = query[j * 64 + lane];
-        qs = fmaf(q[j].x, q[j].x, qs); qs = fmaf(q[j].y, q[j].y, qs);
-        qs = fmaf(q[j].z, q[j].z, qs); qs = fmaf(q[j].w, q[j].w, qs);
-    }
-    const float q_len = sqrtf(wave_sum(qs));
+    const float q_len = load_query_frags(query, lane, q);
     const int m_pad = pow2_at_least(m, 64);
     for (int t = m + tid; t < m_pad; t += 1024) s[t] = 0ull;
     for (int c0 = wave * 4; c0 < m; c0 += 64) {                               // four candidates per wave and round: one latency per round
@@ -289,25 +253,14 @@ __global__ __launch_bounds__(1024) void prefilter_final_kernel(const uint64_t* _
         if (lane == 0) {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                if (i < nr) s[c0 + i] = ((uint64_t)order_bits(sim[i]) << 32) | (uint64_t)row[i];
+                if (i < nr) s[c0 + i] = make_key(sim[i], row[i]);
         }
     }
     __syncthreads();
     HMM_PF_STAMP(6);                                                          // candidates re-scored
     top64_desc(s, m_pad);
     HMM_PF_STAMP(7);
-    if (tid == 0 && n_out) *n_out = k;
-    for (int t = tid; t < k; t += 1024) {
-        idx_out[t] = (int64_t)(s[t] & 0xFFFFFFFFull);
-        sim_out[t] = order_bits_inverse((uint32_t)(s[t] >> 32));
-    }
-}
-
-// Entries a block keeps: at least twice k and at least 32, so that a handful of near-ties inside one block (k = 1: ANY second
-// candidate) does not saturate its list; 64 at most (the tournament's width).
-static int prefilter_list_len(int k) {
-    int kk = 2 * k < 32 ? 32 : 2 * k;
-    return kk > kPrefilterMaxK ? kPrefilterMaxK : kk;
+    write_hits(s, k, k, idx_out, sim_out, n_out);
 }
 
 // ---- per-event variant (hmm_cosine_topk_segmented through the shadow) -------------------------------------------------------
@@ -318,14 +271,7 @@ __global__ __launch_bounds__(256) void prefilter_sims_kernel(const uint4* __rest
     const int lane = threadIdx.x & 63;
     const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * 4;
     float4 q[4];
-    float qs = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float4 t = query[j * 64 + lane];
-        qs = fmaf(t.x, t.x, qs); qs = fmaf(t.y, t.y, qs); qs = fmaf(t.z, t.z, qs); qs = fmaf(t.w, t.w, qs);
-    }
-    q[0] = query[2 * lane]; q[1] = query[2 * lane + 1]; q[2] = query[128 + 2 * lane]; q[3] = query[128 + 2 * lane + 1];
-    const float inv_qlen = 1.0f / sqrtf(wave_sum(qs));
+    const float inv_qlen = load_shadow_query_frags(query, lane, q);
     for (int64_t base = wave * 32; base < n_rows; base += n_waves * 32) {
         float mine = 0.f;                                         // lane l < 32: s~ of row base + l
         const int64_t left = n_rows - base;
@@ -363,15 +309,8 @@ __global__ __launch_bounds__(256) void prefilter_sims_deferred_kernel(const uint
     const int lane = threadIdx.x & 63;
     const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * 4;
     float4 q[4];
-    float qs = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float4 t = query[j * 64 + lane];
-        qs = fmaf(t.x, t.x, qs); qs = fmaf(t.y, t.y, qs); qs = fmaf(t.z, t.z, qs); qs = fmaf(t.w, t.w, qs);
-    }
-    q[0] = query[2 * lane]; q[1] = query[2 * lane + 1]; q[2] = query[128 + 2 * lane]; q[3] = query[128 + 2 * lane + 1];
-    const float inv_qlen = 1.0f / sqrtf(wave_sum(qs));
-    for (int64_t it0 = 0; (wave + it0 * n_waves) * 4 < n_rows; it0 += 64 * kPrefilterSimsHeld) {
+    const float inv_qlen = load_shadow_query_frags(query, lane, q);
+    for (int64_t it0 = 0; PrefilterDealing::first_row(wave, it0, n_waves) < n_rows; it0 += 64 * kPrefilterSimsHeld) {
         float h[kPrefilterSimsHeld][4];
 #pragma unroll
         for (int j = 0; j < kPrefilterSimsHeld; ++j)
@@ -380,7 +319,7 @@ __global__ __launch_bounds__(256) void prefilter_sims_deferred_kernel(const uint
 #pragma unroll
         for (int j = 0; j < kPrefilterSimsHeld; ++j) {
             for (int l = 0; l < 64; ++l) {
-                const int64_t r0 = (wave + (it0 + j * 64 + l) * n_waves) * 4;
+                const int64_t r0 = PrefilterDealing::first_row(wave, it0 + j * 64 + l, n_waves);
                 if (r0 >= n_rows) break;                                     // wave-uniform; every later iteration is past the end too
                 uint4 x[4][2];
 #pragma unroll
@@ -401,7 +340,7 @@ __global__ __launch_bounds__(256) void prefilter_sims_deferred_kernel(const uint
         }
 #pragma unroll
         for (int j = 0; j < kPrefilterSimsHeld; ++j) {
-            const int64_t r0 = (wave + (it0 + j * 64 + lane) * n_waves) * 4;
+            const int64_t r0 = PrefilterDealing::first_row(wave, it0 + j * 64 + lane, n_waves);
             if (r0 + 3 < n_rows) {
                 *reinterpret_cast<float4*>(sims + r0) = make_float4(h[j][0], h[j][1], h[j][2], h[j][3]);
             } else {
@@ -413,100 +352,28 @@ __global__ __launch_bounds__(256) void prefilter_sims_deferred_kernel(const uint
     }
 }
 
-// pass 2: one workgroup per event.  The event's k-th largest s~ gives the threshold, the rows at or above it are re-scored on the
-// fp32 store (exact_row_sim) and the k best of those are the event's answer -- what segment_topk_kernel returns on the exact
-// similarities.  More candidates than the buffer holds (an event of near-identical rows): every row of the event is re-scored.
-constexpr int kSegCandCap = 1024;
-template <int CHUNK, int THREADS>
-__global__ __launch_bounds__(THREADS) void segment_prefilter_kernel(const float* __restrict__ sims, const int64_t* __restrict__ seg_off,
-                                                                 int k, const float4* __restrict__ store,
-                                                                 const float4* __restrict__ query, int64_t* __restrict__ idx_out,
-                                                                 float* __restrict__ sim_out, int32_t* __restrict__ n_out) {
-    __shared__ uint64_t s[CHUNK];
-    __shared__ uint32_t cand[kSegCandCap];
-    __shared__ int n_cand;
-    const int e = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t lo = seg_off[e], hi = seg_off[e + 1];
-    const int64_t n = hi - lo;
-    const int k_out = (int)(n < k ? (n > 0 ? n : 0) : k);
-    if (tid == 0) n_cand = 0;
-    if (n <= 0) {                                                  // block-uniform
-        if (tid == 0) n_out[e] = 0;
-        for (int t = tid; t < k; t += THREADS) { idx_out[(int64_t)e * k + t] = -1; sim_out[(int64_t)e * k + t] = 0.0f; }
-        return;
-    }
-    // ---- the k-th largest approximate key of the event (pieces of a chunk, carrying the running best k) ---------------------
-    uint32_t thr = 0u;                                             // n <= k: every row is a candidate
-    if (n > k) {
-        int have = 0;
-        int64_t base = 0;
-        do {
-            const int64_t left = n - base;
-            const int take = (int)(left < (int64_t)(CHUNK - have) ? left : (int64_t)(CHUNK - have));
-            const int total = have + take;
-            const int n2 = pow2_at_least(total, 64);
-            for (int t = have + tid; t < n2; t += THREADS) {
-                uint64_t key = 0ull;
-                if (t < total) {
-                    const int64_t r = base + (t - have);
-                    key = ((uint64_t)order_bits(sims[lo + r]) << 32) | (uint64_t)(uint32_t)r;
-                }
-                s[t] = key;
-            }
-            __syncthreads();
-            top64_desc(s, n2);
-            have = total < k ? total : k;
-            base += take;
-        } while (base < n);
-        const float t_lo = order_bits_inverse((uint32_t)(s[k - 1] >> 32)) - 2.0f * kPrefilterEps;
-        thr = order_bits(t_lo);
-    }
-    __syncthreads();
-    // ---- candidates ---------------------------------------------------------------------------------------------------------
-    for (int64_t r = tid; r < n; r += THREADS) {
-        if (order_bits(sims[lo + r]) >= thr) {
-            const int pos = atomicAdd(&n_cand, 1);
-            if (pos < kSegCandCap) cand[pos] = (uint32_t)r;
-        }
-    }
-    __syncthreads();
-    const bool all_rows = n_cand > kSegCandCap;                    // block-uniform
-    const int64_t m = all_rows ? n : (int64_t)n_cand;
-    // ---- exact re-score, k best (pieces of a chunk with carry, as above) ------------------------------------------------------
+// pass 2: segment_prefilter_kernel (topk_select.h), one workgroup per event, with this re-scorer: one wave per candidate row and
+// exact_row_sim, the arithmetic of scan_topk_kernel.
+struct RowRescore {
+    static constexpr float kEps = kPrefilterEps;
+    struct Lds {};
+    template <int THREADS>
+    __device__ static __forceinline__ void stage(Lds&, const float*, int) {}
     float4 q[4];
-    float qs = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        q[j] = query[j * 64 + lane];
-        qs = fmaf(q[j].x, q[j].x, qs); qs = fmaf(q[j].y, q[j].y, qs);
-        qs = fmaf(q[j].z, q[j].z, qs); qs = fmaf(q[j].w, q[j].w, qs);
+    float q_len;
+    __device__ __forceinline__ RowRescore(Lds&, const float* __restrict__ queries, int y) {
+        q_len = load_query_frags(reinterpret_cast<const float4*>(queries) + (size_t)y * 256, threadIdx.x & 63, q);
     }
-    const float q_len = sqrtf(wave_sum(qs));
-    int have = 0;
-    int64_t base = 0;
-    do {
-        const int64_t left = m - base;
-        const int take = (int)(left < (int64_t)(CHUNK - have) ? left : (int64_t)(CHUNK - have));
-        const int total = have + take;
-        const int n2 = pow2_at_least(total, 64);
-        for (int t = total + tid; t < n2; t += THREADS) s[t] = 0ull;
-        for (int c = wave; c < take; c += THREADS / 64) {                    // wave-uniform trip count per wave
-            const int64_t r = all_rows ? base + c : (int64_t)cand[base + c];
-            const float sim = exact_row_sim(store + (lo + r) * 256 + lane, q, q_len);
-            if (lane == 0) s[have + c] = ((uint64_t)order_bits(sim) << 32) | (uint64_t)(uint32_t)r;
+    template <int THREADS, class RowOf>
+    __device__ __forceinline__ void score(const float* __restrict__ rows, int take, RowOf row_of, uint64_t* out) const {
+        const int lane = threadIdx.x & 63;
+        for (int c = threadIdx.x >> 6; c < take; c += THREADS / 64) {            // wave-uniform trip count per wave
+            const int64_t r = row_of(c);
+            const float sim = exact_row_sim(reinterpret_cast<const float4*>(rows) + r * 256 + lane, q, q_len);
+            if (lane == 0) out[c] = make_key(sim, (uint32_t)r);
         }
-        __syncthreads();
-        top64_desc(s, n2);
-        have = total < k ? total : k;
-        base += take;
-    } while (base < m);
-    if (tid == 0) n_out[e] = k_out;
-    for (int t = tid; t < k; t += THREADS) {
-        const bool ok = t < k_out;
-        idx_out[(int64_t)e * k + t] = ok ? (int64_t)(s[t] & 0xFFFFFFFFull) : -1;
-        sim_out[(int64_t)e * k + t] = ok ? order_bits_inverse((uint32_t)(s[t] >> 32)) : 0.0f;
     }
-}
+};
 
 struct PrefilterPlan { size_t off_exact, off_lists, off_maxima, off_flag, total; int blocks; };
 
@@ -515,9 +382,7 @@ static PrefilterPlan prefilter_plan(int64_t n, int k) {
     p.off_exact = 0;
     const size_t exact = hmm_cosine_topk_workspace_bytes(n, k);
     p.off_lists = align_up(exact, 256);
-    int64_t waves_needed = (n + 3) / 4;
-    int blocks = (int)((waves_needed + 3) / 4);
-    p.blocks = blocks > g_prefilter_blocks ? g_prefilter_blocks : blocks;
+    p.blocks = PrefilterDealing::grid(n, g_prefilter_blocks);
     p.off_maxima = p.off_lists + align_up((size_t)kScanBlocks * (size_t)kPrefilterMaxK * 8, 256);
     p.off_flag = p.off_maxima + align_up((size_t)kScanBlocks * 8, 256);          // int flag, then the fallback's unsigned ticket
     p.total = p.off_flag + 256;                                                  // the flag and the ticket use 8 of these 256 bytes; the rest is margin
@@ -584,7 +449,7 @@ extern "C" int hmm_cosine_topk_prefilter(const float* store_dev, const void* sha
     prefilter_topk_kernel<<<p.blocks, 256, 0, st>>>(static_cast<const uint4*>(shadow_dev), n_rows,
                                                     reinterpret_cast<const float4*>(query_dev), kk, lists, maxima);
     HMM_LAUNCH_CHECK();
-    prefilter_final_kernel<<<1, 1024, 0, st>>>(lists, maxima, ticket, p.blocks, k, kk, (int64_t)p.blocks * 4,
+    prefilter_final_kernel<<<1, 1024, 0, st>>>(lists, maxima, ticket, p.blocks, k, kk,
                                                reinterpret_cast<const float4*>(store_dev), reinterpret_cast<const float4*>(query_dev),
                                                idx_out_dev, sim_out_dev, n_out_dev, flag, stats_out_dev HMM_PF_STAMP_ARG);
     HMM_LAUNCH_CHECK();
@@ -627,20 +492,16 @@ extern "C" int hmm_cosine_topk_segmented_prefilter(const float* store_dev, const
     }
 #endif
     if (deferred) {
-        int64_t blocks = (n_rows + 15) / 16;                                // 4 waves x 4 rows
-        if (blocks > g_prefilter_blocks) blocks = g_prefilter_blocks;
-        prefilter_sims_deferred_kernel<<<(unsigned)blocks, 256, 0, st>>>(static_cast<const uint4*>(shadow_dev), n_rows,
+        prefilter_sims_deferred_kernel<<<PrefilterDealing::grid(n_rows, g_prefilter_blocks), 256, 0, st>>>(static_cast<const uint4*>(shadow_dev), n_rows,
                                                                          reinterpret_cast<const float4*>(query_dev), sims);
     }
     HMM_LAUNCH_CHECK();
     if (segments_are_small(n_rows, n_segments, k))          // the two shapes of segment_topk_kernel, for the same reason
-        segment_prefilter_kernel<kSmallSegChunk, 256><<<n_segments, 256, 0, st>>>(
-            sims, seg_offsets_dev, k, reinterpret_cast<const float4*>(store_dev), reinterpret_cast<const float4*>(query_dev), idx_out_dev,
-            sim_out_dev, n_out_dev);
+        segment_prefilter_kernel<kSmallSegChunk, 256, RowRescore><<<n_segments, 256, 0, st>>>(
+            sims, 0, seg_offsets_dev, k, store_dev, query_dev, idx_out_dev, sim_out_dev, n_out_dev, nullptr);
     else
-        segment_prefilter_kernel<kChunk, 1024><<<n_segments, 1024, 0, st>>>(
-            sims, seg_offsets_dev, k, reinterpret_cast<const float4*>(store_dev), reinterpret_cast<const float4*>(query_dev), idx_out_dev,
-            sim_out_dev, n_out_dev);
+        segment_prefilter_kernel<kChunk, 1024, RowRescore><<<n_segments, 1024, 0, st>>>(
+            sims, 0, seg_offsets_dev, k, store_dev, query_dev, idx_out_dev, sim_out_dev, n_out_dev, nullptr);
     HMM_LAUNCH_CHECK();
     return HMM_OK;
 }

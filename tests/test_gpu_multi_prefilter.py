@@ -71,10 +71,11 @@ def seg_both(es, queries, k):
 
 @pytest.mark.parametrize("sizes,k", [([300, 1, 0, 57, 5, 4096, 4097, 2], 5), ([9000, 3, 12000], 32), ([40] * 200, 5), ([500] * 64, 5),
                                      ([1500, 2, 0, 700, 1025, 64, 3000, 1], 5), ([200] * 50, 64),
-                                     ([5000], 64), ([5000], 100)])
+                                     ([5000], 64), ([5000], 100), ([1019, 1020, 1024, 1025, 2039, 2044, 1, 0, 2, 3], 5)])
 def test_per_event_equals_the_exact_batched_per_event_scan(sizes, k):
     """Empty and one-row events, events above one chunk, a tie and a zero row inside an event, k = 64 and k = 100, with 5 and with 17
-    questions."""
+    questions.  The last list crosses the SMALL chunk (1024 keys: its events average at most 1024 rows) with a carry of k = 5, see
+    tests/test_gpu_scan_prefilter.py."""
     from hippomm_amd.vector_ops import EventStore
     events = _events(sizes, seed=len(sizes) * 7 + k)
     if len(events) > 3 and events[3].shape[0] > 10:

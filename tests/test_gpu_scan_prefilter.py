@@ -160,10 +160,12 @@ def _events(sizes, seed):
 
 @pytest.mark.parametrize("sizes,k", [([300, 1, 0, 57, 5, 4096, 4097, 2], 5), ([9000, 3, 12000], 32), ([40] * 200, 5), ([500] * 64, 5),
                                      ([1500, 2, 0, 700, 1025, 64, 3000, 1], 5), ([200] * 50, 64),
-                                     ([5000], 64), ([5000], 100)])
+                                     ([5000], 64), ([5000], 100), ([1019, 1020, 1024, 1025, 2039, 2044, 1, 0, 2, 3], 5)])
 def test_per_event_prefilter_equals_the_exact_per_event_scan(sizes, k):
     """hmm_cosine_topk_segmented_prefilter vs hmm_cosine_topk_segmented: identical indices, similarity bits and counts for every
-    event -- empty and one-row events, events above one chunk, a tie and a NaN row inside an event, k above the prefilter's limit."""
+    event -- empty and one-row events, events above one chunk, a tie and a NaN row inside an event, k above the prefilter's limit.
+    The last list crosses the SMALL chunk (1024 keys, chosen because the events average at most 1024 rows) with a carry of k = 5:
+    1019 + 5 fills it exactly, 1020 / 1024 / 1025 sit around its edges, 2039 and 2044 around the edge of the second piece."""
     from hippomm_amd.vector_ops import EventStore
     events = _events(sizes, seed=len(sizes) * 7 + k)
     if len(events) > 3 and events[3].shape[0] > 10:

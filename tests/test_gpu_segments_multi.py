@@ -19,7 +19,8 @@ SIZE_LISTS = [([300, 1, 0, 57, 5, 4096, 4097, 2], 5),                   # the li
               ([9000, 3, 12000], 32),
               ([40] * 200, 5),
               ([1500, 2, 0, 700, 1025, 64, 3000, 1], 5),
-              ([200] * 50, 64)]
+              ([200] * 50, 64),
+              ([1019, 1020, 1024, 1025, 2039, 2044, 1, 0, 2, 3], 5)]     # around the edges of the SMALL chunk (1024 keys) with a carry of 5
 QS = [1, 3, 16, 17, 33]
 
 
