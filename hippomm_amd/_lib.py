@@ -74,6 +74,11 @@ _SIGNATURES = {
     "hmm_jpeg_workspace_bytes": (C.c_size_t, [c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "hmm_jpeg_reconstruct": (C.c_int, [c_ptr, C.c_int, C.c_size_t, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr,
                                        C.c_size_t, c_ptr]),
+    "hmm_jpeg_entropy_slot_bytes": (C.c_int64, [C.c_size_t]),
+    "hmm_jpeg_prepare_entropy": (C.c_int, [c_ptr, C.c_size_t, c_ptr, c_ptr, C.c_size_t]),
+    "hmm_jpeg_entropy_workspace_bytes": (C.c_size_t, [c_ptr, C.c_int, C.c_size_t]),
+    "hmm_jpeg_decode_coefs_device": (C.c_int, [c_ptr, C.c_int, C.c_size_t, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr,
+                                               C.c_size_t, c_ptr, c_ptr, C.c_size_t, c_ptr]),
     "hmm_encoder_create":(C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
     "hmm_encoder_destroy": (None, [c_ptr]),
     "hmm_encoder_load_param": (C.c_int, [c_ptr, C.c_char_p, c_ptr, C.c_int64, c_ptr]),

@@ -11,6 +11,7 @@
 // Called through ctypes, one frame per call, with the interpreter lock released: the package's decode thread pool runs it.
 #include "hmm_common.h"
 #include "jpeg_layout.h"
+#include "jpeg_entropy_core.h"
 
 #include <cstring>
 
@@ -377,5 +378,102 @@ extern "C" int hmm_jpeg_decode_coefs(const uint8_t* data, size_t n, const int32_
         if (b.nbits < b.npad) return HMM_JPEG_UNSUPPORTED;                 // read past the end of the data
     }
     if (!b.marker_is(0xD9)) return HMM_JPEG_UNSUPPORTED;                   // EOI right after the scan (no DNL, no second scan)
+    return HMM_JPEG_DECODED;
+}
+
+// ---- the device entropy route: the host's share ---------------------------------------------------------------------------------
+// Marker parse as above, then the scan's entropy bytes without their FF 00 stuffing plus the tables the kernel needs, into a
+// bitstream slot (jpeg_entropy_core.h).  No Huffman decoding here: that is jpeg_entropy.hip's.  Files with a restart interval,
+// with more than four distinct Huffman tables in use, or whose scan does not run up to an EOI marker keep the host entropy pass.
+
+extern "C" int64_t hmm_jpeg_entropy_slot_bytes(size_t file_bytes) {
+    return (int64_t)((file_bytes + (size_t)hmm::kEntropyDataOff + hmm::kEntropyPad + 255) / 256 * 256);
+}
+
+extern "C" int hmm_jpeg_prepare_entropy(const uint8_t* data, size_t n, const int32_t* geometry, void* slot, size_t slot_bytes) {
+    HMM_REQUIRE(data && geometry && slot, HMM_E_INVALID, "jpeg_prepare_entropy: null pointer");
+    HMM_REQUIRE(((uintptr_t)slot & 15) == 0, HMM_E_INVALID, "jpeg_prepare_entropy: the slot must be 16-byte aligned");
+    Frame f;
+    if (!parse(data, n, f)) return HMM_JPEG_UNSUPPORTED;
+    const int hmax = f.ncomp == 3 ? f.hmax : 1, vmax = f.ncomp == 3 ? f.vmax : 1;
+    if (f.W != geometry[0] || f.H != geometry[1] || f.ncomp != geometry[2] || hmax != geometry[3] || vmax != geometry[4])
+        return HMM_JPEG_OTHER_GEOMETRY;
+    if (f.restart) return HMM_JPEG_UNSUPPORTED;
+
+    // The entropy segment: up to the first FF that is not followed by 00, which must be the EOI marker (marker_is(0xD9)).
+    size_t stuffed = 0, end = 0;
+    bool eoi = false;
+    for (size_t i = f.scan; i < n;) {
+        const uint8_t* p = static_cast<const uint8_t*>(memchr(data + i, 0xFF, n - i));
+        if (!p) break;
+        const size_t k = (size_t)(p - data);
+        if (k + 1 < n && data[k + 1] == 0) {
+            ++stuffed;
+            i = k + 2;
+            continue;
+        }
+        eoi = k + 1 < n && data[k + 1] == 0xD9;
+        end = k;
+        break;
+    }
+    if (!eoi) return HMM_JPEG_UNSUPPORTED;
+    const size_t len = end - f.scan - stuffed;
+    if (len > hmm::kEntropyMaxBytes) return HMM_JPEG_UNSUPPORTED;
+    const size_t padded = (len + hmm::kEntropyPad - 1) / hmm::kEntropyPad * hmm::kEntropyPad;
+    HMM_REQUIRE(slot_bytes >= (size_t)hmm::kEntropyDataOff + padded, HMM_E_WORKSPACE,
+                "jpeg_prepare_entropy: slot of %zu bytes, %zu needed", slot_bytes, (size_t)hmm::kEntropyDataOff + padded);
+
+    // Table slots: the distinct (class, id) pairs the components select, four at the most.
+    int slot_class[4], slot_id[4], used = 0;
+    uint32_t selectors = 0;
+    for (int c = 0; c < f.ncomp; ++c)
+        for (int ac = 0; ac < 2; ++ac) {
+            const int id = ac ? f.ta[c] : f.td[c];
+            int s = 0;
+            while (s < used && !(slot_class[s] == ac && slot_id[s] == id)) ++s;
+            if (s == used) {
+                if (used == 4) return HMM_JPEG_UNSUPPORTED;
+                slot_class[used] = ac;
+                slot_id[used++] = id;
+            }
+            selectors |= (uint32_t)s << (4 * c + 2 * ac);
+        }
+
+    uint8_t* out = static_cast<uint8_t*>(slot);
+    memset(out, 0, hmm::kEntropyDataOff);
+    int32_t* head = reinterpret_cast<int32_t*>(out);
+    head[hmm::kEhMagic] = (int32_t)hmm::kEntropyMagic;
+    head[hmm::kEhBytes] = (int32_t)len;
+    head[hmm::kEhComps] = f.ncomp;
+    head[hmm::kEhHmax] = hmax;
+    head[hmm::kEhVmax] = vmax;
+    head[hmm::kEhSelectors] = (int32_t)selectors;
+    head[hmm::kEhPadded] = (int32_t)padded;
+    uint16_t* qt = reinterpret_cast<uint16_t*>(out + hmm::kEntropyQtOff);
+    for (int c = 0; c < f.ncomp; ++c) memcpy(qt + 64 * c, f.q[f.tq[c]], 64 * sizeof(uint16_t));
+    hmm::EntropyHuff* tables = reinterpret_cast<hmm::EntropyHuff*>(out + hmm::kEntropyHuffOff);
+    for (int s = 0; s < used; ++s) {
+        const Huff& h = slot_class[s] ? f.ac[slot_id[s]] : f.dc[slot_id[s]];
+        hmm::EntropyHuff& t = tables[s];
+        memcpy(t.look, h.look, sizeof(t.look));
+        int count = 0;
+        for (int l = 1; l <= 16; ++l) {
+            t.maxcode[l] = h.maxcode[l];
+            t.valoff[l] = h.bits[l] ? h.valoff[l] : 0;
+            count += h.bits[l];
+        }
+        t.maxcode[0] = t.maxcode[17] = -1;
+        memcpy(t.vals, h.vals, (size_t)count);
+    }
+
+    uint8_t* dst = out + hmm::kEntropyDataOff;
+    for (size_t i = f.scan; i < end;) {
+        const uint8_t* p = static_cast<const uint8_t*>(memchr(data + i, 0xFF, end - i));
+        const size_t k = p ? (size_t)(p - data) + 1 : end;            // through the FF; its 00 is dropped
+        memcpy(dst, data + i, k - i);
+        dst += k - i;
+        i = p ? k + 1 : end;
+    }
+    memset(dst, 0, padded - len);
     return HMM_JPEG_DECODED;
 }

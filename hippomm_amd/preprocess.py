@@ -412,6 +412,32 @@ def _get_coef_staging(key, slot_bytes: int, capacity: int) -> _CoefStaging:
     return st
 
 
+class _BitStaging:
+    """Pinned ring of `capacity` bitstream slots (hmm_jpeg_prepare_entropy) beside the coefficient ring: the device entropy
+    route (HMM_JPEG_ENTROPY=device), and pinned status words for the read-back of each upload run."""
+
+    def __init__(self, slot_bytes: int, capacity: int):
+        self.capacity, self.slot_bytes = capacity, slot_bytes
+        self.pinned = torch.empty(capacity, slot_bytes, dtype=torch.uint8, pin_memory=True)
+        self.host = self.pinned.numpy()
+        self.status = torch.empty(capacity, 2, dtype=torch.int32, pin_memory=True)     # by frame of the call; grown to its n
+        self.last_upload = None
+
+
+_bit_staging = {}
+
+
+def _get_bit_staging(key, slot_bytes: int, capacity: int) -> _BitStaging:
+    st = _bit_staging.get(key)
+    if st is None or st.capacity < capacity or st.slot_bytes < slot_bytes:
+        for k in list(_bit_staging):
+            if _bit_staging[k].last_upload is not None:
+                _bit_staging[k].last_upload.synchronize()
+            del _bit_staging[k]                                              # one ring: the last geometry's
+        st = _bit_staging[key] = _BitStaging(slot_bytes, capacity)
+    return st
+
+
 def _side_stream(dev):
     key = str(dev)
     if key not in _side_streams:
@@ -436,7 +462,14 @@ def vision_pipeline(image_paths: Sequence[str], device=None, consume=None, worke
     frames unless the call has a single path, so a tower stays in one arithmetic regime whatever the
     timing: the embedding bits do not depend on how the call happened to be cut.  Frames whose size differs from the first
     file's take the same route one by one.  Returns when everything has been ISSUED; the result is ordered on the caller's
-    stream like any kernel output."""
+    stream like any kernel output.
+
+    HMM_JPEG_ENTROPY=device (read at call time; hippomm_amd/jpeg.py) moves the Huffman pass of the frames on the JPEG device
+    route to the GPU: the decode threads only run the prepare pass into a pinned ring of bitstream slots, the upload of a run
+    is followed by hmm_jpeg_decode_coefs_device into the coefficient buffer the reconstruction reads, and the run's status
+    words are read before its frames are handed on; a frame the kernel did not decode is redone by _decode_file's route.  The
+    result has the same bits either way."""
+    import os
     import threading
     import time
     from collections import deque
@@ -472,10 +505,29 @@ def vision_pipeline(image_paths: Sequence[str], device=None, consume=None, worke
             coef = _get_coef_staging((geom[:5], window, str(dev)), jpeg.slot_bytes(geom, window), cap)
             if coef.last_upload is not None:
                 coef.last_upload.synchronize()
+        # the device entropy pass (opt-in): bitstream slots ride in a pinned ring beside the coefficient ring
+        bits = None
+        if coef is not None and jpeg.entropy_mode() == "device" and geom[5] == 0 and jpeg.entropy_route_ok(head, dev):
+            largest = 0
+            for q in paths:
+                try:
+                    largest = max(largest, os.path.getsize(q))
+                except OSError:
+                    pass                                                  # the decode raises for it
+            bits = _get_bit_staging((geom[:5], str(dev)), jpeg.entropy_slot_bytes(largest), cap)
+            if bits.last_upload is not None:
+                bits.last_upload.synchronize()
+            if bits.status.shape[0] < n:                                  # every earlier call has read its status words
+                bits.status = torch.empty(n, 2, dtype=torch.int32, pin_memory=True)
         del head
         on_dev = [False] * n                                              # frame -> its coefficients are in the coefficient ring
+        by_kernel = [False] * n                                           # frame -> its bitstream slot is in the bitstream ring
+        pending = deque()                                                 # (first, end, event behind the status read-back) per upload run
         side, cur = _side_stream(dev), torch.cuda.current_stream(dev)
         side.wait_stream(cur)                                             # x (and whatever memory it reuses) is ours from here
+        if bits is not None:                                              # one workspace for every upload run of the call: the
+            with torch.cuda.stream(side):                                 # runs follow each other on the side stream, which owns it
+                ent_ws = torch.empty(jpeg.entropy_workspace_bytes(geom, cap, bits.slot_bytes), dtype=torch.uint8, device=dev)
 
         cond = threading.Condition()
         done = [False] * n
@@ -499,7 +551,10 @@ def vision_pipeline(image_paths: Sequence[str], device=None, consume=None, worke
                 if coef is not None:
                     with open(paths[i], "rb") as fh:
                         data = fh.read()
-                    if jpeg.decode_coefs(data, geom, window, coef.host[i % cap]) == jpeg.DECODED:
+                    if (bits is not None and jpeg.entropy_slot_bytes(len(data)) <= bits.slot_bytes
+                            and jpeg.prepare_entropy(data, geom, bits.host[i % cap]) == jpeg.DECODED):
+                        arr, on_dev[i], by_kernel[i] = None, True, True
+                    elif jpeg.decode_coefs(data, geom, window, coef.host[i % cap]) == jpeg.DECODED:
                         arr, on_dev[i] = None, True
                     else:
                         arr = _decode_bytes(data, W, H, st.host[i % cap], lib, window)
@@ -532,15 +587,28 @@ def vision_pipeline(image_paths: Sequence[str], device=None, consume=None, worke
                         ev, b = True, a + 1
                     else:
                         b = a + 1
-                        while b < hi and b not in odd and b % cap != 0 and on_dev[b] == on_dev[a]:
+                        while b < hi and b not in odd and b % cap != 0 and on_dev[b] == on_dev[a] and by_kernel[b] == by_kernel[a]:
                             b += 1
                         d = torch.empty(b - a, WH, WW, 3, dtype=torch.uint8, device=dev)
                         ring = coef if on_dev[a] else st
                         src = torch.empty((b - a,) + tuple(ring.pinned.shape[1:]), dtype=torch.uint8, device=dev) if on_dev[a] else d
-                        src.copy_(ring.pinned[a % cap:a % cap + (b - a)], non_blocking=True)
+                        if by_kernel[a]:                                  # bitstream slots up, the entropy pass fills src
+                            ring = bits
+                            up = torch.empty(b - a, bits.slot_bytes, dtype=torch.uint8, device=dev)
+                            up.copy_(bits.pinned[a % cap:a % cap + (b - a)], non_blocking=True)
+                        else:
+                            src.copy_(ring.pinned[a % cap:a % cap + (b - a)], non_blocking=True)
                         ev = torch.cuda.Event()
                         ev.record(side)
                         ring.last_upload = ev
+                        if by_kernel[a]:
+                            status = jpeg.decode_coefs_device(up, geom, window, src,
+                                                              torch.empty(b - a, 2, dtype=torch.int32, device=dev), ent_ws)
+                            bits.status[a:b].copy_(status, non_blocking=True)
+                            back = torch.cuda.Event()
+                            back.record(side)
+                            pending.append((a, b, back))
+                            del up, status
                         if on_dev[a]:
                             jpeg.reconstruct(src, geom, window, d)                # coefficients -> the window's RGB
                         _preprocess_into(d, x[a:b], (H, W))
@@ -553,6 +621,24 @@ def vision_pipeline(image_paths: Sequence[str], device=None, consume=None, worke
                 ready = torch.cuda.Event(enable_timing=trace is not None)
                 ready.record(side)
             return ready
+
+        def settle(upto):
+            """Before frames below `upto` are handed on: the status words of their upload runs.  A frame the entropy kernel did
+            not decode takes _decode_file's route here, on the caller's stream, behind the run's own writes."""
+            while pending and pending[0][0] < upto:
+                a, b, back = pending.popleft()
+                back.synchronize()
+                flags = bits.status[a:b, 0].tolist()
+                for i in (a + k for k, f in enumerate(flags) if f != jpeg.DECODED):
+                    cur.wait_event(back)
+                    dst = np.empty((WH, WW, 3), dtype=np.uint8)
+                    arr = _decode_file(paths[i], W, H, dst, lib, window)
+                    on_dev[i] = by_kernel[i] = False
+                    if arr is None:
+                        _preprocess_into(torch.from_numpy(dst).unsqueeze(0).to(dev), x[i:i + 1], (H, W))
+                    else:
+                        state["odd"] += 1
+                        _preprocess_into(torch.from_numpy(arr).unsqueeze(0).to(dev), x[i:i + 1])
 
         futures = None
         if workers > 1:
@@ -610,6 +696,7 @@ def vision_pipeline(image_paths: Sequence[str], device=None, consume=None, worke
                             while batches[0][0] < hi:
                                 batches.popleft()
                             cur.wait_event(batches[0][1])
+                            settle(hi)
                             consume(x, issued, hi)
                             fin = torch.cuda.Event(enable_timing=trace is not None)
                             fin.record(cur)
@@ -626,6 +713,7 @@ def vision_pipeline(image_paths: Sequence[str], device=None, consume=None, worke
                             cond.wait(poll_s if running else 0.002)
             if consume is None:
                 cur.wait_event(batches[-1][1])
+                settle(n)
         finally:
             if (issued < n if consume is not None else uploaded < n):     # an error: nobody may still be writing into the ring
                 with cond:
@@ -639,7 +727,7 @@ def vision_pipeline(image_paths: Sequence[str], device=None, consume=None, worke
                         f.result()                                        # work() never raises: errors are in state["error"]
         if stats is not None:
             stats.update(chunks=chunks, workers=workers, ring_frames=cap, frame_hw=(H, W), window=window, odd_sized=state["odd"],
-                         device_decoded=sum(on_dev),
+                         device_decoded=sum(on_dev), **({"entropy_device": sum(by_kernel)} if bits is not None else {}),
                          uploads=len(batches) if consume is None else None)
             if trace is not None and trace:                               # diagnostic: synchronises
                 torch.cuda.synchronize(dev)

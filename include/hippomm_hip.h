@@ -429,6 +429,42 @@ int     hmm_jpeg_reconstruct(const void* slots_dev, int n, size_t slot_stride, c
                              uint8_t* rgb_out_dev, void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The entropy (Huffman) pass of the same files on the GPU: an opt-in replacement of hmm_jpeg_decode_coefs that fills the same
+ * coefficient slots, byte for byte, in device memory.  hmm_jpeg_reconstruct and everything after it are unchanged.
+ *
+ * hmm_jpeg_entropy_slot_bytes: bytes of a bitstream slot for a file of file_bytes bytes (the file size plus a constant, a
+ *   multiple of 256).
+ * hmm_jpeg_prepare_entropy: marker parse, then the scan's entropy bytes without FF 00 stuffing, the quantisation tables and up to
+ *   four Huffman tables into `slot` (host memory, 16-byte aligned; pinned if it is to be uploaded asynchronously).  Host, no GPU
+ *   call, no interpreter state.  -> HMM_JPEG_DECODED (the slot is ready), HMM_JPEG_OTHER_GEOMETRY, or HMM_JPEG_UNSUPPORTED, which
+ *   here means "not by this route": everything hmm_jpeg_parse refuses, files with a restart interval, files whose components
+ *   select more than four distinct Huffman tables, and scans that do not run up to an EOI marker (FF D9) with no other marker
+ *   between.  HMM_E_WORKSPACE when slot_bytes is too small, HMM_E_INVALID for bad arguments.
+ * hmm_jpeg_entropy_workspace_bytes: workspace of a call with n frames of `geometry` whose bitstream slots are max_entropy_bytes
+ *   apart at the most (pass the bitslot stride); 0 for a bad geometry or n < 1.  Calls with more than 32 frames are run in
+ *   chunks of 32 inside the call, so the size stops growing there.
+ * hmm_jpeg_decode_coefs_device: n bitstream slots at bitslots_dev + i * bitslot_stride -> coefficient slots at coef_slots_dev +
+ *   i * coef_slot_stride for the window, and status_dev[i] = (status, rounds): status HMM_JPEG_DECODED or HMM_JPEG_UNSUPPORTED,
+ *   rounds the number of fixed-point rounds the frame took.  For status HMM_JPEG_DECODED the slot holds exactly the
+ *   hmm_jpeg_slot_bytes bytes hmm_jpeg_decode_coefs writes for the same file and window (quantisation header, kept blocks) with
+ *   zero padding; for any other status its contents are unspecified and must not be used -- decode that file with
+ *   hmm_jpeg_decode_coefs, and with Pillow if that refuses too.  Every refusal of the host pass is made here over all blocks:
+ *   an invalid code, an index past 63, |v| q > 32767, a DC predictor outside int16, a column of dequantised magnitudes above
+ *   5800, a bit taken from past the end of the data, 8 or more unused bits at the end.
+ *   The stream is cut into subsequences of 1024 bits that are decoded in parallel from guessed entry states and re-decoded until
+ *   every exit state equals the next entry state; the loop is bounded by subsequences + 1 rounds, the proven bound, so no frame
+ *   is refused for taking long.  Caller-owned memory, the caller's stream, no synchronisation, no allocation; the workspace
+ *   needs no initialisation; all pointers 16-byte aligned (status_dev: 4), both strides multiples of 16; n = 0 is HMM_OK
+ *   without a launch; HMM_E_WORKSPACE when workspace_bytes is below hmm_jpeg_entropy_workspace_bytes(geometry, n, bitslot_stride).
+ * ---------------------------------------------------------------------------------------- */
+int64_t hmm_jpeg_entropy_slot_bytes(size_t file_bytes);
+int     hmm_jpeg_prepare_entropy(const uint8_t* data, size_t n, const int32_t* geometry, void* slot, size_t slot_bytes);
+size_t  hmm_jpeg_entropy_workspace_bytes(const int32_t* geometry, int n, size_t max_entropy_bytes);
+int     hmm_jpeg_decode_coefs_device(const void* bitslots_dev, int n, size_t bitslot_stride, const int32_t* geometry, int x0, int y0,
+                                     int w, int h, void* coef_slots_dev, size_t coef_slot_stride, int32_t* status_dev,
+                                     void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Building blocks of the encoder, exported so that each kernel is parity-tested on its own
  * against a torch fp32 reference of the same op (tests/test_gpu_ops.py) and timed on its own
  * (bench.py roofline).  bf16 tensors are raw uint16 bit patterns in device memory.
