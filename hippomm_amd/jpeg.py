@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._pinned import stage
 
 GEOMETRY_INTS = 6
 DECODED, UNSUPPORTED, OTHER_GEOMETRY = 0, 1, 2
@@ -36,7 +37,7 @@ _route = {"on": True}                  # private A/B switch for measurements (Fa
 _check = {"ok": None}                  # None: not verified in this process yet; False: this Pillow disagrees, route off
 _check_lock = threading.Lock()
 _counts = {"device": 0, "host": 0}     # frames per route since the process started (decode_stats)
-_pinned = {}                           # device (+ kind) -> [pinned u8 buffer, event behind its last upload]
+_staging = {}                          # device (+ kind) -> PinnedStage of flat u8; _stage_lock held
 _entropy_check = {"ok": None}          # the device entropy pass: None: not verified in this process yet; False: off
 
 
@@ -209,17 +210,11 @@ def takes(geometry) -> bool:
     return limit is None or geometry[0] * geometry[1] <= limit
 
 
-def _pinned_slots(dev, nbytes: int, kind: str = "") -> list:
+def _pinned_slots(dev, nbytes: int, kind: str = ""):
     """The pinned staging buffer of `dev` (at least nbytes), once its previous upload has left it.  Caller holds _stage_lock.
     kind: "" coefficient slots, "bits" bitstream slots."""
-    key = str(dev) + kind
-    ent = _pinned.get(key)
-    if ent is None or ent[0].numel() < nbytes:
-        if ent is not None and ent[1] is not None:
-            ent[1].synchronize()
-        ent = _pinned[key] = [torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, pin_memory=True), None]
-    elif ent[1] is not None:
-        ent[1].synchronize()                         # the previous call's upload has left the buffer
+    ent = stage(_staging, str(dev) + kind, (max(nbytes, 1 << 20),))
+    ent.wait()                                       # the previous call's upload has left the buffer
     return ent
 
 
@@ -248,7 +243,7 @@ def _entropy_on_device(jobs, plan, datas, geoms, up, dev, pool) -> set:
         layout.append((total, stride))
         total += stride * len(idx)
     ent = _pinned_slots(dev, total, "bits")
-    host = ent[0].numpy()
+    host = ent.host
 
     def prep(job):
         i, g5, at, stride = job
@@ -259,9 +254,8 @@ def _entropy_on_device(jobs, plan, datas, geoms, up, dev, pool) -> set:
     pjobs = [(i, g5, at + k * stride, stride) for (g5, crop, idx, off, sb), (at, stride) in zip(plan, layout) for k, i in enumerate(idx)]
     prepared = list(pool.map(prep, pjobs)) if pool and len(pjobs) > 1 else [prep(j) for j in pjobs]
     bits = torch.empty(total, dtype=torch.uint8, device=dev)
-    bits.copy_(ent[0][:total], non_blocking=True)
-    ent[1] = torch.cuda.Event()
-    ent[1].record()
+    bits.copy_(ent.pinned[:total], non_blocking=True)
+    ent.mark()
     status = torch.empty(len(pjobs), 2, dtype=torch.int32, device=dev)
     row = 0
     for (g5, crop, idx, off, sb), (at, stride) in zip(plan, layout):
@@ -304,7 +298,7 @@ def _decode_many(srcs: Sequence, dev, window=None, entropy: Optional[str] = None
     on_dev = {}
     with torch.cuda.device(dev), _stage_lock:
         ent = _pinned_slots(dev, total) if total else None
-        host_all = ent[0].numpy() if ent else None
+        host_all = ent.host if ent else None
 
         def entropy(job):
             g5, crop, i, off, sb = job
@@ -321,13 +315,12 @@ def _decode_many(srcs: Sequence, dev, window=None, entropy: Optional[str] = None
         on_dev.update({j[2]: st == DECODED for j, st in zip(todo, status)})
         if total:
             if not by_kernel:
-                up.copy_(ent[0][:total], non_blocking=True)
+                up.copy_(ent.pinned[:total], non_blocking=True)
             else:                                    # only the slots the host pass filled: the kernel's are in place
                 for j, st in zip(todo, status):
                     if st == DECODED:
-                        up[j[3]:j[3] + j[4]].copy_(ent[0][j[3]:j[3] + j[4]], non_blocking=True)
-            ent[1] = torch.cuda.Event()
-            ent[1].record()
+                        up[j[3]:j[3] + j[4]].copy_(ent.pinned[j[3]:j[3] + j[4]], non_blocking=True)
+            ent.mark()
             for g5, crop, idx, off, sb in plan:
                 keep = [k for k, i in enumerate(idx) if on_dev[i]]
                 if not keep:

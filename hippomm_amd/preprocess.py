@@ -15,7 +15,7 @@ from typing import List, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib, jpeg
+from . import _lib, _pinned, jpeg
 
 OUT = 224
 PRECISION_BITS = 32 - 8 - 2
@@ -253,6 +253,17 @@ _direct = {"ok": None, "fails": 0}                                 # ok None: no
 _thread_images = None
 
 
+def _capsule_ptr(capsule):
+    """Address of the ArrowArray in the capsule Pillow's __arrow_c_array__ hands out."""
+    global _capsule_pointer
+    if _capsule_pointer is None:
+        import ctypes as C
+        fn = C.pythonapi.PyCapsule_GetPointer
+        fn.restype, fn.argtypes = C.c_void_p, [C.py_object, C.c_char_p]
+        _capsule_pointer = fn
+    return _capsule_pointer(capsule, b"arrow_array")
+
+
 def _decode_jpeg_direct(data: bytes, w: int, h: int, dst: np.ndarray, lib, window=None) -> bool:
     """A w x h plain JPEG -> dst through Pillow's libjpeg decoder object driven directly: Image.open's marker parsing, the
     per-frame 4-bytes-per-pixel image allocation (3.7 MB of fresh pages per 720p frame) and its release are what the decode
@@ -280,15 +291,9 @@ def _decode_jpeg_direct(data: bytes, w: int, h: int, dst: np.ndarray, lib, windo
             decoder.cleanup()
         if n >= 0 or err < 0:
             return False                                           # truncated / broken: let Pillow's route raise its error
-        global _capsule_pointer
-        if _capsule_pointer is None:
-            import ctypes as C
-            fn = C.pythonapi.PyCapsule_GetPointer
-            fn.restype, fn.argtypes = C.c_void_p, [C.py_object, C.c_char_p]
-            _capsule_pointer = fn
         x0, y0, ww, wh = window if window is not None else (0, 0, w, h)
         capsule = core.__arrow_c_array__()                         # must outlive the call: dropping it releases the export
-        if lib.hmm_host_arrow_rgbx_to_rgb(_capsule_pointer(capsule, b"arrow_array"), w, h, x0, y0, ww, wh, dst.ctypes.data) != 0:
+        if lib.hmm_host_arrow_rgbx_to_rgb(_capsule_ptr(capsule), w, h, x0, y0, ww, wh, dst.ctypes.data) != 0:
             raise RuntimeError(lib.hmm_last_error().decode())
         del capsule
         if _direct["ok"] is None:                                  # first frame of the process: Pillow's own route must agree
@@ -325,12 +330,6 @@ def _decode_bytes(data: bytes, w: int, h: int, dst: np.ndarray, lib, window=None
 def _pack_into(im, dst: np.ndarray, lib, window=None) -> None:
     """Pixels of a loaded RGB Pillow image (or its window (x0, y0, w, h)) -> dst (h,w,3) uint8; without the interpreter lock
     when Pillow exports its block."""
-    global _capsule_pointer
-    if _capsule_pointer is None:
-        import ctypes as C
-        fn = C.pythonapi.PyCapsule_GetPointer
-        fn.restype, fn.argtypes = C.c_void_p, [C.py_object, C.c_char_p]
-        _capsule_pointer = fn
     x0, y0, ww, wh = window if window is not None else (0, 0, im.size[0], im.size[1])
     export = getattr(im, "__arrow_c_array__", None)               # Pillow >= 11.2
     if export is not None:
@@ -338,7 +337,7 @@ def _pack_into(im, dst: np.ndarray, lib, window=None) -> None:
             _, array = export()                                   # refused for an image kept in several blocks (> 16 MB)
         except Exception:                                         # noqa: BLE001 - any refusal: the copying route below
             array = None
-        if array is not None and lib.hmm_host_arrow_rgbx_to_rgb(_capsule_pointer(array, b"arrow_array"), im.size[0], im.size[1],
+        if array is not None and lib.hmm_host_arrow_rgbx_to_rgb(_capsule_ptr(array), im.size[0], im.size[1],
                                                                 x0, y0, ww, wh, dst.ctypes.data) == 0:
             return
     np.copyto(dst, np.asarray(im, dtype=np.uint8)[y0:y0 + wh, x0:x0 + ww])
@@ -363,79 +362,14 @@ def decode_rgb(image_paths: Sequence[str], workers: int = 0) -> List[np.ndarray]
     return list(_decode_pool(workers).map(one, image_paths))
 
 
-class _Staging:
-    """Pinned ring of `capacity` frame slots of one frame size (one per device and size, reused by every call)."""
-
-    def __init__(self, h: int, w: int, capacity: int):
-        self.capacity = capacity
-        self.pinned = torch.empty(capacity, h, w, 3, dtype=torch.uint8, pin_memory=True)       # h x w: the needed_window
-        self.host = self.pinned.numpy()
-        self.last_upload = None                    # event behind the last H2D issued from this ring
-
-
-def _get_staging(h: int, w: int, need: int, dev) -> _Staging:
-    key = (h, w, str(dev))
-    st = _staging.get(key)
-    if st is None or st.capacity < need:
-        if st is not None and st.last_upload is not None:
-            st.last_upload.synchronize()
-        others = [k for k in _staging if k != key]
-        for k in others[: max(0, len(others) - 2)]:                     # at most three frame sizes stay pinned
-            if _staging[k].last_upload is not None:
-                _staging[k].last_upload.synchronize()
-            del _staging[k]
-        st = _staging[key] = _Staging(h, w, need)
-    return st
-
-
-class _CoefStaging:
-    """Pinned ring of `capacity` coefficient slots (hmm_jpeg_decode_coefs) for one frame geometry and window."""
-
-    def __init__(self, slot_bytes: int, capacity: int):
-        self.capacity = capacity
-        self.pinned = torch.empty(capacity, slot_bytes, dtype=torch.uint8, pin_memory=True)
-        self.host = self.pinned.numpy()
-        self.last_upload = None
-
-
+# The pinned rings of vision_pipeline (_pinned.stage; _pipeline_lock held), reused by every call.  Frame ring: (h, w, device) ->
+# `capacity` slots of h x w x 3, the needed_window; at most three frame sizes stay pinned.  Coefficient ring (hmm_jpeg_decode_coefs)
+# and bitstream ring (hmm_jpeg_prepare_entropy; the device entropy route, HMM_JPEG_ENTROPY=device): one each, the last geometry's.
+# The pinned status words for the read-back of each upload run of the bitstream ring: one (frames of the call, 2) int32 buffer.
 _coef_staging = {}
-
-
-def _get_coef_staging(key, slot_bytes: int, capacity: int) -> _CoefStaging:
-    st = _coef_staging.get(key)
-    if st is None or st.capacity < capacity:
-        for k in list(_coef_staging):
-            if _coef_staging[k].last_upload is not None:
-                _coef_staging[k].last_upload.synchronize()
-            del _coef_staging[k]                                             # one ring: the last geometry's
-        st = _coef_staging[key] = _CoefStaging(slot_bytes, capacity)
-    return st
-
-
-class _BitStaging:
-    """Pinned ring of `capacity` bitstream slots (hmm_jpeg_prepare_entropy) beside the coefficient ring: the device entropy
-    route (HMM_JPEG_ENTROPY=device), and pinned status words for the read-back of each upload run."""
-
-    def __init__(self, slot_bytes: int, capacity: int):
-        self.capacity, self.slot_bytes = capacity, slot_bytes
-        self.pinned = torch.empty(capacity, slot_bytes, dtype=torch.uint8, pin_memory=True)
-        self.host = self.pinned.numpy()
-        self.status = torch.empty(capacity, 2, dtype=torch.int32, pin_memory=True)     # by frame of the call; grown to its n
-        self.last_upload = None
-
-
 _bit_staging = {}
-
-
-def _get_bit_staging(key, slot_bytes: int, capacity: int) -> _BitStaging:
-    st = _bit_staging.get(key)
-    if st is None or st.capacity < capacity or st.slot_bytes < slot_bytes:
-        for k in list(_bit_staging):
-            if _bit_staging[k].last_upload is not None:
-                _bit_staging[k].last_upload.synchronize()
-            del _bit_staging[k]                                              # one ring: the last geometry's
-        st = _bit_staging[key] = _BitStaging(slot_bytes, capacity)
-    return st
+_bit_status = {}
+_RGB, _COEF, _BITS, _OWN = range(4)                 # where a decoded frame lies: one of the three rings, or an array of its own
 
 
 def _side_stream(dev):
@@ -444,6 +378,66 @@ def _side_stream(dev):
         # high priority: a resize launch must not queue behind the tower's kernels of the previous range, it is what the next one waits for
         _side_streams[key] = torch.cuda.Stream(device=dev, priority=-1)
     return _side_streams[key]
+
+
+def _jpeg_rings(head: bytes, paths, size, window, cap: int, dev):
+    """The JPEG device route (hippomm_amd/jpeg.py) of a vision_pipeline call whose first file has the bytes `head` and is
+    `size` = (W, H): the first file decides; a file the route does not take uses _decode_file's.  -> (geometry, coefficient ring,
+    bitstream ring, status words), each ring waited on; all None off the route, the last two None without the device entropy
+    pass (opt-in), whose bitstream slots ride in a pinned ring beside the coefficient ring, sized by the largest file."""
+    import os
+    geom = jpeg.parse(head)
+    if geom is None or geom[:2] != size or not jpeg.takes(geom) or not jpeg.route_ok(head, dev):
+        return None, None, None, None
+    coef = _pinned.stage(_coef_staging, (geom[:5], window, str(dev)), (cap, jpeg.slot_bytes(geom, window)), keep=1)
+    coef.wait()
+    if jpeg.entropy_mode() != "device" or geom[5] != 0 or not jpeg.entropy_route_ok(head, dev):
+        return geom, coef, None, None
+    largest = 0
+    for q in paths:
+        try:
+            largest = max(largest, os.path.getsize(q))
+        except OSError:
+            pass                                                          # the decode raises for it
+    key = (geom[:5], str(dev))                                            # without the slot size: a larger file regrows the ring
+    bits = _pinned.stage(_bit_staging, key, (cap, jpeg.entropy_slot_bytes(largest)), keep=1)
+    bits.wait()
+    # by frame of the call; every earlier call has read its status words
+    return geom, coef, bits, _pinned.stage(_bit_status, key, (len(paths), 2), torch.int32, keep=1)
+
+
+def _run_end(a: int, hi: int, cap: int, kind) -> int:
+    """End of the upload run that starts at frame `a` of the decoded frames [a, hi): a frame in an array of its own goes up
+    alone; frames in a ring go up together while they lie in the same ring and the ring does not wrap."""
+    b = a + 1
+    if kind[a] != _OWN:
+        while b < hi and kind[b] == kind[a] and b % cap != 0:
+            b += 1
+    return b
+
+
+def _next_range(n: int, issued: int, uploaded: int, running: int, ready_upto, first_chunk: int, depth: int, max_chunk: int,
+                tail_wait: int) -> int:
+    """End of the range [issued, hi) the consumer gets now, 0 for none yet.  Of the n frames of the call, `uploaded` (> issued)
+    have their upload and resize queued; `running` ranges handed on earlier have not finished; ready_upto() -> the frame up to
+    which the resize has FINISHED (asked only where the answer matters: it queries events)."""
+    need = first_chunk if issued == 0 else 2
+    hi = 0
+    if uploaded == n:
+        hi = min(n, issued + max_chunk)                                   # everything is on its way: queue the rest behind the running range
+    elif n - uploaded <= tail_wait and issued > 0:
+        pass                                                              # the last few frames are about to arrive: one range, not two
+    elif running < depth and uploaded - issued >= need:
+        # the GPU has room: hand it the frames whose resize has FINISHED (a range waits for its last upload; while the
+        # tower is busy that wait is free, on an idle GPU it is not)
+        ready = ready_upto()
+        if ready - issued >= need:
+            hi = min(ready, issued + max_chunk)
+        elif not running:
+            hi = min(uploaded, issued + max_chunk)                        # an idle GPU and nothing finished: it waits either way
+    if hi and n - hi == 1:                                                # never leave a single frame for the last range
+        hi = hi - 1 if hi - issued >= 3 else 0
+    return hi
 
 
 def vision_pipeline(image_paths: Sequence[str], device=None, consume=None, workers: int = 0, first_chunk: int = 0,
@@ -469,7 +463,6 @@ def vision_pipeline(image_paths: Sequence[str], device=None, consume=None, worke
     is followed by hmm_jpeg_decode_coefs_device into the coefficient buffer the reconstruction reads, and the run's status
     words are read before its frames are handed on; a frame the kernel did not decode is redone by _decode_file's route.  The
     result has the same bits either way."""
-    import os
     import threading
     import time
     from collections import deque
@@ -494,40 +487,20 @@ def vision_pipeline(image_paths: Sequence[str], device=None, consume=None, worke
         window = needed_window(H, W)                                      # only these pixels are kept, uploaded and read
         WW, WH = window[2], window[3]
         cap = min(n, max(STAGING_BYTES // (WH * WW * 3), workers + 2 * max(first_chunk, upload_min)))
-        st = _get_staging(WH, WW, cap, dev)
+        st = _pinned.stage(_staging, (WH, WW, str(dev)), (cap, WH, WW, 3), keep=3)
         cap = st.capacity
-        if st.last_upload is not None:
-            st.last_upload.synchronize()                                  # the previous call's uploads have left the ring
-        # the JPEG device route (hippomm_amd/jpeg.py): the first file decides; a file it does not take uses the route above
-        geom = jpeg.parse(head)
-        coef = None
-        if geom is not None and geom[:2] == (W, H) and jpeg.takes(geom) and jpeg.route_ok(head, dev):
-            coef = _get_coef_staging((geom[:5], window, str(dev)), jpeg.slot_bytes(geom, window), cap)
-            if coef.last_upload is not None:
-                coef.last_upload.synchronize()
-        # the device entropy pass (opt-in): bitstream slots ride in a pinned ring beside the coefficient ring
-        bits = None
-        if coef is not None and jpeg.entropy_mode() == "device" and geom[5] == 0 and jpeg.entropy_route_ok(head, dev):
-            largest = 0
-            for q in paths:
-                try:
-                    largest = max(largest, os.path.getsize(q))
-                except OSError:
-                    pass                                                  # the decode raises for it
-            bits = _get_bit_staging((geom[:5], str(dev)), jpeg.entropy_slot_bytes(largest), cap)
-            if bits.last_upload is not None:
-                bits.last_upload.synchronize()
-            if bits.status.shape[0] < n:                                  # every earlier call has read its status words
-                bits.status = torch.empty(n, 2, dtype=torch.int32, pin_memory=True)
+        st.wait()                                                         # the previous call's uploads have left the ring
+        geom, coef, bits, status_words = _jpeg_rings(head, paths, (W, H), window, cap, dev)
         del head
-        on_dev = [False] * n                                              # frame -> its coefficients are in the coefficient ring
-        by_kernel = [False] * n                                           # frame -> its bitstream slot is in the bitstream ring
+        rings = (st, coef, bits)                                          # by kind
+        kind = [_RGB] * n                                                 # frame -> where its decoded form lies
         pending = deque()                                                 # (first, end, event behind the status read-back) per upload run
         side, cur = _side_stream(dev), torch.cuda.current_stream(dev)
         side.wait_stream(cur)                                             # x (and whatever memory it reuses) is ours from here
         if bits is not None:                                              # one workspace for every upload run of the call: the
+            bit_bytes = bits.pinned.shape[1]
             with torch.cuda.stream(side):                                 # runs follow each other on the side stream, which owns it
-                ent_ws = torch.empty(jpeg.entropy_workspace_bytes(geom, cap, bits.slot_bytes), dtype=torch.uint8, device=dev)
+                ent_ws = torch.empty(jpeg.entropy_workspace_bytes(geom, cap, bit_bytes), dtype=torch.uint8, device=dev)
 
         cond = threading.Condition()
         done = [False] * n
@@ -551,18 +524,18 @@ def vision_pipeline(image_paths: Sequence[str], device=None, consume=None, worke
                 if coef is not None:
                     with open(paths[i], "rb") as fh:
                         data = fh.read()
-                    if (bits is not None and jpeg.entropy_slot_bytes(len(data)) <= bits.slot_bytes
+                    if (bits is not None and jpeg.entropy_slot_bytes(len(data)) <= bit_bytes
                             and jpeg.prepare_entropy(data, geom, bits.host[i % cap]) == jpeg.DECODED):
-                        arr, on_dev[i], by_kernel[i] = None, True, True
+                        arr, kind[i] = None, _BITS
                     elif jpeg.decode_coefs(data, geom, window, coef.host[i % cap]) == jpeg.DECODED:
-                        arr, on_dev[i] = None, True
+                        arr, kind[i] = None, _COEF
                     else:
                         arr = _decode_bytes(data, W, H, st.host[i % cap], lib, window)
                 else:
                     arr = _decode_file(paths[i], W, H, st.host[i % cap], lib, window)
                 with cond:
                     if arr is not None:
-                        odd[i] = arr
+                        odd[i], kind[i] = arr, _OWN
                         state["odd"] += 1
                     done[i] = True
                     old = p = state["prefix"]
@@ -582,34 +555,28 @@ def vision_pipeline(image_paths: Sequence[str], device=None, consume=None, worke
             """H2D + resize of the decoded frames [a, hi) on the side stream -> event behind their resize."""
             with torch.cuda.stream(side):
                 while a < hi:
-                    if a in odd:
+                    b, k = _run_end(a, hi, cap, kind), kind[a]
+                    if k == _OWN:
                         _preprocess_into(torch.from_numpy(odd.pop(a)).unsqueeze(0).to(dev), x[a:a + 1])
-                        ev, b = True, a + 1
+                        ev = True
                     else:
-                        b = a + 1
-                        while b < hi and b not in odd and b % cap != 0 and on_dev[b] == on_dev[a] and by_kernel[b] == by_kernel[a]:
-                            b += 1
+                        ring, lo = rings[k], a % cap
                         d = torch.empty(b - a, WH, WW, 3, dtype=torch.uint8, device=dev)
-                        ring = coef if on_dev[a] else st
-                        src = torch.empty((b - a,) + tuple(ring.pinned.shape[1:]), dtype=torch.uint8, device=dev) if on_dev[a] else d
-                        if by_kernel[a]:                                  # bitstream slots up, the entropy pass fills src
-                            ring = bits
-                            up = torch.empty(b - a, bits.slot_bytes, dtype=torch.uint8, device=dev)
-                            up.copy_(bits.pinned[a % cap:a % cap + (b - a)], non_blocking=True)
-                        else:
-                            src.copy_(ring.pinned[a % cap:a % cap + (b - a)], non_blocking=True)
-                        ev = torch.cuda.Event()
-                        ev.record(side)
-                        ring.last_upload = ev
-                        if by_kernel[a]:
+                        # coefficient slots for the reconstruction: copied up, or filled by the entropy pass from the bitstream slots
+                        src = d if k == _RGB else torch.empty(b - a, coef.pinned.shape[1], dtype=torch.uint8, device=dev)
+                        up = src if k != _BITS else torch.empty(b - a, bit_bytes, dtype=torch.uint8, device=dev)
+                        up.copy_(ring.pinned[lo:lo + (b - a)], non_blocking=True)
+                        ev = ring.mark(side)
+                        if k == _BITS:
                             status = jpeg.decode_coefs_device(up, geom, window, src,
                                                               torch.empty(b - a, 2, dtype=torch.int32, device=dev), ent_ws)
-                            bits.status[a:b].copy_(status, non_blocking=True)
+                            status_words.pinned[a:b].copy_(status, non_blocking=True)
                             back = torch.cuda.Event()
                             back.record(side)
                             pending.append((a, b, back))
-                            del up, status
-                        if on_dev[a]:
+                            del status
+                        del up                                            # bitstream slots: the kernels below may have their memory
+                        if k != _RGB:
                             jpeg.reconstruct(src, geom, window, d)                # coefficients -> the window's RGB
                         _preprocess_into(d, x[a:b], (H, W))
                         del d, src
@@ -628,17 +595,28 @@ def vision_pipeline(image_paths: Sequence[str], device=None, consume=None, worke
             while pending and pending[0][0] < upto:
                 a, b, back = pending.popleft()
                 back.synchronize()
-                flags = bits.status[a:b, 0].tolist()
+                flags = status_words.pinned[a:b, 0].tolist()
                 for i in (a + k for k, f in enumerate(flags) if f != jpeg.DECODED):
                     cur.wait_event(back)
                     dst = np.empty((WH, WW, 3), dtype=np.uint8)
                     arr = _decode_file(paths[i], W, H, dst, lib, window)
-                    on_dev[i] = by_kernel[i] = False
+                    kind[i] = _RGB                                        # redone here: not a device decode
                     if arr is None:
                         _preprocess_into(torch.from_numpy(dst).unsqueeze(0).to(dev), x[i:i + 1], (H, W))
                     else:
                         state["odd"] += 1
                         _preprocess_into(torch.from_numpy(arr).unsqueeze(0).to(dev), x[i:i + 1])
+
+        def ready_upto():
+            """The frame up to which the resize has finished: the end of the last batch past `issued` whose event has passed."""
+            upto = issued
+            for end, ev in batches:
+                if end <= issued:
+                    continue
+                if not ev.query():
+                    break
+                upto = end
+            return upto
 
         futures = None
         if workers > 1:
@@ -669,44 +647,22 @@ def vision_pipeline(image_paths: Sequence[str], device=None, consume=None, worke
                 if consume is not None and uploaded > issued:
                     while running and running[0].query():
                         running.popleft()
-                    need = first_chunk if issued == 0 else 2
-                    hi = 0
-                    if uploaded == n:
-                        hi = min(n, issued + max_chunk)                   # everything is on its way: queue the rest behind the running range
-                    elif n - uploaded <= tail_wait and issued > 0:
-                        pass                                              # the last few frames are about to arrive: one range, not two
-                    elif len(running) < depth and uploaded - issued >= need:
-                        # the GPU has room: hand it the frames whose resize has FINISHED (a range waits for its last upload; while the
-                        # tower is busy that wait is free, on an idle GPU it is not)
-                        ready_upto = issued
-                        for end, ev in batches:
-                            if end <= issued:
-                                continue
-                            if not ev.query():
-                                break
-                            ready_upto = end
-                        if ready_upto - issued >= need:
-                            hi = min(ready_upto, issued + max_chunk)
-                        elif not running:
-                            hi = min(uploaded, issued + max_chunk)        # an idle GPU and nothing finished: it waits either way
+                    hi = _next_range(n, issued, uploaded, len(running), ready_upto, first_chunk, depth, max_chunk, tail_wait)
                     if hi:
-                        if n - hi == 1:                                   # never leave a single frame for the last range
-                            hi = hi - 1 if hi - issued >= 3 else 0
-                        if hi:
-                            while batches[0][0] < hi:
-                                batches.popleft()
-                            cur.wait_event(batches[0][1])
-                            settle(hi)
-                            consume(x, issued, hi)
-                            fin = torch.cuda.Event(enable_timing=trace is not None)
-                            fin.record(cur)
-                            running.append(fin)
-                            chunks.append(hi - issued)
-                            if trace is not None:
-                                trace.append({"frames": hi - issued, "issued_at": round((time.perf_counter() - t_begin) * 1e3, 2),
-                                              "decoded_then": state["prefix"], "_ready": batches[0][1], "_fin": fin})
-                            issued = hi
-                            progress = True
+                        while batches[0][0] < hi:
+                            batches.popleft()
+                        cur.wait_event(batches[0][1])
+                        settle(hi)
+                        consume(x, issued, hi)
+                        fin = torch.cuda.Event(enable_timing=trace is not None)
+                        fin.record(cur)
+                        running.append(fin)
+                        chunks.append(hi - issued)
+                        if trace is not None:
+                            trace.append({"frames": hi - issued, "issued_at": round((time.perf_counter() - t_begin) * 1e3, 2),
+                                          "decoded_then": state["prefix"], "_ready": batches[0][1], "_fin": fin})
+                        issued = hi
+                        progress = True
                 if not progress and (futures is not None or sequential_next >= n):
                     with cond:                                            # decoders or the GPU have to move first
                         if state["prefix"] == prefix and state["error"] is None:
@@ -727,7 +683,8 @@ def vision_pipeline(image_paths: Sequence[str], device=None, consume=None, worke
                         f.result()                                        # work() never raises: errors are in state["error"]
         if stats is not None:
             stats.update(chunks=chunks, workers=workers, ring_frames=cap, frame_hw=(H, W), window=window, odd_sized=state["odd"],
-                         device_decoded=sum(on_dev), **({"entropy_device": sum(by_kernel)} if bits is not None else {}),
+                         device_decoded=kind.count(_COEF) + kind.count(_BITS),
+                         **({"entropy_device": kind.count(_BITS)} if bits is not None else {}),
                          uploads=len(batches) if consume is None else None)
             if trace is not None and trace:                               # diagnostic: synchronises
                 torch.cuda.synchronize(dev)
@@ -917,7 +874,7 @@ def melspec_clips_device(clips: torch.Tensor, mean: float = AUDIO_MEAN, std: flo
     return out
 
 
-_audio_staging = {}                                 # device -> [pinned (rows, len) fp32, event behind its last upload]
+_audio_staging = {}                                 # device -> PinnedStage of (rows, len) fp32
 
 
 def _clips_to_melspec(clips: Sequence[np.ndarray], n_files: int, device) -> torch.Tensor:
@@ -930,22 +887,15 @@ def _clips_to_melspec(clips: Sequence[np.ndarray], n_files: int, device) -> torc
     lengths = {c.shape[0] for c in clips}
     if len(lengths) == 1:
         n, length = len(clips), lengths.pop()
-        st = _audio_staging.get(str(dev))
-        if st is None or st[0].shape[0] < n or st[0].shape[1] < length:
-            if st is not None and st[1] is not None:
-                st[1].synchronize()
-            st = _audio_staging[str(dev)] = [torch.empty(max(n, 48), max(length, AUDIO_CLIP_DURATION * AUDIO_SAMPLE_RATE),
-                                                         dtype=torch.float32, pin_memory=True), None]
-        if st[1] is not None:
-            st[1].synchronize()                      # the previous call's upload has left the buffer
-        host = st[0].numpy()
+        st = _pinned.stage(_audio_staging, str(dev), (max(n, 48), max(length, AUDIO_CLIP_DURATION * AUDIO_SAMPLE_RATE)),
+                           torch.float32)
+        st.wait()                                    # the previous call's upload has left the buffer
         for r, c in enumerate(clips):
-            _pcm_to_float(c, host[r, :length])
+            _pcm_to_float(c, st.host[r, :length])
         with torch.cuda.device(dev):
             batch = torch.empty(n, length, dtype=torch.float32, device=dev)
-            batch.copy_(st[0][:n, :length], non_blocking=True)
-            st[1] = torch.cuda.Event()
-            st[1].record()
+            batch.copy_(st.pinned[:n, :length], non_blocking=True)
+            st.mark()
             melspec_clips_device(batch, out=out)
         return out
     groups = {}                                      # clip length -> positions in `clips`

@@ -55,6 +55,38 @@ def test_vision_pipeline_from_files_equals_host_chain_bitwise(tmp_path):
     assert torch.equal(fused, direct)
 
 
+def test_vision_pipeline_wrapped_rings_of_mixed_kinds_equal_host_chain_bitwise(tmp_path, monkeypatch):
+    """14 paths through rings of 2 + 2*2 = 6 slots, so the coefficient ring (and, with the switch, the bitstream ring) is reused
+    while the call runs, with a progressive file (the frame ring), a file with a restart interval (the host entropy pass) and
+    a frame of another size (its own array) between them: the host chain's bits either way, and no single-frame range."""
+    from host_vision_pipeline import load_and_transform_vision_data
+    from hippomm_amd import preprocess as pp
+    paths = _scene_frames(tmp_path, 14, size=(160, 96))
+    Image.open(paths[3]).save(paths[3], quality=90, progressive=True)
+    Image.open(paths[6]).save(paths[6], quality=90, restart_marker_blocks=4)
+    Image.open(paths[9]).resize((128, 120)).save(paths[9], quality=88)
+    want = load_and_transform_vision_data(paths, "cpu")
+    monkeypatch.setattr(pp, "STAGING_BYTES", 1)
+    torch.cuda.synchronize()
+    for table in (pp._staging, pp._coef_staging, pp._bit_staging):
+        table.clear()
+    for mode in (None, "device"):
+        if mode is None:
+            monkeypatch.delenv("HMM_JPEG_ENTROPY", raising=False)
+        else:
+            monkeypatch.setenv("HMM_JPEG_ENTROPY", mode)
+        stats, ranges = {}, []
+        got = pp.vision_pipeline(paths, "cuda", lambda x, lo, hi: ranges.append((lo, hi)), workers=2, first_chunk=2,
+                                 upload_min=2, stats=stats)
+        torch.cuda.synchronize()
+        assert torch.equal(got.cpu(), want), mode
+        assert stats["ring_frames"] == 6 < 14 and stats["odd_sized"] == 1 and stats["device_decoded"] == 12, (mode, stats)
+        assert stats.get("entropy_device") == (11 if mode else None), stats
+        assert [lo for lo, _ in ranges] == [0] + [hi for _, hi in ranges[:-1]] and ranges[-1][1] == 14, ranges
+        assert all(hi - lo >= 2 for lo, hi in ranges), ranges
+    pp._staging.clear()
+
+
 def test_segment_sequence_on_jpeg_frames_equals_the_oracle(tmp_path):
     """segment_sequence through the device route: the segments the window walk makes from the SSIM numpy oracle on
     Pillow-decoded gray frames."""
