@@ -14,6 +14,10 @@ and the two SSIM call sites of the formation path (frame SSIM in hippomm_amd/csr
     hippomm_amd.segmentation._segment_sequence          <- hippomm/core/hippocampal_memory.py:1002-1114
     hippomm_amd.sharding                             one-process-per-GPU sharding (RCCL all-gather)
 
+and the audio of a whole video in one call (clip gather, peak normalisation and resampling in hippomm_amd/csrc/audio_track.hip):
+
+    hippomm_amd.audio_track.AudioTrack, ImageBind.extract_audio_segments  <- hippomm/core/hippocampal_memory.py:1198-1251
+
 and a baseline JPEG decoder with the pixel work on the GPU, bit-exact with Pillow (hippomm_amd/csrc/jpeg.hip):
 
     hippomm_amd.decode_jpeg                          <- Image.open(path).convert("RGB") of the reference's frame reads

@@ -1,0 +1,227 @@
+// The audio track of a video on the device: the two kernels behind AudioTrack (hippomm_amd/audio_track.py), which replace the
+// per-segment slice / mono / float32 / peak-normalise / wav round trip / resample / clip of the reference's process_sequence
+// (hippomm/core/hippocampal_memory.py:1198-1251 and imagebind.data.load_and_transform_audio_data behind it).
+//
+//   peaks    span_peaks_kernel: one workgroup per span, max |x| over the NARROWED samples (fp64 -> fp32 round-to-nearest-even, the
+//            bits of ndarray.astype(float32)).  The maximum is taken on the bit patterns of |x| as unsigned integers: for numbers
+//            that is the order of the values, and every NaN pattern lies above infinity, so a NaN anywhere in the span is what
+//            comes out -- np.abs(x).max() -- where an fmaxf reduction would drop it.  16-byte loads over the part of the span that
+//            is 16-byte aligned (span starts are arbitrary sample indices), element loads for the head and the tail: no byte
+//            outside [start, end) is read.
+//   gather   gather_clips_kernel: grid over (clip, block of 256 output samples).  A sample of the span is narrowed and, when the
+//            span's peak p > 1.0f, divided by p (one correctly rounded fp32 division; p == 1.0f and a NaN p leave it alone).
+//            orig == new: that value is the output sample -- a copy, bit-exact.  Otherwise the span is resampled as a file of its
+//            own: out[j] = sum_t taps[j % new][t] * x[(j / new) * orig - width + t] with x zero outside [0, span_len) -- samples
+//            of the track outside the span never enter.  The workgroup stages the input window of its 256 outputs in LDS (already
+//            narrowed and scaled); the tap table is tap-major, (T, new), so the lanes of a wave -- consecutive j, hence
+//            consecutive phases -- read consecutive floats.  fp32 fused multiply-adds into four partial sums (t mod 4), added as
+//            (a0 + a1) + (a2 + a3): one fixed order, so a clip's bits do not depend on the batch it rides in or on the run.
+//
+// Both read the span / clip tables from the device and clamp what they find there to the track, so a device table that disagrees
+// with the host copy the entry point has checked reads and writes less, never elsewhere.  No scratch, vector stores only.
+#include "hmm_common.h"
+
+namespace hmm {
+
+typedef float at_f32x4 __attribute__((ext_vector_type(4)));
+typedef double at_f64x2 __attribute__((ext_vector_type(2)));
+
+constexpr int kClipBlock = 256;                                               // output samples (= threads) per workgroup of the gather
+
+__device__ __forceinline__ uint32_t abs_bits(float x) { return __float_as_uint(x) & 0x7FFFFFFFu; }
+__device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
+
+template <bool F64>
+__device__ __forceinline__ float load_narrow(const void* __restrict__ track, int64_t i) {
+    if constexpr (F64) return (float)static_cast<const double*>(track)[i];    // v_cvt_f32_f64: round to nearest even
+    else return static_cast<const float*>(track)[i];
+}
+
+template <bool F64>
+__device__ __forceinline__ uint32_t abs_bits16(const void* __restrict__ track, int64_t first, int64_t v) {
+    if constexpr (F64) {
+        const at_f64x2 d = reinterpret_cast<const at_f64x2*>(static_cast<const double*>(track) + first)[v];
+        return umax(abs_bits((float)d[0]), abs_bits((float)d[1]));
+    } else {
+        const at_f32x4 f = reinterpret_cast<const at_f32x4*>(static_cast<const float*>(track) + first)[v];
+        return umax(umax(abs_bits(f[0]), abs_bits(f[1])), umax(abs_bits(f[2]), abs_bits(f[3])));
+    }
+}
+
+template <bool F64>
+__global__ __launch_bounds__(256) void span_peaks_kernel(const void* __restrict__ track, int64_t track_len,
+                                                         const int64_t* __restrict__ spans, float* __restrict__ peaks) {
+    constexpr int V = F64 ? 2 : 4;                                            // elements per 16 bytes
+    __shared__ uint32_t part[4];
+    const int tid = threadIdx.x;
+    int64_t a = spans[2 * blockIdx.x], b = spans[2 * blockIdx.x + 1];
+    a = a < 0 ? 0 : (a > track_len ? track_len : a);
+    b = b < a ? a : (b > track_len ? track_len : b);
+    int64_t body = (a + V - 1) / V * V;                                       // the track is 16-byte aligned: so is element `body`
+    if (body > b) body = b;
+    const int64_t n_vec = (b - body) / V;
+    uint32_t m = 0;
+    for (int64_t i = a + tid; i < body; i += 256) m = umax(m, abs_bits(load_narrow<F64>(track, i)));
+    int64_t v = tid;
+    for (; v + 768 < n_vec; v += 1024) {                                      // four loads in flight per lane
+        const uint32_t m0 = abs_bits16<F64>(track, body, v), m1 = abs_bits16<F64>(track, body, v + 256);
+        const uint32_t m2 = abs_bits16<F64>(track, body, v + 512), m3 = abs_bits16<F64>(track, body, v + 768);
+        m = umax(m, umax(umax(m0, m1), umax(m2, m3)));
+    }
+    for (; v < n_vec; v += 256) m = umax(m, abs_bits16<F64>(track, body, v));
+    for (int64_t i = body + n_vec * V + tid; i < b; i += 256) m = umax(m, abs_bits(load_narrow<F64>(track, i)));
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = umax(m, (uint32_t)__shfl_xor((int)m, off, 64));
+    if ((tid & 63) == 0) part[tid >> 6] = m;
+    __syncthreads();
+    if (tid == 0) peaks[blockIdx.x] = __uint_as_float(umax(umax(part[0], part[1]), umax(part[2], part[3])));
+}
+
+// clips: per clip (span start, span length, first output sample of the clip in the span's 16 kHz signal, span index).
+template <bool F64, bool RESAMPLE>
+__global__ __launch_bounds__(kClipBlock) void gather_clips_kernel(const void* __restrict__ track, int64_t track_len,
+                                                                  const int64_t* __restrict__ clips, const float* __restrict__ peaks,
+                                                                  int n_spans, int clip_len, int blocks_per_clip, int orig, int new_,
+                                                                  int width, const float* __restrict__ taps, float* __restrict__ out) {
+    extern __shared__ float window[];
+    const int tid = threadIdx.x;
+    const int c = blockIdx.x / blocks_per_clip, i0 = (blockIdx.x % blocks_per_clip) * kClipBlock;
+    int64_t start = clips[4 * c], len = clips[4 * c + 1];
+    const int64_t first = clips[4 * c + 2], span = clips[4 * c + 3];
+    if (start < 0 || start > track_len || len < 0 || first < 0 || span < 0 || span >= n_spans) return;       // workgroup-uniform
+    if (len > track_len - start) len = track_len - start;
+    const float p = peaks[span];
+    const bool scale = p > 1.0f;                                              // false for p == 1 and for a NaN peak
+    const int i = i0 + tid;                                                   // sample of the clip
+    float* dst = out + (int64_t)c * clip_len;
+    if constexpr (!RESAMPLE) {
+        if (i < clip_len && first + i < len) {
+            const float x = load_narrow<F64>(track, start + first + i);
+            dst[i] = scale ? __fdiv_rn(x, p) : x;
+        }
+    } else {
+        const int taps_n = 2 * width + orig;
+        const int last = (i0 + kClipBlock <= clip_len ? i0 + kClipBlock : clip_len) - 1;
+        const int64_t f0 = (first + i0) / new_, f1 = (first + last) / new_;  // input frames of the block's first / last output
+        const int64_t x0 = f0 * orig - width;
+        const int n_win = (int)(f1 - f0) * orig + taps_n;
+        for (int k = tid; k < n_win; k += kClipBlock) {
+            const int64_t xi = x0 + k;
+            float x = 0.0f;                                                   // outside the span: zero, whatever the track holds there
+            if (xi >= 0 && xi < len) {
+                x = load_narrow<F64>(track, start + xi);
+                if (scale) x = __fdiv_rn(x, p);
+            }
+            window[k] = x;
+        }
+        __syncthreads();
+        const int64_t n_out = (len * new_ + orig - 1) / orig;
+        if (i < clip_len && first + i < n_out) {
+            const int64_t j = first + i;
+            const float* __restrict__ tp = taps + (int)(j % new_);
+            const float* xp = window + (int)(j / new_ - f0) * orig;
+            float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+            int t = 0;
+            for (; t + 4 <= taps_n; t += 4) {
+                a0 = __fmaf_rn(tp[(int64_t)t * new_], xp[t], a0);
+                a1 = __fmaf_rn(tp[(int64_t)(t + 1) * new_], xp[t + 1], a1);
+                a2 = __fmaf_rn(tp[(int64_t)(t + 2) * new_], xp[t + 2], a2);
+                a3 = __fmaf_rn(tp[(int64_t)(t + 3) * new_], xp[t + 3], a3);
+            }
+            if (t < taps_n) a0 = __fmaf_rn(tp[(int64_t)t * new_], xp[t], a0);
+            if (t + 1 < taps_n) a1 = __fmaf_rn(tp[(int64_t)(t + 1) * new_], xp[t + 1], a1);
+            if (t + 2 < taps_n) a2 = __fmaf_rn(tp[(int64_t)(t + 2) * new_], xp[t + 2], a2);
+            dst[i] = (a0 + a1) + (a2 + a3);
+        }
+    }
+}
+
+static bool track_overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
+    const uint64_t x = (uint64_t)(uintptr_t)a, y = (uint64_t)(uintptr_t)b;
+    return a_bytes != 0 && b_bytes != 0 && x < y + b_bytes && y < x + a_bytes;
+}
+
+}  // namespace hmm
+
+using namespace hmm;
+
+extern "C" int hmm_audio_span_peaks(const void* track_dev, int track_dtype, int64_t track_len, const int64_t* spans_host,
+                                    const int64_t* spans_dev, int n_spans, float* peaks_out_dev, hmm_stream_t stream) {
+    HMM_REQUIRE(track_dtype == 0 || track_dtype == 1, HMM_E_INVALID, "audio_span_peaks: track_dtype must be 0 (fp32) or 1 (fp64), got %d",
+                track_dtype);
+    HMM_REQUIRE(track_len >= 0 && n_spans >= 0, HMM_E_INVALID, "audio_span_peaks: negative count (track_len=%lld, n_spans=%d)",
+                (long long)track_len, n_spans);
+    if (n_spans == 0) return HMM_OK;                                          // nothing to write: no pointer is looked at
+    HMM_REQUIRE(track_dev && spans_host && spans_dev && peaks_out_dev, HMM_E_INVALID, "audio_span_peaks: null pointer");
+    HMM_REQUIRE(((uintptr_t)track_dev & 15) == 0 && ((uintptr_t)spans_dev & 7) == 0 && ((uintptr_t)peaks_out_dev & 3) == 0, HMM_E_INVALID,
+                "audio_span_peaks: the track must be 16-byte aligned, the tables aligned to their element size");
+    for (int s = 0; s < n_spans; ++s) {
+        const int64_t a = spans_host[2 * s], b = spans_host[2 * s + 1];
+        HMM_REQUIRE(a >= 0 && a <= b && b <= track_len, HMM_E_INVALID,
+                    "audio_span_peaks: span %d = [%lld, %lld) lies outside the track [0, %lld]", s, (long long)a, (long long)b,
+                    (long long)track_len);
+    }
+    HMM_REQUIRE(!track_overlap(track_dev, (uint64_t)track_len * (track_dtype == 1 ? 8 : 4), peaks_out_dev, (uint64_t)n_spans * 4),
+                HMM_E_INVALID, "audio_span_peaks: the output overlaps the track");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (track_dtype == 1) span_peaks_kernel<true><<<n_spans, 256, 0, st>>>(track_dev, track_len, spans_dev, peaks_out_dev);
+    else span_peaks_kernel<false><<<n_spans, 256, 0, st>>>(track_dev, track_len, spans_dev, peaks_out_dev);
+    HMM_LAUNCH_CHECK();
+    return HMM_OK;
+}
+
+extern "C" int hmm_audio_gather_clips(const void* track_dev, int track_dtype, int64_t track_len, const int64_t* clips_host,
+                                      const int64_t* clips_dev, int n_clips, const float* peaks_dev, int n_spans, int clip_len,
+                                      int orig, int new_, int width, const float* taps_dev, float* clips_out_dev,
+                                      hmm_stream_t stream) {
+    HMM_REQUIRE(track_dtype == 0 || track_dtype == 1, HMM_E_INVALID, "audio_gather_clips: track_dtype must be 0 (fp32) or 1 (fp64), got %d",
+                track_dtype);
+    HMM_REQUIRE(track_len >= 0 && n_clips >= 0 && n_spans >= 0 && clip_len >= 0 && width >= 0, HMM_E_INVALID,
+                "audio_gather_clips: negative count (track_len=%lld, n_clips=%d, n_spans=%d, clip_len=%d, width=%d)",
+                (long long)track_len, n_clips, n_spans, clip_len, width);
+    HMM_REQUIRE(orig >= 1 && new_ >= 1, HMM_E_INVALID, "audio_gather_clips: orig and new must be at least 1, got %d and %d", orig, new_);
+    if (n_clips == 0 || clip_len == 0) return HMM_OK;                         // nothing to write: no pointer is looked at
+    HMM_REQUIRE(track_dev && clips_host && clips_dev && peaks_dev && clips_out_dev, HMM_E_INVALID, "audio_gather_clips: null pointer");
+    HMM_REQUIRE(orig == new_ || taps_dev != nullptr, HMM_E_INVALID,
+                "audio_gather_clips: taps must be given when orig != new (%d -> %d): null pointer", orig, new_);
+    HMM_REQUIRE(((uintptr_t)track_dev & 15) == 0 && ((uintptr_t)clips_dev & 7) == 0 && ((uintptr_t)peaks_dev & 3) == 0 &&
+                    ((uintptr_t)taps_dev & 3) == 0 && ((uintptr_t)clips_out_dev & 3) == 0, HMM_E_INVALID,
+                "audio_gather_clips: the track must be 16-byte aligned, tables and clips aligned to their element size");
+    // the input window of one workgroup: the frames its 256 outputs start in, plus one filter length
+    const int64_t win = orig == new_ ? 0 : ((int64_t)((kClipBlock - 1) / new_ + 1) * orig + 2 * (int64_t)width + orig);
+    HMM_REQUIRE(win * 4 <= 65536, HMM_E_INVALID,
+                "audio_gather_clips: resampling %d -> %d with width %d needs a window of %lld samples per workgroup, 16384 fit", orig,
+                new_, width, (long long)win);
+    for (int c = 0; c < n_clips; ++c) {
+        const int64_t a = clips_host[4 * c], len = clips_host[4 * c + 1], first = clips_host[4 * c + 2], span = clips_host[4 * c + 3];
+        HMM_REQUIRE(a >= 0 && len >= 0 && a <= track_len && len <= track_len - a, HMM_E_INVALID,
+                    "audio_gather_clips: clip %d: span [%lld, %lld + %lld) lies outside the track [0, %lld]", c, (long long)a,
+                    (long long)a, (long long)len, (long long)track_len);
+        HMM_REQUIRE(span >= 0 && span < n_spans, HMM_E_INVALID, "audio_gather_clips: clip %d: span index %lld is not in [0, %d)", c,
+                    (long long)span, n_spans);
+        const int64_t n_out = orig == new_ ? len : (len / orig * new_ + (len % orig * new_ + orig - 1) / orig);      // ceil(new len / orig)
+        HMM_REQUIRE(first >= 0 && first <= n_out && clip_len <= n_out - first, HMM_E_INVALID,
+                    "audio_gather_clips: clip %d: samples [%lld, %lld + %d) reach past the span's output length %lld", c,
+                    (long long)first, (long long)first, clip_len, (long long)n_out);
+    }
+    HMM_REQUIRE(!track_overlap(track_dev, (uint64_t)track_len * (track_dtype == 1 ? 8 : 4), clips_out_dev,
+                               (uint64_t)n_clips * (uint64_t)clip_len * 4),
+                HMM_E_INVALID, "audio_gather_clips: the output overlaps the track");
+    const int blocks_per_clip = (clip_len + kClipBlock - 1) / kClipBlock;
+    HMM_REQUIRE((int64_t)blocks_per_clip * n_clips <= 0x7FFFFFFF, HMM_E_INVALID,
+                "audio_gather_clips: %d clips of %d samples exceed one launch", n_clips, clip_len);
+    const unsigned grid = (unsigned)(blocks_per_clip * n_clips);
+    const size_t lds = (size_t)win * 4;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+#define HMM_GATHER(F64, RS)                                                                                                          \
+    gather_clips_kernel<F64, RS><<<grid, kClipBlock, lds, st>>>(track_dev, track_len, clips_dev, peaks_dev, n_spans, clip_len,       \
+                                                                blocks_per_clip, orig, new_, width, taps_dev, clips_out_dev)
+    if (orig == new_) {
+        if (track_dtype == 1) HMM_GATHER(true, false); else HMM_GATHER(false, false);
+    } else {
+        if (track_dtype == 1) HMM_GATHER(true, true); else HMM_GATHER(false, true);
+    }
+#undef HMM_GATHER
+    HMM_LAUNCH_CHECK();
+    return HMM_OK;
+}

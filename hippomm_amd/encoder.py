@@ -351,6 +351,27 @@ class ImageBind(nn.Module):
         vision_pipeline(paths, self.device, embed, max_chunk=step)
         return emb
 
+    def extract_audio_segments(self, audio, sample_rate: int, spans) -> torch.Tensor:
+        """The audio embeddings of all segments of a video in one call: (len(spans), 1024) fp32 on the device, in span order.
+        Stands for the audio block of the reference's process_sequence loop (hippocampal_memory.py:1198-1251), which writes one
+        temporary wav per segment and embeds it alone.  audio: the video's waveform as np.load of audio.npy yields it, or an
+        hippomm_amd.audio_track.AudioTrack already on the device; spans: [(start_sample, end_sample), ...]
+        (audio_track.spans_of).  The tower sees the segments in ranges of its max_batch, like every other forward."""
+        from .audio_track import AudioTrack
+        a = ModalityType.AUDIO
+        if a not in self.model.towers:
+            raise KeyError(f"modality {a!r} is not built on this device (have {list(self.model.towers)})")
+        if isinstance(audio, AudioTrack):
+            if audio.sample_rate != int(sample_rate):
+                raise ValueError(f"the track is at {audio.sample_rate} Hz, the call says {int(sample_rate)} Hz")
+            track = audio
+        else:
+            track = AudioTrack(audio, sample_rate, self.device)
+        if len(spans) == 0:
+            return torch.empty(0, 1024, dtype=torch.float32, device=self.device)
+        with torch.no_grad():
+            return self.model.towers[a](track.melspec(spans), self.model.max_batch.get(a, 256))
+
     def extract_features(self, inputs, modalities):
         """load_data + forward (reference :135-151).  Vision given as files (the reference's formation calls,
         hippocampal_memory.py:1180-1186, :1328-1335) runs decode, upload, resize and the tower as one overlapped pipeline;

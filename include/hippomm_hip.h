@@ -365,6 +365,40 @@ int    hmm_audio_fbank(const float* clips_dev, int n_clips, int clip_len, int64_
                        void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The audio track of a video on the device: all segments of process_sequence in one call.  Replaces, per segment, the slice,
+ * `audio_data.mean(axis=1)` (done once on the host for C > 1), `.astype(np.float32)`, the peak normalisation, the temporary wav
+ * (hippomm/core/hippocampal_memory.py:1198-1251; :1206, :1212, :1215-1216, :1219) and, inside
+ * imagebind.data.load_and_transform_audio_data [upstream, recalled] (hippomm/models/foundation_models.py:106-109), the
+ * torchaudio resampling of a file that is not at 16 kHz and the cut into three clips.  The result is the clip batch
+ * hmm_audio_fbank takes.
+ *
+ * track_dev: the mono track, track_len samples, fp32 (track_dtype 0) or fp64 (1: narrowed on the fly with round-to-nearest-even,
+ * the bits of astype(float32)); 16-byte aligned.  Every table is given twice: *_host is what the entry point checks before it
+ * launches anything (a host pointer, read during the call only), *_dev the same table on the device, which the kernel reads --
+ * and clamps to the track, so a device copy that differs reads and writes less, never elsewhere.
+ *
+ * hmm_audio_span_peaks: spans: n_spans x (start, end) int64, 0 <= start <= end <= track_len.  peaks_out_dev[s] = max |x| over the
+ *   narrowed samples of span s, NaN when the span holds a NaN (np.abs(x).max()), 0 for an empty span.
+ * hmm_audio_gather_clips: clips: n_clips x (span start, span length, first output sample, span index) int64; peaks_dev[n_spans]
+ *   from hmm_audio_span_peaks.  A sample of a span with peak p > 1.0f is x / p (one correctly rounded fp32 division), else x
+ *   as it is (p == 1 and a NaN p do not scale).  orig == new (the rate divided by its gcd with 16000, and 16000 divided by it):
+ *   clips_out_dev[c][i] = sample first + i of the span, bit-exact; taps_dev may be null.  Otherwise the span is resampled as a
+ *   file of its own, torchaudio.functional.resample's polyphase windowed sinc:
+ *       out[j] = sum_t taps[j % new][t] * x[(j / new) * orig - width + t],   x = 0 outside [0, span length),
+ *   ceil(new * length / orig) output samples, of which clips_out_dev[c][i] is j = first + i.  taps_dev is TAP-MAJOR:
+ *   (2 * width + orig, new) floats, taps_dev[t * new + phase].  fp32 fused multiply-adds into four partial sums (t mod 4) added as
+ *   (a0 + a1) + (a2 + a3): within (T + 2) 2^-24 sum_t |taps_t x_t| of the exact sum, and the same bits whatever else is in the
+ *   batch.  first + clip_len may not exceed the span's output length; the window of one workgroup,
+ *   (255 / new + 2) * orig + 2 * width samples, must fit 64 KiB of LDS (HMM_E_INVALID otherwise).  clips_out_dev: (n_clips,
+ *   clip_len) fp32, contiguous, not overlapping the track.  Zero n_spans / n_clips / clip_len: HMM_OK, nothing is launched.
+ * ---------------------------------------------------------------------------------------- */
+int hmm_audio_span_peaks(const void* track_dev, int track_dtype, int64_t track_len, const int64_t* spans_host,
+                         const int64_t* spans_dev, int n_spans, float* peaks_out_dev, hmm_stream_t stream);
+int hmm_audio_gather_clips(const void* track_dev, int track_dtype, int64_t track_len, const int64_t* clips_host,
+                           const int64_t* clips_dev, int n_clips, const float* peaks_dev, int n_spans, int clip_len,
+                           int orig, int new_, int width, const float* taps_dev, float* clips_out_dev, hmm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Frame SSIM (structural similarity) for sequence segmentation and frame differences.  Replaces skimage 0.18.3
  * structural_similarity as hippomm/core/hippocampal_memory.py:980-991 (_compute_frame_similarity, consulted by
  * _segment_sequence :1002-1114) and hippomm/core/batch_process.py:32-69 (compute_frame_difference) call it on gray frames.
