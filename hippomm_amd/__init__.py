@@ -5,6 +5,7 @@ through the C ABI in include/hippomm_hip.h:
 
     hippomm_amd.encoder.ImageBind                    <- hippomm/models/foundation_models.py:21-151
     hippomm_amd.consolidation._select_key_frames     <- hippomm/core/hippocampal_memory.py:944-967
+    hippomm_amd.consolidation.KeyFrameSelector       the same selection grown batch by batch (live path, :1290-1365)
     hippomm_amd.vector_ops.top_k_cosine_similarity   <- hippomm/utils/vector_ops.py:151-188
 
 and the two SSIM call sites of the formation path (frame SSIM in hippomm_amd/csrc/ssim.hip):

@@ -56,6 +56,9 @@ _SIGNATURES = {
                                                             c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, C.c_size_t, c_ptr]),
     "hmm_gram_select_workspace_bytes": (C.c_size_t, [C.c_int]),
     "hmm_gram_select": (C.c_int, [c_ptr, C.c_int, C.c_int, C.c_float, c_ptr, c_ptr, c_ptr, C.c_size_t, c_ptr]),
+    "hmm_keyframe_extend_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "hmm_keyframe_extend": (C.c_int, [c_ptr, C.c_int, C.c_int, C.c_float, c_ptr, c_ptr, C.c_int64, c_ptr, C.c_int64, C.c_int64,
+                                      c_ptr, C.c_size_t, c_ptr]),
     "hmm_preprocess_vision_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "hmm_preprocess_vision_u8": (C.c_int, [c_ptr, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr, C.c_int, c_ptr, c_ptr, C.c_int,
                                            C.c_int, C.c_int, c_ptr, c_ptr, C.c_size_t, c_ptr]),

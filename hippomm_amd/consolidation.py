@@ -1,6 +1,7 @@
 """Consolidation similarity on MI355X -- host-side mirror of
 ``HippocampalMemory._select_key_frames`` (hippomm/core/hippocampal_memory.py:944-967),
-bound to ``hmm_gram_select`` (fp32 normalise, fp64-accumulated gram via f64 MFMA, greedy scan).
+bound to ``hmm_gram_select`` (fp32 normalise, fp64-accumulated gram via f64 MFMA, greedy scan).  ``KeyFrameSelector`` is the
+same selection grown batch by batch (``hmm_keyframe_extend``): each frame is decided when its embedding arrives.
 """
 from __future__ import annotations
 
@@ -92,3 +93,110 @@ def _select_key_frames(self, features: np.ndarray, times: np.ndarray,
     """Drop-in for ``HippocampalMemory._select_key_frames`` (assign it on the class; ``self`` is
     unused there as well)."""
     return select_key_frames(features, times, similarity_threshold)
+
+
+class KeyFrameSelector:
+    """The key-frame selection of one video, grown batch by batch: ``extend`` takes the embeddings of the next frames and decides
+    each of them at once, so that the kept frames can be used (captioned, stored) while later frames are still being encoded.
+
+    After any number of ``extend`` calls ``kept()`` is what ``select_key_frames`` answers for all rows given so far, bit for bit,
+    pairs within 1e-7 of the threshold included: new rows are compared with the kept rows and with each other by the kernels'
+    one gram mainloop (``hmm_keyframe_extend``).  The state on the device is the normalised kept rows alone, 4 KB each.
+
+    Rows must arrive in time order: the reference sorts by time before it selects, and its live path delivers frames in order.
+    A frame's decision is final on arrival, with one exception: the reference keeps both rows of a two-row video without
+    comparing them (hippocampal_memory.py:947-948), so ``kept()`` is ``arange(n_seen)`` while ``n_seen <= 2`` and the greedy
+    state from the third row on -- row 1's status is provisional until a third row has arrived.
+
+    The threshold is fixed for the selector's life (compared in float32, as ``select_key_frames`` does).  One selector's calls
+    belong on one stream.  There is no CPU fallback."""
+
+    def __init__(self, similarity_threshold: float = 0.9, device=None, capacity: int = 1024):
+        self.similarity_threshold = float(np.float32(similarity_threshold))     # the reference compares in float32 (:960)
+        self._device = None if device is None else torch.device(device)
+        self._initial_capacity = max(int(capacity), 1)
+        self._rows = None            # (capacity,1024) fp32: the normalised kept rows, in kept order
+        self._meta = None            # int64[1 + capacity]: the kept count, then the kept global indices (one read-back gets both)
+        self._ws = None
+        self._n_seen = 0
+        self._bound = 0              # min(n_seen, last count read + rows given since) >= the count on the device
+
+    @property
+    def n_seen(self) -> int:
+        return self._n_seen
+
+    @property
+    def capacity(self) -> int:
+        return 0 if self._rows is None else self._rows.shape[0]
+
+    def reset(self):
+        """Start over (the next ``extend`` begins a selection); the buffers stay."""
+        self._n_seen = self._bound = 0
+        return self
+
+    def _read_count(self) -> int:
+        count = min(max(int(self._meta[0].item()), 0), self._bound) if self._n_seen else 0
+        self._bound = count
+        return count
+
+    def _reserve(self, m: int, dev):
+        if self._rows is not None and self._bound + m <= self.capacity:
+            return
+        count = self._read_count() if self._rows is not None else 0      # the exact count: grow only when needed
+        if self._rows is not None and count + m <= self.capacity:
+            return
+        capacity = max(count + m, 2 * self.capacity, self._initial_capacity)
+        rows = torch.empty(capacity, FEATURE_DIM, dtype=torch.float32, device=dev)
+        meta = torch.empty(1 + capacity, dtype=torch.int64, device=dev)
+        if count:
+            rows[:count].copy_(self._rows[:count])
+            meta[: 1 + count].copy_(self._meta[: 1 + count])
+        self._rows, self._meta = rows, meta
+
+    def extend(self, features: Union[np.ndarray, torch.Tensor]) -> "KeyFrameSelector":
+        """Append the next rows, in time order: (m,1024) or one (1024,) row, numpy or torch.  Features are taken as float32; a
+        float64 numpy array is converted as ``select_key_frames`` converts it.  With a device tensor the call is launch-only on
+        the current stream (it reads the count back only when the kept rows may outgrow their buffer)."""
+        dev = _lib.require_gpu() if self._device is None else self._device
+        if self._device is not None:
+            _lib.require_gpu()
+        if isinstance(features, np.ndarray):
+            features = torch.from_numpy(np.ascontiguousarray(features, dtype=np.float32))
+        if features.dim() == 1:
+            features = features.unsqueeze(0)
+        f = _prepare(features.to(dev))
+        m = f.shape[0]
+        if m == 0:
+            return self
+        self._device = dev
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            self._reserve(m, dev)
+            need = lib.hmm_keyframe_extend_workspace_bytes(m)
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            _lib.check(lib.hmm_keyframe_extend(f.data_ptr(), m, FEATURE_DIM, self.similarity_threshold, self._rows.data_ptr(),
+                                               self._meta.data_ptr() + 8, self.capacity, self._meta.data_ptr(), self._n_seen,
+                                               self._bound, self._ws.data_ptr(), self._ws.numel(), _lib.stream_ptr()),
+                       "hmm_keyframe_extend")
+        self._n_seen += m
+        self._bound = min(self._n_seen, self._bound + m)
+        return self
+
+    def kept_device(self) -> torch.Tensor:
+        """The kept indices as an int64 tensor of its own on the device (synchronises once to read the count)."""
+        if self._n_seen <= 2:                                # hippocampal_memory.py:947-948
+            dev = self._device if self._device is not None else _lib.require_gpu()
+            return torch.arange(self._n_seen, dtype=torch.int64, device=dev)
+        count = self._read_count()
+        return self._meta[1: 1 + count].clone()
+
+    def kept(self) -> np.ndarray:
+        """The kept indices so far, int64, increasing, first is 0.  One read-back of the count and the indices (one
+        synchronisation); it also tightens the host's bound on the count."""
+        if self._n_seen <= 2:                                # hippocampal_memory.py:947-948
+            return np.arange(self._n_seen, dtype=np.int64)
+        host = self._meta[: 1 + self._bound].cpu().numpy()
+        count = min(max(int(host[0]), 0), self._bound)
+        self._bound = count
+        return host[1: 1 + count].copy()

@@ -256,6 +256,33 @@ int    hmm_gram_select(const float* features_dev, int n, int dim, float threshol
                        int64_t* kept_out_dev, int32_t* n_kept_out_dev,
                        void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
 
+/* A selection that grows: hmm_keyframe_extend appends m rows (in time order) to a selection whose state lives in caller-owned
+ * device memory, and decides each of them on arrival -- the greedy rule is causal.  After any number of calls the state is what
+ * hmm_gram_select answers for all rows given so far, bit for bit (the dots run the same f64-MFMA sequence on the same normalised
+ * rows), except for the n <= 2 clause: the call keeps the pure greedy state, and "n_seen <= 2 lists all rows" is the caller's
+ * read-out rule (row 1 of two identical rows is dropped here, listed by the reference; from the third row on the two agree).
+ *
+ *   kept_rows_dev (capacity_kept, 1024) fp32: the NORMALISED rows of the kept frames, in kept order
+ *   kept_idx_dev  int64[capacity_kept]: their global indices      n_kept_dev: one int64, their number
+ *   n_seen_before  the host's exact count of rows given so far; 0 starts a selection: *n_kept_dev and the state buffers need
+ *                  no initialisation then, the call treats the count as 0
+ *   kept_bound     the host's upper bound on *n_kept_dev (<= n_seen_before): it sizes the new x kept grid, and every kernel clamps
+ *                  the device count to it and to capacity_kept -- a stale or wrong count reads or copies less, never elsewhere
+ *
+ * Writes kept_rows / kept_idx at slots [old n_kept, new n_kept) only and touches no other byte of either; *n_kept_dev becomes the
+ * new count.  m == 0 returns HMM_OK without a launch and without looking at a pointer.  HMM_E_INVALID, before anything is launched:
+ * dim != 1024, a negative count, kept_bound > n_seen_before, kept_bound + m > capacity_kept, a null pointer, a row pointer or the
+ * workspace not 16-byte aligned (kept_idx_dev / n_kept_dev: 8-byte), new rows that overlap the state, an m whose bitmap exceeds LDS (as hmm_gram_select refuses it).
+ * HMM_E_WORKSPACE: workspace_bytes below hmm_keyframe_extend_workspace_bytes(m).  The workspace needs no initialisation and may be
+ * reused across calls and sizes on one stream.  Launch-only: nothing is allocated, copied to the host or synchronised. */
+size_t hmm_keyframe_extend_workspace_bytes(int m);
+int    hmm_keyframe_extend(const float* new_rows_dev, int m, int dim, float threshold,
+                           float* kept_rows_dev, int64_t* kept_idx_dev, int64_t capacity_kept,
+                           int64_t* n_kept_dev,
+                           int64_t n_seen_before,   /* host's exact count of rows given so far */
+                           int64_t kept_bound,      /* host's upper bound on *n_kept_dev     */
+                           void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Perceptual encoder.  Replaces ImageBind._load_model / ImageBind.forward
  * (hippomm/models/foundation_models.py:31-35, :116-133), i.e. upstream
