@@ -10,6 +10,8 @@ call, which is correct but PCIe-bound.
 """
 from __future__ import annotations
 
+import functools
+import math
 import threading
 import weakref
 import zlib
@@ -28,6 +30,70 @@ from . import _lib
 
 FEATURE_DIM = 1024
 
+# The scan routes: (shape, through the bf16 shadow) -> (C entry point, its workspace-size function, takes a stats pointer).
+# FeatureStore._scan assembles every argument list from these, in the one order the entry points share:
+#   store, [shadow,] n, dim, queries, [Q,] [seg_offsets, E,] k, outputs..., [stats,] workspace, workspace bytes, stream
+# and sizes the workspace with (n, [E,] [Q,] k).  "keys" is the flat scan that returns packed order keys; it has no shadow variant.
+_ROUTES = {
+    ("flat", False): ("hmm_cosine_topk", "hmm_cosine_topk_workspace_bytes", False),
+    ("flat", True): ("hmm_cosine_topk_prefilter", "hmm_cosine_topk_prefilter_workspace_bytes", True),
+    ("keys", False): ("hmm_cosine_topk_keys", "hmm_cosine_topk_workspace_bytes", False),
+    ("segmented", False): ("hmm_cosine_topk_segmented", "hmm_cosine_topk_segmented_workspace_bytes", False),
+    ("segmented", True): ("hmm_cosine_topk_segmented_prefilter", "hmm_cosine_topk_segmented_prefilter_workspace_bytes", False),
+    ("multi", False): ("hmm_cosine_topk_multi", "hmm_cosine_topk_multi_workspace_bytes", False),
+    ("multi", True): ("hmm_cosine_topk_multi_prefilter", "hmm_cosine_topk_multi_prefilter_workspace_bytes", True),
+    ("segmented_multi", False): ("hmm_cosine_topk_segmented_multi", "hmm_cosine_topk_segmented_multi_workspace_bytes", False),
+    ("segmented_multi", True): ("hmm_cosine_topk_segmented_multi_prefilter",
+                                "hmm_cosine_topk_segmented_multi_prefilter_workspace_bytes", True),
+}
+
+
+_I64, _F32, _I32 = (torch.int64, np.int64, 8), (torch.float32, np.float32, 4), (torch.int32, np.int32, 4)
+
+
+class _Packed:
+    """Arrays laid out back to back in one uint8 buffer, so that the device writes them through ``device_views`` and the host
+    reads them through ``host_views`` after ONE copy -- the same offsets on both sides.  fields: ((torch dtype, numpy dtype,
+    item size), shape)."""
+
+    def __init__(self, *fields):
+        self.fields, self.offsets, self.nbytes = [], [], 0
+        for (torch_dtype, numpy_dtype, size), shape in fields:
+            end = self.nbytes + size * math.prod(shape)
+            self.fields.append((self.nbytes, end, torch_dtype, numpy_dtype, shape if len(shape) > 1 else None))
+            self.offsets.append(self.nbytes)
+            self.nbytes = end
+
+    def device_views(self, packed: torch.Tensor):                # a typed slice is 1-D already: only the others are reshaped
+        return [packed[a:b].view(dtype) if shape is None else packed[a:b].view(dtype).view(shape)
+                for a, b, dtype, _, shape in self.fields]
+
+    def host_views(self, raw: np.ndarray):
+        return [raw[a:b].view(dtype) if shape is None else raw[a:b].view(dtype).reshape(shape)
+                for a, b, _, dtype, shape in self.fields]
+
+
+@functools.lru_cache(maxsize=64)                                 # a caller's shapes repeat from call to call
+def _hits_layout(*shape):
+    """idx | sims | counts of a segmented scan; shape = (E, k) or (Q, E, k)."""
+    return _Packed((_I64, shape), (_F32, shape), (_I32, shape[:-1]))
+
+
+@functools.lru_cache(maxsize=64)
+def _ranking_layout(*shape):
+    """event | row | sim | count of a ranking; shape = (keep,) or (Q, keep), one count per question."""
+    return _Packed((_I64, shape), (_I64, shape), (_F32, shape), (_I32, shape[:-1] or (1,)))
+
+
+def _queries_2d(queries, device=None) -> torch.Tensor:
+    """queries (numpy or torch) as a (Q,1024) tensor with Q >= 1; with ``device``, contiguous fp32 on it."""
+    q = queries if isinstance(queries, torch.Tensor) else torch.from_numpy(np.asarray(queries))
+    if q.dim() != 2 or q.shape[1] != FEATURE_DIM:
+        raise ValueError(f"queries must be (Q,{FEATURE_DIM}), got {tuple(q.shape)}")
+    if q.shape[0] == 0:
+        raise ValueError("no queries")
+    return q if device is None else q.detach().to(device=device, dtype=torch.float32).contiguous()
+
 
 class FeatureStore:
     """(N,1024) fp32 feature matrix resident in HBM (the ``memory_store`` vision/audio matrix
@@ -39,53 +105,85 @@ class FeatureStore:
         The rows must stay unchanged while a shadow exists (see ``build_shadow``)."""
         dev = device or _lib.require_gpu()
         if isinstance(rows, np.ndarray):
-            self.source_dtype = rows.dtype
+            source_dtype = rows.dtype
             host = np.ascontiguousarray(rows.reshape(1, -1) if rows.ndim == 1 else rows, dtype=np.float32)
             t = torch.from_numpy(host).to(dev)
         else:
-            self.source_dtype = np.dtype(str(rows.dtype).replace("torch.", "")) if rows.dtype in (
+            source_dtype = np.dtype(str(rows.dtype).replace("torch.", "")) if rows.dtype in (
                 torch.float32, torch.float64) else np.dtype(np.float32)
             t = rows.reshape(1, -1) if rows.dim() == 1 else rows
             t = t.to(device=dev, dtype=torch.float32).contiguous()
         if t.dim() != 2 or t.shape[1] != FEATURE_DIM:
             raise ValueError(f"store must be (N,{FEATURE_DIM}), got {tuple(t.shape)}")
-        self.rows = t
-        self._ws = None
-        self._ws_key = None
-        self.use_shadow = False
+        self._init_state(t, source_dtype)
         if shadow and t.shape[0] > 0:
             self.build_shadow()
             self.use_shadow = True
 
+    def _init_state(self, rows: torch.Tensor, source_dtype):
+        """Every field of a store, in one place (EventStore adds ``lengths`` and ``offsets``)."""
+        self.rows, self.source_dtype = rows, source_dtype
+        self.use_shadow = False                          # search / search_device go through the shadow
+        self._shadow, self._shadow_version = None, None  # the bf16 shadow of `rows` and the torch version of `rows` it was built at
+        self._ws = None                                  # the scan workspace every route shares (_scratch)
+        self._buf, self._shadow_buf = None, None         # the capacity-sized buffers of a store that has grown (EventStore)
+        self._pinned = None                              # the read-back staging buffer (EventStore._read_back)
+
     def __len__(self):
         return self.rows.shape[0]
 
-    def _workspace(self, k: int):
-        lib = _lib.load()
-        need = lib.hmm_cosine_topk_workspace_bytes(len(self), k)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.rows.device)
+    def _scratch(self, need_bytes: int) -> torch.Tensor:
+        """The workspace, reallocated only when it is too small.  No route reads what an earlier call left in it."""
+        if self._ws is None or self._ws.numel() < need_bytes:
+            self._ws = torch.empty(need_bytes, dtype=torch.uint8, device=self.rows.device)
         return self._ws
+
+    def _scan(self, shape: str, prefilter: bool, queries: torch.Tensor, k: int, outputs, Q: int = None,
+              seg_offsets: torch.Tensor = None, stats: torch.Tensor = None):
+        """One launch of the route (shape, prefilter) of _ROUTES into ``outputs`` (the tensors the entry point fills, in its
+        order).  Builds the shadow when the route streams it; does not synchronise."""
+        name, size_name, takes_stats = _ROUTES[shape, prefilter]
+        lib = _lib.load()
+        if prefilter:
+            self.build_shadow()
+        n = len(self)
+        batch = () if Q is None else (Q,)
+        segments = () if seg_offsets is None else (seg_offsets.data_ptr(), seg_offsets.numel() - 1)
+        ws = self._scratch(getattr(lib, size_name)(n, *segments[1:], *batch, k))
+        store = (self.rows.data_ptr(), self._shadow.data_ptr()) if prefilter else (self.rows.data_ptr(),)
+        tail = (stats.data_ptr() if stats is not None else None,) if takes_stats else ()
+        _lib.check(getattr(lib, name)(*store, n, FEATURE_DIM, queries.data_ptr(), *batch, *segments, k,
+                                      *[t.data_ptr() for t in outputs], *tail, ws.data_ptr(), ws.numel(), _lib.stream_ptr()), name)
+
+    def _search_flat(self, query: torch.Tensor, k: int, prefilter: bool, stats: torch.Tensor = None):
+        if k < 1:
+            raise ValueError("k must be >= 1")
+        dev, k_out = self.rows.device, min(k, len(self))
+        idx = torch.empty(k_out, dtype=torch.int64, device=dev)
+        sims = torch.empty(k_out, dtype=torch.float32, device=dev)
+        n_out = torch.empty(1, dtype=torch.int32, device=dev)
+        self._scan("flat", prefilter, query, k, (idx, sims, n_out), stats=stats)
+        return idx, sims
 
     def search_device(self, query: torch.Tensor, k: int):
         """query: (1024,) fp32 CUDA tensor.  Returns CUDA tensors (idx int64[k'], sims fp32[k'])
         without synchronising (k' = min(k, N))."""
-        if getattr(self, "use_shadow", False):
+        if self.use_shadow:
             return self.search_prefiltered_device(query, k)
-        lib = _lib.load()
-        n = len(self)
-        if k < 1:
-            raise ValueError("k must be >= 1")
-        k_out = min(k, n)
-        ws = self._workspace(k)
-        idx = torch.empty(k_out, dtype=torch.int64, device=self.rows.device)
-        sims = torch.empty(k_out, dtype=torch.float32, device=self.rows.device)
-        n_out = torch.empty(1, dtype=torch.int32, device=self.rows.device)
-        _lib.check(lib.hmm_cosine_topk(self.rows.data_ptr(), n, FEATURE_DIM, query.data_ptr(), k,
-                                       idx.data_ptr(), sims.data_ptr(), n_out.data_ptr(),
-                                       ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
-                   "hmm_cosine_topk")
-        return idx, sims
+        return self._search_flat(query, k, False)
+
+    def _rows_version(self) -> int:
+        try:
+            return self.rows._version
+        except (RuntimeError, AttributeError):       # an inference tensor tracks no version: a snapshot until invalidate_shadow()
+            return 0
+
+    def _shadow_is_current(self) -> bool:
+        """True when a shadow exists and matches the rows.  A stale one (the rows were edited through torch since) is dropped:
+        the next prefiltered search rebuilds it whole, as it would have anyway."""
+        if self._shadow is not None and self._shadow_version != self._rows_version():
+            self.invalidate_shadow()
+        return self._shadow is not None
 
     def build_shadow(self, force: bool = False):
         """Build the bf16 shadow of the store (2048 B per row beside the 4096-B fp32 rows; hmm_shadow_store_build) that
@@ -95,19 +193,25 @@ class FeatureStore:
         a caller's fp32 CUDA tensor without copying).  An in-place update made through torch bumps the tensor's version
         counter, which the searches check: the shadow is then rebuilt before it is used.  Writes that bypass torch (a raw
         kernel on ``rows.data_ptr()``) need ``invalidate_shadow()`` or ``build_shadow(force=True)``.  The build is enqueued
-        on the current stream; searches on another stream must be ordered after it by the caller."""
-        try:
-            version = self.rows._version
-        except (RuntimeError, AttributeError):       # an inference tensor tracks no version: a snapshot until invalidate_shadow()
-            version = 0
-        if force or getattr(self, "_shadow", None) is None or getattr(self, "_shadow_version", version) != version:
-            lib = _lib.load()
-            n = len(self)
-            need = lib.hmm_shadow_store_bytes(n)
-            if getattr(self, "_shadow", None) is None or self._shadow.numel() != need:
-                self._shadow = torch.empty(need, dtype=torch.uint8, device=self.rows.device)
-            _lib.check(lib.hmm_shadow_store_build(self.rows.data_ptr(), n, FEATURE_DIM, self._shadow.data_ptr(),
-                                                  self._shadow.numel(), _lib.stream_ptr()), "hmm_shadow_store_build")
+        on the current stream; searches on another stream must be ordered after it by the caller.
+
+        On a store that owns its buffers (an EventStore that has grown) the shadow is built into the capacity-sized buffer, where
+        later appends keep it current row by row (an append never rebuilds it).  The ingest and the gather write rows behind
+        torch's back AND their shadow rows with them, so the version the shadow was built at stays the one it is checked
+        against; edits of ``rows`` made through torch still bump it and cause a rebuild."""
+        version = self._rows_version()
+        if force or self._shadow is None or self._shadow_version != version:
+            n, owned = len(self), self._buf is not None
+            buf = self._shadow_buf if owned else self._shadow
+            size = self._buf.shape[0] * 2048 if owned else _lib.load().hmm_shadow_store_bytes(n)
+            if buf is None or buf.numel() != size:
+                buf = torch.empty(size, dtype=torch.uint8, device=self.rows.device)
+            if owned:
+                self._shadow_buf = buf
+            if n > 0 or not owned:                       # without rows an owned store launches nothing; an aliased one lets the library refuse
+                _lib.check(_lib.load().hmm_shadow_store_build(self.rows.data_ptr(), n, FEATURE_DIM, buf.data_ptr(), n * 2048,
+                                                              _lib.stream_ptr()), "hmm_shadow_store_build")
+            self._shadow = buf[: n * 2048]
             self._shadow_version = version
         return self
 
@@ -121,34 +225,13 @@ class FeatureStore:
         """``search_device`` through the bf16 shadow: candidates from one pass over 2048 B per row, re-scored exactly on the
         fp32 rows -- the same (idx, sims) as ``search_device``, bit for bit (hmm_cosine_topk_prefilter).  ``stats``: optional
         int32[2] CUDA tensor receiving (candidates re-scored, saturated lists)."""
-        lib = _lib.load()
-        self.build_shadow()
-        n = len(self)
-        if k < 1:
-            raise ValueError("k must be >= 1")
-        k_out = min(k, n)
-        need = lib.hmm_cosine_topk_prefilter_workspace_bytes(n, k)
-        if getattr(self, "_ws_pre", None) is None or self._ws_pre.numel() < need:
-            self._ws_pre = torch.empty(need, dtype=torch.uint8, device=self.rows.device)
-        idx = torch.empty(k_out, dtype=torch.int64, device=self.rows.device)
-        sims = torch.empty(k_out, dtype=torch.float32, device=self.rows.device)
-        n_out = torch.empty(1, dtype=torch.int32, device=self.rows.device)
-        _lib.check(lib.hmm_cosine_topk_prefilter(self.rows.data_ptr(), self._shadow.data_ptr(), n, FEATURE_DIM, query.data_ptr(), k,
-                                                 idx.data_ptr(), sims.data_ptr(), n_out.data_ptr(),
-                                                 stats.data_ptr() if stats is not None else None,
-                                                 self._ws_pre.data_ptr(), self._ws_pre.numel(), _lib.stream_ptr()),
-                   "hmm_cosine_topk_prefilter")
-        return idx, sims
+        return self._search_flat(query, k, True, stats)
 
     def search_keys_device(self, query: torch.Tensor, k: int) -> torch.Tensor:
         """Local top-k as packed order keys (uint64 bit patterns in an int64 tensor, 0-padded to k)
         for the sharded scan (hippomm_amd.sharding.sharded_top_k)."""
-        lib = _lib.load()
-        ws = self._workspace(k)
         keys = torch.empty(k, dtype=torch.int64, device=self.rows.device)
-        _lib.check(lib.hmm_cosine_topk_keys(self.rows.data_ptr(), len(self), FEATURE_DIM, query.data_ptr(), k,
-                                            keys.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
-                   "hmm_cosine_topk_keys")
+        self._scan("keys", False, query, k, (keys,))
         return keys
 
     def search_segments_device(self, query: torch.Tensor, seg_offsets: torch.Tensor, k: int, prefilter: bool = False):
@@ -159,32 +242,13 @@ class FeatureStore:
         return self._search_segments_packed(query, seg_offsets, k, prefilter)[1:]
 
     def _search_segments_packed(self, query: torch.Tensor, seg_offsets: torch.Tensor, k: int, prefilter: bool = False):
-        """search_segments_device, returning (packed, idx, sims, counts): the three outputs are views of `packed`."""
-        lib = _lib.load()
-        dev = self.rows.device
-        E = seg_offsets.numel() - 1
-        need = lib.hmm_cosine_topk_segmented_workspace_bytes(len(self), E, k)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        # the three outputs are views of ONE buffer (idx | sims | counts), so that a caller who wants them on the host reads them back
-        # with one copy (top_k_per_event)
-        packed = torch.empty(E * k * 12 + E * 4, dtype=torch.uint8, device=dev)
-        idx = packed[: E * k * 8].view(torch.int64).view(E, k)
-        sims = packed[E * k * 8: E * k * 12].view(torch.float32).view(E, k)
-        counts = packed[E * k * 12:].view(torch.int32)
-        if prefilter and len(self) > 0:
-            self.build_shadow()
-            _lib.check(lib.hmm_cosine_topk_segmented_prefilter(self.rows.data_ptr(), self._shadow.data_ptr(), len(self), FEATURE_DIM,
-                                                               query.data_ptr(), seg_offsets.data_ptr(), E, k, idx.data_ptr(),
-                                                               sims.data_ptr(), counts.data_ptr(), self._ws.data_ptr(),
-                                                               self._ws.numel(), _lib.stream_ptr()),
-                       "hmm_cosine_topk_segmented_prefilter")
-            return packed, idx, sims, counts
-        _lib.check(lib.hmm_cosine_topk_segmented(self.rows.data_ptr(), len(self), FEATURE_DIM, query.data_ptr(),
-                                                 seg_offsets.data_ptr(), E, k, idx.data_ptr(), sims.data_ptr(),
-                                                 counts.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
-                                                 _lib.stream_ptr()), "hmm_cosine_topk_segmented")
-        return packed, idx, sims, counts
+        """search_segments_device, returning (packed, idx, sims, counts): the three outputs are views of ONE buffer
+        (_hits_layout), so that a caller who wants them on the host reads them back with one copy (top_k_per_event)."""
+        layout = _hits_layout(seg_offsets.numel() - 1, k)
+        packed = torch.empty(layout.nbytes, dtype=torch.uint8, device=self.rows.device)
+        outputs = layout.device_views(packed)
+        self._scan("segmented", bool(prefilter and len(self) > 0), query, k, outputs, seg_offsets=seg_offsets)
+        return (packed, *outputs)
 
     def search_segments_multi_device(self, queries, seg_offsets: torch.Tensor, k: int, prefilter: bool = False,
                                      stats: torch.Tensor = None):
@@ -200,45 +264,19 @@ class FeatureStore:
     def _search_segments_multi_packed(self, queries, seg_offsets: torch.Tensor, k: int, prefilter: bool = False,
                                       stats: torch.Tensor = None):
         """search_segments_multi_device, returning (packed, idx, sims, counts): the three outputs are views of `packed`."""
-        dev = self.rows.device
-        q = queries if isinstance(queries, torch.Tensor) else torch.from_numpy(np.asarray(queries))
-        if q.dim() != 2 or q.shape[1] != FEATURE_DIM:
-            raise ValueError(f"queries must be (Q,{FEATURE_DIM}), got {tuple(q.shape)}")
-        q = q.detach().to(device=dev, dtype=torch.float32).contiguous()
+        q = _queries_2d(queries, self.rows.device)
         Q, E, k = q.shape[0], seg_offsets.numel() - 1, int(k)
-        if Q == 0:
-            raise ValueError("no queries")
         if k < 1:
             raise ValueError("k must be >= 1")
-        packed = torch.empty(Q * E * (k * 12 + 4), dtype=torch.uint8, device=dev)      # idx | sims | counts, as one read-back
-        idx = packed[: Q * E * k * 8].view(torch.int64).view(Q, E, k)
-        sims = packed[Q * E * k * 8: Q * E * k * 12].view(torch.float32).view(Q, E, k)
-        counts = packed[Q * E * k * 12:].view(torch.int32).view(Q, E)
-        if E == 0:
-            return packed, idx, sims, counts
-        if len(self) == 0:                                       # events without a row: nothing to scan, the padding is the answer
+        layout = _hits_layout(Q, E, k)
+        packed = torch.empty(layout.nbytes, dtype=torch.uint8, device=self.rows.device)
+        idx, sims, counts = layout.device_views(packed)
+        if E > 0 and len(self) == 0:                             # events without a row: nothing to scan, the padding is the answer
             idx.fill_(-1)
             sims.zero_()
             counts.zero_()
-            return packed, idx, sims, counts
-        lib = _lib.load()
-        if prefilter:
-            self.build_shadow()
-            need = lib.hmm_cosine_topk_segmented_multi_prefilter_workspace_bytes(len(self), E, Q, k)
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-            _lib.check(lib.hmm_cosine_topk_segmented_multi_prefilter(
-                self.rows.data_ptr(), self._shadow.data_ptr(), len(self), FEATURE_DIM, q.data_ptr(), Q, seg_offsets.data_ptr(), E, k,
-                idx.data_ptr(), sims.data_ptr(), counts.data_ptr(), stats.data_ptr() if stats is not None else None,
-                self._ws.data_ptr(), self._ws.numel(), _lib.stream_ptr()), "hmm_cosine_topk_segmented_multi_prefilter")
-            return packed, idx, sims, counts
-        need = lib.hmm_cosine_topk_segmented_multi_workspace_bytes(len(self), E, Q, k)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        _lib.check(lib.hmm_cosine_topk_segmented_multi(self.rows.data_ptr(), len(self), FEATURE_DIM, q.data_ptr(), Q,
-                                                       seg_offsets.data_ptr(), E, k, idx.data_ptr(), sims.data_ptr(),
-                                                       counts.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
-                                                       _lib.stream_ptr()), "hmm_cosine_topk_segmented_multi")
+        elif E > 0:
+            self._scan("segmented_multi", bool(prefilter), q, k, (idx, sims, counts), Q=Q, seg_offsets=seg_offsets, stats=stats)
         return packed, idx, sims, counts
 
     def search_multi_device(self, queries: torch.Tensor, k: int, prefilter: bool = None, stats: torch.Tensor = None):
@@ -248,36 +286,13 @@ class FeatureStore:
         (hmm_cosine_topk_multi_prefilter).  ``None`` is the exact pass even on a store built with ``shadow=True``: the shadow
         route has not been timed against it yet, and the results are the same either way; ``stats``: optional int32 (Q,2) CUDA tensor receiving per
         question (candidates re-scored, saturated lists), -1 / -1 when the exact function was the whole call."""
-        if queries.dim() != 2 or queries.shape[1] != FEATURE_DIM:
-            raise ValueError(f"queries must be (Q,{FEATURE_DIM}), got {tuple(queries.shape)}")
-        queries = queries.to(device=self.rows.device, dtype=torch.float32).contiguous()
-        nq, n = queries.shape[0], len(self)
-        if nq == 0:
-            raise ValueError("no queries")
-        lib = _lib.load()
-        if prefilter is None:                                   # not self.use_shadow until tools/multi_prefilter_probe.py has placed the limits
-            prefilter = False
-        idx = torch.empty(nq, k, dtype=torch.int64, device=self.rows.device)
-        sims = torch.empty(nq, k, dtype=torch.float32, device=self.rows.device)
-        n_out = torch.empty(nq, dtype=torch.int32, device=self.rows.device)
-        if prefilter and n > 0:
-            self.build_shadow()
-            need = lib.hmm_cosine_topk_multi_prefilter_workspace_bytes(n, nq, k)
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=self.rows.device)
-            _lib.check(lib.hmm_cosine_topk_multi_prefilter(
-                self.rows.data_ptr(), self._shadow.data_ptr(), n, FEATURE_DIM, queries.data_ptr(), nq, k, idx.data_ptr(),
-                sims.data_ptr(), n_out.data_ptr(), stats.data_ptr() if stats is not None else None, self._ws.data_ptr(),
-                self._ws.numel(), _lib.stream_ptr()), "hmm_cosine_topk_multi_prefilter")
-            kk = min(k, n)
-            return idx[:, :kk], sims[:, :kk]
-        need = lib.hmm_cosine_topk_multi_workspace_bytes(n, nq, k)
-        if self._ws is None or self._ws.numel() < need:      # kept between calls, like the single-query workspace
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.rows.device)
-        ws = self._ws
-        _lib.check(lib.hmm_cosine_topk_multi(self.rows.data_ptr(), n, FEATURE_DIM, queries.data_ptr(), nq, k,
-                                                   idx.data_ptr(), sims.data_ptr(), n_out.data_ptr(), ws.data_ptr(),
-                                                   ws.numel(), _lib.stream_ptr()), "hmm_cosine_topk_multi")
+        queries = _queries_2d(queries, self.rows.device)
+        nq, n, dev = queries.shape[0], len(self), self.rows.device
+        idx = torch.empty(nq, k, dtype=torch.int64, device=dev)
+        sims = torch.empty(nq, k, dtype=torch.float32, device=dev)
+        n_out = torch.empty(nq, dtype=torch.int32, device=dev)
+        # prefilter None: not self.use_shadow until tools/multi_prefilter_probe.py has placed the limits
+        self._scan("multi", bool(prefilter and n > 0), queries, k, (idx, sims, n_out), Q=nq, stats=stats)
         kk = min(k, n)
         return idx[:, :kk], sims[:, :kk]
 
@@ -433,37 +448,41 @@ def top_k_cosine_similarity(
     return idx.astype(np.int64, copy=False), sims.astype(out_dtype, copy=False)
 
 
+def _index_of(i, E: int) -> int:
+    """Event index ``i`` (negative ones count from the end) as 0 <= j < E."""
+    j = int(i)
+    if j != i or not -E <= j < E:
+        raise IndexError(f"event index {i!r} out of range for {E} events")
+    return j + E if j < 0 else j
+
+
 class EventStore(FeatureStore):
     """All events' feature matrices of one modality concatenated in HBM, with their row offsets: what
     ``QARecallSystem._find_relevant_*_segments`` iterates over (hippocampal_memory.py:3143, :3294)."""
 
     def __init__(self, event_features, device=None):
         mats = [np.ascontiguousarray(np.asarray(f).reshape(-1, FEATURE_DIM), dtype=np.float32) for f in event_features]
-        self.lengths = [m.shape[0] for m in mats]
-        rows = np.concatenate(mats, axis=0) if mats and sum(self.lengths) else np.zeros((0, FEATURE_DIM), np.float32)
-        dev = device or _lib.require_gpu()
-        if rows.shape[0] == 0:
-            self.source_dtype = np.dtype(np.float32)
-            self.rows = torch.zeros(0, FEATURE_DIM, dtype=torch.float32, device=dev)
-            self._ws = None
-        else:
-            super().__init__(rows, dev)
-        self.offsets = torch.tensor(np.concatenate([[0], np.cumsum(self.lengths)]), dtype=torch.int64, device=dev)
+        lengths = [m.shape[0] for m in mats]
+        super().__init__(np.concatenate(mats, axis=0) if sum(lengths) else np.zeros((0, FEATURE_DIM), np.float32), device)
+        self._set_events(lengths)
 
     @classmethod
     def from_device_rows(cls, rows: torch.Tensor, lengths) -> "EventStore":
         """An EventStore over a (N,1024) fp32 matrix that is already resident (events = consecutive row ranges of the
         given lengths); nothing is copied."""
-        self = cls.__new__(cls)
         if rows.dim() != 2 or rows.shape[1] != FEATURE_DIM or rows.dtype != torch.float32 or not rows.is_contiguous():
             raise ValueError("rows must be a contiguous (N,1024) fp32 tensor")
-        self.lengths = [int(n) for n in lengths]
-        if sum(self.lengths) != rows.shape[0]:
-            raise ValueError(f"event lengths sum to {sum(self.lengths)}, store has {rows.shape[0]} rows")
-        self.source_dtype = np.dtype(np.float32)
-        self.rows, self._ws, self._ws_key = rows, None, None
-        self.offsets = torch.tensor(np.concatenate([[0], np.cumsum(self.lengths)]), dtype=torch.int64, device=rows.device)
+        lengths = [int(n) for n in lengths]
+        if sum(lengths) != rows.shape[0]:
+            raise ValueError(f"event lengths sum to {sum(lengths)}, store has {rows.shape[0]} rows")
+        self = cls.__new__(cls)
+        self._init_state(rows, np.dtype(np.float32))
+        self._set_events(lengths)
         return self
+
+    def _set_events(self, lengths):
+        self.lengths = lengths
+        self.offsets = torch.tensor(np.concatenate([[0], np.cumsum(lengths)]), dtype=torch.int64, device=self.rows.device)
 
     def top_hits(self, query, k: int = 5, keep: int = 5, prefilter: bool = False):
         """The caller's whole step in one go (hippocampal_memory.py:3143-3153 + :3275-3277): top-k per event, then every hit of
@@ -485,19 +504,14 @@ class EventStore(FeatureStore):
             flat_idx, flat_sims = idx.reshape(-1)[order], sims.reshape(-1)[order]
             hits = torch.stack([(order // idx.shape[1]).double(), flat_idx.double(), flat_sims.double()]).cpu().numpy()
             return [(int(e), int(r), float(np.float32(v))) for e, r, v in zip(hits[0], hits[1], hits[2])]
-        # one launch ranks the (E, k) hits (hmm_rank_segment_hits), one copy brings the `keep` best back: event | row | sim | count
-        lib = _lib.load()
-        packed = torch.empty(keep * 20 + 4, dtype=torch.uint8, device=idx.device)
-        ev = packed[: keep * 8].view(torch.int64)
-        row = packed[keep * 8: keep * 16].view(torch.int64)
-        val = packed[keep * 16: keep * 20].view(torch.float32)
-        n_out = packed[keep * 20:].view(torch.int32)
-        _lib.check(lib.hmm_rank_segment_hits(idx.data_ptr(), sims.data_ptr(), counts.data_ptr(), E, idx.shape[1], keep, ev.data_ptr(),
-                                             row.data_ptr(), val.data_ptr(), n_out.data_ptr(), _lib.stream_ptr()), "hmm_rank_segment_hits")
-        raw = packed.cpu().numpy()
-        n = int(raw[keep * 20:].view(np.int32)[0])
-        ev_h, row_h, val_h = raw[: keep * 8].view(np.int64), raw[keep * 8: keep * 16].view(np.int64), raw[keep * 16: keep * 20].view(np.float32)
-        return [(int(ev_h[t]), int(row_h[t]), float(val_h[t])) for t in range(n)]
+        # one launch ranks the (E, k) hits (hmm_rank_segment_hits), one copy brings the `keep` best back (_ranking_layout)
+        layout = _ranking_layout(keep)
+        packed = torch.empty(layout.nbytes, dtype=torch.uint8, device=idx.device)
+        _lib.check(_lib.load().hmm_rank_segment_hits(idx.data_ptr(), sims.data_ptr(), counts.data_ptr(), E, idx.shape[1], keep,
+                                                     *[t.data_ptr() for t in layout.device_views(packed)], _lib.stream_ptr()),
+                   "hmm_rank_segment_hits")
+        ev_h, row_h, val_h, n = layout.host_views(packed.cpu().numpy())
+        return [(int(ev_h[t]), int(row_h[t]), float(val_h[t])) for t in range(int(n[0]))]
 
     def top_k_per_event(self, query, k: int = 5, prefilter: bool = False):
         """[(indices int64[k_e], sims float32[k_e]) for every event], each exactly what
@@ -508,28 +522,18 @@ class EventStore(FeatureStore):
         if E == 0:
             return []
         # one copy of the packed (idx | sims | counts) buffer into pinned memory instead of three synchronising .cpu() calls
-        host = self._readback_buffer(packed.numel())
-        host.copy_(packed, non_blocking=True)
-        torch.cuda.current_stream(packed.device).synchronize()
-        raw = host.numpy()
-        idx_h = raw[: E * k * 8].view(np.int64).reshape(E, k).copy()
-        sims_h = raw[E * k * 8: E * k * 12].view(np.float32).reshape(E, k).copy()
-        counts_h = raw[E * k * 12:].view(np.int32)
+        idx_h, sims_h, counts_h = _hits_layout(E, k).host_views(self._read_back(packed))
+        idx_h, sims_h = idx_h.copy(), sims_h.copy()
         if int(counts_h.min()) == k:                             # every event has k rows: plain row views, no slicing
             return list(zip(idx_h, sims_h))
         return [(idx_h[e, :counts_h[e]], sims_h[e, :counts_h[e]]) for e in range(E)]
 
-    def _queries_2d(self, queries):
-        q = queries if isinstance(queries, torch.Tensor) else torch.from_numpy(np.asarray(queries))
-        if q.dim() != 2 or q.shape[1] != FEATURE_DIM:
-            raise ValueError(f"queries must be (Q,{FEATURE_DIM}), got {tuple(q.shape)}")
-        if q.shape[0] == 0:
-            raise ValueError("no queries")
-        return q
-
     def _read_back(self, packed: torch.Tensor) -> np.ndarray:
         """One copy of a packed device buffer into pinned memory; the bytes are valid until the next read-back."""
-        host = self._readback_buffer(packed.numel())
+        nbytes = packed.numel()
+        if self._pinned is None or self._pinned.numel() < nbytes:
+            self._pinned = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, pin_memory=True)
+        host = self._pinned[:nbytes]
         host.copy_(packed, non_blocking=True)
         torch.cuda.current_stream(packed.device).synchronize()
         return host.numpy()
@@ -538,15 +542,13 @@ class EventStore(FeatureStore):
         """``top_k_per_event`` for a batch of questions: per query the list that ``top_k_per_event(query, k)`` returns, from one
         pass over the store per 16 questions and one read-back.  ``prefilter``: through the bf16 shadow, the same results
         (``search_segments_multi_device``)."""
-        q = self._queries_2d(queries)
+        q = _queries_2d(queries)
         Q, E, k = q.shape[0], len(self.lengths), int(k)
         if E == 0 or len(self) == 0:
             return [[(np.zeros(0, np.int64), np.zeros(0, np.float32)) for _ in range(E)] for _ in range(Q)]
         packed = self._search_segments_multi_packed(q, self.offsets, k, prefilter)[0]
-        raw = self._read_back(packed)
-        idx_h = raw[: Q * E * k * 8].view(np.int64).reshape(Q, E, k).copy()
-        sims_h = raw[Q * E * k * 8: Q * E * k * 12].view(np.float32).reshape(Q, E, k).copy()
-        counts_h = raw[Q * E * k * 12:].view(np.int32).reshape(Q, E)[0].copy()     # min(k, n_e): the same for every query
+        idx_h, sims_h, counts_h = _hits_layout(Q, E, k).host_views(self._read_back(packed))
+        idx_h, sims_h, counts_h = idx_h.copy(), sims_h.copy(), counts_h[0].copy()      # counts = min(k, n_e): the same for every query
         if int(counts_h.min()) == k:
             return [list(zip(idx_h[qi], sims_h[qi])) for qi in range(Q)]
         return [[(idx_h[qi, e, :counts_h[e]], sims_h[qi, e, :counts_h[e]]) for e in range(E)] for qi in range(Q)]
@@ -556,34 +558,20 @@ class EventStore(FeatureStore):
         store per 16 questions, one ranking launch for all of them (hmm_rank_segment_hits_multi), one read-back of Q x `keep`
         hits.  keep > 64 is served by ``top_hits`` per query.  ``prefilter``: the pass streams the bf16 shadow, the same results
         (``search_segments_multi_device``)."""
-        q = self._queries_2d(queries)
+        q = _queries_2d(queries)
         Q, E, k, keep = q.shape[0], len(self.lengths), int(k), int(keep)
         if E == 0 or len(self) == 0 or keep < 1:
             return [[] for _ in range(Q)]
         if keep > 64:
             return [self.top_hits(q[qi], k, keep, prefilter) for qi in range(Q)]
         idx, sims, counts = self.search_segments_multi_device(q, self.offsets, k, prefilter)
-        lib = _lib.load()
-        packed = torch.empty(Q * (keep * 20 + 4), dtype=torch.uint8, device=idx.device)      # event | row | sim | count
-        ev = packed[: Q * keep * 8].view(torch.int64)
-        row = packed[Q * keep * 8: Q * keep * 16].view(torch.int64)
-        val = packed[Q * keep * 16: Q * keep * 20].view(torch.float32)
-        n_out = packed[Q * keep * 20:].view(torch.int32)
-        _lib.check(lib.hmm_rank_segment_hits_multi(idx.data_ptr(), sims.data_ptr(), counts.data_ptr(), Q, E, k, keep, ev.data_ptr(),
-                                                   row.data_ptr(), val.data_ptr(), n_out.data_ptr(), _lib.stream_ptr()),
+        layout = _ranking_layout(Q, keep)
+        packed = torch.empty(layout.nbytes, dtype=torch.uint8, device=idx.device)
+        _lib.check(_lib.load().hmm_rank_segment_hits_multi(idx.data_ptr(), sims.data_ptr(), counts.data_ptr(), Q, E, k, keep,
+                                                           *[t.data_ptr() for t in layout.device_views(packed)], _lib.stream_ptr()),
                    "hmm_rank_segment_hits_multi")
-        raw = self._read_back(packed)
-        ev_h = raw[: Q * keep * 8].view(np.int64).reshape(Q, keep)
-        row_h = raw[Q * keep * 8: Q * keep * 16].view(np.int64).reshape(Q, keep)
-        val_h = raw[Q * keep * 16: Q * keep * 20].view(np.float32).reshape(Q, keep)
-        n_h = raw[Q * keep * 20:].view(np.int32)
+        ev_h, row_h, val_h, n_h = layout.host_views(self._read_back(packed))
         return [[(int(ev_h[qi, t]), int(row_h[qi, t]), float(val_h[qi, t])) for t in range(int(n_h[qi]))] for qi in range(Q)]
-
-    def _readback_buffer(self, nbytes: int) -> torch.Tensor:
-        buf = getattr(self, "_pinned", None)
-        if buf is None or buf.numel() < nbytes:
-            buf = self._pinned = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, pin_memory=True)
-        return buf[:nbytes]
 
     # ---- a store that grows: append, replace and drop events on the device ----------------------------------------------------
     # The constructor and from_device_rows leave `rows` as they always did (an exact-size upload, or the caller's tensor).  The
@@ -598,45 +586,7 @@ class EventStore(FeatureStore):
     @property
     def capacity(self) -> int:
         """Rows the store holds without moving (its row count while it still aliases the tensor it was built from)."""
-        buf = getattr(self, "_buf", None)
-        return len(self) if buf is None else buf.shape[0]
-
-    def _rows_version(self) -> int:
-        try:
-            return self.rows._version
-        except (RuntimeError, AttributeError):       # an inference tensor tracks no version (see FeatureStore.build_shadow)
-            return 0
-
-    def _shadow_is_current(self) -> bool:
-        """True when a shadow exists and matches the rows.  A stale one (the rows were edited through torch since) is dropped:
-        the next prefiltered search rebuilds it whole, as it would have anyway."""
-        if getattr(self, "_shadow", None) is None:
-            return False
-        version = self._rows_version()
-        if getattr(self, "_shadow_version", version) != version:
-            self._shadow = None
-            return False
-        return True
-
-    def build_shadow(self, force: bool = False):
-        """FeatureStore.build_shadow; on a store that owns its buffers the shadow is built into the capacity-sized buffer, where
-        later appends keep it current row by row (an append never rebuilds it).  The ingest and the gather write rows behind
-        torch's back AND their shadow rows with them, so the version the shadow was built at stays the one it is checked
-        against; edits of ``rows`` made through torch still bump it and cause a rebuild."""
-        buf = getattr(self, "_buf", None)
-        if buf is None:
-            return super().build_shadow(force)
-        version = self._rows_version()
-        if force or getattr(self, "_shadow", None) is None or getattr(self, "_shadow_version", version) != version:
-            n = len(self)
-            if getattr(self, "_shadow_buf", None) is None or self._shadow_buf.numel() != buf.shape[0] * 2048:
-                self._shadow_buf = torch.empty(buf.shape[0] * 2048, dtype=torch.uint8, device=buf.device)
-            if n > 0:
-                _lib.check(_lib.load().hmm_shadow_store_build(buf.data_ptr(), n, FEATURE_DIM, self._shadow_buf.data_ptr(), n * 2048,
-                                                              _lib.stream_ptr()), "hmm_shadow_store_build")
-            self._shadow = self._shadow_buf[: n * 2048]
-            self._shadow_version = version
-        return self
+        return len(self) if self._buf is None else self._buf.shape[0]
 
     def _set_buffers(self, buf: torch.Tensor, shadow_buf, n: int, shadow: bool):
         self._buf, self._shadow_buf = buf, shadow_buf
@@ -694,8 +644,7 @@ class EventStore(FeatureStore):
         if t.dim() != 2 or t.shape[1] != FEATURE_DIM:
             raise ValueError(f"event features must be (n,{FEATURE_DIM}) or ({FEATURE_DIM},), got {tuple(t.shape)}")
         t = t.to(self.rows.device).contiguous()
-        buf = getattr(self, "_buf", None)
-        for mine in (self.rows if buf is None else buf, getattr(self, "_shadow_buf", None)):
+        for mine in (self.rows if self._buf is None else self._buf, self._shadow_buf):
             if mine is not None and mine.numel() > 0:
                 a0, b0 = t.data_ptr(), mine.data_ptr()
                 if a0 < b0 + mine.numel() * mine.element_size() and b0 < a0 + t.numel() * t.element_size():
@@ -738,7 +687,7 @@ class EventStore(FeatureStore):
         n = len(self)
         needed = n + sum(s.shape[0] for s in srcs)
         shadow = self._shadow_is_current()
-        if getattr(self, "_buf", None) is None or needed > self._buf.shape[0]:
+        if self._buf is None or needed > self._buf.shape[0]:
             self._move_to(self._grown(needed), shadow)
         at = n
         for s in srcs:
@@ -754,7 +703,7 @@ class EventStore(FeatureStore):
         of new_lengths[j] rows (-1)."""
         needed = int(sum(new_lengths))
         shadow = self._shadow_is_current()
-        owned = getattr(self, "_buf", None) is not None
+        owned = self._buf is not None
         capacity = max(self.capacity, 1) if needed <= self.capacity else self._grown(needed)
         offsets, seg = self._upload_tables(new_lengths, src_segment)
         copies = any(s >= 0 and n > 0 for s, n in zip(src_segment, new_lengths))
@@ -779,10 +728,7 @@ class EventStore(FeatureStore):
         E = len(self.lengths)
         drop = set()
         for i in indices:
-            j = int(i)
-            if j != i or not -E <= j < E:
-                raise IndexError(f"event index {i!r} out of range for {E} events")
-            j += E if j < 0 else 0
+            j = _index_of(i, E)
             if j in drop:
                 raise ValueError(f"event {j} is named twice")
             drop.add(j)
@@ -796,10 +742,7 @@ class EventStore(FeatureStore):
         """Event ``i`` gets new rows, of any length, and keeps its index: a gather with a hole at ``i`` (out of place, transient
         2 x memory as in ``remove_events``), then an ingest into the hole."""
         E = len(self.lengths)
-        j = int(i)
-        if j != i or not -E <= j < E:
-            raise IndexError(f"event index {i!r} out of range for {E} events")
-        j += E if j < 0 else 0
+        j = _index_of(i, E)
         src = self._source_rows(features)
         lengths = list(self.lengths)
         lengths[j] = int(src.shape[0])

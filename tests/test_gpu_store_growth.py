@@ -467,3 +467,64 @@ def test_refresh_event_store_follows_the_index(tmp_path):
     assert audio.lengths == [2, 0, 0, 0, 0]
     save(7, {"vision": _rows(2, 99), "audio": _rows(8, 90)})
     assert es.refresh_event_store(audio, audio_ids, base, modality="audio") == list(index) and audio.lengths == [2, 0, 0, 0, 0, 8]
+
+
+# ---- one scratch buffer for every scan route ----------------------------------------------------------------------------------
+def _snapshot(out):
+    """A result as bytes on the host: tensors and arrays as (dtype, shape, bytes), lists and tuples element by element."""
+    if isinstance(out, torch.Tensor):
+        return (str(out.dtype), tuple(out.shape), _bytes(out).cpu().numpy().tobytes())
+    if isinstance(out, np.ndarray):
+        return (str(out.dtype), out.shape, out.tobytes())
+    if isinstance(out, (list, tuple)):
+        return [_snapshot(o) for o in out]
+    return out
+
+
+def test_every_route_shares_one_scratch_and_answers_as_a_fresh_store_does():
+    """The scan routes keep ONE workspace per store, grown when a route needs more and otherwise handed on as the last route left
+    it.  16 640 rows (the smallest store on which the flat shadow route runs its own kernels: n >= 4 x 4096), 8 events with an
+    empty one among them and 2080 rows on average (the segmented shadow routes run their own kernels from 128), 17 questions (two
+    passes of the batched routes), k = 5: every route and every read-back method, smallest workspace first, then largest first on
+    the same store, then largest first on a store whose scratch starts empty -- each result against the same call on a store that
+    has made no other call, byte for byte."""
+    from hippomm_amd.vector_ops import EventStore
+    lengths = [3000, 0, 129, 2511, 4096, 1, 4903, 2000]
+    assert sum(lengths) == 130 * 128 and len(lengths) == 8
+    rng = np.random.default_rng(77)
+    rows = torch.from_numpy(rng.standard_normal((sum(lengths), D), dtype=np.float32)).to(DEV)
+    q = torch.from_numpy(rng.standard_normal(D, dtype=np.float32)).to(DEV)
+    qs = torch.from_numpy(rng.standard_normal((17, D), dtype=np.float32)).to(DEV)
+
+    def store():
+        return EventStore.from_device_rows(rows, lengths).build_shadow()
+
+    calls = [lambda s: s.search_device(q, 5),
+             lambda s: s.search_prefiltered_device(q, 5),
+             lambda s: s.search_keys_device(q, 5),
+             lambda s: s.search_segments_device(q, s.offsets, 5),
+             lambda s: s.search_segments_device(q, s.offsets, 5, prefilter=True),
+             lambda s: s.top_hits(q, 5, 5),
+             lambda s: s.top_hits(q, 5, 5, prefilter=True),
+             lambda s: s.top_k_per_event(q, 5),
+             lambda s: s.top_k_per_event(q, 5, prefilter=True),
+             lambda s: s.search_multi_device(qs, 5),
+             lambda s: s.search_multi_device(qs, 5, prefilter=True),
+             lambda s: s.search_segments_multi_device(qs, s.offsets, 5),
+             lambda s: s.search_segments_multi_device(qs, s.offsets, 5, prefilter=True),
+             lambda s: s.top_hits_multi(qs, 5, 5),
+             lambda s: s.top_hits_multi(qs, 5, 5, prefilter=True),
+             lambda s: s.top_k_per_event_multi(qs, 5),
+             lambda s: s.top_k_per_event_multi(qs, 5, prefilter=True)]
+    want = [_snapshot(call(store())) for call in calls]
+    stats = torch.zeros(2, dtype=torch.int32, device=DEV)
+    store().search_prefiltered_device(q, 5, stats)
+    assert stats[0].item() >= 0                                               # the shadow route's own kernels, not the exact scan behind it
+    order = list(range(len(calls)))
+    one, other = store(), store()
+    for name, s, sequence in (("ascending", one, order), ("descending on the same store", one, order[::-1]),
+                              ("descending on a new store", other, order[::-1])):
+        for i in sequence:
+            assert _snapshot(calls[i](s)) == want[i], (name, i)
+    per_event = one.top_k_per_event(q, 5)
+    assert [len(idx) for idx, _ in per_event] == [min(5, n) for n in lengths]  # the empty event and the one-row event among them
