@@ -104,6 +104,17 @@ _SIGNATURES = {
     "hmm_op_qkv_attention_bf16": (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, c_ptr]),
     "hmm_op_qkv_attention_audio_bf16": (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, c_ptr]),
     "hmm_op_attention_causal_bf16": (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr]),
+    "hmm_op_im2col_vision_bf16": (C.c_int, [c_ptr, c_ptr, C.c_int, c_ptr]),
+    "hmm_op_im2col_audio_bf16": (C.c_int, [c_ptr, c_ptr, C.c_int, c_ptr]),
+    "hmm_op_fold_conv3d_bf16": (C.c_int, [c_ptr, c_ptr, C.c_int, c_ptr]),
+    "hmm_op_assemble_tokens": (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, C.c_float, c_ptr, c_ptr, C.c_float, c_ptr,
+                                         C.c_int, C.c_int, C.c_int, c_ptr]),
+    "hmm_op_layernorm_strided_bf16": (C.c_int, [c_ptr, C.c_size_t, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_float, c_ptr]),
+    "hmm_op_gather_rows": (C.c_int, [c_ptr, C.c_size_t, c_ptr, C.c_int, C.c_int, c_ptr]),
+    "hmm_op_attention_cls_bf16": (C.c_int, [c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr, c_ptr]),
+    "hmm_op_embed_tokens": (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, c_ptr]),
+    "hmm_op_layernorm_eos_bf16": (C.c_int, [c_ptr, c_ptr, C.c_int, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_float, c_ptr]),
+    "hmm_op_l2norm_rows": (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, c_ptr, c_ptr]),
     "hmm_op_scan_topk_only": (C.c_int, [c_ptr, C.c_int64, c_ptr, C.c_int, c_ptr, c_ptr]),
     "hmm_op_scan_sims": (C.c_int, [c_ptr, C.c_int64, c_ptr, c_ptr, c_ptr]),
     "hmm_json_find_matrices": (C.c_int, [C.c_char_p, C.c_size_t, C.c_size_t, c_ptr, C.c_int, C.POINTER(C.c_int)]),

@@ -281,3 +281,16 @@ extern "C" int hmm_op_attention_causal_bf16(const uint16_t* qkv_dev, uint16_t* o
     return attention_bf16(reinterpret_cast<const bf16_t*>(qkv_dev), reinterpret_cast<bf16_t*>(out_dev), batch, tokens,
                           heads, head_dim, nullptr, nullptr, static_cast<hipStream_t>(stream), true);
 }
+
+// The last block's one-query attention on its own.  The launcher takes bias_k alone as "one more key"; here the pair goes together.
+extern "C" int hmm_op_attention_cls_bf16(const uint16_t* q_cls_dev, const uint16_t* kv_dev, uint16_t* out_dev, int batch, int tokens,
+                                         int heads, int head_dim, const float* bias_k_dev, const float* bias_v_dev,
+                                         hmm_stream_t stream) {
+    HMM_REQUIRE((bias_k_dev == nullptr) == (bias_v_dev == nullptr), HMM_E_INVALID, "attention_cls: bias_k and bias_v go together");
+    HMM_REQUIRE(batch >= 1 && tokens >= 1 && heads >= 1, HMM_E_INVALID, "attention_cls: bad shape (batch %d, tokens %d, heads %d)",
+                batch, tokens, heads);
+    HMM_REQUIRE(head_dim == 64 || head_dim == 80, HMM_E_INVALID, "attention_cls: unsupported head_dim %d", head_dim);
+    return attention_cls_bf16(reinterpret_cast<const bf16_t*>(q_cls_dev), reinterpret_cast<const bf16_t*>(kv_dev),
+                              reinterpret_cast<bf16_t*>(out_dev), batch, tokens, heads, head_dim, bias_k_dev, bias_v_dev,
+                              static_cast<hipStream_t>(stream));
+}

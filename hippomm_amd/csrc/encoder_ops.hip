@@ -204,7 +204,8 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(const float* __restric
             ss = fmaf(x[j].x, x[j].x, ss); ss = fmaf(x[j].y, x[j].y, ss);
             ss = fmaf(x[j].z, x[j].z, ss); ss = fmaf(x[j].w, x[j].w, ss);
         }
-        const float f = scale / fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
+        const float nrm = sqrtf(wave_sum(ss));
+        const float f = scale / (nrm < 1e-12f ? 1e-12f : nrm);   // not fmaxf: a NaN norm must stay NaN (torch's clamp_min), fmaxf would return the floor
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             acc[j].x = fmaf(x[j].x, f, acc[j].x); acc[j].y = fmaf(x[j].y, f, acc[j].y);
@@ -468,4 +469,80 @@ extern "C" int hmm_op_layernorm_reduce_bf16(float* x_dev, const float* part_dev,
     HMM_REQUIRE(x_dev && part_dev && bias_dev && gamma_dev && beta_dev && y_dev, HMM_E_INVALID, "layernorm_reduce: null pointer");
     return launch_layernorm_reduce_bf16(x_dev, part_dev, (size_t)rows * D, splits, bias_dev, gamma_dev, beta_dev,
                                         reinterpret_cast<bf16_t*>(y_dev), rows, D, eps, static_cast<hipStream_t>(stream));
+}
+
+// ---- the remaining stage kernels, each callable on its own (tests/test_gpu_stage_ops.py) ------------------------------
+// Thin wrappers: every refusal happens before the launch, the launchers above are unchanged.
+extern "C" int hmm_op_im2col_vision_bf16(const float* frames_dev, uint16_t* out_dev, int n_img, hmm_stream_t stream) {
+    HMM_REQUIRE(frames_dev && out_dev, HMM_E_INVALID, "im2col_vision: null pointer");
+    HMM_REQUIRE(n_img >= 1, HMM_E_INVALID, "im2col_vision: n_img must be positive, got %d", n_img);
+    return launch_im2col_vision(frames_dev, reinterpret_cast<bf16_t*>(out_dev), n_img, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int hmm_op_im2col_audio_bf16(const float* mels_dev, uint16_t* out_dev, int n_clip, hmm_stream_t stream) {
+    HMM_REQUIRE(mels_dev && out_dev, HMM_E_INVALID, "im2col_audio: null pointer");
+    HMM_REQUIRE(n_clip >= 1, HMM_E_INVALID, "im2col_audio: n_clip must be positive, got %d", n_clip);
+    return launch_im2col_audio(mels_dev, reinterpret_cast<bf16_t*>(out_dev), n_clip, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int hmm_op_fold_conv3d_bf16(const float* w_dev, uint16_t* dst_dev, int D, hmm_stream_t stream) {
+    HMM_REQUIRE(w_dev && dst_dev, HMM_E_INVALID, "fold_conv3d: null pointer");
+    HMM_REQUIRE(D >= 1, HMM_E_INVALID, "fold_conv3d: D must be positive, got %d", D);
+    return launch_fold_conv3d(w_dev, reinterpret_cast<bf16_t*>(dst_dev), D, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int hmm_op_assemble_tokens(const float* patches_dev, const float* cls_dev, const float* pos_dev,
+                                      const float* stem_gamma_dev, const float* stem_beta_dev, float stem_eps,
+                                      const float* pre_gamma_dev, const float* pre_beta_dev, float pre_eps,
+                                      float* x_dev, int n_img, int T, int D, hmm_stream_t stream) {
+    HMM_REQUIRE(patches_dev && cls_dev && pos_dev && x_dev, HMM_E_INVALID, "assemble: null pointer");
+    HMM_REQUIRE((stem_gamma_dev == nullptr) == (stem_beta_dev == nullptr), HMM_E_INVALID, "assemble: stem gamma and beta go together");
+    HMM_REQUIRE((pre_gamma_dev == nullptr) == (pre_beta_dev == nullptr), HMM_E_INVALID, "assemble: pre gamma and beta go together");
+    HMM_REQUIRE(n_img >= 1 && T >= 1, HMM_E_INVALID, "assemble: n_img and T must be positive, got %d and %d", n_img, T);
+    HMM_REQUIRE((int64_t)n_img * T <= INT32_MAX, HMM_E_INVALID, "assemble: %d x %d rows exceed the row index", n_img, T);
+    return launch_assemble_tokens(patches_dev, cls_dev, pos_dev, stem_gamma_dev, stem_beta_dev, stem_eps, pre_gamma_dev, pre_beta_dev,
+                                  pre_eps, x_dev, n_img, T, D, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int hmm_op_layernorm_strided_bf16(const float* x_dev, size_t in_stride, const float* gamma_dev, const float* beta_dev,
+                                             uint16_t* y_dev, int rows, int D, float eps, hmm_stream_t stream) {
+    HMM_REQUIRE(x_dev && gamma_dev && beta_dev && y_dev, HMM_E_INVALID, "layernorm_strided: null pointer");
+    HMM_REQUIRE(rows >= 1, HMM_E_INVALID, "layernorm_strided: rows must be positive, got %d", rows);
+    HMM_REQUIRE(D >= 1 && in_stride >= (size_t)D, HMM_E_INVALID, "layernorm_strided: in_stride %zu is below D = %d", in_stride, D);
+    HMM_REQUIRE(in_stride % 4 == 0, HMM_E_INVALID, "layernorm_strided: in_stride %zu is not a multiple of 4 floats", in_stride);
+    return launch_layernorm_bf16(x_dev, in_stride, gamma_dev, beta_dev, reinterpret_cast<bf16_t*>(y_dev), rows, D, eps,
+                                 static_cast<hipStream_t>(stream));
+}
+
+extern "C" int hmm_op_gather_rows(const void* src_dev, size_t src_row_stride_bytes, void* dst_dev, int n_rows, int row_bytes,
+                                  hmm_stream_t stream) {
+    HMM_REQUIRE(src_dev && dst_dev, HMM_E_INVALID, "gather_rows: null pointer");
+    HMM_REQUIRE(n_rows >= 1 && row_bytes >= 1, HMM_E_INVALID, "gather_rows: n_rows and row_bytes must be positive, got %d and %d", n_rows, row_bytes);
+    HMM_REQUIRE(row_bytes % 16 == 0, HMM_E_INVALID, "gather_rows: row_bytes %d is not a multiple of 16", row_bytes);
+    HMM_REQUIRE(src_row_stride_bytes >= (size_t)row_bytes, HMM_E_INVALID, "gather_rows: stride %zu is below row_bytes %d", src_row_stride_bytes, row_bytes);
+    HMM_REQUIRE(src_row_stride_bytes % 16 == 0, HMM_E_INVALID, "gather_rows: stride %zu is not a multiple of 16", src_row_stride_bytes);
+    return launch_gather_rows(src_dev, src_row_stride_bytes, dst_dev, n_rows, row_bytes, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int hmm_op_embed_tokens(const int64_t* ids_dev, const float* table_dev, const float* pos_dev, float* x_dev, int n_rows,
+                                   int T, int vocab, hmm_stream_t stream) {
+    HMM_REQUIRE(ids_dev && table_dev && pos_dev && x_dev, HMM_E_INVALID, "embed_tokens: null pointer");
+    HMM_REQUIRE(n_rows >= 1 && T >= 1 && vocab >= 1, HMM_E_INVALID, "embed_tokens: n_rows, T and vocab must be positive, got %d, %d and %d",
+                n_rows, T, vocab);
+    return launch_embed_tokens(ids_dev, table_dev, pos_dev, x_dev, n_rows, T, vocab, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int hmm_op_layernorm_eos_bf16(const float* x_dev, const int64_t* ids_dev, int T, const float* gamma_dev,
+                                         const float* beta_dev, uint16_t* y_dev, int batch, int D, float eps, hmm_stream_t stream) {
+    HMM_REQUIRE(x_dev && ids_dev && gamma_dev && beta_dev && y_dev, HMM_E_INVALID, "layernorm_eos: null pointer");
+    HMM_REQUIRE(batch >= 1 && T >= 1, HMM_E_INVALID, "layernorm_eos: batch and T must be positive, got %d and %d", batch, T);
+    return launch_layernorm_eos_bf16(x_dev, ids_dev, T, gamma_dev, beta_dev, reinterpret_cast<bf16_t*>(y_dev), batch, D, eps,
+                                     static_cast<hipStream_t>(stream));
+}
+
+extern "C" int hmm_op_l2norm_rows(const float* v_dev, float* out_dev, int n_out, int clips, const float* log_scale_dev,
+                                  hmm_stream_t stream) {
+    HMM_REQUIRE(v_dev && out_dev, HMM_E_INVALID, "l2norm_rows: null pointer");
+    HMM_REQUIRE(n_out >= 1 && clips >= 1, HMM_E_INVALID, "l2norm_rows: n_out and clips must be positive, got %d and %d", n_out, clips);
+    return launch_l2norm_rows(v_dev, out_dev, n_out, clips, log_scale_dev, static_cast<hipStream_t>(stream));
 }

@@ -527,8 +527,8 @@ int     hmm_jpeg_decode_coefs_device(const void* bitslots_dev, int n, size_t bit
 
 /* ------------------------------------------------------------------------------------------
  * Building blocks of the encoder, exported so that each kernel is parity-tested on its own
- * against a torch fp32 reference of the same op (tests/test_gpu_ops.py) and timed on its own
- * (bench.py roofline).  bf16 tensors are raw uint16 bit patterns in device memory.
+ * against a reference of the same op (GEMM, LayerNorm, attention core: tests/test_gpu_ops.py; every other
+ * stage: tests/test_gpu_stage_ops.py) and timed on its own (bench.py roofline).  bf16 tensors are raw uint16 bit patterns in device memory.
  * ---------------------------------------------------------------------------------------- */
 #define HMM_EPI_BIAS_BF16        0  /* C_bf16 = A W^T + bias                                  */
 #define HMM_EPI_BIAS_GELU_BF16   1  /* C_bf16 = gelu_erf(A W^T + bias)                        */
@@ -601,6 +601,56 @@ int hmm_op_qkv_attention_audio_bf16(const uint16_t* a_dev, const uint16_t* w_dev
 /* Causal variant (text tower): key j is visible to query i iff j <= i; no bias_kv. */
 int hmm_op_attention_causal_bf16(const uint16_t* qkv_dev, uint16_t* out_dev, int batch, int tokens,
                                  int heads, int head_dim, hmm_stream_t stream);
+
+/* ---- the tower stages that are neither a GEMM nor the attention core, each on its own (tests/test_gpu_stage_ops.py) ----
+ * Thin entry points over the launchers hmm_encoder_forward uses.  Every one refuses null required pointers and
+ * non-positive counts with HMM_E_INVALID before any launch.  All tensors are dense row-major unless a stride is named. */
+/* Vision im2col: frames_dev [n_img][3][224][224] fp32 -> out_dev [n_img*256][640] bf16; row = image*256 + py*16 + px (16 x 16
+ * patches of 14 x 14), column k = c*196 + dy*14 + dx = pixel (c, py*14 + dy, px*14 + dx); columns 588..639 are 0. */
+int hmm_op_im2col_vision_bf16(const float* frames_dev, uint16_t* out_dev, int n_img, hmm_stream_t stream);
+/* Audio im2col: mels_dev [n_clip][128][204] fp32 -> out_dev [n_clip*228][256] bf16; row = clip*228 + py*19 + px (py < 12,
+ * px < 19, stride 10), column k = dy*16 + dx = mel (py*10 + dy, px*10 + dx).  Mel rows >= 126 and columns >= 196 are not read. */
+int hmm_op_im2col_audio_bf16(const float* mels_dev, uint16_t* out_dev, int n_clip, hmm_stream_t stream);
+/* Conv3d weight fold: w_dev [D][3][2][14][14] fp32 -> dst_dev [D][640] bf16; column k = c*196 + dy*14 + dx holds
+ * bf16(w[d][c][0][dy][dx] + w[d][c][1][dy][dx]) (one fp32 add), columns 588..639 are 0. */
+int hmm_op_fold_conv3d_bf16(const float* w_dev, uint16_t* dst_dev, int D, hmm_stream_t stream);
+/* Token assembly: x_dev [n_img*T][D] fp32, row b*T + t = pre_ln((t == 0 ? cls : stem_ln(patches[b*(T-1) + t-1])) + pos[t]).
+ * patches_dev [n_img*(T-1)][D], cls_dev [D], pos_dev [T][D], the LayerNorm vectors [D], all fp32; D in {768, 1280}.  Either
+ * LayerNorm is skipped when its gamma AND beta are null; one of a pair null and the other set is refused. */
+int hmm_op_assemble_tokens(const float* patches_dev, const float* cls_dev, const float* pos_dev,
+                           const float* stem_gamma_dev, const float* stem_beta_dev, float stem_eps,
+                           const float* pre_gamma_dev, const float* pre_beta_dev, float pre_eps,
+                           float* x_dev, int n_img, int T, int D, hmm_stream_t stream);
+/* hmm_op_layernorm_bf16 on rows that lie in_stride FLOATS apart: y_bf16[r][D] = LayerNorm(x_dev[r*in_stride .. + D)) -- the
+ * form the fused path uses for token 0 of every image (in_stride = T*D).  Only the D floats of each row are read.
+ * in_stride >= D and a multiple of 4; D in {768, 1024, 1280}. */
+int hmm_op_layernorm_strided_bf16(const float* x_dev, size_t in_stride, const float* gamma_dev, const float* beta_dev,
+                                  uint16_t* y_dev, int rows, int D, float eps, hmm_stream_t stream);
+/* dst_dev[r][0, row_bytes) = src_dev[r*src_row_stride_bytes .. + row_bytes) for r < n_rows, in 16-byte pieces: row_bytes and
+ * the stride are multiples of 16, the stride >= row_bytes, both pointers 16-byte aligned.  Nothing past the last byte of the
+ * last gathered row is read. */
+int hmm_op_gather_rows(const void* src_dev, size_t src_row_stride_bytes, void* dst_dev, int n_rows, int row_bytes,
+                       hmm_stream_t stream);
+/* One-query attention of the last block: q_cls_dev [batch][D] bf16 (D = heads*head_dim), kv_dev [batch*tokens][2D] bf16 =
+ * [k | v], heads contiguous inside each half; out_dev [batch][D] bf16 = softmax(q k^T / sqrt(head_dim)) v per (sample, head).
+ * bias_k / bias_v ([D] fp32, rounded to bf16) append one key / value position and come together or not at all; at most 320
+ * keys including it; head_dim 64 or 80.  Scores, softmax and P.V are fp32 (P is not rounded); the output is rounded once. */
+int hmm_op_attention_cls_bf16(const uint16_t* q_cls_dev, const uint16_t* kv_dev, uint16_t* out_dev, int batch, int tokens,
+                              int heads, int head_dim, const float* bias_k_dev, const float* bias_v_dev,
+                              hmm_stream_t stream);
+/* Text embedding: x_dev [n_rows][1024] fp32, row r = table_dev[clamp(ids_dev[r], 0, vocab-1)] + pos_dev[r % T] (one fp32
+ * add); ids_dev [n_rows] int64, table_dev [vocab][1024], pos_dev [T][1024]. */
+int hmm_op_embed_tokens(const int64_t* ids_dev, const float* table_dev, const float* pos_dev, float* x_dev, int n_rows,
+                        int T, int vocab, hmm_stream_t stream);
+/* Text head: y_dev [batch][D] bf16, row b = LayerNorm(x_dev[b*T + e(b)]) with e(b) the FIRST position of the largest id in
+ * ids_dev[b][0, T) (int64); x_dev [batch*T][D] fp32.  Same bits as hmm_op_layernorm_bf16 on that row.  D in {768, 1024, 1280}. */
+int hmm_op_layernorm_eos_bf16(const float* x_dev, const int64_t* ids_dev, int T, const float* gamma_dev,
+                              const float* beta_dev, uint16_t* y_dev, int batch, int D, float eps, hmm_stream_t stream);
+/* Post-processing: out_dev [n_out][1024] fp32, row i = mean over s < clips of scale * v[i*clips + s] / max(||v[i*clips + s]||, 1e-12)
+ * (each clip normalised first, then the mean); v_dev [n_out*clips][1024] fp32; scale = min(exp(*log_scale_dev), 100), or 1 when
+ * log_scale_dev is null. */
+int hmm_op_l2norm_rows(const float* v_dev, float* out_dev, int n_out, int clips, const float* log_scale_dev,
+                       hmm_stream_t stream);
 
 /* Timing / test hooks of the scan (bench.py roofline, tests): the streaming kernel of hmm_cosine_topk alone --
  * scan_topk_kernel writing its per-block candidate keys (cand_keys_dev: 2048*k uint64) -- and the plain similarity

@@ -157,3 +157,30 @@ def test_towers_match_committed_fixture():
         # (the weight bytes are not compared: trunc-normal sampling differs in the last bit between host CPUs)
         got = HipTower(name, st, depth=spec.depth)(x)
         _check(got, torch.tensor(gold[name]["embeddings"]), scale=scale[name], what=f"{name} vs committed fixture")
+
+
+def _small_signal_cases():
+    import eps_oracle
+    return eps_oracle.SMALL_SIGNAL
+
+
+@pytest.mark.parametrize("label", _small_signal_cases())
+def test_layernorm_eps_literals_at_small_signal(label):
+    """encoder.hip passes every LayerNorm eps as a literal at the call site (stem 1e-5, all others 1e-6); with ordinary inputs
+    a wrong literal moves the embedding by a fraction of this file's tolerance.  These inputs (tests/eps_oracle.py) put rows of
+    variance near the eps in front of the named LayerNorms, so that the other eps of the code base at any one of them moves the
+    oracle by at least 4x the tolerance (pinned on the CPU: tests/test_cpu_stage_refs.py); the tower is held to the UNMODIFIED
+    oracle and the unchanged tolerance.  Sites covered: stem (audio), pre-LN (vision), norm_1 and norm_2 of the first and of the
+    last block and the head LayerNorm of all three towers.  The literals differ by regime, not by block (apart from the last
+    block's cls-row forms): the few-row regime (one frame, one segment, up to nine questions) reduces split-K slabs inside its
+    LayerNorms, everything larger runs the plain kernel.  Each case therefore runs once in either regime; within a regime the
+    batches, stream counts and fused / unfused forms are bit-equal to one another (tests/test_gpu_encoder_batch.py,
+    tests/test_gpu_memory_contract.py)."""
+    import eps_oracle
+    from hippomm_amd.encoder import HipTower
+    name, spec, st, x, sites = eps_oracle.small_signal_case(label)
+    want = ib.forward({name: x}, {name: st}, {name: spec})[name]
+    tower = HipTower(name, st, depth=spec.depth)
+    pick = torch.arange(10) % x.shape[0] if name == "text" else torch.arange(x.shape[0])       # ten questions: the large regime
+    for regime, rows in (("few rows", torch.arange(1)), ("large", pick)):
+        _check(tower(x[rows]), want[rows], scale=eps_oracle.TOL_SCALE[name], what=f"{label}, {regime} (eps sites {', '.join(sites)})")

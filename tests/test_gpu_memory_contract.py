@@ -714,6 +714,62 @@ class AttentionOp(Case):
         return {"out": out}
 
 
+class StageOp(Case):
+    """One of the tower-stage entry points (tests/test_gpu_stage_ops.py) on the inputs of one of that module's cases: every
+    buffer at its exact size.  For hmm_op_gather_rows and hmm_op_layernorm_strided_bf16 the source ends with the last byte of
+    the last row read, not at a whole stride."""
+    family = "op stage"
+
+    def __init__(self, entry, label, inputs, outs, args):
+        super().__init__()
+        self.entry, self.label, self.outs, self.args = entry, label, outs, args
+        self.inputs = {k: v.to(DEV) for k, v in inputs.items()}
+
+    def call(self, lib, p, ws, ws_bytes):
+        return getattr(lib, self.entry)(*self.args(p), None)
+
+    def shim(self):
+        bufs = {name: torch.empty(nb, dtype=torch.uint8, device=DEV) for name, nb in self.outs.items()}
+        p = {k: v.data_ptr() for k, v in {**self.inputs, **bufs}.items()}
+        assert self.call(_L()[1], p, None, 0) == 0
+        return bufs
+
+
+def _stage_ops():
+    import stage_cases as S
+    pick = lambda stage, label: next(c for c in S.cases(stage) if c.label == label)
+    iv, ia, fo, em = pick("im2col_vision", "n_img=1"), pick("im2col_audio", "n_clip=1"), pick("fold_conv3d", "D=5"), pick("embed_tokens", "batch=3")
+    ga, asm = pick("gather_rows", "row=2560,T=229,n=3"), pick("assemble_tokens", "both,T=229,D=1280,n_img=2")
+    eos, l2 = pick("layernorm_eos", "T=77,D=1024"), pick("l2norm_rows", "n_out=5,clips=3,scale=log20")
+    at = [pick("attention_cls", "B=3,T=229,H=12,dh=64,bias=True,scale=1.0"), pick("attention_cls", "B=2,T=257,H=16,dh=80,bias=False,scale=1.0")]
+    rows, T, D = 3, 5, 1280
+    xs = _rand((((rows - 1) * T + 1) * D,), 5)
+    ops = [
+        StageOp("hmm_op_im2col_vision_bf16", iv.label, {"frames": iv.frames}, {"out": 256 * 640 * 2}, lambda p: (p["frames"], p["out"], 1)),
+        StageOp("hmm_op_im2col_audio_bf16", ia.label, {"mels": torch.nan_to_num(ia.mels, nan=1.0)}, {"out": 228 * 256 * 2},
+                lambda p: (p["mels"], p["out"], 1)),
+        StageOp("hmm_op_fold_conv3d_bf16", fo.label, {"w": fo.w}, {"dst": 5 * 640 * 2}, lambda p: (p["w"], p["dst"], 5)),
+        StageOp("hmm_op_assemble_tokens", asm.label, {"patches": asm.patches, "cls": asm.cls, "pos": asm.pos, "sg": asm.stem[0], "sb": asm.stem[1],
+                                                      "pg": asm.pre[0], "pb": asm.pre[1]}, {"x": asm.n_img * asm.T * asm.D * 4},
+                lambda p: (p["patches"], p["cls"], p["pos"], p["sg"], p["sb"], 1e-5, p["pg"], p["pb"], 1e-6, p["x"], asm.n_img, asm.T, asm.D)),
+        StageOp("hmm_op_layernorm_strided_bf16", f"rows={rows},stride={T}x{D}", {"x": xs, "gamma": _rand((D,), 1), "beta": _rand((D,), 2)},
+                {"y": rows * D * 2}, lambda p: (p["x"], T * D, p["gamma"], p["beta"], p["y"], rows, D, 1e-6)),
+        StageOp("hmm_op_gather_rows", ga.label, {"src": ga.src}, {"dst": ga.n_rows * ga.row_bytes},
+                lambda p: (p["src"], ga.stride, p["dst"], ga.n_rows, ga.row_bytes)),
+        StageOp("hmm_op_embed_tokens", em.label, {"ids": em.ids, "table": em.table, "pos": em.pos}, {"x": em.n_rows * 1024 * 4},
+                lambda p: (p["ids"], p["table"], p["pos"], p["x"], em.n_rows, em.T, em.vocab)),
+        StageOp("hmm_op_layernorm_eos_bf16", eos.label, {"x": eos.x, "ids": eos.ids, "gamma": eos.gamma, "beta": eos.beta}, {"y": eos.B * eos.D * 2},
+                lambda p: (p["x"], p["ids"], eos.T, p["gamma"], p["beta"], p["y"], eos.B, eos.D, 1e-6)),
+        StageOp("hmm_op_l2norm_rows", l2.label, {"v": torch.nan_to_num(l2.v, nan=1.0), "log_scale": l2.log_scale}, {"out": l2.n_out * 1024 * 4},
+                lambda p: (p["v"], p["out"], l2.n_out, l2.clips, p["log_scale"])),
+    ]
+    for c in at:
+        ins = {"q": c.q, "kv": c.kv} | ({"bias_k": c.bk, "bias_v": c.bv} if c.bk is not None else {})
+        ops.append(StageOp("hmm_op_attention_cls_bf16", c.label, ins, {"out": c.B * c.H * c.dh * 2},
+                           lambda p, c=c: (p["q"], p["kv"], p["out"], c.B, c.T, c.H, c.dh, p.get("bias_k"), p.get("bias_v"))))
+    return ops
+
+
 # =====================================================================================================================
 # the case table
 # =====================================================================================================================
@@ -756,6 +812,7 @@ CASES = {
                     [Jpeg(1280, 720, 2, 1), Jpeg(1280, 720, 2, 6, (275, 0, 730, 720)), Jpeg(1280, 720, 1, 1, (9, 7, 1263, 705))],
     "ops": lambda: [LayerNormOp(1, 768), LayerNormOp(77, 1024), LayerNormOp(257, 1280), AttentionOp(1, 257, 16, 80),
                     AttentionOp(2, 229, 12, 64, bias_kv=True), AttentionOp(3, 77, 16, 64, causal=True)],
+    "stage_ops": _stage_ops,
 }
 # (5) X then Y in one workspace: another shape and another internal path
 REUSE = {

@@ -1,5 +1,7 @@
-"""GPU parity of each encoder kernel on its own against a torch fp32 reference of the same op
-(computed on the CPU from the same bf16-rounded operands)."""
+"""GPU parity of the encoder's GEMM, LayerNorm and attention kernels, each on its own where it is exported (hmm_op_*), against a
+torch fp32 reference of the same op (computed on the CPU from the same bf16-rounded operands).  The tower's other stage kernels
+(im2col, Conv3d fold, token assembly, row gather, one-query attention, text embedding and head, L2 normalise) are checked on
+their own in tests/test_gpu_stage_ops.py; with that module "each encoder kernel on its own" holds for them too."""
 import ctypes as C
 import math
 
@@ -277,7 +279,8 @@ def test_gemm_identity_asymmetric():
         assert torch.equal(y.cpu(), w.float().T)
 
 
-@pytest.mark.parametrize("rows,D", [(1, 768), (5, 1280), (1029, 1280), (700, 768), (333, 1024)])
+@pytest.mark.parametrize("rows,D", [(1, 768), (5, 1280), (1029, 1280), (700, 768), (333, 1024),
+                                    (4096, 1280), (4099, 768)])            # from 4096 rows on: the non-temporal loads
 def test_layernorm(rows, D):
     L, lib = _lib()
     g = torch.Generator().manual_seed(rows + D)
