@@ -70,6 +70,7 @@ _SIGNATURES = {
     "hmm_audio_span_peaks": (C.c_int, [c_ptr, C.c_int, C.c_int64, c_ptr, c_ptr, C.c_int, c_ptr, c_ptr]),
     "hmm_audio_gather_clips": (C.c_int, [c_ptr, C.c_int, C.c_int64, c_ptr, c_ptr, C.c_int, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, c_ptr, c_ptr, c_ptr]),
+    "hmm_audio_window_sums": (C.c_int, [c_ptr, C.c_int, C.c_int64, c_ptr, c_ptr, C.c_int, c_ptr, c_ptr]),
     "hmm_gray_u8": (C.c_int, [c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr, c_ptr]),
     "hmm_ssim_pairs_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "hmm_ssim_pairs": (C.c_int, [c_ptr, C.c_int, C.c_int, C.c_int, c_ptr, C.c_int, C.c_double, c_ptr, c_ptr, c_ptr,

@@ -13,6 +13,14 @@ as it is (fp64 or fp32), and per call two kernels (csrc/audio_track.hip) produce
 At 16 kHz the clips carry the bits of the reference's wav round trip; at another rate each sample lies within the error bound of
 a T-term fp32 dot product of the exact filter output (tests/test_gpu_audio_track.py).  The host does what is left: the mix-down
 of a multi-channel track (once, the reference's own expression) and the span / clip tables.
+
+The same resident track serves the audio-level scan of ``_segment_sequence`` (hippocampal_memory.py:993-1000, :1061-1077), which
+comes before the spans exist: ``AudioTrack.window_levels`` takes the 500 ms windows of a walk step, one launch of
+
+    hmm_audio_window_sums    per window the sum of squares in the track's dtype, in the order of numpy's np.mean(np.square(x))
+
+and one read-back, and forms the levels on the host with numpy scalars of that dtype (``levels_from_sums``): the bits of the
+reference's expression on the host slices (tests/test_cpu_audio_levels_model.py, tests/test_gpu_audio_levels.py).
 """
 from __future__ import annotations
 
@@ -83,6 +91,36 @@ def clip_tables(spans: np.ndarray, orig: int, new: int) -> Dict[int, Tuple[List[
     return {length: (positions, np.asarray(rows, dtype=np.int64).reshape(-1, 4)) for length, (positions, rows) in groups.items()}
 
 
+def window_table(starts: Sequence[int], window: int, track_len: int) -> np.ndarray:
+    """Window starts -> (W, 2) int64 (start, length), each clipped to the track as the numpy slice audio_data[lo:lo + window]
+    would (a window past the track's end is empty).  Negative starts or a negative window raise ValueError."""
+    window = int(window)
+    if window < 0:
+        raise ValueError(f"window must not be negative, got {window}")
+    out = np.empty((len(starts), 2), dtype=np.int64)
+    for i, lo in enumerate(starts):
+        lo = int(lo)
+        if lo < 0:
+            raise ValueError(f"window {i} starts at {lo}: negative sample indices are not supported")
+        a = min(lo, track_len)
+        out[i] = (a, min(lo + window, track_len) - a)
+    return out
+
+
+def levels_from_sums(sums: np.ndarray, counts: Sequence[int]) -> list:
+    """Sums of squares (dtype T) and sample counts -> the levels ``segmentation.audio_level`` returns for those windows, as it
+    returns them: 20 * np.log10(rms), a scalar of dtype T, if rms > 0, else the int -100 -- with rms = np.sqrt(T(sum / n)),
+    which is np.sqrt(np.mean(...)).  An all-zero window, one that holds a NaN and an empty one (0 / 0) have no rms > 0: -100,
+    what the host expression gives (there with numpy's warnings for the empty one)."""
+    out = []
+    with np.errstate(all="ignore"):
+        for s, n in zip(sums, counts):
+            mean = s.dtype.type(s / np.intp(n))                               # np.mean's own expression; 0 / 0 = nan
+            rms = np.sqrt(mean)
+            out.append(20 * np.log10(rms) if rms > 0 else -100)
+    return out
+
+
 def _taps_device(orig: int, new: int, dev: torch.device) -> Tuple[torch.Tensor, int]:
     key = (orig, new, str(dev))
     if key not in _taps:
@@ -108,6 +146,7 @@ class AudioTrack:
         if isinstance(audio_data, torch.Tensor):
             audio_data = audio_data.detach().cpu().numpy()
         x = np.asarray(audio_data)
+        self.source_dtype = x.dtype                 # window_levels refuses a track that was not float32 / float64 at its source
         if x.dtype not in (np.float32, np.float64):
             x = x.astype(np.float32)
         if x.ndim == 2:
@@ -130,6 +169,37 @@ class AudioTrack:
                 dst[lo:hi].copy_(st.pinned[:hi - lo], non_blocking=True)
                 st.mark()
         return dev_track
+
+    # ---- levels -----------------------------------------------------------------------------------------------------------
+    def window_sums(self, table: np.ndarray) -> np.ndarray:
+        """Clipped windows (W, 2) int64 (start, length) -> (W,) sums of squares on the host, in the track's dtype and in numpy's
+        summation order (hmm_audio_window_sums): one launch, one read-back."""
+        lib = _lib.load()
+        table = np.ascontiguousarray(table, dtype=np.int64)
+        np_dtype = np.float64 if self.dtype_code else np.float32
+        if table.shape[0] == 0:
+            return np.empty(0, dtype=np_dtype)
+        with torch.cuda.device(self.device):
+            table_dev = torch.from_numpy(table).to(self.device)
+            sums = torch.empty(table.shape[0], dtype=self.samples.dtype, device=self.device)
+            _lib.check(lib.hmm_audio_window_sums(self.samples.data_ptr(), self.dtype_code, self.n_samples, table.ctypes.data,
+                                                 table_dev.data_ptr(), table.shape[0], sums.data_ptr(), _lib.stream_ptr()),
+                       "hmm_audio_window_sums")
+            return sums.cpu().numpy()
+
+    def window_level_values(self, starts: Sequence[int], window: int) -> list:
+        """The level of audio_data[lo:lo + window] for every lo in starts, each the very object ``segmentation.audio_level``
+        returns for that slice (a numpy scalar of the track's dtype, or the int -100)."""
+        if self.source_dtype not in (np.float32, np.float64):
+            raise TypeError(f"window_levels needs a track that was float32 or float64 at its source, got {self.source_dtype}: "
+                            "the reference's level of such an array is a different computation (keep it on the host route)")
+        table = window_table(starts, window, self.n_samples)
+        return levels_from_sums(self.window_sums(table), table[:, 1].tolist())
+
+    def window_levels(self, starts: Sequence[int], window: int) -> np.ndarray:
+        """dB levels of the windows [lo, lo + window) for lo in starts, clipped to the track, in the track's dtype: bit for bit
+        what ``segmentation.audio_level`` gives on the host slices of the array this track was made from."""
+        return np.asarray(self.window_level_values(starts, window), dtype=np.float64 if self.dtype_code else np.float32)
 
     # ---- clips ------------------------------------------------------------------------------------------------------------
     def span_peaks(self, spans: np.ndarray) -> torch.Tensor:

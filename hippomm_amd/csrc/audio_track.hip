@@ -1,6 +1,7 @@
-// The audio track of a video on the device: the two kernels behind AudioTrack (hippomm_amd/audio_track.py), which replace the
+// The audio track of a video on the device: the kernels behind AudioTrack (hippomm_amd/audio_track.py).  Two replace the
 // per-segment slice / mono / float32 / peak-normalise / wav round trip / resample / clip of the reference's process_sequence
-// (hippomm/core/hippocampal_memory.py:1198-1251 and imagebind.data.load_and_transform_audio_data behind it).
+// (hippomm/core/hippocampal_memory.py:1198-1251 and imagebind.data.load_and_transform_audio_data behind it); the third gives the
+// audio-level scan of _segment_sequence (:993-1000, :1061-1077) its sums of squares.
 //
 //   peaks    span_peaks_kernel: one workgroup per span, max |x| over the NARROWED samples (fp64 -> fp32 round-to-nearest-even, the
 //            bits of ndarray.astype(float32)).  The maximum is taken on the bit patterns of |x| as unsigned integers: for numbers
@@ -17,8 +18,23 @@
 //            consecutive phases -- read consecutive floats.  fp32 fused multiply-adds into four partial sums (t mod 4), added as
 //            (a0 + a1) + (a2 + a3): one fixed order, so a clip's bits do not depend on the batch it rides in or on the run.
 //
-// Both read the span / clip tables from the device and clamp what they find there to the track, so a device table that disagrees
-// with the host copy the entry point has checked reads and writes less, never elsewhere.  No scratch, vector stores only.
+//   levels   window_sums_kernel: one workgroup per window, the sum of squares of its samples in the track's own dtype and in the
+//            order of np.mean(np.square(x)) on a contiguous window (numpy 2.x: the ufunc buffer of 8192 elements, then
+//            pairwise_sum), so that the dB level formed from it on the host carries the bits of the reference's audio level
+//            (hippocampal_memory.py:993-1000).  Squares are a multiply rounded on its own (contraction is off from that kernel
+//            on).  The window is cut into chunks of 8192 squares whose sums are added left to right.  A chunk of m squares is
+//            numpy's split tree: m > 128 splits at (m / 2) - (m / 2) % 8.  The tree (depth <= 7) is expanded level by level into
+//            a heap in LDS, node i with children 2i and 2i + 1.  A leaf (m <= 128) goes to eight lanes: lane j holds numpy's
+//            accumulator r_j (elements 8i + j, in order, from element j), the eight are combined by a butterfly over XOR 1, 2, 4
+//            -- ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) in every lane, addition being commutative -- and the m % 8 tail elements
+//            are added one by one; with no full row of eight that is numpy's running sum from 0 for m < 8.  Inner nodes are then
+//            added bottom-up, left + right.  Element loads (a window starts at any sample): the eight lanes of a leaf read 32 or
+//            64 consecutive bytes, and no byte outside the window is read.  The order is a function of the window's length
+//            alone: not of the grid, the batch or the run.
+//
+// All three read their span / clip / window tables from the device and clamp what they find there to the track, so a device table
+// that disagrees with the host copy the entry point has checked reads and writes less, never elsewhere.  No scratch, vector stores
+// only.
 #include "hmm_common.h"
 
 namespace hmm {
@@ -136,6 +152,87 @@ __global__ __launch_bounds__(kClipBlock) void gather_clips_kernel(const void* __
     }
 }
 
+// ---- window sums: everything from here on is compiled with contraction off (x * x + r must stay a multiply and an add) ----------
+#pragma clang fp contract(off)
+
+constexpr int kSumChunk = 8192;                                               // numpy's ufunc buffer, in elements
+constexpr int kSumLeaf = 128;                                                 // pairwise_sum's PW_BLOCKSIZE
+constexpr int kSumNodes = 256;                                                // heap ids 1 .. 255: depth 7 is the deepest a chunk reaches
+constexpr int kSumDepth = 7;
+
+// The sum of squares of one leaf, s[0 .. len), by the eight lanes j = 0 .. 7 of a group; every lane returns it.  len == 0 (no leaf
+// for this group) reads nothing.  All lanes of the wave execute the shuffles.
+template <typename T>
+__device__ __forceinline__ T leaf_sum_squares(const T* __restrict__ s, int len, int j) {
+    const int rows = len >> 3;                                                // full rows of eight: at most 16
+    T x[kSumLeaf / 8];
+#pragma unroll
+    for (int i = 0; i < kSumLeaf / 8; ++i) x[i] = i < rows ? s[8 * i + j] : T(0);
+    T r = x[0] * x[0];
+#pragma unroll
+    for (int i = 1; i < kSumLeaf / 8; ++i)
+        if (i < rows) r = r + x[i] * x[i];
+    r = r + __shfl_xor(r, 1, 64);
+    r = r + __shfl_xor(r, 2, 64);
+    r = r + __shfl_xor(r, 4, 64);
+    for (int i = rows * 8; i < len; ++i) {                                    // the tail, or all of a leaf shorter than 8
+        const T t = s[i];
+        r = r + t * t;
+    }
+    return r;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void window_sums_kernel(const T* __restrict__ track, int64_t track_len,
+                                                          const int64_t* __restrict__ windows, T* __restrict__ sums) {
+    __shared__ int node_off[kSumNodes], node_len[kSumNodes];
+    __shared__ T node_sum[kSumNodes];
+    const int tid = threadIdx.x, group = tid >> 3, j = tid & 7;
+    int64_t start = windows[2 * blockIdx.x], n = windows[2 * blockIdx.x + 1];
+    start = start < 0 ? 0 : (start > track_len ? track_len : start);
+    n = n < 0 ? 0 : (n > track_len - start ? track_len - start : n);
+    const T* __restrict__ win = track + start;
+    T total = T(0);
+    int expanded = -1;                                                        // the chunk length the heap in LDS was expanded for
+    for (int64_t c0 = 0; c0 < n; c0 += kSumChunk) {                           // workgroup-uniform
+        const int m = (int)(n - c0 < kSumChunk ? n - c0 : kSumChunk);
+        if (m != expanded) {
+            if (tid < 2) {
+                node_off[tid] = 0;
+                node_len[tid] = tid == 1 ? m : 0;
+            }
+            __syncthreads();
+            for (int d = 0; d < kSumDepth; ++d) {
+                if (tid >= (1 << d) && tid < (2 << d)) {
+                    const int len = node_len[tid], off = node_off[tid];
+                    const int half = len >> 1, left = len > kSumLeaf ? half - (half & 7) : 0;
+                    node_off[2 * tid] = off;
+                    node_len[2 * tid] = left;
+                    node_off[2 * tid + 1] = off + left;
+                    node_len[2 * tid + 1] = len > kSumLeaf ? len - left : 0;
+                }
+                __syncthreads();
+            }
+            expanded = m;
+        }
+        for (int node = group; node < kSumNodes; node += 32) {                // leaves: one per group of eight lanes
+            int len = node_len[node];
+            if (len > kSumLeaf) len = 0;                                      // an inner node
+            if (__ballot(len > 0) == 0) continue;                             // wave-uniform
+            const T r = leaf_sum_squares<T>(win + c0 + node_off[node], len, j);
+            if (len > 0 && j == 0) node_sum[node] = r;
+        }
+        __syncthreads();
+        for (int d = kSumDepth - 1; d >= 0; --d) {                            // inner nodes, bottom-up: left + right
+            if (tid >= (1 << d) && tid < (2 << d) && node_len[tid] > kSumLeaf) node_sum[tid] = node_sum[2 * tid] + node_sum[2 * tid + 1];
+            __syncthreads();
+        }
+        total = total + node_sum[1];                                          // chunk sums left to right, the same in every thread
+        __syncthreads();                                                      // node_sum is free for the next chunk
+    }
+    if (tid == 0) sums[blockIdx.x] = total;
+}
+
 static bool track_overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
     const uint64_t x = (uint64_t)(uintptr_t)a, y = (uint64_t)(uintptr_t)b;
     return a_bytes != 0 && b_bytes != 0 && x < y + b_bytes && y < x + a_bytes;
@@ -222,6 +319,36 @@ extern "C" int hmm_audio_gather_clips(const void* track_dev, int track_dtype, in
         if (track_dtype == 1) HMM_GATHER(true, true); else HMM_GATHER(false, true);
     }
 #undef HMM_GATHER
+    HMM_LAUNCH_CHECK();
+    return HMM_OK;
+}
+
+extern "C" int hmm_audio_window_sums(const void* track_dev, int track_dtype, int64_t track_len, const int64_t* windows_host,
+                                     const int64_t* windows_dev, int n_windows, void* sums_out_dev, hmm_stream_t stream) {
+    HMM_REQUIRE(track_dtype == 0 || track_dtype == 1, HMM_E_INVALID, "audio_window_sums: track_dtype must be 0 (fp32) or 1 (fp64), got %d",
+                track_dtype);
+    HMM_REQUIRE(track_len >= 0 && n_windows >= 0, HMM_E_INVALID, "audio_window_sums: negative count (track_len=%lld, n_windows=%d)",
+                (long long)track_len, n_windows);
+    if (n_windows == 0) return HMM_OK;                                        // nothing to write: no pointer is looked at
+    HMM_REQUIRE(track_dev && windows_host && windows_dev && sums_out_dev, HMM_E_INVALID, "audio_window_sums: null pointer");
+    const uint64_t elem = track_dtype == 1 ? 8 : 4;
+    HMM_REQUIRE(((uintptr_t)track_dev & 15) == 0 && ((uintptr_t)windows_dev & 7) == 0 && ((uintptr_t)sums_out_dev & (elem - 1)) == 0,
+                HMM_E_INVALID, "audio_window_sums: the track must be 16-byte aligned, the table and the sums aligned to their element size");
+    for (int w = 0; w < n_windows; ++w) {
+        const int64_t a = windows_host[2 * w], len = windows_host[2 * w + 1];
+        HMM_REQUIRE(a >= 0 && len >= 0 && a <= track_len && len <= track_len - a, HMM_E_INVALID,
+                    "audio_window_sums: window %d = [%lld, %lld + %lld) lies outside the track [0, %lld]", w, (long long)a, (long long)a,
+                    (long long)len, (long long)track_len);
+    }
+    HMM_REQUIRE(!track_overlap(track_dev, (uint64_t)track_len * elem, sums_out_dev, (uint64_t)n_windows * elem), HMM_E_INVALID,
+                "audio_window_sums: the output overlaps the track");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (track_dtype == 1)
+        window_sums_kernel<double><<<n_windows, 256, 0, st>>>(static_cast<const double*>(track_dev), track_len, windows_dev,
+                                                               static_cast<double*>(sums_out_dev));
+    else
+        window_sums_kernel<float><<<n_windows, 256, 0, st>>>(static_cast<const float*>(track_dev), track_len, windows_dev,
+                                                              static_cast<float*>(sums_out_dev));
     HMM_LAUNCH_CHECK();
     return HMM_OK;
 }

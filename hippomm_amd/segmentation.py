@@ -13,9 +13,16 @@ keyed by path (boundary frames are shared between windows), scores the last pair
 not break, the rest of the window in one launch.  Errors -- an unreadable file, frames of different shapes, a side under 7 pixels
 -- are raised only when the walk consults the pair they belong to, which is where the reference raises them.
 
+The audio-level scan of the walk (500 ms windows from the end of a step backwards) has two routes, chosen by the caller.  Given
+only the ndarray, it is the reference's numpy expression on the host, window by window (``audio_level``), and an audio-only call
+needs no GPU.  Given ``audio_track=`` -- the video's ``AudioTrack``, the waveform the caller uploads once anyway to embed its
+segments -- the levels of all windows of a step come from one ``AudioTrack.window_levels`` call (``hmm_audio_window_sums``: the
+sum of squares per window in numpy's own summation order; mean, sqrt and log10 on the host in the track's dtype), bit for bit
+the levels of the host route, so the segment list is the same.
+
 Deliberate deviations from the reference, all documented on the functions: ``compute_frame_difference`` takes uint8 frames only
 (``TypeError`` otherwise); ``_segment_sequence`` raises ``ValueError`` where the reference would loop forever; an unreadable image
-raises ``OSError`` naming the path where the reference raises ``cv2.error``; the audio-level scan stays on the host (numpy).
+raises ``OSError`` naming the path where the reference raises ``cv2.error``.
 There is no CPU fallback for the SSIM: without a GPU these calls raise ``HippoMMHipError``.
 """
 from __future__ import annotations
@@ -426,7 +433,7 @@ def walk_segments(video_frames, frame_times, audio_data, audio_sample_rate,
                   score_window: Callable[[List[Tuple[int, int]]], Iterable[float]],
                   max_segment_duration: float = MAX_SEGMENT_DURATION, min_segment_duration: float = MIN_SEGMENT_DURATION,
                   frame_similarity_threshold: float = FRAME_SIMILARITY_THRESHOLD,
-                  audio_silence_threshold: float = AUDIO_SILENCE_THRESHOLD) -> List[SequenceSegment]:
+                  audio_silence_threshold: float = AUDIO_SILENCE_THRESHOLD, *, audio_track=None) -> List[SequenceSegment]:
     """The window walk of ``_segment_sequence`` as a host function of the scores.  ``score_window(pairs)`` gets one window's pairs
     of frame indices (later, earlier) -- adjacent entries of the window's frame list, scanned from the end -- and yields their
     similarities in that order; the walk stops reading at the first score below the threshold (NaN never breaks).
@@ -435,16 +442,27 @@ def walk_segments(video_frames, frame_times, audio_data, audio_sample_rate,
     start <= t <= end; the audio scan (500 ms windows, from the end backwards, excluding offset 0) runs after the video scan and
     overrides it; then the minimum-duration clamp; segment contents take inclusive time bounds and audio samples
     int(start * sr):int(end * sr).  One deviation: where the reference would loop forever (a start it has already been at, which
-    only happens with min_segment_duration <= 0), this raises ValueError."""
+    only happens with min_segment_duration <= 0), this raises ValueError.
+
+    ``audio_track`` (an ``audio_track.AudioTrack`` of the same waveform): the levels of a step's windows come from one
+    ``window_level_values`` call over all of the step's window starts instead of one host expression per window -- the same
+    objects, so the same segments; the level is a pure function of the window, and the first window from the end below the
+    threshold still decides.  Its rate must be ``audio_sample_rate`` (ValueError).  ``audio_data`` may then be None: the track's
+    length stands in for ``len(audio_data)`` and ``seg.audio_data`` is None (form spans with ``audio_track.spans_of``)."""
     segments: List[SequenceSegment] = []
-    if video_frames is None and audio_data is None:
+    if audio_track is not None:
+        if audio_track.sample_rate != audio_sample_rate:
+            raise ValueError(f"audio_track is at {audio_track.sample_rate} Hz, audio_sample_rate is {audio_sample_rate}")
+        if audio_data is not None and len(audio_data) != audio_track.n_samples:
+            raise ValueError(f"audio_track holds {audio_track.n_samples} samples, audio_data {len(audio_data)}")
+    if video_frames is None and audio_data is None and audio_track is None:
         return segments
     has_video = bool(video_frames and frame_times)
-    has_audio = audio_data is not None and bool(audio_sample_rate)
+    has_audio = (audio_data is not None or audio_track is not None) and bool(audio_sample_rate)
     if has_video:
         total_duration = frame_times[-1] - frame_times[0]
     elif has_audio:
-        total_duration = len(audio_data) / audio_sample_rate
+        total_duration = (len(audio_data) if audio_data is not None else audio_track.n_samples) / audio_sample_rate
     else:
         return segments
 
@@ -471,9 +489,13 @@ def walk_segments(video_frames, frame_times, audio_data, audio_sample_rate,
             start_sample = int(current_start * audio_sample_rate)
             end_sample = int(current_end * audio_sample_rate)
             window = int(0.5 * audio_sample_rate)
+            if audio_track is not None:                      # every window of this step in one launch
+                starts = [start_sample + off for off in range(end_sample - start_sample - window, 0, -window)]
+                resident = dict(zip(starts, audio_track.window_level_values(starts, window)))
             for off in range(end_sample - start_sample - window, 0, -window):
                 lo = start_sample + off
-                if audio_level(audio_data[lo:lo + window], audio_sample_rate) < audio_silence_threshold:
+                level = resident[lo] if audio_track is not None else audio_level(audio_data[lo:lo + window], audio_sample_rate)
+                if level < audio_silence_threshold:
                     optimal_end = lo / audio_sample_rate
                     break
 
@@ -484,7 +506,7 @@ def walk_segments(video_frames, frame_times, audio_data, audio_sample_rate,
         if has_video:
             seg.frames = [f for f, t in zip(video_frames, frame_times) if current_start <= t <= optimal_end]
             seg.frame_times = [t for t in frame_times if current_start <= t <= optimal_end]
-        if has_audio:
+        if has_audio and audio_data is not None:
             seg.audio_data = audio_data[int(current_start * audio_sample_rate):int(optimal_end * audio_sample_rate)]
         segments.append(seg)
         current_start = optimal_end
@@ -507,21 +529,27 @@ def segment_sequence(video_frames: Optional[List[str]] = None, frame_times: Opti
                      max_segment_duration: float = MAX_SEGMENT_DURATION, min_segment_duration: float = MIN_SEGMENT_DURATION,
                      frame_similarity_threshold: float = FRAME_SIMILARITY_THRESHOLD,
                      audio_silence_threshold: float = AUDIO_SILENCE_THRESHOLD,
-                     scorer: Optional[PathScorer] = None) -> List[SequenceSegment]:
+                     scorer: Optional[PathScorer] = None, audio_track=None) -> List[SequenceSegment]:
     """``_segment_sequence`` as a function; the four parameters default to the reference's __init__ defaults.  Frame similarities
-    come from the GPU (``PathScorer``); an audio-only call needs no GPU (the audio scan is host numpy, as in the reference)."""
+    come from the GPU (``PathScorer``).  Without ``audio_track`` an audio-only call needs no GPU (the audio scan is host numpy,
+    as in the reference); with the video's ``AudioTrack`` the scan reads the resident track (see ``walk_segments``)."""
     if video_frames and frame_times and scorer is None:
         scorer = PathScorer()
     score_window = _window_scorer(video_frames, scorer) if scorer is not None else None
     return walk_segments(video_frames, frame_times, audio_data, audio_sample_rate, score_window,
-                         max_segment_duration, min_segment_duration, frame_similarity_threshold, audio_silence_threshold)
+                         max_segment_duration, min_segment_duration, frame_similarity_threshold, audio_silence_threshold,
+                         audio_track=audio_track)
 
 
 def _segment_sequence(self, video_frames: Optional[List[str]] = None, frame_times: Optional[List[float]] = None,
-                      audio_data: Optional[np.ndarray] = None, audio_sample_rate: Optional[int] = None) -> List[SequenceSegment]:
+                      audio_data: Optional[np.ndarray] = None, audio_sample_rate: Optional[int] = None,
+                      audio_track=None) -> List[SequenceSegment]:
     """Drop-in for ``HippocampalMemory._segment_sequence`` (assign it on the class): reads self.max_segment_duration,
-    self.min_segment_duration, self.frame_similarity_threshold and self.audio_silence_threshold."""
+    self.min_segment_duration, self.frame_similarity_threshold and self.audio_silence_threshold.  The video's ``AudioTrack``,
+    given as the ``audio_track`` argument or set as ``self.audio_track``, moves the audio-level scan to the device."""
+    if audio_track is None:
+        audio_track = getattr(self, "audio_track", None)
     return segment_sequence(video_frames, frame_times, audio_data, audio_sample_rate,
                             max_segment_duration=self.max_segment_duration, min_segment_duration=self.min_segment_duration,
                             frame_similarity_threshold=self.frame_similarity_threshold,
-                            audio_silence_threshold=self.audio_silence_threshold)
+                            audio_silence_threshold=self.audio_silence_threshold, audio_track=audio_track)

@@ -426,6 +426,25 @@ int hmm_audio_gather_clips(const void* track_dev, int track_dtype, int64_t track
                            int orig, int new_, int width, const float* taps_dev, float* clips_out_dev, hmm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The audio-level scan of _segment_sequence (hippomm/core/hippocampal_memory.py:993-1000, :1061-1077) on the same track: the sum
+ * of squares of every 500 ms window of a walk step in one launch, in numpy's order, so that the host forms the reference's level
+ * bit for bit from it: mean = T(sum / n), rms = sqrt(mean), 20 * log10(rms) if rms > 0 else -100.
+ *
+ * hmm_audio_window_sums: windows: n_windows x (start, length) int64, start >= 0, length >= 0, start + length <= track_len; given
+ *   twice like the tables above (the host copy is checked before anything is launched; the kernel reads the device copy and clamps
+ *   it to the track).  sums_out_dev[w], in the track's dtype T (fp32 or fp64; aligned to it, not overlapping the track), is
+ *   np.sum(np.square(x[start : start + length])) as np.mean evaluates it on a contiguous window: s_i = x_i * x_i rounded to T (a
+ *   multiply and a separate add, never fused); consecutive chunks of 8192 squares summed left to right; a chunk of m squares by
+ *   pairwise summation -- m < 8 a running sum from 0; m <= 128 eight accumulators r_j over elements 8 i + j combined as
+ *   ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the m % 8 tail elements one by one; otherwise split at (m / 2) - (m / 2) % 8 and add
+ *   the halves.  0 for an empty window, NaN for one that holds a NaN.  The order depends on the window's length alone: the same
+ *   window gives the same bits alone, in any batch and on every run.  No workspace, no synchronisation, no allocation;
+ *   n_windows == 0: HMM_OK, nothing is launched.
+ * ---------------------------------------------------------------------------------------- */
+int hmm_audio_window_sums(const void* track_dev, int track_dtype, int64_t track_len, const int64_t* windows_host,
+                          const int64_t* windows_dev, int n_windows, void* sums_out_dev, hmm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Frame SSIM (structural similarity) for sequence segmentation and frame differences.  Replaces skimage 0.18.3
  * structural_similarity as hippomm/core/hippocampal_memory.py:980-991 (_compute_frame_similarity, consulted by
  * _segment_sequence :1002-1114) and hippomm/core/batch_process.py:32-69 (compute_frame_difference) call it on gray frames.
