@@ -593,8 +593,7 @@ static int launch_gemm(const bf16_t* A, const bf16_t* W, const float* bias, void
                        hipStream_t st) {
     constexpr int LDS = STAGES * KSUB * (BM + BN) * 128;
     static_assert(LDS <= 160 * 1024, "ring of the tiled GEMM: LDS");
-    HMM_REQUIRE(K % splits == 0 && ((K / splits) / 64) % KSUB == 0 && (K / splits) % 64 == 0, HMM_E_INVALID,
-                "gemm: K = %d / %d splits is not a multiple of %d", K, splits, 64 * KSUB);
+    // (K / splits is a multiple of 64 KSUB: plan_push has refused the call otherwise)
     auto kern = gemm_bf16_kernel<BM, BN, WM, WN, EPI, STAGES, KSUB>;
     HMM_ENSURE_DYN_LDS(kern, LDS);
     const int tiles_m = (M + BM - 1) / BM, tiles_n = N / BN;
@@ -728,36 +727,70 @@ static int dispatch_epi(int epi, F&& launch) {
         case HMM_EPI_BIAS_RESID_F32: return launch(std::integral_constant<int, HMM_EPI_BIAS_RESID_F32>());
         case HMM_EPI_F32:            return launch(std::integral_constant<int, HMM_EPI_F32>());
     }
-    set_error("gemm: unknown epilogue %d", epi);
+    set_error("gemm: epilogue %d was not planned", epi);     // plan_push refuses an unknown epilogue before anything is launched
     return HMM_E_INVALID;
+}
+
+// the ping-pong kernel's staging offsets are 32-bit
+static bool pp_offsets_fit(int M, int N, int K) { return (size_t)M * K < (1ull << 31) && (size_t)N * K < (1ull << 31); }
+
+// The LDS-staged geometries as data, indexed by HMM_GEMM_TILE_* (a zero row: the id names no such kernel).  launch_tile
+// instantiates from this table and plan_push checks K against its KSUB column: a new geometry is one row here and one case there.
+struct TileGeom { int bm, bn, wm, wn, stages, ksub; };
+constexpr int kNumTileIds = HMM_GEMM_TILE_64x128_RING8 + 1;
+constexpr TileGeom tile_geom(int tile) {
+    switch (tile) {                                       //  BM   BN  WM WN STAGES KSUB
+        case HMM_GEMM_TILE_128x128:       return {128, 128, 2, 2, 2, 1};
+        case HMM_GEMM_TILE_256x128:       return {256, 128, 2, 2, 2, 1};
+        case HMM_GEMM_TILE_256x256:       return {256, 256, 2, 4, 2, 1};
+        case HMM_GEMM_TILE_128x128_RING:  return {128, 128, 2, 2, 4, 1};
+        case HMM_GEMM_TILE_64x64_RING:    return { 64,  64, 2, 2, 4, 1};
+        case HMM_GEMM_TILE_32x32_RING:    return { 32,  32, 2, 2, 4, 1};
+        case HMM_GEMM_TILE_32x32_RING_K2: return { 32,  32, 2, 2, 4, 2};
+        case HMM_GEMM_TILE_32x32_RING_K4: return { 32,  32, 2, 2, 4, 4};
+        case HMM_GEMM_TILE_64x64_RING_K2: return { 64,  64, 2, 2, 3, 2};
+        case HMM_GEMM_TILE_128x64_RING:   return {128,  64, 2, 2, 4, 1};
+        case HMM_GEMM_TILE_64x128_RING:   return { 64, 128, 2, 2, 4, 1};
+        case HMM_GEMM_TILE_128x128_RING8: return {128, 128, 2, 4, 4, 1};
+        case HMM_GEMM_TILE_128x64_RING8:  return {128,  64, 4, 2, 4, 1};
+        case HMM_GEMM_TILE_64x128_RING8:  return { 64, 128, 2, 4, 4, 1};
+    }
+    return {0, 0, 0, 0, 0, 0};
+}
+template <int TILE, int EPI>
+static int launch_staged(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K, int splits, hipStream_t st) {
+    constexpr TileGeom g = tile_geom(TILE);
+    static_assert(g.bm > 0, "not an LDS-staged geometry");
+    return launch_gemm<g.bm, g.bn, g.wm, g.wn, EPI, g.stages, g.ksub>(A, W, bias, C, M, N, K, splits, st);
 }
 
 // splits > 1 for the tiled geometries only (gemm_bf16_splitk)
 static int launch_tile(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K, int epi, int tile,
                        int splits, hipStream_t st) {
-    if (tile == HMM_GEMM_TILE_256x256_PP && ((size_t)M * K >= (1ull << 31) || (size_t)N * K >= (1ull << 31)))
-        tile = HMM_GEMM_TILE_256x256;                   // the ping-pong kernel's staging offsets are 32-bit
+    if (tile == HMM_GEMM_TILE_256x256_PP && !pp_offsets_fit(M, N, K)) tile = HMM_GEMM_TILE_256x256;
     return dispatch_epi(epi, [&](auto epi_c) {
         constexpr int E = decltype(epi_c)::value;
-        switch (tile) {                                                          // BM   BN  WM WN   STAGES KSUB
-            case HMM_GEMM_TILE_SLIVER:        return launch_gemm_sliver<E>(A, W, bias, C, M, N, K, st);
-            case HMM_GEMM_TILE_256x256_PP:    return launch_gemm_pp<E>(A, W, bias, C, M, N, K, st);
-            case HMM_GEMM_TILE_128x128:       return launch_gemm<128, 128, 2, 2, E, 2, 1>(A, W, bias, C, M, N, K, splits, st);
-            case HMM_GEMM_TILE_256x128:       return launch_gemm<256, 128, 2, 2, E, 2, 1>(A, W, bias, C, M, N, K, splits, st);
-            case HMM_GEMM_TILE_256x256:       return launch_gemm<256, 256, 2, 4, E, 2, 1>(A, W, bias, C, M, N, K, splits, st);
-            case HMM_GEMM_TILE_128x128_RING:  return launch_gemm<128, 128, 2, 2, E, 4, 1>(A, W, bias, C, M, N, K, splits, st);
-            case HMM_GEMM_TILE_64x64_RING:    return launch_gemm< 64,  64, 2, 2, E, 4, 1>(A, W, bias, C, M, N, K, splits, st);
-            case HMM_GEMM_TILE_32x32_RING:    return launch_gemm< 32,  32, 2, 2, E, 4, 1>(A, W, bias, C, M, N, K, splits, st);
-            case HMM_GEMM_TILE_32x32_RING_K2: return launch_gemm< 32,  32, 2, 2, E, 4, 2>(A, W, bias, C, M, N, K, splits, st);
-            case HMM_GEMM_TILE_32x32_RING_K4: return launch_gemm< 32,  32, 2, 2, E, 4, 4>(A, W, bias, C, M, N, K, splits, st);
-            case HMM_GEMM_TILE_64x64_RING_K2: return launch_gemm< 64,  64, 2, 2, E, 3, 2>(A, W, bias, C, M, N, K, splits, st);
-            case HMM_GEMM_TILE_128x64_RING:   return launch_gemm<128,  64, 2, 2, E, 4, 1>(A, W, bias, C, M, N, K, splits, st);
-            case HMM_GEMM_TILE_64x128_RING:   return launch_gemm< 64, 128, 2, 2, E, 4, 1>(A, W, bias, C, M, N, K, splits, st);
-            case HMM_GEMM_TILE_128x128_RING8: return launch_gemm<128, 128, 2, 4, E, 4, 1>(A, W, bias, C, M, N, K, splits, st);
-            case HMM_GEMM_TILE_128x64_RING8:  return launch_gemm<128,  64, 4, 2, E, 4, 1>(A, W, bias, C, M, N, K, splits, st);
-            case HMM_GEMM_TILE_64x128_RING8:  return launch_gemm< 64, 128, 2, 4, E, 4, 1>(A, W, bias, C, M, N, K, splits, st);
+#define HMM_STAGED(ID) case ID: return launch_staged<ID, E>(A, W, bias, C, M, N, K, splits, st)
+        switch (tile) {
+            case HMM_GEMM_TILE_SLIVER:     return launch_gemm_sliver<E>(A, W, bias, C, M, N, K, st);
+            case HMM_GEMM_TILE_256x256_PP: return launch_gemm_pp<E>(A, W, bias, C, M, N, K, st);
+            HMM_STAGED(HMM_GEMM_TILE_128x128);
+            HMM_STAGED(HMM_GEMM_TILE_256x128);
+            HMM_STAGED(HMM_GEMM_TILE_256x256);
+            HMM_STAGED(HMM_GEMM_TILE_128x128_RING);
+            HMM_STAGED(HMM_GEMM_TILE_64x64_RING);
+            HMM_STAGED(HMM_GEMM_TILE_32x32_RING);
+            HMM_STAGED(HMM_GEMM_TILE_32x32_RING_K2);
+            HMM_STAGED(HMM_GEMM_TILE_32x32_RING_K4);
+            HMM_STAGED(HMM_GEMM_TILE_64x64_RING_K2);
+            HMM_STAGED(HMM_GEMM_TILE_128x64_RING);
+            HMM_STAGED(HMM_GEMM_TILE_64x128_RING);
+            HMM_STAGED(HMM_GEMM_TILE_128x128_RING8);
+            HMM_STAGED(HMM_GEMM_TILE_128x64_RING8);
+            HMM_STAGED(HMM_GEMM_TILE_64x128_RING8);
         }
-        set_error("gemm: unknown tile geometry %d", tile);
+#undef HMM_STAGED
+        set_error("gemm: tile geometry %d was not planned", tile);  // plan_push refuses an unknown geometry before anything is launched
         return HMM_E_INVALID;
     });
 }
@@ -775,7 +808,7 @@ HMM_RULE(g_gemm_rect64_min_t64)
 HMM_RULE(g_gemm_rect_rows)
 HMM_RULE(g_gemm_rect_rows_longk)
 HMM_RULE(g_gemm_ring_peel_rows)
-// The geometry of such a launch (tail: the peeled last row tiles of a big ping-pong launch).  Peels are launch_gemm_small's.
+// The geometry of such a launch (tail: the peeled last row tiles of a big ping-pong launch).  Peels are plan_small's.
 static int small_tile(int M, int N, int K, int epi, bool tail) {
     const long t64 = (long)((M + 63) / 64) * (N / 64);
     if ((long)((M + 127) / 128) * (N / 128) > 256) {
@@ -827,8 +860,34 @@ static void* c_row(void* C, int m, int N, int epi) {     // row m of the output
     return static_cast<char*>(C) + (size_t)m * N * (c_bf16 ? 2 : 4);
 }
 
-static int launch_gemm_small(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K, int epi,
-                             bool tail, hipStream_t st) {
+// ---------------------------------------------------------------------------------------------------------------------------
+// The plan of a call: the launches it makes, in order.  gemm_bf16 and gemm_bf16_splitk build the plan and then launch FROM it,
+// and hmm_op_gemm_plan returns the same plan without launching, so that a test can ask which kernel a shape runs on and the
+// answer cannot drift from what runs.  The decisions are small_tile / sliver_wins / plan_small / plan_gemm / plan_splitk above
+// and below; launch_tile is still the only place where an id becomes a kernel.
+struct GemmLaunch { int tile, row0, rows, splits, sliver_mt, flags; };      // the six fields of HMM_GEMM_PLAN_FIELDS
+constexpr int kGemmPlanMax = 4;                                             // a call makes at most two launches today
+struct GemmPlan { int n = 0; GemmLaunch launch[kGemmPlanMax]; };
+
+// One launch of the plan.  THE place where a call is refused for its epilogue, its geometry or the K a geometry cannot walk.
+static int plan_push(GemmPlan& p, int tile, int row0, int rows, int N, int K, int epi, int splits, int flags) {
+    if (tile == HMM_GEMM_TILE_256x256_PP && !pp_offsets_fit(rows, N, K)) tile = HMM_GEMM_TILE_256x256;
+    HMM_REQUIRE(epi >= HMM_EPI_BIAS_BF16 && epi <= HMM_EPI_F32, HMM_E_INVALID, "gemm: unknown epilogue %d", epi);
+    const bool staged = tile >= 0 && tile < kNumTileIds && tile_geom(tile).bm > 0;
+    HMM_REQUIRE(staged || tile == HMM_GEMM_TILE_SLIVER || tile == HMM_GEMM_TILE_256x256_PP, HMM_E_INVALID,
+                "gemm: unknown tile geometry %d", tile);
+    if (staged) {
+        const int ksub = tile_geom(tile).ksub;
+        HMM_REQUIRE(K % splits == 0 && ((K / splits) / 64) % ksub == 0 && (K / splits) % 64 == 0, HMM_E_INVALID,
+                    "gemm: K = %d / %d splits is not a multiple of %d", K, splits, 64 * ksub);
+    }
+    HMM_REQUIRE(p.n < kGemmPlanMax, HMM_E_INVALID, "gemm: a plan of more than %d launches", kGemmPlanMax);
+    p.launch[p.n++] = GemmLaunch{tile, row0, rows, splits, tile == HMM_GEMM_TILE_SLIVER ? sliver_mt(rows, N, K) : 0, flags};
+    return HMM_OK;
+}
+
+// rows [row0, row0 + M) as a launch of few tiles
+static int plan_small(GemmPlan& p, int row0, int M, int N, int K, int epi, bool tail) {
     if (!tail && g_gemm_ring_peel_rows > 0) {
         // A frame is 257 token rows = two 128-row tiles + ONE row: k frames end in a row tile of k rows.  When that sliver of a tile
         // is what pushes the launch past one 128 x 128 ring tile per CU (three frames' fc1: 7 x 40 = 280 tiles for 6 x 40 + 3 rows;
@@ -838,27 +897,28 @@ static int launch_gemm_small(const bf16_t* A, const bf16_t* W, const float* bias
         const long cols = N / 128;
         if (tm > 1 && tail_rows <= g_gemm_ring_peel_rows && tm * cols > kNumCU && (tm - 1) * cols <= kNumCU) {
             const int m_main = (tm - 1) * 128;
-            const int rc = launch_gemm_small(A, W, bias, C, m_main, N, K, epi, false, st);
+            const int rc = plan_small(p, row0, m_main, N, K, epi, false);
             if (rc != HMM_OK) return rc;
-            return launch_tile(A + (size_t)m_main * K, W, bias, c_row(C, m_main, N, epi), tail_rows, N, K, epi, HMM_GEMM_TILE_SLIVER,
-                               1, st);
+            return plan_push(p, HMM_GEMM_TILE_SLIVER, row0 + m_main, tail_rows, N, K, epi, 1, HMM_GEMM_PLAN_SLIVER_PEEL);
         }
     }
-    return launch_tile(A, W, bias, C, M, N, K, epi, small_tile(M, N, K, epi, tail), 1, st);
+    return plan_push(p, small_tile(M, N, K, epi, tail), row0, M, N, K, epi, 1, tail ? HMM_GEMM_PLAN_PP_TAIL : 0);
 }
 
-int gemm_bf16(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K, int epi, int tile,
-              int small_tiles, hipStream_t st) {
-    HMM_REQUIRE(A && W && C, HMM_E_INVALID, "gemm: null pointer");
-    HMM_REQUIRE(M >= 1 && N >= 128 && K >= 64 && K % 64 == 0 && N % 128 == 0, HMM_E_INVALID,
+static bool gemm_shape_ok(int M, int N, int K) {
+    HMM_REQUIRE(M >= 1 && N >= 128 && K >= 64 && K % 64 == 0 && N % 128 == 0, false,
                 "gemm: unsupported shape M=%d N=%d K=%d (need K%%64==0, N%%128==0)", M, N, K);
-    HMM_REQUIRE(epi == HMM_EPI_F32 || bias != nullptr, HMM_E_INVALID, "gemm: epilogue %d needs a bias", epi);
+    return true;
+}
+
+static int plan_gemm(GemmPlan& p, int M, int N, int K, int epi, int tile, int small_tiles) {
+    if (!gemm_shape_ok(M, N, K)) return HMM_E_INVALID;
     const bool sliver_ok = tile == HMM_GEMM_TILE_AUTO;          // AUTO_TILED, and every named geometry: tiled kernels only
     if (tile < 0) tile = HMM_GEMM_TILE_PP_PEELED;
     const bool pp_ok = N % 256 == 0 && K % 128 == 0;
     if ((tile == HMM_GEMM_TILE_PP_PEELED || tile == HMM_GEMM_TILE_256x256_PP) && !pp_ok) tile = HMM_GEMM_TILE_256x256;
     if (tile == HMM_GEMM_TILE_256x256 && N % 256 != 0) tile = HMM_GEMM_TILE_256x128;
-    if (tile != HMM_GEMM_TILE_PP_PEELED) return launch_tile(A, W, bias, C, M, N, K, epi, tile, 1, st);
+    if (tile != HMM_GEMM_TILE_PP_PEELED) return plan_push(p, tile, 0, M, N, K, epi, 1, 0);
 
     // Tile quantisation: with 256 CUs and one 256x256 tile per CU, T tiles take ceil(T/256) rounds.
     // ViT-H at batch 256 has 257 M-tiles (257 = 256 patches + cls per image), i.e. 5..20 tiles left
@@ -871,21 +931,41 @@ int gemm_bf16(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int 
     // two chains -4.8 ... -6.2 % in five rechecks, -1.9 % in the one at round 6's final commit: under the 2 % a rule has to buy
     // ON THAT RUN, so it went, profiles/r6_dispatch_recheck.json.)
     if (tiles < small_tiles)
-        return sliver_ok && sliver_wins(M, N, K, epi) ? launch_tile(A, W, bias, C, M, N, K, epi, HMM_GEMM_TILE_SLIVER, 1, st)
-                                                      : launch_gemm_small(A, W, bias, C, M, N, K, epi, false, st);
+        return sliver_ok && sliver_wins(M, N, K, epi) ? plan_push(p, HMM_GEMM_TILE_SLIVER, 0, M, N, K, epi, 1, 0)
+                                                      : plan_small(p, 0, M, N, K, epi, false);
     // peel p <= 2 row tiles when that leaves the main launch with a last round that is full or nearly full (>= 240 of 256
     // CUs) instead of a nearly empty one
     int peel = 0;
     if (tiles > 256 && tiles % 256 != 0 && tiles % 256 <= 64)
-        for (int p = 1; p <= 2 && !peel; ++p) {
-            const long r = ((long)(tiles_m - p) * tiles_n) % 256;
-            if (r == 0 || r >= 240) peel = p;
+        for (int q = 1; q <= 2 && !peel; ++q) {
+            const long r = ((long)(tiles_m - q) * tiles_n) % 256;
+            if (r == 0 || r >= 240) peel = q;
         }
-    if (!peel) return launch_tile(A, W, bias, C, M, N, K, epi, HMM_GEMM_TILE_256x256_PP, 1, st);
+    if (!peel) return plan_push(p, HMM_GEMM_TILE_256x256_PP, 0, M, N, K, epi, 1, 0);
     const int m_main = (tiles_m - peel) * 256;
-    const int rc = launch_tile(A, W, bias, C, m_main, N, K, epi, HMM_GEMM_TILE_256x256_PP, 1, st);
+    const int rc = plan_push(p, HMM_GEMM_TILE_256x256_PP, 0, m_main, N, K, epi, 1, 0);
     if (rc != HMM_OK) return rc;
-    return launch_gemm_small(A + (size_t)m_main * K, W, bias, c_row(C, m_main, N, epi), M - m_main, N, K, epi, true, st);
+    return plan_small(p, m_main, M - m_main, N, K, epi, true);
+}
+
+static int launch_plan(const GemmPlan& p, const bf16_t* A, const bf16_t* W, const float* bias, void* C, int N, int K, int epi,
+                       hipStream_t st) {
+    for (int i = 0; i < p.n; ++i) {
+        const GemmLaunch& l = p.launch[i];
+        const int rc = launch_tile(A + (size_t)l.row0 * K, W, bias, c_row(C, l.row0, N, epi), l.rows, N, K, epi, l.tile, l.splits, st);
+        if (rc != HMM_OK) return rc;
+    }
+    return HMM_OK;
+}
+
+int gemm_bf16(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K, int epi, int tile,
+              int small_tiles, hipStream_t st) {
+    HMM_REQUIRE(A && W && C, HMM_E_INVALID, "gemm: null pointer");
+    if (!gemm_shape_ok(M, N, K)) return HMM_E_INVALID;
+    HMM_REQUIRE(epi == HMM_EPI_F32 || bias != nullptr, HMM_E_INVALID, "gemm: epilogue %d needs a bias", epi);
+    GemmPlan p;
+    const int rc = plan_gemm(p, M, N, K, epi, tile, small_tiles);
+    return rc != HMM_OK ? rc : launch_plan(p, A, W, bias, C, N, K, epi, st);
 }
 
 // Deterministic split-K for launches of few rows x a long K (out-proj / fc2 of one frame, one question, one segment): the
@@ -893,8 +973,7 @@ int gemm_bf16(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int 
 // workgroups per tile walk K / splits each and write their fp32 partial products to slab[split][M][N]; the consumer (the
 // LayerNorm behind every residual GEMM: launch_layernorm_reduce_bf16) adds the slabs in split order, the bias and the
 // residual, so no launch is added and an element's bits depend on (N, K, splits) only -- not on M, the tile geometry or timing.
-int gemm_bf16_splitk(const bf16_t* A, const bf16_t* W, float* part, int M, int N, int K, int splits, int tile, hipStream_t st) {
-    HMM_REQUIRE(A && W && part, HMM_E_INVALID, "gemm_splitk: null pointer");
+static int plan_splitk(GemmPlan& p, int M, int N, int K, int splits, int tile) {
     HMM_REQUIRE(M >= 1 && N >= 128 && N % 128 == 0 && splits >= 1 && splits <= 8 && K % (64 * splits) == 0, HMM_E_INVALID,
                 "gemm_splitk: unsupported shape M=%d N=%d K=%d splits=%d", M, N, K, splits);
     if (tile < 0) {
@@ -916,7 +995,14 @@ int gemm_bf16_splitk(const bf16_t* A, const bf16_t* W, float* part, int M, int N
     // the ring geometries only (ids 6 ... 16), fp32 partials without a bias
     HMM_REQUIRE(tile >= HMM_GEMM_TILE_128x128_RING && tile <= HMM_GEMM_TILE_64x128_RING8, HMM_E_INVALID,
                 "gemm_splitk: tile geometry %d has no split-K launch", tile);
-    return launch_tile(A, W, nullptr, part, M, N, K, HMM_EPI_F32, tile, splits, st);
+    return plan_push(p, tile, 0, M, N, K, HMM_EPI_F32, splits, 0);
+}
+
+int gemm_bf16_splitk(const bf16_t* A, const bf16_t* W, float* part, int M, int N, int K, int splits, int tile, hipStream_t st) {
+    HMM_REQUIRE(A && W && part, HMM_E_INVALID, "gemm_splitk: null pointer");
+    GemmPlan p;
+    const int rc = plan_splitk(p, M, N, K, splits, tile);
+    return rc != HMM_OK ? rc : launch_plan(p, A, W, nullptr, part, N, K, HMM_EPI_F32, st);
 }
 
 }  // namespace hmm
@@ -927,6 +1013,19 @@ extern "C" int hmm_op_gemm_bf16_splitk(const uint16_t* a_dev, const uint16_t* w_
                                        int splits, int tile, hmm_stream_t stream) {
     return gemm_bf16_splitk(reinterpret_cast<const bf16_t*>(a_dev), reinterpret_cast<const bf16_t*>(w_dev), part_dev, M, N, K,
                             splits, tile, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int hmm_op_gemm_plan(int M, int N, int K, int epilogue, int tile, int small_tiles, int splits, int32_t* out, int cap) {
+    GemmPlan p;
+    HMM_REQUIRE(splits >= 0 && (out || cap <= 0), HMM_E_INVALID, "gemm_plan: splits = %d, out = %p, cap = %d", splits, (void*)out, cap);
+    const int rc = splits == 0 ? plan_gemm(p, M, N, K, epilogue, tile, small_tiles) : plan_splitk(p, M, N, K, splits, tile);
+    if (rc != HMM_OK) return rc;
+    for (int i = 0; i < p.n && i < cap; ++i) {
+        const GemmLaunch& l = p.launch[i];
+        const int32_t rec[HMM_GEMM_PLAN_FIELDS] = {l.tile, l.row0, l.rows, l.splits, l.sliver_mt, l.flags};
+        for (int f = 0; f < HMM_GEMM_PLAN_FIELDS; ++f) out[i * HMM_GEMM_PLAN_FIELDS + f] = rec[f];
+    }
+    return p.n;
 }
 
 extern "C" int hmm_op_gemm_bf16(const uint16_t* a_dev, const uint16_t* w_dev, const float* bias_dev, void* c_dev,

@@ -562,7 +562,8 @@ int hmm_op_gemm_bf16(const uint16_t* a_dev, const uint16_t* w_dev, const float* 
  * can choose is parity-tested on every shape.  Every geometry adds the K products of an output element in the same
  * order, so results are bitwise equal across geometries. */
 #define HMM_GEMM_TILE_AUTO       -1  /* by shape; few rows may go to the sliver kernel                              */
-#define HMM_GEMM_TILE_AUTO_TILED -2  /* by shape among the tiled kernels only (what a large-batch forward uses)       */
+#define HMM_GEMM_TILE_AUTO_TILED -2  /* by shape, the sliver kernel never as the whole launch (what a large-batch forward uses); it still takes the
+                                        last <= 16 rows that are peeled off a ring launch (HMM_GEMM_PLAN_SLIVER_PEEL) */
 #define HMM_GEMM_TILE_128x128     0  /* 4 waves, double-buffered LDS-DMA                                  */
 #define HMM_GEMM_TILE_256x128     1
 #define HMM_GEMM_TILE_256x256     2  /* 8 waves, same loop                                                */
@@ -588,6 +589,17 @@ int hmm_op_gemm_bf16_tile(const uint16_t* a_dev, const uint16_t* w_dev, const fl
  * bits depend on (K, splits) only -- every geometry walks a split's K range in the same order. */
 int hmm_op_gemm_bf16_splitk(const uint16_t* a_dev, const uint16_t* w_dev, float* part_dev, int M, int N, int K,
                             int splits, int tile, hmm_stream_t stream);
+/* What hmm_op_gemm_bf16_tile (splits == 0; small_tiles = 128, or 64 as a forward on two chains passes) or
+ * hmm_op_gemm_bf16_splitk (splits >= 1; epilogue and small_tiles ignored) would launch for these arguments.  Host only:
+ * launches nothing, needs no GPU.  The calls launch from the same plan.  Returns the number of launches -- the first
+ * min(that, cap) are written to out, HMM_GEMM_PLAN_FIELDS int32 each, in launch order -- or the status and hmm_last_error text
+ * of the real call for the same shape, epilogue and tile.  A record: [0] the geometry that runs, one of the ids 0..16 that
+ * name a kernel (never AUTO*, never PP_PEELED); [1] first row; [2] rows; [3] splits (1 unless split-K); [4] 16-row blocks per
+ * wave of the sliver kernel (1 / 2 / 4), 0 for every other geometry; [5] HMM_GEMM_PLAN_* flags. */
+#define HMM_GEMM_PLAN_FIELDS       6
+#define HMM_GEMM_PLAN_PP_TAIL      1  /* the peeled last row tile(s) of a ping-pong launch */
+#define HMM_GEMM_PLAN_SLIVER_PEEL  2  /* the last few rows peeled off a ring launch */
+int hmm_op_gemm_plan(int M, int N, int K, int epilogue, int tile, int small_tiles, int splits, int32_t* out, int cap);
 /* The consumer of those slabs: x_f32[rows, D] = ((part[0] + part[1] + ... + part[splits-1]) + bias) + x (in place, the
  * slabs in split order) and y_bf16 = LayerNorm(x) * gamma + beta -- the residual epilogue of the GEMM and the LayerNorm
  * behind it in one launch.  part_dev [splits][rows][D] fp32; D in {768, 1024, 1280}. */

@@ -770,6 +770,87 @@ def _stage_ops():
     return ops
 
 
+class HotOp(StageOp):
+    """One of the encoder's hot entry points (GEMM by named route, split-K and the LayerNorm that reduces it, the fused in_proj +
+    attention kernels).  ``inout``: buffers the call reads AND writes (the fp32 residual stream); they are outputs of the case,
+    carved like any output, and hold their initial value instead of the poison when the call starts."""
+    family = "op hot"
+
+    def __init__(self, entry, label, inputs, outs, args, inout=None):
+        super().__init__(entry, label, inputs, outs, args)
+        self.inout = {k: v.to(DEV) for k, v in (inout or {}).items()}
+        self._ar = None
+
+    def place_inputs(self, ar):
+        self._ar = ar
+        return super().place_inputs(ar)
+
+    def call(self, lib, p, ws, ws_bytes):
+        if self._ar is not None:                                    # in the arena: the initial value into the carved in/out buffer
+            for name, t in self.inout.items():
+                flat = _u8_dev(t)
+                off = p[name] - self._ar.bytes.data_ptr()
+                assert flat.numel() == self.outs[name] and 0 <= off <= self._ar.bytes.numel() - flat.numel()
+                self._ar.bytes[off: off + flat.numel()].copy_(flat)
+        return super().call(lib, p, ws, ws_bytes)
+
+    def shim(self):
+        bufs = {name: torch.empty(nb, dtype=torch.uint8, device=DEV) for name, nb in self.outs.items()}
+        for name, t in self.inout.items():
+            bufs[name].copy_(_u8_dev(t))
+        p = {k: v.data_ptr() for k, v in {**self.inputs, **bufs}.items()}
+        ar, self._ar = self._ar, None
+        try:
+            assert super().call(_L()[1], p, None, 0) == 0
+        finally:
+            self._ar = ar
+        return bufs
+
+
+def _u8_dev(t):
+    return t.contiguous().reshape(-1).view(torch.uint8)
+
+
+def _hot_ops():
+    """hmm_op_gemm_bf16_tile at a ragged M, one shape per kind of launch, over the four epilogues; split-K with four splits and
+    the LayerNorm that reduces its slabs; the fused in_proj + attention kernels of the vision (3 images) and audio (5 clips) towers."""
+    _, lib = _L()
+    ops = []
+    gemm_routes = [  # label, M, N, K, tile: the launches are pinned by tests/test_cpu_gemm_cases.py through hmm_op_gemm_plan
+        ("sliver", 77, 256, 256, 5), ("ring", 77, 256, 256, 7), ("ring + sliver peel", 1283, 3072, 128, -2),
+        ("ping-pong, guarded last row tile", 300, 256, 128, 3), ("ping-pong + peeled tail", 3077, 5120, 128, -1)]
+    for what, M, N, K, tile in gemm_routes:
+        a, w, bias = _rand((M, K), M, torch.bfloat16), _rand((N, K), N + K, torch.bfloat16) * 0.05, _rand((N,), 3)
+        for epi in (0, 1, 2, 3):
+            size = 2 if epi < 2 else 4
+            ops.append(HotOp("hmm_op_gemm_bf16_tile", f"{what}: M={M},N={N},K={K},epi={epi},tile={tile}", {"a": a, "w": w, "bias": bias},
+                             {"c": M * N * size}, lambda p, s=(M, N, K, epi, tile): (p["a"], p["w"], p["bias"], p["c"], *s),
+                             inout={"c": _rand((M, N), 11)} if epi == 2 else None))
+    M, N, K, splits = 77, 1024, 1024, 4
+    a, w = _rand((M, K), 5, torch.bfloat16), _rand((N, K), 6, torch.bfloat16) * 0.05
+    ops.append(HotOp("hmm_op_gemm_bf16_splitk", f"M={M},N={N},K={K},splits={splits}", {"a": a, "w": w}, {"part": splits * M * N * 4},
+                     lambda p: (p["a"], p["w"], p["part"], M, N, K, splits, -1)))
+    ops.append(HotOp("hmm_op_layernorm_reduce_bf16", f"rows={M},D={N},splits={splits}",
+                     {"part": _rand((splits, M, N), 7), "bias": _rand((N,), 8), "gamma": _rand((N,), 1), "beta": _rand((N,), 2)},
+                     {"x": M * N * 4, "y": M * N * 2},
+                     lambda p: (p["x"], p["part"], splits, p["bias"], p["gamma"], p["beta"], p["y"], M, N, 1e-6),
+                     inout={"x": _rand((M, N), 9)}))
+    n_img, T, D = 3, 257, 1280
+    a, w, bias = _rand((n_img * T, D), 21, torch.bfloat16), _rand((3 * D, D), 22, torch.bfloat16) * 0.03, _rand((3 * D,), 23) * 0.1
+    cls_rows = a.view(n_img, T, D)[:, 0].contiguous()
+    qkv_cls = torch.empty(n_img, 3 * D, dtype=torch.bfloat16, device=DEV)
+    assert lib.hmm_op_gemm_bf16(cls_rows.data_ptr(), w.data_ptr(), bias.data_ptr(), qkv_cls.data_ptr(), n_img, 3 * D, D, 0, None) == 0
+    torch.cuda.synchronize()
+    ops.append(HotOp("hmm_op_qkv_attention_bf16", f"n_img={n_img}", {"a": a, "w": w, "bias": bias, "qkv_cls": qkv_cls},
+                     {"out": n_img * T * D * 2}, lambda p: (p["a"], p["w"], p["bias"], p["qkv_cls"], p["out"], n_img)))
+    n_clips, T, D = 5, 229, 768
+    a, w, bias = _rand((n_clips * T, D), 31, torch.bfloat16), _rand((3 * D, D), 32, torch.bfloat16) * 0.04, _rand((3 * D,), 33) * 0.1
+    ops.append(HotOp("hmm_op_qkv_attention_audio_bf16", f"n_clips={n_clips}",
+                     {"a": a, "w": w, "bias": bias, "bias_k": _rand((D,), 34) * 0.5, "bias_v": _rand((D,), 35) * 0.5},
+                     {"out": n_clips * T * D * 2}, lambda p: (p["a"], p["w"], p["bias"], p["bias_k"], p["bias_v"], p["out"], n_clips)))
+    return ops
+
+
 # =====================================================================================================================
 # the case table
 # =====================================================================================================================
@@ -811,7 +892,7 @@ CASES = {
                     [Jpeg(130, 90, sub, 6, win) for sub in (0, 1, 2, "grey") for win in ((3, 5, 100, 70), (129, 89, 1, 1), (0, 0, 1, 1), (1, 1, 128, 88))] +
                     [Jpeg(1280, 720, 2, 1), Jpeg(1280, 720, 2, 6, (275, 0, 730, 720)), Jpeg(1280, 720, 1, 1, (9, 7, 1263, 705))],
     "ops": lambda: [LayerNormOp(1, 768), LayerNormOp(77, 1024), LayerNormOp(257, 1280), AttentionOp(1, 257, 16, 80),
-                    AttentionOp(2, 229, 12, 64, bias_kv=True), AttentionOp(3, 77, 16, 64, causal=True)],
+                    AttentionOp(2, 229, 12, 64, bias_kv=True), AttentionOp(3, 77, 16, 64, causal=True)] + _hot_ops(),
     "stage_ops": _stage_ops,
 }
 # (5) X then Y in one workspace: another shape and another internal path
