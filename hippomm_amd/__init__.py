@@ -22,7 +22,12 @@ and the audio of a whole video in one call (clip gather, peak normalisation and 
 and a baseline JPEG decoder with the pixel work on the GPU, bit-exact with Pillow (hippomm_amd/csrc/jpeg.hip):
 
     hippomm_amd.decode_jpeg                          <- Image.open(path).convert("RGB") of the reference's frame reads
+
+and its counterpart, a baseline JPEG encoder on the GPU, byte for byte Pillow's file (hippomm_amd/csrc/jpeg_encode.hip):
+
+    hippomm_amd.encode_jpeg                          <- Image.fromarray(rgb).save(buf, "JPEG", quality=q, subsampling=s)
+    hippomm_amd.segmentation.save_frame, save_frames <- hippomm/core/batch_process.py:73-114 (cv2.imwrite)
 """
 __version__ = "0.1.0"
 
-from .jpeg import decode_jpeg  # noqa: E402,F401
+from .jpeg import decode_jpeg, encode_jpeg  # noqa: E402,F401

@@ -14,6 +14,11 @@ for every file is the host route's.
 
 The first frame a process decodes on the device is compared with Pillow's decode of the same bytes; on a mismatch (another
 Pillow or libjpeg-turbo build) the route is turned off for the process and a warning is logged.
+
+Encoding goes the other way (hippomm_amd/csrc/jpeg_encode.hip): ``encode_jpeg`` turns uint8 frames, resident or on the host,
+into complete baseline files on the GPU -- colour transform, chroma downsampling, islow forward DCT, quantisation, the Huffman
+pass, padding and byte stuffing -- each, byte for byte, the file ``Image.fromarray(x).save(buf, "JPEG", quality=q,
+subsampling=s)`` writes.  The same self-check guards it, and a frame the kernel does not report as encoded is encoded by Pillow.
 """
 from __future__ import annotations
 
@@ -384,3 +389,241 @@ def decode_jpeg(sources: Sequence[Union[str, bytes]], device=None, window=None,
     if len({tuple(r.shape) for r in results}) == 1:
         return torch.stack(results)
     return results
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# encoding (hippomm_amd/csrc/jpeg_encode.hip): frames -> baseline files, byte for byte Pillow's
+# ---------------------------------------------------------------------------------------------------------------------------------
+ENCODED, ENCODE_OVERFLOW = 0, 1
+SAMPLING = {"4:4:4": (1, 1), "4:2:2": (2, 1), "4:2:0": (2, 2)}
+CHANNEL_ORDER = {"RGB": 0, "BGR": 1}
+ENCODE_SLOT_AT_BOUND = 1 << 20                 # geometries whose proven bound is at most this get slots of the bound itself
+_QT_BYTES = 256                                # two tables of 64 uint16 in front of the header in the uploaded table block
+
+_encode_route = {"on": True}                   # private A/B switch for measurements (False: Pillow encodes); no user option
+_encode_check = {"ok": None}                   # None: not verified in this process yet; False: this Pillow disagrees, route off
+_encode_counts = {"device": 0, "host": 0, "overflow": 0}
+_encode_tables = {}                            # (device, geometry, quality) -> u8 tensor [quantisation tables | header]
+
+
+def encode_geometry(h: int, w: int, channels: int, subsampling: str = "4:2:0") -> Tuple[int, ...]:
+    """The geometry words of frames of (h, w, channels): sampling 1 x 1 for grey, whatever `subsampling` says."""
+    hs, vs = SAMPLING[subsampling] if channels == 3 else (1, 1)
+    return (int(w), int(h), int(channels), hs, vs, 0)
+
+
+def encode_header(geometry, quality: int) -> Tuple[bytes, np.ndarray]:
+    """-> (the bytes FF D8 .. SOS of every file of `geometry` at `quality`, the two quantisation tables (2, 64) uint16 in
+    natural order).  Host only."""
+    g = _geom_array(geometry)
+    head = np.zeros(1024, dtype=np.uint8)
+    qt = np.zeros((2, 64), dtype=np.uint16)
+    n = _lib.load().hmm_jpeg_encode_header(g.ctypes.data, int(quality), head.ctypes.data, head.nbytes, qt.ctypes.data)
+    if n < 0:
+        _lib.check(n, "hmm_jpeg_encode_header")
+    return head[:n].tobytes(), qt
+
+
+def encode_bound(geometry) -> int:
+    """A proven upper bound on the bytes of one file of `geometry`; 0: the device route does not take the geometry."""
+    g = _geom_array(geometry)
+    return int(_lib.load().hmm_jpeg_encode_bound(g.ctypes.data))
+
+
+def encode_workspace_bytes(geometry, n: int) -> int:
+    g = _geom_array(geometry)
+    return max(int(_lib.load().hmm_jpeg_encode_workspace_bytes(g.ctypes.data, int(n))), 16)
+
+
+def encode_tables(geometry, quality: int, dev) -> torch.Tensor:
+    """The quantisation tables and the header of (geometry, quality) on `dev`, uploaded once per process."""
+    key = (str(dev), tuple(int(v) for v in geometry[:5]), int(quality))
+    block = _encode_tables.get(key)
+    if block is None:
+        head, qt = encode_header(geometry, quality)
+        host = np.concatenate([qt.reshape(-1).view(np.uint8), np.frombuffer(head, dtype=np.uint8)])
+        block = _encode_tables[key] = torch.from_numpy(host).to(dev)
+    return block
+
+
+def encode_device(frames: torch.Tensor, geometry, quality: int, channel_order: str, out: torch.Tensor, status: torch.Tensor,
+                  workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """frames (n, h, w, channels) u8, contiguous, on the GPU -> the file of frame i in out[i] (out: (n, stride) u8) and
+    status (n, 2) int32 = (ENCODED or ENCODE_OVERFLOW, bytes), on the current stream; nothing is synchronised.  workspace: a u8
+    tensor of at least encode_workspace_bytes(geometry, n); allocated here when not given."""
+    lib = _lib.load()
+    g = _geom_array(geometry)
+    n = frames.shape[0]
+    tables = encode_tables(geometry, quality, frames.device)
+    ws = workspace if workspace is not None else torch.empty(encode_workspace_bytes(geometry, n), dtype=torch.uint8,
+                                                             device=frames.device)
+    _lib.check(lib.hmm_jpeg_encode(frames.data_ptr(), n, g.ctypes.data, int(geometry[2]), CHANNEL_ORDER[channel_order],
+                                   tables.data_ptr(), tables.data_ptr() + _QT_BYTES, tables.numel() - _QT_BYTES, out.data_ptr(),
+                                   out.stride(0), status.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
+               "hmm_jpeg_encode")
+    return status
+
+
+def pillow_encode(frame: np.ndarray, quality: int = 95, subsampling: str = "4:2:0", channel_order: str = "RGB") -> bytes:
+    """The file the device route reproduces: Pillow's, for an (h, w, 3) frame in `channel_order` or an (h, w) grey frame."""
+    from PIL import Image
+    buf = io.BytesIO()
+    if frame.ndim == 3 and frame.shape[2] == 1:
+        frame = frame[..., 0]
+    if frame.ndim == 2:
+        Image.fromarray(np.ascontiguousarray(frame), "L").save(buf, "JPEG", quality=int(quality))
+    else:
+        rgb = frame[..., ::-1] if channel_order == "BGR" else frame
+        Image.fromarray(np.ascontiguousarray(rgb), "RGB").save(buf, "JPEG", quality=int(quality), subsampling=subsampling)
+    return buf.getvalue()
+
+
+def encode_stats() -> dict:
+    """Frames encoded per route since the process started: "device", "host" (Pillow) and, among the latter, "overflow" (frames
+    the kernel reported as not fitting their slot)."""
+    return dict(_encode_counts)
+
+
+def _encode_slot_bytes(geometry) -> int:
+    """Bytes of an output slot: the proven bound where that is small; else the raw frame's size plus the header, which a file
+    exceeds only for noise at the highest qualities -- such a frame is reported as overflowing and Pillow encodes it."""
+    bound = encode_bound(geometry)
+    if bound <= ENCODE_SLOT_AT_BOUND:
+        return bound
+    return min(bound, geometry[0] * geometry[1] * geometry[2] + 4096)
+
+
+def _as_batches(frames) -> List[Tuple[object, List[int]]]:
+    """frames -> [(a (n, h, w, c) uint8 numpy array or CUDA tensor, the positions of its frames in the result)], validated."""
+    def check(a):
+        if isinstance(a, torch.Tensor):
+            if a.dtype != torch.uint8:
+                raise TypeError(f"encode_jpeg takes uint8 frames, got a {a.dtype} tensor")
+            if not a.is_cuda:
+                raise TypeError("encode_jpeg takes numpy arrays or CUDA tensors, got a CPU tensor")
+        elif isinstance(a, np.ndarray):
+            if a.dtype != np.uint8:
+                raise TypeError(f"encode_jpeg takes uint8 frames, got a {a.dtype} array")
+        else:
+            raise TypeError(f"encode_jpeg takes uint8 numpy arrays or CUDA tensors, got {type(a).__name__}")
+        shape = tuple(a.shape)
+        if len(shape) == 2:
+            a = a[None, :, :, None]
+        elif len(shape) == 3 and shape[2] == 3:
+            a = a[None]
+        elif not (len(shape) == 4 and shape[3] in (1, 3)):
+            raise ValueError(f"encode_jpeg takes frames of shape (h, w, 3), (n, h, w, 3), (h, w) or (n, h, w, 1), got {shape}")
+        if not (1 <= a.shape[1] <= 65535 and 1 <= a.shape[2] <= 65535):
+            raise ValueError(f"encode_jpeg: a frame of {a.shape[2]} x {a.shape[1]} pixels (sides of 1..65535 are encoded)")
+        return a
+
+    if not isinstance(frames, (list, tuple)):
+        a = check(frames)
+        return [(a, list(range(a.shape[0])))]
+    groups, at = {}, 0                               # (on the device?, its device, h, w, channels) -> [(positions, frames)]
+    for f in frames:
+        a = check(f)
+        key = (isinstance(a, torch.Tensor), str(a.device) if isinstance(a, torch.Tensor) else "", *a.shape[1:])
+        groups.setdefault(key, []).append((list(range(at, at + a.shape[0])), a))
+        at += a.shape[0]
+    out = []
+    for key, members in groups.items():
+        stack = torch.cat if key[0] else np.concatenate
+        out.append((members[0][1] if len(members) == 1 else stack([a for _, a in members]), [i for where, _ in members for i in where]))
+    return out
+
+
+def _encode_batch(batch, quality: int, subsampling: str, channel_order: str, dev, slot_bytes: Optional[int]) -> Tuple[List[bytes], int, int]:
+    """One geometry -> (the files, how many the device encoded, how many overflowed their slot)."""
+    n, h, w, c = batch.shape
+    geometry = encode_geometry(h, w, c, subsampling)
+    resident = isinstance(batch, torch.Tensor)
+    host = None if resident else batch
+
+    def by_pillow(i):
+        nonlocal host
+        if host is None:
+            host = batch.cpu().numpy()
+        return pillow_encode(host[i], quality, subsampling, channel_order)
+
+    if not _encode_route["on"] or _encode_check["ok"] is False or encode_bound(geometry) == 0:
+        return [by_pillow(i) for i in range(n)], 0, 0
+    dev = batch.device if resident else dev
+    stride = int(slot_bytes) if slot_bytes else (_encode_slot_bytes(geometry) + 15) // 16 * 16
+    with torch.cuda.device(dev):
+        if resident:
+            frames = batch.contiguous()              # a contiguous tensor is encoded where it lies
+        else:
+            with _stage_lock:
+                ent = _pinned_slots(dev, batch.size, "frames")
+                ent.host[:batch.size].reshape(batch.shape)[...] = batch
+                frames = torch.empty(batch.shape, dtype=torch.uint8, device=dev)
+                frames.view(-1).copy_(ent.pinned[:batch.size], non_blocking=True)
+                ent.mark()
+        out = torch.empty(n, stride, dtype=torch.uint8, device=dev)
+        status = encode_device(frames, geometry, quality, channel_order, out, torch.empty(n, 2, dtype=torch.int32, device=dev)).cpu()
+        done = [i for i in range(n) if int(status[i, 0]) == ENCODED]
+        sizes = [int(status[i, 1]) for i in done]
+        packed = torch.cat([out[i, :size] for i, size in zip(done, sizes)]).cpu().numpy() if done else np.zeros(0, np.uint8)
+    files, at = [None] * n, 0
+    for i, size in zip(done, sizes):
+        files[i] = packed[at:at + size].tobytes()
+        at += size
+    if done and _encode_check["ok"] is None:
+        with _check_lock:
+            if _encode_check["ok"] is None:
+                ok = files[done[0]] == by_pillow(done[0])
+                if not ok:
+                    _log.warning("hippomm_amd.jpeg: the device JPEG encoder disagrees with this Pillow's encoder; "
+                                 "every frame is encoded by Pillow in this process")
+                _encode_check["ok"] = ok
+    if _encode_check["ok"] is False:
+        return [by_pillow(i) for i in range(n)], 0, 0
+    for i in range(n):
+        if files[i] is None:
+            files[i] = by_pillow(i)
+    return files, len(done), n - len(done)
+
+
+def encode_jpeg(frames, quality: int = 95, subsampling: str = "4:2:0", channel_order: str = "RGB", device=None,
+                stats: dict = None, _slot_bytes: Optional[int] = None) -> List[bytes]:
+    """Frames -> baseline JPEG files, encoded on the GPU; element i is, byte for byte, what
+    ``Image.fromarray(rgb_i).save(buf, "JPEG", quality=quality, subsampling=subsampling)`` writes ("L" mode for grey input): the
+    whole file, FF D8 to FF D9, no ``optimize``, no ``progressive``, no extra markers.
+
+    frames: a uint8 numpy array or CUDA tensor of shape (h, w, 3), (n, h, w, 3), (h, w) or (n, h, w, 1) (grey), or a list of
+    such arrays, which may differ in size and are grouped by geometry; the result follows the list's order.  A CUDA tensor is encoded where it lies; numpy frames
+    are uploaded through the package's pinned staging.  The read-back is the lengths, then one copy of the used bytes.
+    quality: 1..100.  subsampling: "4:4:4", "4:2:2" or "4:2:0"; ignored for grey.  channel_order: "RGB", or "BGR" (cv2 frames): the
+    kernel swaps.  Other dtypes raise ``TypeError``; other shapes, a side of 0 or above 65535 and other options ``ValueError``.
+
+    The first frame a process encodes on the device is compared with Pillow's bytes for the same input; on a mismatch (another
+    Pillow or libjpeg build) the device route is off for the process, a warning is logged and Pillow encodes.  A frame the kernel
+    does not report as encoded (its file would not fit its slot: noise at the highest qualities in large frames) is encoded by
+    Pillow too, so every call returns Pillow's bytes.  `stats`, when given, receives the frames per route: "device", "host" and,
+    among the latter, "overflow"."""
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= int(quality) <= 100:
+        raise ValueError(f"encode_jpeg: quality must be an integer in 1..100, not {quality!r}")
+    if subsampling not in SAMPLING:
+        raise ValueError(f"encode_jpeg: subsampling must be one of {sorted(SAMPLING)}, not {subsampling!r}")
+    if channel_order not in CHANNEL_ORDER:
+        raise ValueError(f"encode_jpeg: channel_order must be 'RGB' or 'BGR', not {channel_order!r}")
+    batches = _as_batches(frames)
+    total = sum(len(where) for _, where in batches)
+    files, on_device, overflow = [None] * total, 0, 0
+    if total:
+        dev = torch.device(device) if device is not None else _lib.require_gpu()
+        for batch, where in batches:
+            if not where:
+                continue
+            got, n_dev, n_over = _encode_batch(batch, int(quality), subsampling, channel_order, dev, _slot_bytes)
+            for i, data in zip(where, got):
+                files[i] = data
+            on_device += n_dev
+            overflow += n_over
+    _encode_counts["device"] += on_device
+    _encode_counts["host"] += total - on_device
+    _encode_counts["overflow"] += overflow
+    if stats is not None:
+        stats.update(device=on_device, host=total - on_device, overflow=overflow)
+    return files

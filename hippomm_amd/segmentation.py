@@ -4,6 +4,10 @@
     _compute_frame_similarity     <- hippomm/core/hippocampal_memory.py:980-991
     _segment_sequence             <- hippomm/core/hippocampal_memory.py:1002-1114 (segment_sequence: the same as a function)
 
+and for the write of every frame the formation path keeps (the JPEG is encoded on the GPU, byte for byte Pillow's file):
+
+    save_frame, save_frames       <- hippomm/core/batch_process.py:73-114 (cv2.imwrite)
+
 The SSIM is skimage 0.18.3 ``structural_similarity`` with its defaults, computed by ``hmm_ssim_pairs`` (exact integer 7x7 box sums,
 fp64 formula, fixed-order mean; include/hippomm_hip.h), on gray frames made by ``hmm_gray_u8`` with OpenCV's 8-bit BGR2GRAY rule.
 
@@ -27,10 +31,12 @@ There is no CPU fallback for the SSIM: without a GPU these calls raise ``HippoMM
 """
 from __future__ import annotations
 
+import logging
 import os
 import threading
 from collections import OrderedDict
 from dataclasses import dataclass
+from pathlib import Path
 from typing import Callable, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -553,3 +559,82 @@ def _segment_sequence(self, video_frames: Optional[List[str]] = None, frame_time
                             max_segment_duration=self.max_segment_duration, min_segment_duration=self.min_segment_duration,
                             frame_similarity_threshold=self.frame_similarity_threshold,
                             audio_silence_threshold=self.audio_silence_threshold, audio_track=audio_track)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# frames to disk: the write of extract_frames_from_video
+# ---------------------------------------------------------------------------------------------------------------------------------
+SAVE_QUALITY, SAVE_SUBSAMPLING = 95, "4:2:0"       # libjpeg's defaults under cv2.imwrite (recalled, not checkable here)
+_save_log = logging.getLogger(__name__)
+
+
+def _encode_bgr(frames) -> List[bytes]:
+    return jpeg.encode_jpeg(frames, quality=SAVE_QUALITY, subsampling=SAVE_SUBSAMPLING, channel_order="BGR")
+
+
+def save_frame(frame, frame_path) -> bool:
+    """Drop-in for ``batch_process.save_frame`` (batch_process.py:73-114) with the JPEG encoded on the GPU instead of by
+    ``cv2.imwrite``: a BGR (or grey) uint8 frame, a numpy array or a CUDA tensor, at quality 95 and 4:2:0.  The same return rules:
+    an existing file returns True untouched; ``None`` or an empty frame returns False; the parent directory is created; every
+    error is logged and returns False.  The bytes are Pillow's for the channel-swapped array (``jpeg.encode_jpeg``); they are not
+    claimed to equal OpenCV's file.
+
+    Measured on one MI355X (profiles/jpeg_encode.json; the encode alone, without the file write): one
+    1280 x 720 host frame 0.41 ms against 2.14 ms for Pillow on one thread, one 1920 x 1080 host frame 0.68 against 4.69 ms,
+    upload and read-back included; a resident frame 0.29 and 0.44 ms.  ``save_frames`` on 32 host frames: 5.9 ms (720p) and
+    12.6 ms (1080p) against 68 and 152 ms, bound by the upload.  No point measured was slower than Pillow on one thread; several
+    Pillow threads, and a GPU busy with the tower at the same time, were not measured."""
+    try:
+        frame_path = Path(frame_path)
+        if frame_path.exists():
+            return True
+        if frame is None or (frame.numel() if isinstance(frame, torch.Tensor) else frame.size) == 0:
+            _save_log.error(f"Invalid frame data for {frame_path}")
+            return False
+        frame_path.parent.mkdir(parents=True, exist_ok=True)
+        frame_path.write_bytes(_encode_bgr(frame)[0])
+        if not frame_path.exists():
+            _save_log.error(f"Frame file not found after save: {frame_path}")
+            return False
+        _save_log.debug(f"Successfully saved frame to {frame_path}")
+        return True
+    except Exception as e:                           # noqa: BLE001 - the reference's rule: log and return False
+        _save_log.error(f"Error saving frame to {frame_path}: {e}")
+        return False
+
+
+def save_frames(frames, paths) -> List[bool]:
+    """``save_frame`` for a batch: the frames that still need a file are encoded in one ``encode_jpeg`` call (one upload, one launch
+    sequence per geometry, one read-back).  frames: a list of frames or an (n, h, w, 3) array or tensor; paths: one per frame.
+    -> save_frame's answer for each."""
+    paths = [Path(p) for p in paths]
+    frames = list(frames) if frames is not None else []
+    if len(frames) != len(paths):
+        raise ValueError(f"save_frames: {len(frames)} frames for {len(paths)} paths")
+    results = [False] * len(paths)
+    todo = []
+    for i, (frame, path) in enumerate(zip(frames, paths)):
+        try:
+            if path.exists():
+                results[i] = True
+            elif frame is None or (frame.numel() if isinstance(frame, torch.Tensor) else frame.size) == 0:
+                _save_log.error(f"Invalid frame data for {path}")
+            else:
+                todo.append(i)
+        except Exception as e:                       # noqa: BLE001
+            _save_log.error(f"Error saving frame to {path}: {e}")
+    if not todo:
+        return results
+    try:
+        files = _encode_bgr([frames[i] for i in todo])
+    except Exception as e:                           # noqa: BLE001
+        _save_log.error(f"Error encoding {len(todo)} frames: {e}")
+        return results
+    for i, data in zip(todo, files):
+        try:
+            paths[i].parent.mkdir(parents=True, exist_ok=True)
+            paths[i].write_bytes(data)
+            results[i] = paths[i].exists()
+        except Exception as e:                       # noqa: BLE001
+            _save_log.error(f"Error saving frame to {paths[i]}: {e}")
+    return results

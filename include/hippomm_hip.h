@@ -545,6 +545,47 @@ int     hmm_jpeg_decode_coefs_device(const void* bitslots_dev, int n, size_t bit
                                      void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Baseline JPEG encoding on the GPU.  Replaces the libjpeg encode inside cv2.imwrite(frame_path, frame) of save_frame
+ * (batch_process.py:202-218), called by extract_frames_from_video (batch_process.py:73-114) for every frame it keeps.  The file
+ * is, byte for byte, what Pillow's Image.fromarray(rgb).save(buf, "JPEG", quality=q, subsampling=s) writes ("L" mode for grey):
+ * libjpeg's defaults -- the standard tables scaled by jpeg_quality_scaling with force_baseline, the standard Huffman tables, islow
+ * forward DCT, one interleaved scan, no restart markers, JFIF 1.01 with density 1 x 1.  Equality with OpenCV's own file is not claimed.
+ *
+ * geometry: int32[HMM_JPEG_GEOMETRY_INTS] as above = (width, height, components 1 or 3, luma h sampling, luma v sampling, unused):
+ *   sides of 1..65535; sampling 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0), ignored for grey; at most 2^32 / 1660 blocks a frame.
+ * hmm_jpeg_encode_header: host only, no GPU call.  Writes the bytes FF D8 .. SOS of every file of `geometry` at `quality` (1..100)
+ *   into header_out (header_capacity bytes of room; 623 are written for colour, 328 for grey) and the two quantisation tables,
+ *   natural order, into qtables_out (uint16[2][64]) -> the number of header bytes, or HMM_E_INVALID.
+ * hmm_jpeg_encode_workspace_bytes: workspace of a call with n frames of `geometry`; 0 for a bad geometry or n < 1.
+ * hmm_jpeg_encode_bound: an upper bound on the bytes of one file of `geometry`, proven in jpeg_layout.h (kJpegMaxBlockBits): no
+ *   block takes more than 22 + 63 * 26 bits, stuffing at most doubles the scan; 0 for a bad geometry.
+ * hmm_jpeg_encode: n frames at frames_dev, packed (n, height, width, channels) u8 with channels = components, channel_order
+ *   HMM_JPEG_ORDER_RGB or _BGR (ignored for grey) -> the complete file of frame i at out_dev + i * out_stride and status_dev[i] =
+ *   (status, bytes): HMM_JPEG_ENCODED and the file's length, or HMM_JPEG_ENCODE_OVERFLOW and the length it would have had when
+ *   that exceeds out_stride.  On overflow nothing at or beyond out_dev + (i + 1) * out_stride is touched and the slot's bytes
+ *   are unspecified; bytes of a slot beyond the file's length are never written.  qtables_dev (uint16[2][64]) and header_dev
+ *   (header_bytes bytes) are hmm_jpeg_encode_header's outputs for the same geometry, in device memory: the caller uploads them
+ *   (the library neither copies from host memory nor synchronises).  Five kernels and a memset of the workspace's bitstream part
+ *   on `stream`; the workspace needs no initialisation and no call reads what another left there.  After the call its first
+ *   n * blocks * 128 bytes hold the quantised blocks (int16[64] in zigzag order, blocks in scan order): the tests read them.
+ *   HMM_E_INVALID before any launch for
+ *   a null pointer, a bad geometry, channels != components, an unknown channel order, a header_bytes other than the geometry's,
+ *   a workspace not 16-byte aligned, a status not 4-byte aligned, out_stride 0; HMM_E_WORKSPACE for a workspace below
+ *   hmm_jpeg_encode_workspace_bytes(geometry, n); n = 0 is HMM_OK without a launch.
+ * ---------------------------------------------------------------------------------------- */
+#define HMM_JPEG_ENCODED          0
+#define HMM_JPEG_ENCODE_OVERFLOW  1
+#define HMM_JPEG_ORDER_RGB        0
+#define HMM_JPEG_ORDER_BGR        1
+int     hmm_jpeg_encode_header(const int32_t* geometry, int quality, uint8_t* header_out, size_t header_capacity,
+                               uint16_t* qtables_out);
+size_t  hmm_jpeg_encode_workspace_bytes(const int32_t* geometry, int n);
+size_t  hmm_jpeg_encode_bound(const int32_t* geometry);
+int     hmm_jpeg_encode(const uint8_t* frames_dev, int n, const int32_t* geometry, int channels, int channel_order,
+                        const uint16_t* qtables_dev, const uint8_t* header_dev, size_t header_bytes, uint8_t* out_dev,
+                        size_t out_stride, int32_t* status_dev, void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Building blocks of the encoder, exported so that each kernel is parity-tested on its own
  * against a reference of the same op (GEMM, LayerNorm, attention core: tests/test_gpu_ops.py; every other
  * stage: tests/test_gpu_stage_ops.py) and timed on its own (bench.py roofline).  bf16 tensors are raw uint16 bit patterns in device memory.
