@@ -27,6 +27,10 @@ and its counterpart, a baseline JPEG encoder on the GPU, byte for byte Pillow's 
 
     hippomm_amd.encode_jpeg                          <- Image.fromarray(rgb).save(buf, "JPEG", quality=q, subsampling=s)
     hippomm_amd.segmentation.save_frame, save_frames <- hippomm/core/batch_process.py:73-114 (cv2.imwrite)
+
+and, opt-in, the decoded pixels of the frames just saved kept on the device for the two reads that follow (hmm_jpeg_encoded_pixels):
+
+    save_frames(..., cache=FrameCache, tower_inputs=preprocess.TowerInputCache), ImageBind(..., tower_inputs=)
 """
 __version__ = "0.1.0"
 

@@ -91,6 +91,9 @@ _SIGNATURES = {
     "hmm_jpeg_encode_bound": (C.c_size_t, [c_ptr]),
     "hmm_jpeg_encode": (C.c_int, [c_ptr, C.c_int, c_ptr, C.c_int, C.c_int, c_ptr, c_ptr, C.c_size_t, c_ptr, C.c_size_t, c_ptr,
                                   c_ptr, C.c_size_t, c_ptr]),
+    "hmm_jpeg_encoded_pixels_workspace_bytes": (C.c_size_t, [c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "hmm_jpeg_encoded_pixels": (C.c_int, [c_ptr, C.c_int, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr,
+                                          C.c_size_t, c_ptr]),
     "hmm_encoder_create":(C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
     "hmm_encoder_destroy": (None, [c_ptr]),
     "hmm_encoder_load_param": (C.c_int, [c_ptr, C.c_char_p, c_ptr, C.c_int64, c_ptr]),

@@ -11,6 +11,9 @@
 //      height, edge samples and the first / last row replicated; plain replication when the downsampled width is 2 or less, as
 //      libjpeg-turbo chooses -- then jdcolor.c's fixed-point YCbCr -> RGB (SCALEBITS 16) and packing.  4 pixels per thread, three
 //      dword stores.
+//  (c) jpeg_encoded_idct_kernel: (a) for frames this process has just encoded -- it reads the quantised blocks hmm_jpeg_encode
+//      left in its workspace (scan order, zigzag order) and the encoder's two tables instead of coefficient slots, so the pixels a
+//      decoder would recover from the file are made without the file: hmm_jpeg_encoded_pixels.  (b) follows unchanged.
 // Integer arithmetic only, no scratch, vector stores only; HBM traffic is a few MB per 1080p frame.
 #include "hmm_common.h"
 #include "jpeg_layout.h"
@@ -61,6 +64,50 @@ __device__ __forceinline__ void islow_1d(int64_t d0, int64_t d1, int64_t d2, int
 // the table wraps and the SIMD code saturates, and Pillow's pixels are the SIMD code's.
 __device__ __forceinline__ uint32_t idct_limit(int64_t x) { return (uint32_t)(x < -128 ? 0 : x > 127 ? 255 : x + 128); }
 
+// What both IDCT kernels run once coefficient row t of every block lies in coef (natural order, LDS): column t of pass 1
+// dequantised by q, row t of pass 2, the range limit, and the row's 8 samples as one 8-byte store to dst.  Every thread of the
+// workgroup calls it (the barriers are inside); threads that are not live only take part in the barriers.
+__device__ __forceinline__ void idct_block(bool live, const int16_t* coef, int32_t* ws, int t, const uint16_t* __restrict__ q,
+                                           uint8_t* __restrict__ dst) {
+    __syncthreads();
+    if (live) {                                                     // pass 1: column t, dequantised
+        int64_t d[8], o[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) d[k] = (int64_t)coef[k * 8 + t] * (int64_t)q[k * 8 + t];
+        islow_1d(d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], o);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) ws[k * 8 + t] = (int32_t)descale(o[k], 13 - 2);
+    }
+    __syncthreads();
+    if (live) {                                                     // pass 2: row t
+        const int32_t* w = &ws[t * 8];
+        int64_t o[8];
+        islow_1d(w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], o);
+        uint2 px;
+        px.x = idct_limit(descale(o[0], 18)) | idct_limit(descale(o[1], 18)) << 8 | idct_limit(descale(o[2], 18)) << 16 |
+               idct_limit(descale(o[3], 18)) << 24;
+        px.y = idct_limit(descale(o[4], 18)) | idct_limit(descale(o[5], 18)) << 8 | idct_limit(descale(o[6], 18)) << 16 |
+               idct_limit(descale(o[7], 18)) << 24;
+        *reinterpret_cast<uint2*>(dst) = px;
+    }
+}
+
+// Block b of a frame's stored rectangles: its component, its place (bx, by) in that rectangle, and row t of it in the planes.
+struct IdctBlock {
+    int c, bx, by;
+};
+__device__ __forceinline__ IdctBlock idct_block_at(const JpegLayout& L, int64_t b) {
+    IdctBlock e;
+    e.c = b < L.block_off[1] ? 0 : (b < L.block_off[2] ? 1 : 2);
+    const int64_t local = b - L.block_off[e.c];
+    e.bx = (int)(local % L.nbx[e.c]);
+    e.by = (int)(local / L.nbx[e.c]);
+    return e;
+}
+__device__ __forceinline__ uint8_t* idct_row(uint8_t* __restrict__ planes, const JpegLayout& L, int64_t f, const IdctBlock& e, int t) {
+    return planes + f * L.plane_off[L.ncomp] + L.plane_off[e.c] + (int64_t)(e.by * 8 + t) * (L.nbx[e.c] * 8) + e.bx * 8;
+}
+
 __global__ __launch_bounds__(kIdctBlocks * 8) void jpeg_idct_kernel(const uint8_t* __restrict__ slots, int64_t slot_stride, int n,
                                                                     JpegLayout L, uint8_t* __restrict__ planes) {
     __shared__ int16_t s_coef[kIdctBlocks][64];
@@ -70,37 +117,45 @@ __global__ __launch_bounds__(kIdctBlocks * 8) void jpeg_idct_kernel(const uint8_
     const int64_t g = (int64_t)blockIdx.x * kIdctBlocks + lb;
     const bool live = g < (int64_t)n * per;
     const int64_t f = live ? g / per : 0, b = live ? g - f * per : 0;
-    const int c = b < L.block_off[1] ? 0 : (b < L.block_off[2] ? 1 : 2);
+    const IdctBlock e = idct_block_at(L, b);
     const uint8_t* slot = slots + f * slot_stride;
     if (live) {
         const uint4 row = *reinterpret_cast<const uint4*>(slot + kJpegQtBytes + b * kJpegBlockBytes + t * 16);
         *reinterpret_cast<uint4*>(&s_coef[lb][t * 8]) = row;
     }
-    __syncthreads();
-    if (live) {                                                     // pass 1: column t, dequantised
-        const uint16_t* q = reinterpret_cast<const uint16_t*>(slot) + 64 * c;
-        int64_t d[8], o[8];
+    idct_block(live, s_coef[lb], s_ws[lb], t, reinterpret_cast<const uint16_t*>(slot) + 64 * e.c, idct_row(planes, L, f, e, t));
+}
+
+// The same planes from the workspace a finished hmm_jpeg_encode call left behind: the quantised blocks of every frame, int16[64]
+// in zigzag order, in scan order (E), DC values absolute.  Block (gx, gy) of a component's grid is looked up in the scan -- a
+// colour MCU is hs x vs luma blocks row by row, then Cb, then Cr; a grey MCU is one block -- and the zigzag is undone while the
+// 16-byte row (zigzag positions 8 t .. 8 t + 7) is staged into LDS.  qtables: uint16[2][64], natural order (luma, chroma).
+__global__ __launch_bounds__(kIdctBlocks * 8) void jpeg_encoded_idct_kernel(const int16_t* __restrict__ coefs, int n, JpegLayout L,
+                                                                            JpegEncLayout E, const uint16_t* __restrict__ qtables,
+                                                                            uint8_t* __restrict__ planes) {
+    __shared__ int16_t s_coef[kIdctBlocks][64];
+    __shared__ int32_t s_ws[kIdctBlocks][64 + 1];
+    const int lb = threadIdx.x >> 3, t = threadIdx.x & 7;
+    const int64_t per = L.block_off[L.ncomp];
+    const int64_t g = (int64_t)blockIdx.x * kIdctBlocks + lb;
+    const bool live = g < (int64_t)n * per;
+    const int64_t f = live ? g / per : 0, b = live ? g - f * per : 0;
+    const IdctBlock e = idct_block_at(L, b);
+    if (live) {
+        const int gx = L.bx0[e.c] + e.bx, gy = L.by0[e.c] + e.by;
+        int64_t src;
+        if (E.ncomp == 1)
+            src = (int64_t)gy * E.mcux + gx;
+        else if (e.c == 0)
+            src = ((int64_t)(gy / E.vs) * E.mcux + gx / E.hs) * E.bpm + (gy % E.vs) * E.hs + gx % E.hs;
+        else
+            src = ((int64_t)gy * E.mcux + gx) * E.bpm + E.hs * E.vs + (e.c - 1);
+        const uint4 row = *reinterpret_cast<const uint4*>(coefs + (f * (int64_t)E.blocks + src) * 64 + t * 8);
+        const uint32_t w[4] = {row.x, row.y, row.z, row.w};
 #pragma unroll
-        for (int k = 0; k < 8; ++k) d[k] = (int64_t)s_coef[lb][k * 8 + t] * (int64_t)q[k * 8 + t];
-        islow_1d(d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], o);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s_ws[lb][k * 8 + t] = (int32_t)descale(o[k], 13 - 2);
+        for (int k = 0; k < 8; ++k) s_coef[lb][kJpegZigzag[t * 8 + k]] = (int16_t)(w[k >> 1] >> ((k & 1) * 16));
     }
-    __syncthreads();
-    if (live) {                                                     // pass 2: row t
-        const int32_t* w = &s_ws[lb][t * 8];
-        int64_t o[8];
-        islow_1d(w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], o);
-        uint2 px;
-        px.x = idct_limit(descale(o[0], 18)) | idct_limit(descale(o[1], 18)) << 8 | idct_limit(descale(o[2], 18)) << 16 |
-               idct_limit(descale(o[3], 18)) << 24;
-        px.y = idct_limit(descale(o[4], 18)) | idct_limit(descale(o[5], 18)) << 8 | idct_limit(descale(o[6], 18)) << 16 |
-               idct_limit(descale(o[7], 18)) << 24;
-        const int64_t local = b - L.block_off[c];
-        const int bx = (int)(local % L.nbx[c]), by = (int)(local / L.nbx[c]);
-        uint8_t* dst = planes + f * L.plane_off[L.ncomp] + L.plane_off[c] + (int64_t)(by * 8 + t) * (L.nbx[c] * 8) + bx * 8;
-        *reinterpret_cast<uint2*>(dst) = px;
-    }
+    idct_block(live, s_coef[lb], s_ws[lb], t, qtables + (e.c ? 64 : 0), idct_row(planes, L, f, e, t));
 }
 
 // Sample (sx, sy) of component c (component coordinates; inside the stored rectangle by construction of the layout).
@@ -228,6 +283,47 @@ extern "C" int hmm_jpeg_reconstruct(const void* slots_dev, int n, size_t slot_st
     const int64_t quads = ((int64_t)n * w * h + 3) / 4;
     const int64_t color_groups = (quads + kColorThreads - 1) / kColorThreads;
     HMM_REQUIRE(color_groups <= 0x7FFFFFFF, HMM_E_INVALID, "jpeg_reconstruct: output too large for one call");
+    jpeg_color_kernel<<<(unsigned)color_groups, kColorThreads, 0, st>>>(static_cast<const uint8_t*>(workspace_dev), L, n, rgb_out_dev);
+    HMM_LAUNCH_CHECK();
+    return HMM_OK;
+}
+
+// The window's planes are those of hmm_jpeg_reconstruct for the same geometry and window, so the workspace is too.
+extern "C" size_t hmm_jpeg_encoded_pixels_workspace_bytes(const int32_t* geometry, int n, int x0, int y0, int w, int h) {
+    JpegEncLayout E;
+    if (!geometry || !jpeg_enc_layout(geometry[0], geometry[1], geometry[2], geometry[3], geometry[4], &E)) return 0;
+    return hmm_jpeg_workspace_bytes(geometry, n, x0, y0, w, h);
+}
+
+extern "C" int hmm_jpeg_encoded_pixels(const void* encode_workspace_dev, int n, const int32_t* geometry, const uint16_t* qtables_dev,
+                                       int x0, int y0, int w, int h, uint8_t* rgb_out_dev, void* workspace_dev,
+                                       size_t workspace_bytes, hmm_stream_t stream) {
+    HMM_REQUIRE(encode_workspace_dev && geometry && qtables_dev && rgb_out_dev && workspace_dev, HMM_E_INVALID,
+                "jpeg_encoded_pixels: null pointer");
+    HMM_REQUIRE(n >= 0, HMM_E_INVALID, "jpeg_encoded_pixels: negative frame count %d", n);
+    JpegEncLayout E;
+    HMM_REQUIRE(jpeg_enc_layout(geometry[0], geometry[1], geometry[2], geometry[3], geometry[4], &E), HMM_E_INVALID,
+                "jpeg_encoded_pixels: bad geometry (%d x %d, %d components, sampling %d x %d): what hmm_jpeg_encode takes",
+                geometry[0], geometry[1], geometry[2], geometry[3], geometry[4]);
+    JpegLayout L;
+    HMM_REQUIRE(layout_of(geometry, x0, y0, w, h, &L), HMM_E_INVALID, "jpeg_encoded_pixels: bad window (%d, %d, %d, %d) for a %d x %d frame",
+                x0, y0, w, h, geometry[0], geometry[1]);
+    HMM_REQUIRE(((uintptr_t)encode_workspace_dev & 15) == 0 && ((uintptr_t)workspace_dev & 15) == 0 && ((uintptr_t)rgb_out_dev & 3) == 0 &&
+                    ((uintptr_t)qtables_dev & 1) == 0,
+                HMM_E_INVALID, "jpeg_encoded_pixels: both workspaces must be 16-byte aligned, the output 4-byte and the tables 2-byte aligned");
+    if (n == 0) return HMM_OK;
+    const size_t need = hmm_jpeg_workspace_bytes(geometry, n, x0, y0, w, h);
+    HMM_REQUIRE(workspace_bytes >= need, HMM_E_WORKSPACE, "jpeg_encoded_pixels: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int64_t blocks = (int64_t)n * L.block_off[L.ncomp];
+    const int64_t groups = (blocks + kIdctBlocks - 1) / kIdctBlocks;
+    HMM_REQUIRE(groups <= 0x7FFFFFFF, HMM_E_INVALID, "jpeg_encoded_pixels: %lld blocks in one call is too many", (long long)blocks);
+    const int64_t quads = ((int64_t)n * w * h + 3) / 4;
+    const int64_t color_groups = (quads + kColorThreads - 1) / kColorThreads;
+    HMM_REQUIRE(color_groups <= 0x7FFFFFFF, HMM_E_INVALID, "jpeg_encoded_pixels: output too large for one call");
+    jpeg_encoded_idct_kernel<<<(unsigned)groups, kIdctBlocks * 8, 0, st>>>(static_cast<const int16_t*>(encode_workspace_dev), n, L, E,
+                                                                           qtables_dev, static_cast<uint8_t*>(workspace_dev));
+    HMM_LAUNCH_CHECK();
     jpeg_color_kernel<<<(unsigned)color_groups, kColorThreads, 0, st>>>(static_cast<const uint8_t*>(workspace_dev), L, n, rgb_out_dev);
     HMM_LAUNCH_CHECK();
     return HMM_OK;

@@ -247,6 +247,16 @@ def synthetic_state_dict(towers: Iterable[str] = ("vision",), seed: int = 1234, 
     return sd
 
 
+def _forward_ranges(n: int, step: int):
+    """[lo, hi) ranges of at most max(step, 3) rows covering n rows, none of a single row unless n is 1: where a lone row would be
+    left over, the range before it gives one up (the tower stays in one arithmetic regime; see _vision_from_files)."""
+    step = max(int(step), 3)
+    cuts = list(range(0, n, step)) + [n]
+    if n > 1 and cuts[-1] - cuts[-2] == 1:
+        cuts[-2] -= 1
+    return list(zip(cuts[:-1], cuts[1:]))
+
+
 class ImageBind(nn.Module):
     """ImageBind model for multimodal feature extraction (MI355X towers)."""
 
@@ -255,8 +265,9 @@ class ImageBind(nn.Module):
                  towers: Iterable[str] = ("vision", "audio"),
                  depth: Optional[Dict[str, int]] = None,
                  max_batch: Optional[Dict[str, int]] = None,
-                 tokenizer=None):
+                 tokenizer=None, tower_inputs=None):
         super().__init__()
+        self.tower_inputs = tower_inputs            # a preprocess.TowerInputCache (or None; may be set later): _vision_from_files
         self.tokenizer = tokenizer                  # str list -> (B,77) int64 (imagebind.data.load_and_transform_text)
         if self.tokenizer is None and "text" in tuple(towers):
             from .tokenizer import SimpleTokenizer, find_bpe_vocab     # upstream's merge table, if it is on disk
@@ -337,12 +348,33 @@ class ImageBind(nn.Module):
         """Image paths -> (B,1024) embeddings as ONE pipeline: the host decodes while the GPU uploads, resizes and already
         embeds the frames that are ready (hippomm_amd.preprocess.vision_pipeline).  Same bits as forward(load_data(...)):
         every range the tower sees has at least two frames unless the call has one, and the tower's embedding of a frame
-        does not depend on the batch it rides in within that regime (tests/test_gpu_encoder_batch.py)."""
-        from .preprocess import vision_pipeline
+        does not depend on the batch it rides in within that regime (tests/test_gpu_encoder_batch.py).
+
+        With ``self.tower_inputs`` (a preprocess.TowerInputCache that segmentation.save_frames filled while it wrote these files)
+        the paths it holds are neither read nor decoded: all hits are gathered and forwarded; with some misses, those go through
+        load_and_transform_vision_data_device and every row is placed in call order before the forward.  Same bits again: the
+        cached rows are the preprocess kernel's output for Pillow's decode of the file, and the forward keeps to ranges of at
+        least two frames.  No cache, or no hit at all: the pipeline above, untouched."""
+        from .preprocess import load_and_transform_vision_data_device, vision_pipeline
         paths = [img if isinstance(img, str) else img.filename for img in images]
         tower = self.model.towers[ModalityType.VISION]
         step = int(self.model.max_batch.get(ModalityType.VISION, 256))
         emb = torch.empty(len(paths), 1024, dtype=torch.float32, device=self.device)
+        cache = getattr(self, "tower_inputs", None)
+        rows = [cache.get(p) for p in paths] if cache is not None else []
+        if any(r is not None for r in rows):
+            n = len(paths)
+            misses = [i for i, r in enumerate(rows) if r is None]
+            if misses:
+                x = torch.empty(n, 3, 224, 224, dtype=torch.float32, device=self.device)
+                hits = [i for i, r in enumerate(rows) if r is not None]
+                x[torch.tensor(hits, device=self.device)] = torch.stack([rows[i] for i in hits]).to(self.device)
+                x[torch.tensor(misses, device=self.device)] = load_and_transform_vision_data_device([paths[i] for i in misses], self.device)
+            else:
+                x = torch.stack(rows).to(self.device)
+            for lo, hi in _forward_ranges(n, step):
+                tower.forward_into(x[lo:hi], emb[lo:hi])
+            return emb
 
         def embed(x, lo, hi):
             for s in range(lo, hi, step):

@@ -19,6 +19,10 @@ Encoding goes the other way (hippomm_amd/csrc/jpeg_encode.hip): ``encode_jpeg`` 
 into complete baseline files on the GPU -- colour transform, chroma downsampling, islow forward DCT, quantisation, the Huffman
 pass, padding and byte stuffing -- each, byte for byte, the file ``Image.fromarray(x).save(buf, "JPEG", quality=q,
 subsampling=s)`` writes.  The same self-check guards it, and a frame the kernel does not report as encoded is encoded by Pillow.
+
+``encode_jpeg(..., return_decoded=True)`` also returns what ``decode_jpeg`` would make of those files, without the files: the
+quantised blocks and tables the encoder leaves on the device are all a decoder recovers from a file (hmm_jpeg_encoded_pixels in
+jpeg.hip).  ``segmentation.save_frames(cache=, tower_inputs=)`` hands those pixels to the readers' caches.
 """
 from __future__ import annotations
 
@@ -464,6 +468,31 @@ def encode_device(frames: torch.Tensor, geometry, quality: int, channel_order: s
     return status
 
 
+def encoded_pixels_workspace_bytes(geometry, n: int, window) -> int:
+    g = _geom_array(geometry)
+    return max(int(_lib.load().hmm_jpeg_encoded_pixels_workspace_bytes(g.ctypes.data, int(n), *map(int, window))), 16)
+
+
+def encoded_pixels_device(encode_workspace: torch.Tensor, n: int, geometry, quality: int, window, out: torch.Tensor,
+                          workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The decoded pixels of the n frames an ``encode_device`` call of the same geometry and quality has just encoded, from the
+    workspace tensor that call used (given to it as ``workspace=``): out (n, h, w, 3) u8 = the window (x0, y0, w, h) of
+    ``Image.open(file_i).convert("RGB")``, on the current stream, which must be the stream of the encode.  Nothing is
+    synchronised and the encoder's workspace is only read.  workspace: a u8 tensor of at least
+    encoded_pixels_workspace_bytes(geometry, n, window); allocated here when not given."""
+    if int(n) == 0:
+        return out                                   # an empty tensor has no address to hand over
+    lib = _lib.load()
+    g = _geom_array(geometry)
+    x0, y0, w, h = map(int, window)
+    tables = encode_tables(geometry, quality, encode_workspace.device)
+    ws = workspace if workspace is not None else torch.empty(encoded_pixels_workspace_bytes(geometry, n, window), dtype=torch.uint8,
+                                                             device=encode_workspace.device)
+    _lib.check(lib.hmm_jpeg_encoded_pixels(encode_workspace.data_ptr(), int(n), g.ctypes.data, tables.data_ptr(), x0, y0, w, h,
+                                           out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "hmm_jpeg_encoded_pixels")
+    return out
+
+
 def pillow_encode(frame: np.ndarray, quality: int = 95, subsampling: str = "4:2:0", channel_order: str = "RGB") -> bytes:
     """The file the device route reproduces: Pillow's, for an (h, w, 3) frame in `channel_order` or an (h, w) grey frame."""
     from PIL import Image
@@ -533,12 +562,27 @@ def _as_batches(frames) -> List[Tuple[object, List[int]]]:
     return out
 
 
-def _encode_batch(batch, quality: int, subsampling: str, channel_order: str, dev, slot_bytes: Optional[int]) -> Tuple[List[bytes], int, int]:
-    """One geometry -> (the files, how many the device encoded, how many overflowed their slot)."""
+def _decoded_from_files(files: Sequence[bytes], dev, window) -> List[torch.Tensor]:
+    """The existing decode of the bytes (decode_jpeg's work, per frame), raising the first error."""
+    results, errors, _ = _decode_many(list(files), dev, window)
+    for exc in errors:
+        if exc is not None:
+            raise exc
+    return results
+
+
+def _encode_batch(batch, quality: int, subsampling: str, channel_order: str, dev, slot_bytes: Optional[int],
+                  want_decoded: bool = False, window=None):
+    """One geometry -> (the files, how many the device encoded, how many overflowed their slot, the decoded frames -- an
+    (n, h, w, 3) tensor or a list of (h, w, 3) tensors; None unless want_decoded --, how many of them never left the device)."""
     n, h, w, c = batch.shape
     geometry = encode_geometry(h, w, c, subsampling)
     resident = isinstance(batch, torch.Tensor)
     host = None if resident else batch
+    crop = (0, 0, w, h) if window is None else tuple(int(v) for v in window)
+    if want_decoded and not (crop[0] >= 0 and crop[1] >= 0 and crop[2] > 0 and crop[3] > 0 and crop[0] + crop[2] <= w
+                             and crop[1] + crop[3] <= h):
+        raise ValueError(f"window {tuple(window)} does not fit a {w} x {h} frame")
 
     def by_pillow(i):
         nonlocal host
@@ -546,10 +590,15 @@ def _encode_batch(batch, quality: int, subsampling: str, channel_order: str, dev
             host = batch.cpu().numpy()
         return pillow_encode(host[i], quality, subsampling, channel_order)
 
+    def all_by_pillow():
+        files = [by_pillow(i) for i in range(n)]
+        return files, 0, 0, (_decoded_from_files(files, batch.device if resident else dev, window) if want_decoded else None), 0
+
     if not _encode_route["on"] or _encode_check["ok"] is False or encode_bound(geometry) == 0:
-        return [by_pillow(i) for i in range(n)], 0, 0
+        return all_by_pillow()
     dev = batch.device if resident else dev
     stride = int(slot_bytes) if slot_bytes else (_encode_slot_bytes(geometry) + 15) // 16 * 16
+    pixels = None
     with torch.cuda.device(dev):
         if resident:
             frames = batch.contiguous()              # a contiguous tensor is encoded where it lies
@@ -561,7 +610,13 @@ def _encode_batch(batch, quality: int, subsampling: str, channel_order: str, dev
                 frames.view(-1).copy_(ent.pinned[:batch.size], non_blocking=True)
                 ent.mark()
         out = torch.empty(n, stride, dtype=torch.uint8, device=dev)
-        status = encode_device(frames, geometry, quality, channel_order, out, torch.empty(n, 2, dtype=torch.int32, device=dev)).cpu()
+        ws = torch.empty(encode_workspace_bytes(geometry, n), dtype=torch.uint8, device=dev)
+        status = encode_device(frames, geometry, quality, channel_order, out, torch.empty(n, 2, dtype=torch.int32, device=dev), ws)
+        if want_decoded and _route["on"] and _check["ok"] is not False:
+            # the quantised blocks are still in ws: the pixels a decoder would recover from the files, before the files exist.
+            # Queued behind the encode, ahead of the read-back; kept only for frames whose file is the device's (below).
+            pixels = encoded_pixels_device(ws, n, geometry, quality, crop, torch.empty(n, crop[3], crop[2], 3, dtype=torch.uint8, device=dev))
+        status = status.cpu()
         done = [i for i in range(n) if int(status[i, 0]) == ENCODED]
         sizes = [int(status[i, 1]) for i in done]
         packed = torch.cat([out[i, :size] for i, size in zip(done, sizes)]).cpu().numpy() if done else np.zeros(0, np.uint8)
@@ -578,15 +633,26 @@ def _encode_batch(batch, quality: int, subsampling: str, channel_order: str, dev
                                  "every frame is encoded by Pillow in this process")
                 _encode_check["ok"] = ok
     if _encode_check["ok"] is False:
-        return [by_pillow(i) for i in range(n)], 0, 0
+        return all_by_pillow()
     for i in range(n):
         if files[i] is None:
             files[i] = by_pillow(i)
-    return files, len(done), n - len(done)
+    if not want_decoded:
+        return files, len(done), n - len(done), None, 0
+    # the device decoder is guarded as everywhere: its first frame in this process is compared with Pillow's decode
+    if pixels is None or not done or not route_ok(files[done[0]], dev):
+        return files, len(done), n - len(done), _decoded_from_files(files, dev, window), 0
+    if len(done) == n:
+        return files, n, 0, pixels, n
+    rest = sorted(set(range(n)) - set(done))
+    decoded = list(pixels)
+    for i, frame in zip(rest, _decoded_from_files([files[i] for i in rest], dev, window)):   # Pillow wrote these files
+        decoded[i] = frame
+    return files, len(done), n - len(done), decoded, len(done)
 
 
 def encode_jpeg(frames, quality: int = 95, subsampling: str = "4:2:0", channel_order: str = "RGB", device=None,
-                stats: dict = None, _slot_bytes: Optional[int] = None) -> List[bytes]:
+                stats: dict = None, _slot_bytes: Optional[int] = None, return_decoded: bool = False, window=None):
     """Frames -> baseline JPEG files, encoded on the GPU; element i is, byte for byte, what
     ``Image.fromarray(rgb_i).save(buf, "JPEG", quality=quality, subsampling=subsampling)`` writes ("L" mode for grey input): the
     whole file, FF D8 to FF D9, no ``optimize``, no ``progressive``, no extra markers.
@@ -601,7 +667,16 @@ def encode_jpeg(frames, quality: int = 95, subsampling: str = "4:2:0", channel_o
     Pillow or libjpeg build) the device route is off for the process, a warning is logged and Pillow encodes.  A frame the kernel
     does not report as encoded (its file would not fit its slot: noise at the highest qualities in large frames) is encoded by
     Pillow too, so every call returns Pillow's bytes.  `stats`, when given, receives the frames per route: "device", "host" and,
-    among the latter, "overflow"."""
+    among the latter, "overflow".
+
+    return_decoded=True: -> (files, decoded), where decoded[i] is, bit for bit, ``decode_jpeg([files[i]], window=window)[0]`` --
+    Pillow's decode of the file just written, uint8 RGB (grey: R = G = B) on the device, cut to ``window`` = (x0, y0, w, h) when
+    given (it must fit every frame: ``ValueError``) -- without the file being read or even written: the quantised blocks the
+    encoder left on the device and its tables are all a decoder recovers from the file (hmm_jpeg_encoded_pixels: dequantise, islow
+    IDCT, upsampling, colour).  One (n, h, w, 3) tensor when the sizes agree, else a list, as decode_jpeg returns.  Frames whose
+    file Pillow wrote (the route off, the first-frame check failed, a slot overflowed) take their pixels from the existing decode
+    of those bytes, and so do all frames when the device decoder's own first-frame check (``route_ok``) does not pass.  `stats`
+    then also receives "decoded_resident": the frames whose pixels never left the device."""
     if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= int(quality) <= 100:
         raise ValueError(f"encode_jpeg: quality must be an integer in 1..100, not {quality!r}")
     if subsampling not in SAMPLING:
@@ -611,14 +686,22 @@ def encode_jpeg(frames, quality: int = 95, subsampling: str = "4:2:0", channel_o
     batches = _as_batches(frames)
     total = sum(len(where) for _, where in batches)
     files, on_device, overflow = [None] * total, 0, 0
+    decoded, resident, whole = [None] * total, 0, None
     if total:
         dev = torch.device(device) if device is not None else _lib.require_gpu()
         for batch, where in batches:
             if not where:
                 continue
-            got, n_dev, n_over = _encode_batch(batch, int(quality), subsampling, channel_order, dev, _slot_bytes)
+            got, n_dev, n_over, pixels, n_res = _encode_batch(batch, int(quality), subsampling, channel_order, dev, _slot_bytes,
+                                                              return_decoded, window)
             for i, data in zip(where, got):
                 files[i] = data
+            if return_decoded:
+                if isinstance(pixels, torch.Tensor) and where == list(range(total)):
+                    whole = pixels                   # one geometry, in order: the kernel's output is the result
+                for i, frame in zip(where, pixels):
+                    decoded[i] = frame
+                resident += n_res
             on_device += n_dev
             overflow += n_over
     _encode_counts["device"] += on_device
@@ -626,4 +709,12 @@ def encode_jpeg(frames, quality: int = 95, subsampling: str = "4:2:0", channel_o
     _encode_counts["overflow"] += overflow
     if stats is not None:
         stats.update(device=on_device, host=total - on_device, overflow=overflow)
-    return files
+        if return_decoded:
+            stats["decoded_resident"] = resident
+    if not return_decoded:
+        return files
+    if not total:
+        return files, torch.empty(0, 0, 0, 3, dtype=torch.uint8)
+    if whole is not None:
+        return files, whole
+    return files, (torch.stack(decoded) if len({tuple(d.shape) for d in decoded}) == 1 else decoded)

@@ -9,8 +9,9 @@ The host only computes Pillow's coefficient tables (a few hundred rows of taps p
 from __future__ import annotations
 
 import math
+import os
 from functools import lru_cache
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -134,6 +135,84 @@ def preprocess_frames_device(frames_u8: torch.Tensor) -> torch.Tensor:
     frames_u8 = frames_u8.contiguous()
     out = torch.empty(frames_u8.shape[0], 3, OUT, OUT, dtype=torch.float32, device=frames_u8.device)
     return _preprocess_into(frames_u8, out)
+
+
+TOWER_INPUT_BYTES = 3 * OUT * OUT * 4              # one (3, 224, 224) fp32 tower input: 602 112 bytes
+TOWER_CACHE_BYTES = 4 << 30                        # about 6 900 frames
+
+
+class TowerInputCache:
+    """The vision tower's inputs -- (3, 224, 224) fp32, resized, cropped and normalised -- of image files, on the device, keyed by
+    (path, size, mtime) like ``segmentation.FrameCache``; least recently used entries leave once more than ``cache_bytes`` are held.
+    ``segmentation.save_frames(..., tower_inputs=cache)`` fills it from the decoded pixels of the files it writes (the existing
+    preprocess kernel on the same needed_window cut-outs ``vision_pipeline`` feeds it, so the same bits);
+    ``ImageBind(..., tower_inputs=cache)`` consults it in ``extract_features``.  A file rewritten since it was put has another
+    key: a miss.  The rows put by one call share one allocation, which returns to the allocator when the last of them has left."""
+
+    def __init__(self, cache_bytes: int = TOWER_CACHE_BYTES):
+        from collections import OrderedDict
+        import threading
+        self.cache_bytes = int(cache_bytes)
+        self.entries = OrderedDict()                   # key -> (3, 224, 224) fp32
+        self.by_path = {}                              # path -> its current key
+        self.bytes = 0
+        self.hits = self.misses = 0
+        self.lock = threading.Lock()
+
+    @staticmethod
+    def key(path):
+        st = os.stat(path)
+        return (str(path), st.st_size, st.st_mtime_ns)
+
+    def __len__(self) -> int:
+        return len(self.entries)
+
+    def _drop(self, k) -> None:
+        x = self.entries.pop(k, None)
+        if x is not None:
+            self.bytes -= x.numel() * x.element_size()
+            if self.by_path.get(k[0]) == k:
+                del self.by_path[k[0]]
+
+    def put(self, path, x: torch.Tensor) -> None:
+        """x: the (3, 224, 224) fp32 tower input of the file at `path` as it is now."""
+        if tuple(x.shape) != (3, OUT, OUT) or x.dtype != torch.float32:
+            raise ValueError(f"a tower input is (3, {OUT}, {OUT}) fp32, got {tuple(x.shape)} {x.dtype}")
+        k = self.key(path)
+        with self.lock:
+            old = self.by_path.get(k[0])
+            if old is not None:                        # the same file again, or a rewritten one: one entry per path
+                self._drop(old)
+            self.entries[k] = x
+            self.by_path[k[0]] = k
+            self.bytes += x.numel() * x.element_size()
+            while self.bytes > self.cache_bytes and len(self.entries) > 1:
+                self._drop(next(iter(self.entries)))
+
+    def get(self, path) -> Optional[torch.Tensor]:
+        """-> the tower input of the file as it is now, or None (never put, evicted, rewritten since, or unreadable)."""
+        try:
+            k = self.key(path)
+        except OSError:
+            k = None
+        with self.lock:
+            x = self.entries.get(k) if k is not None else None
+            if x is None:
+                self.misses += 1
+                return None
+            self.entries.move_to_end(k)
+            self.hits += 1
+            return x
+
+    def put_frames(self, paths: Sequence[str], frames_u8: torch.Tensor, full_hw: Tuple[int, int] = None) -> None:
+        """Decoded RGB frames (n, h, w, 3) uint8 on the device of the files at `paths` -> their tower inputs, by the existing
+        preprocess kernel in one launch.  full_hw: the frames are the needed_window cut-outs of full_hw = (height, width) frames."""
+        if len(paths) != frames_u8.shape[0]:
+            raise ValueError(f"{frames_u8.shape[0]} frames for {len(paths)} paths")
+        x = torch.empty(len(paths), 3, OUT, OUT, dtype=torch.float32, device=frames_u8.device)
+        _preprocess_into(frames_u8.contiguous(), x, full_hw)
+        for p, row in zip(paths, x):
+            self.put(p, row)
 
 
 # ---- host side of the vision path: files -> decoded RGB in pinned memory, overlapped with the GPU -------------------------------

@@ -273,6 +273,40 @@ class FrameCache:
                 return slab, slot
         return None
 
+    def _store(self, h: int, w: int, keys: Sequence[tuple], up: torch.Tensor, dev, protect: int = 0) -> Tuple[_Slab, List[int]]:
+        """Frames (n, h, w, 3) u8 RGB `up` on `dev` -> gray + min / max into n slots of the slab of that size, under `keys`.
+        protect: slots of that slab the caller still needs (they are the most recently used: the n new ones do not evict them)."""
+        slab = self._slab(h, w, protect + len(keys), dev)
+        gray = torch.empty((len(keys), h, w), dtype=torch.uint8, device=dev)
+        minmax = torch.empty((len(keys), 2), dtype=torch.int32, device=dev)
+        _gray_into(up, 0, gray, minmax)
+        slots = [slab.take(k) for k in keys]
+        idx = torch.tensor(slots, dtype=torch.int64).to(dev)
+        slab.gray.index_copy_(0, idx, gray)
+        slab.minmax.index_copy_(0, idx, minmax)
+        return slab, slots
+
+    def put(self, path, rgb: torch.Tensor) -> None:
+        """Insert the decoded frame(s) of file(s) that exist: path and an (h, w, 3) uint8 RGB tensor on the device -- what
+        ``load`` would decode from the file, e.g. ``encode_jpeg(..., return_decoded=True)``'s pixels of the file just written -- or
+        a list of paths and an (n, h, w, 3) tensor.  Gray and min / max go under ``key(path)`` of the file as it is now, by the
+        same kernel and into the same slabs as ``load``, with its eviction rules (least recently used first; the frames of one
+        call never evict each other).  ``decodes`` does not move.  An entry of the same path under an older key (the file has
+        been rewritten since) is simply never hit again."""
+        paths = [path] if isinstance(path, (str, os.PathLike)) else list(path)
+        frames = rgb[None] if rgb.dim() == 3 else rgb
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] != len(paths):
+            raise ValueError(f"FrameCache.put takes (h, w, 3) uint8 RGB per path, got {tuple(rgb.shape)} {rgb.dtype} for {len(paths)} paths")
+        keys = [self.key(p) for p in paths]
+        n, h, w = frames.shape[:3]
+        with self.lock:
+            for slab in self.slabs.values():           # a path put twice keeps one slot
+                for k in keys:
+                    slot = slab.slots.pop(k, None)
+                    if slot is not None:
+                        slab.free.append(slot)
+            self._store(h, w, keys, frames.contiguous(), frames.device)
+
     def load(self, paths: Sequence[str], dev) -> dict:
         """Decode the paths that are not cached; -> {path: (slab, slot) or the exception its decode raised}.  The frames of one
         call are never evicted by that call."""
@@ -304,14 +338,7 @@ class FrameCache:
         def store(h, w, items, up):
             """items [(path, key)] of frames (n, h, w, 3) u8 `up` on the device -> gray + min / max into the slab."""
             protect = sum(1 for v in out.values() if isinstance(v, tuple) and v[0].h == h and v[0].w == w)
-            slab = self._slab(h, w, protect + len(items), dev)
-            gray = torch.empty((len(items), h, w), dtype=torch.uint8, device=dev)
-            minmax = torch.empty((len(items), 2), dtype=torch.int32, device=dev)
-            _gray_into(up, 0, gray, minmax)
-            slots = [slab.take(k) for _, k in items]
-            idx = torch.tensor(slots, dtype=torch.int64).to(dev)
-            slab.gray.index_copy_(0, idx, gray)
-            slab.minmax.index_copy_(0, idx, minmax)
+            slab, slots = self._store(h, w, [k for _, k in items], up, dev, protect)
             for (p, _), slot in zip(items, slots):
                 out[p] = (slab, slot)
 
@@ -568,11 +595,31 @@ SAVE_QUALITY, SAVE_SUBSAMPLING = 95, "4:2:0"       # libjpeg's defaults under cv
 _save_log = logging.getLogger(__name__)
 
 
-def _encode_bgr(frames) -> List[bytes]:
-    return jpeg.encode_jpeg(frames, quality=SAVE_QUALITY, subsampling=SAVE_SUBSAMPLING, channel_order="BGR")
+def _encode_bgr(frames, **decoded):
+    """-> the files; with return_decoded=True (and window=), (files, their decoded RGB pixels on the device)."""
+    return jpeg.encode_jpeg(frames, quality=SAVE_QUALITY, subsampling=SAVE_SUBSAMPLING, channel_order="BGR", **decoded)
 
 
-def save_frame(frame, frame_path) -> bool:
+def _fill_caches(written, cache, tower_inputs) -> None:
+    """written: (path, the decoded RGB of the file just written -- the whole frame, or its needed_window when only the tower
+    asks --, the frame's (h, w)).  One gray launch and one preprocess launch per frame size."""
+    from . import preprocess as pp
+    groups = {}
+    for path, rgb, hw in written:
+        groups.setdefault((tuple(rgb.shape), hw), []).append((path, rgb))
+    for (shape, hw), items in groups.items():
+        paths = [str(p) for p, _ in items]
+        frames = torch.stack([f for _, f in items])
+        if cache is not None:
+            cache.put(paths, frames)
+        if tower_inputs is not None:
+            if shape[:2] == hw:                          # whole frames: the tower's taps touch this window of them
+                x0, y0, ww, wh = pp.needed_window(*hw)
+                frames = frames[:, y0:y0 + wh, x0:x0 + ww]
+            tower_inputs.put_frames(paths, frames, hw)
+
+
+def save_frame(frame, frame_path, cache: Optional[FrameCache] = None, tower_inputs=None) -> bool:
     """Drop-in for ``batch_process.save_frame`` (batch_process.py:73-114) with the JPEG encoded on the GPU instead of by
     ``cv2.imwrite``: a BGR (or grey) uint8 frame, a numpy array or a CUDA tensor, at quality 95 and 4:2:0.  The same return rules:
     an existing file returns True untouched; ``None`` or an empty frame returns False; the parent directory is created; every
@@ -583,7 +630,15 @@ def save_frame(frame, frame_path) -> bool:
     1280 x 720 host frame 0.41 ms against 2.14 ms for Pillow on one thread, one 1920 x 1080 host frame 0.68 against 4.69 ms,
     upload and read-back included; a resident frame 0.29 and 0.44 ms.  ``save_frames`` on 32 host frames: 5.9 ms (720p) and
     12.6 ms (1080p) against 68 and 152 ms, bound by the upload.  No point measured was slower than Pillow on one thread; several
-    Pillow threads, and a GPU busy with the tower at the same time, were not measured."""
+    Pillow threads, and a GPU busy with the tower at the same time, were not measured.
+
+    ``cache`` / ``tower_inputs``: see ``save_frames``; the same return rules."""
+    if cache is not None or tower_inputs is not None:
+        try:
+            return save_frames([frame], [frame_path], cache=cache, tower_inputs=tower_inputs)[0]
+        except Exception as e:                       # noqa: BLE001 - the reference's rule: log and return False
+            _save_log.error(f"Error saving frame to {frame_path}: {e}")
+            return False
     try:
         frame_path = Path(frame_path)
         if frame_path.exists():
@@ -603,10 +658,22 @@ def save_frame(frame, frame_path) -> bool:
         return False
 
 
-def save_frames(frames, paths) -> List[bool]:
+def save_frames(frames, paths, cache: Optional[FrameCache] = None, tower_inputs=None) -> List[bool]:
     """``save_frame`` for a batch: the frames that still need a file are encoded in one ``encode_jpeg`` call (one upload, one launch
     sequence per geometry, one read-back).  frames: a list of frames or an (n, h, w, 3) array or tensor; paths: one per frame.
-    -> save_frame's answer for each."""
+    -> save_frame's answer for each.
+
+    Opt-in, for the two reads of these files that follow in the formation path.  While a frame is encoded the GPU holds all a
+    decoder would recover from its file, so the decoded pixels -- Pillow's decode of the file, to the bit -- are made there
+    (``encode_jpeg(return_decoded=True)``) and handed to
+      cache: a ``FrameCache`` -- gray frame and min / max of every file this call wrote, under the key of the file as written, so
+        that ``segment_sequence`` / ``_compute_frame_similarity`` over these paths (``PathScorer(cache)``, or ``default_cache()``)
+        decode nothing: ``cache.decodes`` does not move, scores and segments are the same bits;
+      tower_inputs: a ``preprocess.TowerInputCache`` -- the (3, 224, 224) tower input of every file this call wrote, for
+        ``ImageBind(..., tower_inputs=)``.extract_features over these paths.
+    A frame whose file already existed is not put (the file may not be this frame's), nor one whose write failed.  Rewriting a
+    file later changes its key: the path is then a miss and is decoded from the file as before.  Return values and logging are
+    those without the caches; a failure while filling a cache is logged and leaves the answer True (the file is there)."""
     paths = [Path(p) for p in paths]
     frames = list(frames) if frames is not None else []
     if len(frames) != len(paths):
@@ -625,16 +692,35 @@ def save_frames(frames, paths) -> List[bool]:
             _save_log.error(f"Error saving frame to {path}: {e}")
     if not todo:
         return results
+    resident = cache is not None or tower_inputs is not None
+    decoded = None
     try:
-        files = _encode_bgr([frames[i] for i in todo])
+        if resident:
+            # only the tower asks and every frame has one size: the pixels under the resampling taps are all it needs
+            sizes = {tuple(frames[i].shape[:2]) for i in todo}
+            window = None
+            if cache is None and len(sizes) == 1:
+                from . import preprocess as pp
+                window = pp.needed_window(*next(iter(sizes)))
+            files, decoded = _encode_bgr([frames[i] for i in todo], return_decoded=True, window=window)
+        else:
+            files = _encode_bgr([frames[i] for i in todo])
     except Exception as e:                           # noqa: BLE001
         _save_log.error(f"Error encoding {len(todo)} frames: {e}")
         return results
-    for i, data in zip(todo, files):
+    written = []
+    for k, (i, data) in enumerate(zip(todo, files)):
         try:
             paths[i].parent.mkdir(parents=True, exist_ok=True)
             paths[i].write_bytes(data)
             results[i] = paths[i].exists()
+            if results[i] and resident:
+                written.append((paths[i], decoded[k], tuple(int(v) for v in frames[i].shape[:2])))
         except Exception as e:                       # noqa: BLE001
             _save_log.error(f"Error saving frame to {paths[i]}: {e}")
+    if written:
+        try:
+            _fill_caches(written, cache, tower_inputs)
+        except Exception as e:                       # noqa: BLE001
+            _save_log.error(f"Error keeping {len(written)} decoded frames on the device: {e}")
     return results

@@ -586,6 +586,36 @@ int     hmm_jpeg_encode(const uint8_t* frames_dev, int n, const int32_t* geometr
                         size_t out_stride, int32_t* status_dev, void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The decoded pixels of frames that were just encoded, without their files: Image.open(file_i).convert("RGB") cut to the window,
+ * to the bit, from what hmm_jpeg_encode left on the device.  A decoder recovers from a file the quantised coefficients and the
+ * quantisation tables; both are still there (the encoder's workspace and qtables_dev), so no entropy coding is undone and no
+ * byte crosses the bus.  The reads of _segment_sequence and of load_and_transform_vision_data that follow save_frame in the
+ * formation path need only these pixels.
+ *
+ * hmm_jpeg_encoded_pixels_workspace_bytes: workspace of a call with n frames of `geometry` cut to the window (the u8 sample planes
+ *   of hmm_jpeg_reconstruct); 0 for a geometry hmm_jpeg_encode does not take, a bad window or n < 1.
+ * hmm_jpeg_encoded_pixels: encode_workspace_dev is the workspace a finished hmm_jpeg_encode call of the same `geometry` and n left
+ *   behind, ordered before this call on `stream`; qtables_dev the tables that call was given.  -> rgb_out_dev (n, h, w, 3) u8, the
+ *   window [x0, x0 + w) x [y0, y0 + h) of each frame; grey frames come out with R = G = B.  Two kernels on `stream` (dequantise +
+ *   IDCT of the blocks under the window and its upsampling halo, looked up in scan order with the zigzag undone; then the
+ *   upsampling and colour kernel of hmm_jpeg_reconstruct); the encoder's workspace and the tables are only read; no
+ *   synchronisation, no allocation, no initialisation of the workspace needed.
+ *   No frame can be refused, so there is no status: the decoder's refusal (a column of dequantised magnitudes above 5800, beyond
+ *   which the first IDCT pass would leave int16) guards against corrupt files, and these blocks come from 8-bit samples -- an
+ *   orthonormal block has sum |F| <= sqrt(8) * 1024 < 2897 per column, and dequantising a quantised value adds at most q / 2 per
+ *   coefficient, 8 * 255 / 2 = 1020 per column at the most: under 4000 with the forward DCT's own rounding.  The largest column sum over the test table, which holds
+ *   the largest AC coefficients 8-bit input can give (`extreme`) and the coarsest tables (quality 1), is 2230
+ *   (tests/test_cpu_jpeg_resident.py).
+ *   HMM_E_INVALID before any launch for a null pointer, n < 0, a geometry hmm_jpeg_encode does not take, a window outside the
+ *   frame, a workspace (either) not 16-byte aligned, an output not 4-byte or tables not 2-byte aligned; HMM_E_WORKSPACE for a
+ *   workspace below hmm_jpeg_encoded_pixels_workspace_bytes; n = 0 is HMM_OK without a launch.
+ * ---------------------------------------------------------------------------------------- */
+size_t  hmm_jpeg_encoded_pixels_workspace_bytes(const int32_t* geometry, int n, int x0, int y0, int w, int h);
+int     hmm_jpeg_encoded_pixels(const void* encode_workspace_dev, int n, const int32_t* geometry, const uint16_t* qtables_dev,
+                                int x0, int y0, int w, int h, uint8_t* rgb_out_dev, void* workspace_dev, size_t workspace_bytes,
+                                hmm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Building blocks of the encoder, exported so that each kernel is parity-tested on its own
  * against a reference of the same op (GEMM, LayerNorm, attention core: tests/test_gpu_ops.py; every other
  * stage: tests/test_gpu_stage_ops.py) and timed on its own (bench.py roofline).  bf16 tensors are raw uint16 bit patterns in device memory.
