@@ -31,7 +31,13 @@ and its counterpart, a baseline JPEG encoder on the GPU, byte for byte Pillow's 
 and, opt-in, the decoded pixels of the frames just saved kept on the device for the two reads that follow (hmm_jpeg_encoded_pixels):
 
     save_frames(..., cache=FrameCache, tower_inputs=preprocess.TowerInputCache), ImageBind(..., tower_inputs=)
+
+and the callers' retrieval step with the reference's row and fallback rules applied on the device (hmm_rank_segment_hits_filtered):
+
+    hippomm_amd.find_relevant_video_segments         <- hippomm/core/hippocampal_memory.py:3127-3279
+    hippomm_amd.find_relevant_audio_segments         <- hippomm/core/hippocampal_memory.py:3281-3383
 """
 __version__ = "0.1.0"
 
 from .jpeg import decode_jpeg, encode_jpeg  # noqa: E402,F401
+from .retrieval import feature_entries, find_relevant_audio_segments, find_relevant_video_segments  # noqa: E402,F401

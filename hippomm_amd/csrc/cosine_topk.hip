@@ -446,6 +446,78 @@ struct ScanPlan {
 // One workgroup: a best-64 tournament over the (E, k) keys through a 4096-key window.  Key = (monotone(sim) << 32) | ~position, so
 // equal similarities rank by position (event, then rank inside the event) and every key is unique; slots beyond an event's count
 // are 0 and never chosen.  NaN similarities rank first, as they do inside an event.
+// Which slots are candidates is a compile-time policy (FILTER): RankEveryHit is hmm_rank_segment_hits[_multi], RankRelevantHits adds
+// the reference's per-event rules (see there).  select(want, has_bound, bound) leaves the `want` <= 64 best candidate keys -- with
+// has_bound, of those strictly below `bound` -- sorted at w[0 ..), zeros behind them, and ends on a barrier.
+struct RankEveryHit {
+    const float* __restrict__ sims; const int32_t* __restrict__ counts;      // of this workgroup's question
+    using pos_t = int64_t;
+    __device__ __forceinline__ int count(int64_t e) const { return counts[e]; }
+    __device__ __forceinline__ float sim(int64_t pos) const { return sims[pos]; }
+    __device__ __forceinline__ bool candidate(int64_t, int64_t) const { return true; }
+};
+
+template <class FILTER>
+__device__ __forceinline__ void select_ranked_hits(uint64_t* w, int* n_cand, int64_t total, int k, int want, bool has_bound,
+                                                   uint64_t bound, const FILTER& filter) {
+    using pos_t = typename FILTER::pos_t;                                    // positions are below 2^32: a policy may index in 32 bits
+    auto key_at = [&](pos_t pos) -> uint64_t {
+        if (pos < (pos_t)total && (int)(pos % k) < filter.count(pos / k) && filter.candidate(pos, pos / k)) {
+            const uint64_t key = make_key(filter.sim(pos), 0xFFFFFFFFu - (uint32_t)pos);
+            return has_bound && key >= bound ? 0ull : key;
+        }
+        return 0ull;
+    };
+    if (total <= (int64_t)1024 * (kChunk / 64)) {
+        // Quick route (2000 events x 5 hits: 33 -> ~10 us): every thread's largest key -> the want-th largest of those 1024 maxima, M,
+        // is a lower bound of the want-th largest key, and since keys are unique exactly `want` threads hold keys >= M: the at most
+        // want x ceil(total / 1024) <= 4096 keys at or above M contain the answer and are ranked alone.
+        uint64_t best = 0ull;
+        for (pos_t pos = threadIdx.x; pos < (pos_t)total; pos += 1024) {
+            const uint64_t key = key_at(pos);
+            best = key > best ? key : best;
+        }
+        w[threadIdx.x] = best;
+        if (threadIdx.x == 0) *n_cand = 0;
+        __syncthreads();
+        top64_desc(w, 1024);
+        const uint64_t m = w[want - 1];                                      // 0: fewer than `want` threads hold a hit at all
+        __syncthreads();
+        for (pos_t pos = threadIdx.x; pos < (pos_t)total; pos += 1024) {
+            const uint64_t key = key_at(pos);
+            if (key != 0ull && key >= m) w[atomicAdd(n_cand, 1)] = key;      // m == 0: fewer than want x ceil(total / 1024) hits exist
+        }
+        __syncthreads();
+        const int n2 = pow2_at_least(*n_cand, 64);
+        for (int t = *n_cand + threadIdx.x; t < n2; t += 1024) w[t] = 0ull;
+        __syncthreads();
+        top64_desc(w, n2);
+    } else {
+        fold_topk<kChunk, 1024, false>(w, total, want, [&](int64_t base, int have, int take) {
+            for (int t = threadIdx.x; t < take; t += 1024) w[have + t] = key_at((pos_t)(base + t));
+        });
+    }
+}
+
+// w[0 .. want): sorted keys, zeros last.  count_ranked_hits: the keys that are hits (every thread the same count);
+// write_ranked_hits: the n hits behind them at out[0 .. n), -1 / -1 / 0 up to `want`.
+__device__ __forceinline__ int count_ranked_hits(const uint64_t* w, int want) {
+    int n = 0;
+    for (int t = 0; t < want; ++t) n += w[t] != 0ull;
+    return n;
+}
+__device__ __forceinline__ void write_ranked_hits(const uint64_t* w, int n, int want, int k, const int64_t* __restrict__ idx,
+                                                  const float* __restrict__ sims, int64_t* __restrict__ event_out,
+                                                  int64_t* __restrict__ row_out, float* __restrict__ sim_out) {
+    for (int t = threadIdx.x; t < want; t += 1024) {
+        const bool valid = t < n;
+        const int64_t pos = valid ? (int64_t)(0xFFFFFFFFu - (uint32_t)key_row(w[t])) : 0;
+        event_out[t] = valid ? pos / k : -1;
+        row_out[t] = valid ? idx[pos] : -1;
+        sim_out[t] = valid ? sims[pos] : 0.0f;
+    }
+}
+
 __global__ __launch_bounds__(1024) void rank_segment_hits_kernel(const int64_t* __restrict__ idx, const float* __restrict__ sims,
                                                                  const int32_t* __restrict__ counts, int n_segments, int k, int keep,
                                                                  int64_t* __restrict__ event_out, int64_t* __restrict__ row_out,
@@ -457,50 +529,124 @@ __global__ __launch_bounds__(1024) void rank_segment_hits_kernel(const int64_t* 
     idx += blockIdx.x * total; sims += blockIdx.x * total; counts += (int64_t)blockIdx.x * n_segments;
     event_out += (int64_t)blockIdx.x * keep; row_out += (int64_t)blockIdx.x * keep; sim_out += (int64_t)blockIdx.x * keep;
     n_out += blockIdx.x;
-    auto key_at = [&](int64_t pos) -> uint64_t {
-        if (pos < total && (int)(pos % k) < counts[pos / k])
-            return make_key(sims[pos], 0xFFFFFFFFu - (uint32_t)pos);
-        return 0ull;
-    };
-    if (total <= (int64_t)1024 * (kChunk / 64)) {
-        // Quick route (2000 events x 5 hits: 33 -> ~10 us): every thread's largest key -> the keep-th largest of those 1024 maxima, M,
-        // is a lower bound of the keep-th largest key, and since keys are unique exactly `keep` threads hold keys >= M: the at most
-        // keep x ceil(total / 1024) <= 4096 keys at or above M contain the answer and are ranked alone.
-        uint64_t best = 0ull;
-        for (int64_t pos = threadIdx.x; pos < total; pos += 1024) {
-            const uint64_t key = key_at(pos);
-            best = key > best ? key : best;
-        }
-        w[threadIdx.x] = best;
-        if (threadIdx.x == 0) n_cand = 0;
-        __syncthreads();
-        top64_desc(w, 1024);
-        const uint64_t m = w[keep - 1];                                      // 0: fewer than `keep` threads hold a hit at all
-        __syncthreads();
-        for (int64_t pos = threadIdx.x; pos < total; pos += 1024) {
-            const uint64_t key = key_at(pos);
-            if (key != 0ull && key >= m) w[atomicAdd(&n_cand, 1)] = key;     // m == 0: fewer than keep x ceil(total / 1024) hits exist
-        }
-        __syncthreads();
-        const int n2 = pow2_at_least(n_cand, 64);
-        for (int t = n_cand + threadIdx.x; t < n2; t += 1024) w[t] = 0ull;
-        __syncthreads();
-        top64_desc(w, n2);
-    } else {
-        fold_topk<kChunk, 1024, false>(w, total, keep, [&](int64_t base, int have, int take) {
-            for (int t = threadIdx.x; t < take; t += 1024) w[have + t] = key_at(base + t);
-        });
-    }
-    int n = 0;
-    for (int t = 0; t < keep; ++t) n += w[t] != 0ull;                        // every thread the same count (keys are sorted, zeros last)
+    select_ranked_hits(w, &n_cand, total, k, keep, false, 0ull, RankEveryHit{sims, counts});
+    const int n = count_ranked_hits(w, keep);
     if (threadIdx.x == 0) *n_out = n;
-    for (int t = threadIdx.x; t < keep; t += 1024) {
-        const bool valid = t < n;
-        const int64_t pos = valid ? (int64_t)(0xFFFFFFFFu - (uint32_t)key_row(w[t])) : 0;
-        event_out[t] = valid ? pos / k : -1;
-        row_out[t] = valid ? idx[pos] : -1;
-        sim_out[t] = valid ? sims[pos] : 0.0f;
+    write_ranked_hits(w, n, keep, k, idx, sims, event_out, row_out, sim_out);
+}
+
+// The reference's two per-event rules ahead of that ranking (hippocampal_memory.py:3143-3277, :3294-3381), for one question:
+//   fallback rule   an event flagged in `defer` whose best similarity (slot 0; NaN ranks first, and NaN < x is false, as
+//                   np.max(...) < 0.4 is) is below min_similarity leaves the ranking: it is DEFERRED to the caller;
+//   row rule        a hit of any other event counts only when its row is below the event's row limit (the kept key frames).
+struct RankRelevantHits {
+    const int64_t* __restrict__ idx; const float* __restrict__ sims; const int32_t* __restrict__ counts;   // of this question
+    const int64_t* __restrict__ row_limits; const uint8_t* __restrict__ defer;
+    int k; float min_similarity;
+    using pos_t = uint32_t;                                                  // fewer than 2^32 slots per question (checked by the host)
+    __device__ __forceinline__ int count(uint32_t e) const { return counts[e]; }
+    __device__ __forceinline__ float sim(uint32_t pos) const { return sims[pos]; }
+    __device__ __forceinline__ bool deferred(uint32_t e) const {
+        return defer && defer[e] != 0 && counts[e] > 0 && sims[(uint64_t)e * k] < min_similarity;
     }
+    __device__ __forceinline__ bool candidate(uint32_t pos, uint32_t e) const {
+        return !deferred(e) && (!row_limits || idx[pos] < row_limits[e]);
+    }
+};
+// Where the question's outputs go.
+struct RankedOutputs {
+    int64_t* event; int64_t* row; float* sim; int32_t* n; int32_t* n_deferred;
+};
+
+// hmm_rank_segment_hits_filtered[_multi]: one workgroup per question.  First the deferred events, compacted in ascending order
+// (chunks of 1024 events, a block-wide prefix sum of the flags in each: wave ballots, then the 16 wave totals) with their (idx, sims,
+// count) slices behind them; then the ranking of the remaining candidates in rounds of 64: round r ranks the keys strictly below
+// the last key of round r - 1, and since keys are unique the rounds' lists, one after the other, are the stable order.
+__global__ __attribute__((amdgpu_flat_work_group_size(1024, 1024))) void rank_segment_hits_filtered_kernel(
+        const int64_t* __restrict__ idx, const float* __restrict__ sims, const int32_t* __restrict__ counts, int n_segments, int k,
+        int keep, const int64_t* __restrict__ row_limits, const uint8_t* __restrict__ defer, float min_similarity,
+        int64_t* __restrict__ event_out, int64_t* __restrict__ row_out, float* __restrict__ sim_out, int32_t* __restrict__ n_out,
+        int32_t* __restrict__ deferred_event_out, int32_t* __restrict__ n_deferred_out, int64_t* __restrict__ deferred_idx_out,
+        float* __restrict__ deferred_sim_out, int32_t* __restrict__ deferred_count_out) {
+    __shared__ uint64_t w[kChunk];
+    __shared__ uint64_t ranked[1024];                                        // the keys of all rounds, best first
+    __shared__ int n_cand;
+    __shared__ int wave_total[16];
+    __shared__ int slot_of[1024];
+    // Scalar registers are the scarce resource here: the tournament (three inlined copies) keeps its lane masks in them, and with
+    // 18 arguments, the per-question pointers computed from them and the round loop's invariants the allocator spilled 41 of them
+    // to vector lanes.  So: the question's inputs and outputs wait in LDS and are read where they are used (as vector values);
+    // the outputs are decoded once, behind the last round; the work-group size is fixed, so no tournament reads the dispatch
+    // packet; and what a round derives from the slot count and k is derived in that round, not kept from before the loop.
+    __shared__ RankRelevantHits filter;
+    __shared__ RankedOutputs out;
+    const int64_t total = (int64_t)n_segments * k;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid < 64) {                                                          // one wave, every lane the same values
+        filter = RankRelevantHits{idx + blockIdx.x * total, sims + blockIdx.x * total, counts + (int64_t)blockIdx.x * n_segments, row_limits,
+                                  defer, k, min_similarity};
+        const int64_t q_keep = (int64_t)blockIdx.x * keep;
+        out = RankedOutputs{event_out + q_keep, row_out + q_keep, sim_out + q_keep, n_out + blockIdx.x, n_deferred_out + blockIdx.x};
+    }
+    __syncthreads();
+
+    int n_deferred = 0;
+    deferred_event_out += (int64_t)blockIdx.x * n_segments;
+    if (defer) {                                                             // block-uniform
+        deferred_count_out += (int64_t)blockIdx.x * n_segments;
+        deferred_idx_out += blockIdx.x * total; deferred_sim_out += blockIdx.x * total;
+        for (int e0 = 0; e0 < n_segments; e0 += 1024) {
+            const int here = n_segments - e0 < 1024 ? n_segments - e0 : 1024;
+            const bool flag = tid < here && filter.deferred(e0 + tid);
+            const unsigned long long ballot = __ballot(flag);
+            if (lane == 0) wave_total[wave] = __popcll(ballot);
+            __syncthreads();
+            int before = __popcll(ballot & ((1ull << lane) - 1ull)), chunk_total = 0;
+            for (int v = 0; v < 16; ++v) {
+                before += v < wave ? wave_total[v] : 0;
+                chunk_total += wave_total[v];
+            }
+            const int slot = n_deferred + before;                            // slot <= e0 + tid < n_segments
+            slot_of[tid] = flag ? slot : -1;
+            if (flag) {
+                deferred_event_out[slot] = e0 + tid;
+                deferred_count_out[slot] = filter.counts[e0 + tid];
+            }
+            __syncthreads();
+            for (int64_t i = tid; i < (int64_t)here * k; i += 1024) {        // the slices of this chunk's deferred events, unchanged
+                const int local = (int)(i / k), s = slot_of[local];
+                if (s >= 0) {
+                    const int64_t from = (int64_t)e0 * k + i, to = (int64_t)s * k + (i - (int64_t)local * k);
+                    deferred_idx_out[to] = filter.idx[from];
+                    deferred_sim_out[to] = filter.sims[from];
+                }
+            }
+            n_deferred += chunk_total;
+            __syncthreads();                                                 // wave_total and slot_of are rewritten by the next chunk
+        }
+    }
+    for (int e = n_deferred + tid; e < n_segments; e += 1024) deferred_event_out[e] = -1;
+
+    int n = 0;
+    uint64_t bound = 0ull;
+    int64_t slots = total;
+    int per_event = k;
+    for (int first = 0; first < keep; first += 64) {
+        const int want = keep - first < 64 ? keep - first : 64;
+        asm volatile("" : "+s"(slots), "+s"(per_event));                     // opaque per round: nothing derived from them is hoisted
+        select_ranked_hits(w, &n_cand, slots, per_event, want, first > 0, bound, filter);
+        const int found = count_ranked_hits(w, want);
+        if (tid < found) ranked[first + tid] = w[tid];
+        n += found;
+        bound = w[want - 1];
+        __syncthreads();                                                     // w is rewritten by the next round
+        if (found < want) break;                                             // block-uniform: no candidate is left
+    }
+    if (tid == 0) {
+        *out.n = n;
+        *out.n_deferred = n_deferred;
+    }
+    write_ranked_hits(ranked, n, keep, k, filter.idx, filter.sims, out.event, out.row, out.sim);
 }
 
 static int64_t next_pow2(int64_t x) { int64_t p = 1; while (p < x) p <<= 1; return p; }
@@ -781,4 +927,47 @@ extern "C" int hmm_rank_segment_hits_multi(const int64_t* idx_dev, const float* 
                                                                                       n_out_dev);
     HMM_LAUNCH_CHECK();
     return HMM_OK;
+}
+
+// Both filtered rankings: `what` names the entry point in its errors.
+static int rank_filtered(const char* what, const int64_t* idx, const float* sims, const int32_t* counts, int n_queries, int n_segments,
+                         int k, int keep, const int64_t* row_limits, const uint8_t* defer, float min_similarity, int64_t* event_out,
+                         int64_t* row_out, float* sim_out, int32_t* n_out, int32_t* deferred_event_out, int32_t* n_deferred_out,
+                         int64_t* deferred_idx_out, float* deferred_sim_out, int32_t* deferred_count_out, hmm_stream_t stream) {
+    HMM_REQUIRE(idx && sims && counts && event_out && row_out && sim_out && n_out && deferred_event_out && n_deferred_out &&
+                    deferred_idx_out && deferred_sim_out && deferred_count_out, HMM_E_INVALID,
+                "%s: null pointer (only row_limits and defer may be null)", what);
+    HMM_REQUIRE(n_queries >= 1 && n_segments >= 1 && k >= 1 && keep >= 1 && keep <= 1024 &&
+                    (int64_t)n_segments * k < (int64_t)0xFFFFFFFFll, HMM_E_INVALID,
+                "%s: need n_queries >= 1, n_segments >= 1, k >= 1, 1 <= keep <= 1024 and fewer than 2^32 hits per query "
+                "(got %d x %d x %d, keep %d)", what, n_queries, n_segments, k, keep);
+    rank_segment_hits_filtered_kernel<<<n_queries, 1024, 0, static_cast<hipStream_t>(stream)>>>(
+        idx, sims, counts, n_segments, k, keep, row_limits, defer, min_similarity, event_out, row_out, sim_out, n_out,
+        deferred_event_out, n_deferred_out, deferred_idx_out, deferred_sim_out, deferred_count_out);
+    HMM_LAUNCH_CHECK();
+    return HMM_OK;
+}
+
+extern "C" int hmm_rank_segment_hits_filtered(const int64_t* idx_dev, const float* sims_dev, const int32_t* counts_dev, int n_segments,
+                                              int k, int keep, const int64_t* row_limits_dev, const uint8_t* defer_dev,
+                                              float min_similarity, int64_t* event_out_dev, int64_t* row_out_dev, float* sim_out_dev,
+                                              int32_t* n_out_dev, int32_t* deferred_event_out_dev, int32_t* n_deferred_out_dev,
+                                              int64_t* deferred_idx_out_dev, float* deferred_sim_out_dev,
+                                              int32_t* deferred_count_out_dev, hmm_stream_t stream) {
+    return rank_filtered("rank_segment_hits_filtered", idx_dev, sims_dev, counts_dev, 1, n_segments, k, keep, row_limits_dev, defer_dev,
+                         min_similarity, event_out_dev, row_out_dev, sim_out_dev, n_out_dev, deferred_event_out_dev, n_deferred_out_dev,
+                         deferred_idx_out_dev, deferred_sim_out_dev, deferred_count_out_dev, stream);
+}
+
+extern "C" int hmm_rank_segment_hits_filtered_multi(const int64_t* idx_dev, const float* sims_dev, const int32_t* counts_dev,
+                                                    int n_queries, int n_segments, int k, int keep, const int64_t* row_limits_dev,
+                                                    const uint8_t* defer_dev, float min_similarity, int64_t* event_out_dev,
+                                                    int64_t* row_out_dev, float* sim_out_dev, int32_t* n_out_dev,
+                                                    int32_t* deferred_event_out_dev, int32_t* n_deferred_out_dev,
+                                                    int64_t* deferred_idx_out_dev, float* deferred_sim_out_dev,
+                                                    int32_t* deferred_count_out_dev, hmm_stream_t stream) {
+    return rank_filtered("rank_segment_hits_filtered_multi", idx_dev, sims_dev, counts_dev, n_queries, n_segments, k, keep,
+                         row_limits_dev, defer_dev, min_similarity, event_out_dev, row_out_dev, sim_out_dev, n_out_dev,
+                         deferred_event_out_dev, n_deferred_out_dev, deferred_idx_out_dev, deferred_sim_out_dev,
+                         deferred_count_out_dev, stream);
 }

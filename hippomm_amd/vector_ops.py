@@ -85,6 +85,21 @@ def _ranking_layout(*shape):
     return _Packed((_I64, shape), (_I64, shape), (_F32, shape), (_I32, shape[:-1] or (1,)))
 
 
+@functools.lru_cache(maxsize=64)
+def _relevant_layout(*shape):
+    """A filtered ranking: event | row | sim | count, then deferred events | their number | their counts; shape = (E, keep) or
+    (Q, E, keep).  Everything the host needs to decide whether the deferred events' hits have to be read at all."""
+    lead, (E, keep) = shape[:-2], shape[-2:]
+    return _Packed((_I64, lead + (keep,)), (_I64, lead + (keep,)), (_F32, lead + (keep,)), (_I32, lead + (1,)),
+                   (_I32, lead + (E,)), (_I32, lead + (1,)), (_I32, lead + (E,)))
+
+
+@functools.lru_cache(maxsize=64)
+def _deferred_layout(n_queries, cells):
+    """The deferred events' own hits, compacted per question: idx (Q, E * k) | sims (Q, E * k)."""
+    return _Packed((_I64, (n_queries, cells)), (_F32, (n_queries, cells)))
+
+
 def _queries_2d(queries, device=None) -> torch.Tensor:
     """queries (numpy or torch) as a (Q,1024) tensor with Q >= 1; with ``device``, contiguous fp32 on it."""
     q = queries if isinstance(queries, torch.Tensor) else torch.from_numpy(np.asarray(queries))
@@ -128,6 +143,7 @@ class FeatureStore:
         self._ws = None                                  # the scan workspace every route shares (_scratch)
         self._buf, self._shadow_buf = None, None         # the capacity-sized buffers of a store that has grown (EventStore)
         self._pinned = None                              # the read-back staging buffer (EventStore._read_back)
+        self._pinned_rules = None                        # the upload staging buffer of row_limits | defer (EventStore._upload_rules)
 
     def __len__(self):
         return self.rows.shape[0]
@@ -489,7 +505,9 @@ class EventStore(FeatureStore):
         every event ranked by similarity and the best `keep` returned as [(event index, row inside the event, similarity)].
         The ranking runs on the device (a stable descending sort of the (E, k) similarities in event order, i.e. what Python's
         stable ``sorted(..., reverse=True)`` does to the list the reference builds event by event); only `keep` hits are read
-        back.  NaN similarities (zero-norm rows) rank first, as they do per event."""
+        back.  NaN similarities (zero-norm rows) rank first, as they do per event.  This IS the reference's answer only on a store
+        where every row of every event is a kept row and no event has captions / a transcription: the reference drops hits of
+        rows that were not kept and defers low-similarity events to the LLM BEFORE its sort -- ``relevant_hits`` applies both."""
         q = _query_to_device(query, self.rows.device)
         idx, sims, counts = self.search_segments_device(q, self.offsets, int(k), prefilter)
         E, keep = idx.shape[0], int(keep)
@@ -528,14 +546,20 @@ class EventStore(FeatureStore):
             return list(zip(idx_h, sims_h))
         return [(idx_h[e, :counts_h[e]], sims_h[e, :counts_h[e]]) for e in range(E)]
 
-    def _read_back(self, packed: torch.Tensor) -> np.ndarray:
-        """One copy of a packed device buffer into pinned memory; the bytes are valid until the next read-back."""
-        nbytes = packed.numel()
+    def _read_back(self, packed: torch.Tensor, *more: torch.Tensor) -> np.ndarray:
+        """One copy of a packed device buffer into pinned memory; the bytes are valid until the next read-back.  With ``more``:
+        every part (any dtype, possibly a strided slice) is copied behind the one before it, then ONE synchronisation."""
+        parts = (packed,) + more
+        sizes = [p.numel() * p.element_size() for p in parts]
+        nbytes = sum(sizes)
         if self._pinned is None or self._pinned.numel() < nbytes:
-            self._pinned = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, pin_memory=True)
-        host = self._pinned[:nbytes]
-        host.copy_(packed, non_blocking=True)
-        torch.cuda.current_stream(packed.device).synchronize()
+            self._pinned = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, pin_memory=packed.is_cuda)
+        host, at = self._pinned[:nbytes], 0
+        for part, size in zip(parts, sizes):
+            host[at: at + size].view(part.dtype).view(part.shape).copy_(part, non_blocking=True)
+            at += size
+        if packed.is_cuda:
+            torch.cuda.current_stream(packed.device).synchronize()
         return host.numpy()
 
     def top_k_per_event_multi(self, queries, k: int = 5, prefilter: bool = False):
@@ -572,6 +596,130 @@ class EventStore(FeatureStore):
                    "hmm_rank_segment_hits_multi")
         ev_h, row_h, val_h, n_h = layout.host_views(self._read_back(packed))
         return [[(int(ev_h[qi, t]), int(row_h[qi, t]), float(val_h[qi, t])) for t in range(int(n_h[qi]))] for qi in range(Q)]
+
+    # ---- the reference's own selection: row rule and fallback rule ahead of the ranking -----------------------------------------
+    # _find_relevant_video_segments / _find_relevant_audio_segments (hippocampal_memory.py:3143-3277, :3294-3381) do not rank every
+    # hit: a hit counts only when its row is below the event's number of KEPT rows (`idx < len(event.frame_times)`), and an event
+    # whose best similarity is below 0.4 and that has captions / a transcription is answered by the LLM instead.  top_hits ranks
+    # every hit, so its `keep` hits are in general not the reference's; these two methods apply both rules on the device
+    # (hmm_rank_segment_hits_filtered[_multi]) and hand the deferred events back with their own hits.
+
+    def relevant_hits(self, query, k: int = 5, keep: int = 5, *, row_limits=None, defer=None, min_similarity: float = 0.4,
+                      prefilter: bool = False):
+        """(hits, deferred).  hits: [(event, row inside the event, similarity)], best first, the best `keep` of the hits that
+        pass the row rule (``row < row_limits[event]``) in events that are not deferred.  deferred: [(event, idx int64[k_e],
+        sims float32[k_e])] in event order -- the events with ``defer[event]`` set whose best similarity is below
+        ``np.float32(min_similarity)``, each with exactly what ``top_k_per_event`` returns for it.  ``row_limits`` / ``defer``: one
+        entry per event, or None (no row rule / nothing deferred).  Same order rules as ``top_hits`` (stable, NaN first; a NaN best
+        similarity never defers, as ``max(...) < 0.4`` is False).  keep <= 1024.  One scan, one ranking launch, one packed read-back,
+        and -- only when events were deferred -- a second one of their hits alone."""
+        rules = self._relevance_rules("relevant_hits", k, keep, row_limits, defer, min_similarity)
+        q = _query_to_device(query, self.rows.device)
+        if not self.lengths:
+            return [], []
+        packed = self._search_segments_packed(q, self.offsets, int(k), prefilter)
+        return self._rank_relevant(packed[1:], None, int(keep), rules)[0]
+
+    def relevant_hits_multi(self, queries, k: int = 5, keep: int = 5, *, row_limits=None, defer=None, min_similarity: float = 0.4,
+                            prefilter: bool = False):
+        """``relevant_hits`` for a batch of questions: per query the (hits, deferred) pair, from one pass over the store per 16
+        questions, one ranking launch for all of them (hmm_rank_segment_hits_filtered_multi) and the same one or two read-backs.
+        The similarities are those of ``top_k_per_event_multi``."""
+        rules = self._relevance_rules("relevant_hits_multi", k, keep, row_limits, defer, min_similarity)
+        q = _queries_2d(queries)
+        if not self.lengths:
+            return [([], []) for _ in range(q.shape[0])]
+        packed = self._search_segments_multi_packed(q, self.offsets, int(k), prefilter)
+        return self._rank_relevant(packed[1:], q.shape[0], int(keep), rules)
+
+    def _relevance_rules(self, what: str, k, keep, row_limits, defer, min_similarity):
+        """The host-side checks of relevant_hits[_multi], before anything is launched -> (limits int64[E] or None, flags uint8[E]
+        or None, the threshold as fp32)."""
+        E = len(self.lengths)
+        if int(k) < 1:
+            raise ValueError(f"{what}: k must be >= 1")
+        if not 1 <= int(keep) <= 1024:
+            raise ValueError(f"{what}: keep must be between 1 and 1024, got {keep}")
+        if E and min(self.lengths) == 0:                         # the reference's np.max / max of an empty array raises there
+            raise ValueError(f"{what}: event {list(self.lengths).index(0)} has no rows")
+        limits = flags = None
+        if row_limits is not None:
+            limits = np.asarray(row_limits).reshape(-1)
+            if limits.size and limits.dtype.kind not in "iu":
+                raise ValueError(f"{what}: row_limits must be integers, got {limits.dtype}")
+            limits = np.ascontiguousarray(limits, dtype=np.int64)
+            if limits.shape[0] != E:
+                raise ValueError(f"{what}: row_limits has {limits.shape[0]} entries for {E} events")
+            if E and int(limits.min()) < 0:
+                raise ValueError(f"{what}: row_limits must be >= 0")
+        if defer is not None:
+            flags = np.asarray(defer).reshape(-1)
+            if flags.shape[0] != E:
+                raise ValueError(f"{what}: defer has {flags.shape[0]} entries for {E} events")
+            flags = np.ascontiguousarray(flags.astype(bool).astype(np.uint8))
+        return limits, flags, np.float32(min_similarity)
+
+    def _upload_rules(self, limits, flags):
+        """row_limits | defer in one pinned buffer, one asynchronous copy -> their device addresses (None where not given)."""
+        parts = [a.view(np.uint8) for a in (limits, flags) if a is not None]
+        if not parts:
+            return None, None, None
+        host = torch.from_numpy(np.concatenate(parts))
+        if self.rows.is_cuda:
+            # one pinned staging buffer per store.  A call that returns has synchronised on its read-back, so its copy has landed
+            # before the next call overwrites the buffer; a call that RAISED after queueing the copy has not, and the next call
+            # may overwrite bytes still in flight -- of an upload whose result nobody reads any more.
+            if self._pinned_rules is None or self._pinned_rules.numel() < host.numel():
+                self._pinned_rules = torch.empty(max(host.numel(), 1 << 12), dtype=torch.uint8, pin_memory=True)
+            staged = self._pinned_rules[: host.numel()]
+            staged.copy_(host)
+            dev = staged.to(self.rows.device, non_blocking=True)
+        else:
+            dev = host
+        base, at = dev.data_ptr(), (limits.nbytes if limits is not None else 0)
+        return dev, (base if limits is not None else None), (base + at if flags is not None else None)
+
+    def _rank_relevant(self, hits, Q, keep: int, rules):
+        """The filtered ranking of the (idx, sims, counts) of a segmented scan and its read-backs; Q None: one question."""
+        idx, sims, counts = hits
+        lead = () if Q is None else (Q,)
+        n_q, (E, k) = Q or 1, idx.shape[-2:]
+        limits, flags, threshold = rules
+        layout = _relevant_layout(*lead, E, keep)
+        packed = torch.empty(layout.nbytes, dtype=torch.uint8, device=idx.device)
+        outputs = layout.device_views(packed)
+        if flags is not None:
+            d_idx, d_sims = _deferred_layout(n_q, E * k).device_views(
+                torch.empty(_deferred_layout(n_q, E * k).nbytes, dtype=torch.uint8, device=idx.device))
+            d_ptrs = (d_idx.data_ptr(), d_sims.data_ptr())
+        else:                                                     # nothing can be deferred: the two arrays are never written, any
+            d_ptrs = (packed.data_ptr(), packed.data_ptr())       # non-null address satisfies the argument check
+        keepalive, limits_ptr, flags_ptr = self._upload_rules(limits, flags)
+        name = "hmm_rank_segment_hits_filtered" if Q is None else "hmm_rank_segment_hits_filtered_multi"
+        ev, row, val, n, d_ev, n_d, d_cnt = outputs
+        _lib.check(getattr(_lib.load(), name)(idx.data_ptr(), sims.data_ptr(), counts.data_ptr(), *lead, E, k, keep, limits_ptr,
+                                              flags_ptr, float(threshold), ev.data_ptr(), row.data_ptr(), val.data_ptr(), n.data_ptr(),
+                                              d_ev.data_ptr(), n_d.data_ptr(), *d_ptrs, d_cnt.data_ptr(),
+                                              _lib.stream_ptr()), name)
+        ev_h, row_h, val_h, n_h, d_ev_h, n_d_h, d_cnt_h = [v.reshape((n_q,) + v.shape[len(lead):]) for v in
+                                                           layout.host_views(self._read_back(packed))]
+        found = [[(int(ev_h[qi, t]), int(row_h[qi, t]), float(val_h[qi, t])) for t in range(int(n_h[qi, 0]))] for qi in range(n_q)]
+        n_def = [int(n_d_h[qi, 0]) for qi in range(n_q)]
+        if max(n_def) == 0:
+            return [(found[qi], []) for qi in range(n_q)]
+        d_ev_h, d_cnt_h = d_ev_h.copy(), d_cnt_h.copy()           # the staging buffer is rewritten by the second read-back
+        # per question the compacted front of both arrays, n_deferred * k entries: contiguous pieces, copied as they lie (two
+        # per question that deferred anything; every idx piece, then every sims piece), one synchronisation
+        asked = [qi for qi in range(n_q) if n_def[qi]]
+        raw = self._read_back(*[a[qi, : n_def[qi] * k] for a in (d_idx, d_sims) for qi in asked]).copy()
+        out, at, sims_at = [(found[qi], []) for qi in range(n_q)], 0, sum(n_def) * k * 8
+        for qi in asked:
+            cells = n_def[qi] * k
+            idx_h, sims_h = raw[at: at + cells * 8].view(np.int64), raw[sims_at: sims_at + cells * 4].view(np.float32)
+            at, sims_at = at + cells * 8, sims_at + cells * 4
+            out[qi][1].extend((int(d_ev_h[qi, j]), idx_h[j * k: j * k + d_cnt_h[qi, j]], sims_h[j * k: j * k + d_cnt_h[qi, j]])
+                              for j in range(n_def[qi]))
+        return out
 
     # ---- a store that grows: append, replace and drop events on the device ----------------------------------------------------
     # The constructor and from_device_rows leave `rows` as they always did (an exact-size upload, or the caller's tensor).  The

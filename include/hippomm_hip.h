@@ -241,6 +241,48 @@ int    hmm_rank_segment_hits_multi(const int64_t* idx_dev, const float* sims_dev
                                    int64_t* event_out_dev, int64_t* row_out_dev, float* sim_out_dev, int32_t* n_out_dev,
                                    hmm_stream_t stream);
 
+/* hmm_rank_segment_hits with the reference's two per-event rules applied BEFORE the global sort (hippocampal_memory.py:3143-3277,
+ * :3294-3381).  Inputs: the three outputs of hmm_cosine_topk_segmented[_prefilter], plus
+ *   row_limits_dev  (nullable) int64[n_segments]: a hit of event e counts only when its row idx < row_limits[e] -- the reference's
+ *                   `idx < len(event.frame_times)` (:3247, :3262) / `idx < len(event.feature_times['audio_times'])` (:3336, :3370);
+ *                   null: no row rule;
+ *   defer_dev       (nullable) uint8[n_segments]: event e is DEFERRED iff defer[e] != 0, n_e > 0 and its best similarity (slot 0 of
+ *                   the event) < min_similarity, compared as fp32 -- the reference's `max(similarities) < 0.4 and captions` (:3156,
+ *                   :3307).  NaN ranks first inside an event, so a NaN makes the comparison false, as np.max(...) < 0.4 and
+ *                   max(...) < 0.4 are on an array holding a NaN.  No fp32 value lies strictly between 0.4 and (float)0.4, so
+ *                   np.float32(x) < 0.4 decides the same under numpy 1.x (which widens x) and numpy 2 (which narrows 0.4) for every
+ *                   fp32 x: pass min_similarity = (float)0.4.  null: nothing is deferred.
+ * A deferred event leaves the ranking with all its hits; the hits of the others that pass the row rule are ranked with
+ * hmm_rank_segment_hits' key and stable order (NaN first).  keep <= 1024: the best-64 tournament runs in rounds, round r over the
+ * keys strictly below the last key of round r - 1; keep <= 64 is one round.
+ * Outputs: event_out / row_out / sim_out [keep]: the best keep' = min(keep, candidates) hits, -1 / -1 / 0 padded; *n_out = keep'.
+ *   deferred_event_out int32[n_segments]: the deferred events, ascending, -1 padded; *n_deferred_out their number n_d;
+ *   deferred_idx_out int64[n_segments*k], deferred_sim_out float[n_segments*k], deferred_count_out int32[n_segments]: for the j-th
+ *   deferred event its own (idx, sims, count) slice, copied unchanged, at [j*k ..] / [j].  Entries at and after n_d*k (counts: n_d)
+ *   are NOT WRITTEN: they keep whatever the caller left there.
+ * One workgroup, no workspace.  For stores converted from fp64 the similarities are fp32 results: a decision within 2e-6 of the
+ * threshold can differ from the reference's fp64 comparison. */
+int    hmm_rank_segment_hits_filtered(const int64_t* idx_dev, const float* sims_dev, const int32_t* counts_dev, int n_segments, int k,
+                                      int keep, const int64_t* row_limits_dev /* nullable */, const uint8_t* defer_dev /* nullable */,
+                                      float min_similarity,
+                                      int64_t* event_out_dev, int64_t* row_out_dev, float* sim_out_dev, int32_t* n_out_dev,
+                                      int32_t* deferred_event_out_dev, int32_t* n_deferred_out_dev,
+                                      int64_t* deferred_idx_out_dev, float* deferred_sim_out_dev, int32_t* deferred_count_out_dev,
+                                      hmm_stream_t stream);
+
+/* hmm_rank_segment_hits_filtered for every question of a batch in one launch (one workgroup per question): inputs are the three
+ * outputs of hmm_cosine_topk_segmented_multi[_prefilter]; row_limits and defer are shared by all questions.  Every output is
+ * query-major: question q's part starts at q*keep (hits), q (counts), q*n_segments (deferred events and counts), q*n_segments*k
+ * (deferred slices), and equals what the single call writes for that question, unwritten tails included. */
+int    hmm_rank_segment_hits_filtered_multi(const int64_t* idx_dev, const float* sims_dev, const int32_t* counts_dev,
+                                            int n_queries, int n_segments, int k, int keep,
+                                            const int64_t* row_limits_dev /* nullable */, const uint8_t* defer_dev /* nullable */,
+                                            float min_similarity,
+                                            int64_t* event_out_dev, int64_t* row_out_dev, float* sim_out_dev, int32_t* n_out_dev,
+                                            int32_t* deferred_event_out_dev, int32_t* n_deferred_out_dev,
+                                            int64_t* deferred_idx_out_dev, float* deferred_sim_out_dev,
+                                            int32_t* deferred_count_out_dev, hmm_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Consolidation similarity.  Replaces HippocampalMemory._select_key_frames(features, times,
  * similarity_threshold=0.9) (hippomm/core/hippocampal_memory.py:944-967; caller :855).
