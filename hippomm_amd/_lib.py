@@ -109,6 +109,9 @@ _SIGNATURES = {
     "hmm_encoder_flops_executed": (C.c_double, [c_ptr, C.c_int]),
     "hmm_encoder_set_streams": (C.c_int, [c_ptr, C.c_int]),
     "hmm_encoder_set_fused_attention": (C.c_int, [c_ptr, C.c_int]),
+    "hmm_encoder_text_packed_workspace_bytes": (C.c_size_t, [c_ptr, C.c_int, C.c_int64]),
+    "hmm_encoder_forward_text_packed": (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, c_ptr, c_ptr, C.c_size_t, c_ptr]),
+    "hmm_op_attention_causal_packed_bf16": (C.c_int, [c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr]),
     "hmm_op_gemm_bf16": (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr]),
     "hmm_op_layernorm_bf16": (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_float, c_ptr]),
     "hmm_op_gemm_bf16_tile": (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr]),

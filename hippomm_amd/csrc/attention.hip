@@ -120,6 +120,81 @@ __global__ __launch_bounds__(kAttnWaves * 64) void attention_kernel(
                             out + (size_t)b * T * D + h * DH, T, Lk, D, scale_log2e, causal, q_part, q_parts);
 }
 
+// Causal attention over PACKED sequences (text tower, questions at their own lengths): sample b owns rows off[b] .. off[b+1]-1 of
+// the packed qkv matrix and of the output, with T = Lk = off[b+1] - off[b] queries and keys.  One workgroup per (sample, head) on
+// the block map attention_kernel uses for T <= 128; K / V staging as there (no bias position, no query split), then the same
+// attention_core: a sample of T rows gets the bits attention_kernel<DH, NKT> gives a sample of T tokens.  T is uniform over the
+// workgroup (scalar loads of the table).  A table entry that does not describe 1 .. 32 NKT rows inside [0, total_rows] is skipped.
+template <int DH, int NKT>
+__global__ __launch_bounds__(kAttnWaves * 64) void attention_packed_kernel(
+    const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out, const int32_t* __restrict__ off, int n_img, int total_rows, int H,
+    float scale_log2e) {
+    using C = AttnCfg<DH, NKT>;
+    constexpr int NT = kAttnWaves * 64;
+    constexpr int CPR = DH / 8;                      // 16-B chunks per K/V row
+    constexpr int NCHUNK = C::NKEY * CPR;
+    constexpr int PER_THREAD = (NCHUNK + NT - 1) / NT;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* k_lds = smem;
+    char* v_lds = smem + C::K_BYTES;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = blockIdx.x >> 3;
+    const int b_lin = (blockIdx.x & 7) + 8 * (n / H);
+    const int h = n % H;
+    if (b_lin >= n_img) return;
+    const int b = n_img - 1 - b_lin;
+    const int r0 = off[b], T = off[b + 1] - r0;
+    if (r0 < 0 || T < 1 || T > C::NKEY || T > total_rows - r0) return;      // workgroup-uniform: before any barrier
+    const int D = H * DH;
+    const size_t row_stride = (size_t)3 * D;
+    const bf16_t* base = qkv + (size_t)r0 * row_stride + h * DH;
+
+    const int r = lane & 31, hh = lane >> 5;
+    bf16x8 qf[C::KS];
+    {
+        const int qrow = wave * 32 + r;
+        const int qr = qrow < T ? qrow : T - 1;
+        const bf16_t* qp = base + (size_t)qr * row_stride + hh * 8;
+#pragma unroll
+        for (int ks = 0; ks < C::KS; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qp + ks * 16);
+    }
+    {
+        uint4 kv[PER_THREAD], vv[PER_THREAD];
+#pragma unroll
+        for (int i = 0; i < PER_THREAD; ++i) {
+            const int idx = tid + i * NT;
+            const int row = idx / CPR, c = idx - row * CPR;
+            const int rr = row < T ? row : T - 1;        // clamp: always a row of this sample; rows >= T are not written
+            const bf16_t* p = base + (size_t)rr * row_stride + c * 8;
+            kv[i] = *reinterpret_cast<const uint4*>(p + D);
+            vv[i] = *reinterpret_cast<const uint4*>(p + 2 * D);
+        }
+        for (int idx = T * CPR + tid; idx < NCHUNK; idx += NT) {         // rows T .. NKEY-1: zeros
+            const int row = idx / CPR, c = idx - row * CPR;
+            *reinterpret_cast<uint4*>(k_lds + row * C::KROW + c * 16) = make_uint4(0u, 0u, 0u, 0u);
+            *reinterpret_cast<uint4*>(v_lds + row * C::VROW + c * 16) = make_uint4(0u, 0u, 0u, 0u);
+        }
+#pragma unroll
+        for (int i = 0; i < PER_THREAD; ++i) {
+            const int idx = tid + i * NT;
+            const int row = idx / CPR, c = idx - row * CPR;
+            if (row < T) {
+                *reinterpret_cast<uint4*>(k_lds + row * C::KROW + c * 16) = kv[i];
+                *reinterpret_cast<uint4*>(v_lds + row * C::VROW + c * 16) = vv[i];
+            }
+        }
+    }
+    __syncthreads();
+
+    auto load_q = [&](int row, int ks) {
+        return *reinterpret_cast<const bf16x8*>(base + (size_t)row * row_stride + hh * 8 + ks * 16);
+    };
+    attention_core<DH, NKT>(k_lds, v_lds, reinterpret_cast<float*>(smem + C::K_BYTES + C::V_BYTES), load_q, qf,
+                            out + (size_t)r0 * D + h * DH, T, T, D, scale_log2e, true);
+}
+
 template <int DH, int NKT>
 static int launch_attention(const bf16_t* qkv, bf16_t* out, int batch, int T, int Lk, int H,
                             const float* bias_k, const float* bias_v, hipStream_t st, bool causal) {
@@ -231,6 +306,105 @@ __global__ __launch_bounds__(256) void attention_cls_kernel(const bf16_t* __rest
     }
 }
 
+// The LAST block of the packed text tower: the head reads only each question's last (EOS) row, and under the causal mask that
+// row sees all of the question's keys, so it is ONE unmasked query over rows off[b] .. off[b+1]-1 of kv ([total_rows][2D] =
+// [k | v]); q_last / out: one row per sample.  attention_cls_kernel's scheme at the text tower's sizes: T <= MAXK = 96 keys, so
+// thread j < T scores key j in one pass; no bias position.  One 256-thread workgroup per (sample, head); a table entry outside
+// 1 .. MAXK rows or outside [0, total_rows] is skipped.
+template <int DH>
+__global__ __launch_bounds__(256) void attention_last_packed_kernel(const bf16_t* __restrict__ q_last, const bf16_t* __restrict__ kv,
+                                                                    bf16_t* __restrict__ out, const int32_t* __restrict__ off,
+                                                                    int total_rows, int H, float scale) {
+    constexpr int MAXK = 96;
+    __shared__ float qs[DH];
+    __shared__ float p[MAXK];
+    __shared__ float red[8];
+    __shared__ float opart[4 * (64 / (DH / 8))][DH];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int b = blockIdx.x / H, h = blockIdx.x % H;
+    const int r0 = off[b], T = off[b + 1] - r0;
+    if (r0 < 0 || T < 1 || T > MAXK || T > total_rows - r0) return;         // workgroup-uniform: before any barrier
+    const int D = H * DH;
+    const size_t kv_stride = (size_t)2 * D;
+    const bf16_t* kbase = kv + (size_t)r0 * kv_stride + h * DH;
+    if (tid < DH) qs[tid] = (float)q_last[(size_t)b * D + h * DH + tid];
+    __syncthreads();
+
+    float s = -INFINITY;
+    if (tid < T) {
+        const bf16_t* kr = kbase + (size_t)tid * kv_stride;
+        s = 0.f;
+#pragma unroll
+        for (int c = 0; c < DH / 8; ++c) {
+            const bf16x8 kk = *reinterpret_cast<const bf16x8*>(kr + c * 8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s = fmaf(qs[c * 8 + e], (float)kk[e], s);
+        }
+        s *= scale;
+    }
+    const float wm = wave_max(s);
+    if (lane == 0) red[w] = wm;
+    __syncthreads();
+    const float m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));      // finite: key 0 exists
+    const float e = tid < T ? __expf(s - m) : 0.f;
+    if (tid < T) p[tid] = e;
+    const float ws = wave_sum(e);
+    if (lane == 0) red[4 + w] = ws;
+    __syncthreads();
+    const float l = (red[4] + red[5]) + (red[6] + red[7]);
+
+    // P.V with 16-B loads: a lane owns one 8-wide d chunk (c) of one key slot; a wave covers SL keys per step, the 4 waves 4*SL
+    constexpr int CPR = DH / 8, SL = 64 / CPR;
+    const int slot = lane / CPR, c = lane - slot * CPR;
+    const bf16_t* vbase = kbase + D;
+    float acc[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] = 0.f;
+    if (slot < SL) {
+        for (int j = w * SL + slot; j < T; j += 4 * SL) {
+            const float pj = p[j];
+            const bf16x8 vv = *reinterpret_cast<const bf16x8*>(vbase + (size_t)j * kv_stride + c * 8);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) acc[i] = fmaf(pj, (float)vv[i], acc[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) opart[w * SL + slot][c * 8 + i] = acc[i];
+    }
+    __syncthreads();
+    if (tid < DH) {
+        float o = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4 * SL; ++i) o += opart[i][tid];
+        out[(size_t)b * D + h * DH + tid] = (bf16_t)(o / l);
+    }
+}
+
+int attention_causal_packed_bf16(const bf16_t* qkv, bf16_t* out, const int32_t* offsets, int batch, int total_rows, int heads,
+                                 int head_dim, hipStream_t st) {
+    HMM_REQUIRE(qkv && out && offsets, HMM_E_INVALID, "attention_causal_packed: null pointer");
+    HMM_REQUIRE(batch >= 1 && heads >= 1 && total_rows >= batch, HMM_E_INVALID,
+                "attention_causal_packed: bad shape (batch %d, total_rows %d, heads %d)", batch, total_rows, heads);
+    HMM_REQUIRE(head_dim == 64, HMM_E_INVALID, "attention_causal_packed: unsupported head_dim %d (built: 64, <= 96 rows per sample)", head_dim);
+    using C = AttnCfg<64, 3>;
+    auto kern = attention_packed_kernel<64, 3>;
+    HMM_ENSURE_DYN_LDS(kern, C::LDS);
+    const float scale_log2e = 1.4426950408889634f / sqrtf(64.0f);
+    kern<<<8 * ((batch + 7) / 8) * heads, kAttnWaves * 64, C::LDS, st>>>(qkv, out, offsets, batch, total_rows, heads, scale_log2e);
+    HMM_LAUNCH_CHECK();
+    return HMM_OK;
+}
+
+int attention_last_packed_bf16(const bf16_t* q_last, const bf16_t* kv, bf16_t* out, const int32_t* offsets, int batch, int total_rows,
+                               int heads, int head_dim, hipStream_t st) {
+    HMM_REQUIRE(q_last && kv && out && offsets, HMM_E_INVALID, "attention_last_packed: null pointer");
+    HMM_REQUIRE(batch >= 1 && heads >= 1 && total_rows >= batch, HMM_E_INVALID,
+                "attention_last_packed: bad shape (batch %d, total_rows %d, heads %d)", batch, total_rows, heads);
+    HMM_REQUIRE(head_dim == 64, HMM_E_INVALID, "attention_last_packed: unsupported head_dim %d", head_dim);
+    attention_last_packed_kernel<64><<<batch * heads, 256, 0, st>>>(q_last, kv, out, offsets, total_rows, heads, 1.0f / sqrtf(64.0f));
+    HMM_LAUNCH_CHECK();
+    return HMM_OK;
+}
+
 int attention_cls_bf16(const bf16_t* q_cls, const bf16_t* kv, bf16_t* out, int batch, int tokens, int heads,
                        int head_dim, const float* bias_k, const float* bias_v, hipStream_t st) {
     HMM_REQUIRE(q_cls && kv && out, HMM_E_INVALID, "attention_cls: null pointer");
@@ -280,6 +454,12 @@ extern "C" int hmm_op_attention_causal_bf16(const uint16_t* qkv_dev, uint16_t* o
                                              int head_dim, hmm_stream_t stream) {
     return attention_bf16(reinterpret_cast<const bf16_t*>(qkv_dev), reinterpret_cast<bf16_t*>(out_dev), batch, tokens,
                           heads, head_dim, nullptr, nullptr, static_cast<hipStream_t>(stream), true);
+}
+
+extern "C" int hmm_op_attention_causal_packed_bf16(const uint16_t* qkv_dev, uint16_t* out_dev, const int32_t* offsets_dev, int batch,
+                                                    int total_rows, int heads, int head_dim, hmm_stream_t stream) {
+    return attention_causal_packed_bf16(reinterpret_cast<const bf16_t*>(qkv_dev), reinterpret_cast<bf16_t*>(out_dev), offsets_dev, batch,
+                                        total_rows, heads, head_dim, static_cast<hipStream_t>(stream));
 }
 
 // The last block's one-query attention on its own.  The launcher takes bias_k alone as "one more key"; here the pair goes together.

@@ -174,17 +174,19 @@ struct WsPlan { int n_img, R; size_t off_x, off_a, off_big, off_im2col, off_patc
 // frames with a different best split factor per size, 0 at the reference's 32-frame buffer, losses above; under the 5 % bar it
 // was removed: profiles/r5_mid_splitk_probe.json, profiles/LABNOTES_r5.md.)
 static int fc2_splits(const hmm_encoder* e) { return e->tower == HMM_TOWER_TEXT ? g_enc_splitk_fc2_text : g_enc_splitk_fc2; }
-static int splitk_mode(const hmm_encoder* e, int batch) {
-    const int64_t rows = (int64_t)batch * e->clips * e->T;
+static int splitk_mode_rows(const hmm_encoder* e, int64_t rows) {
     const int limit = e->tower == HMM_TOWER_VISION ? g_enc_splitk_rows_vision : g_enc_splitk_rows;
     return limit > 0 && rows <= limit && e->D % (64 * g_enc_splitk_out) == 0 && e->mlp % (64 * fc2_splits(e)) == 0 ? 1 : 0;
 }
+static int splitk_mode(const hmm_encoder* e, int batch) { return splitk_mode_rows(e, (int64_t)batch * e->clips * e->T); }
 static int mode_splits(const hmm_encoder* e, int) { return fc2_splits(e); }
 
-static WsPlan ws_plan(const hmm_encoder* e, int batch, int sk_mode) {
+// n_img samples (clips) owning R token rows in all.  packed (text tower, questions at their own lengths): R is the sum of the lengths
+// and there is no patch stage to alias into the big buffer.
+static WsPlan ws_plan_rows(const hmm_encoder* e, int n_img, int R, int sk_mode, bool packed) {
     WsPlan p{};
-    p.n_img = batch * e->clips;
-    p.R = p.n_img * e->T;
+    p.n_img = n_img;
+    p.R = R;
     const size_t D = e->D;
     size_t cur = 0;
     p.off_x = cur;   cur = align_up(cur + (size_t)p.R * D * 4, 256);
@@ -194,7 +196,7 @@ static WsPlan ws_plan(const hmm_encoder* e, int batch, int sk_mode) {
     p.off_im2col = p.off_big;
     const size_t im2col = align_up((size_t)p.n_img * e->n_patches * e->patch_k_pad * 2, 256);
     p.off_patch = p.off_big + im2col;
-    const size_t pre = im2col + (size_t)p.n_img * e->n_patches * D * 4;
+    const size_t pre = packed ? 0 : im2col + (size_t)p.n_img * e->n_patches * D * 4;
     cur = align_up(cur + (big > pre ? big : pre), 256);
     p.off_hl = cur;  cur = align_up(cur + (size_t)p.n_img * D * 2, 256);
     p.off_hv = cur;  cur = align_up(cur + (size_t)p.n_img * HMM_FEATURE_DIM * 4, 256);
@@ -209,6 +211,9 @@ static WsPlan ws_plan(const hmm_encoder* e, int batch, int sk_mode) {
     p.off_part = cur; cur = align_up(cur + (sk_mode ? (size_t)max_splits * p.R * D * 4 : 0), 256);
     p.total = cur + 256;  // + 256: margin only -- no kernel touches it (tests/test_gpu_memory_contract.py, profiles/memory_contract.json)
     return p;
+}
+static WsPlan ws_plan(const hmm_encoder* e, int batch, int sk_mode) {
+    return ws_plan_rows(e, batch * e->clips, batch * e->clips * e->T, sk_mode, false);
 }
 
 }  // namespace hmm
@@ -390,6 +395,8 @@ struct Chain {                 // one (half-)batch travelling through the tower 
     bool fuse;                 // in_proj + attention as one kernel (large enough forwards only, see hmm_encoder_forward)
     int sk_mode;               // splitk_mode() of the forward: fc2 as a split-K launch reduced by the LayerNorm behind it
     mutable const float* pending_bias;   // fc2 of the previous block left partial slabs: the next LayerNorm adds them (+ this bias)
+    const int32_t* pk_off = nullptr;     // text tower, packed rows (hmm_encoder_forward_text_packed): the device table int32[batch + 1],
+    int pk_max_len = 0;                  // sample b owns rows pk_off[b] .. pk_off[b+1]-1 of p.R; the longest length (launch sizes)
 };
 static float* chain_x(const Chain& c) { return reinterpret_cast<float*>(c.ws + c.p.off_x); }
 
@@ -403,6 +410,7 @@ static int chain_tokens(hmm_encoder* e, const Chain& c) {
     const int D = e->D, n_img = p.n_img;
     if (e->tower == HMM_TOWER_TEXT) {                  // ids (B,77) int64 -> token embedding + positions; EOS rows
         const int64_t* ids = static_cast<const int64_t*>(c.input);
+        if (c.pk_off) return launch_embed_tokens_packed(ids, c.pk_off, e->tok_emb, e->pos, x, n_img, e->T, c.pk_max_len, p.R, e->vocab, c.st);
         HMM_TRY(launch_embed_tokens(ids, e->tok_emb, e->pos, x, n_img * e->T, e->T, e->vocab, c.st));
         if (!g_enc_text_head_fused) HMM_TRY(launch_select_eos(ids, reinterpret_cast<int32_t*>(c.ws + p.off_sel), n_img, e->T, c.st));
         return HMM_OK;
@@ -442,7 +450,8 @@ static int chain_block(hmm_encoder* e, const Chain& c, int i) {
     bf16_t* hc = reinterpret_cast<bf16_t*>(c.ws + p.off_hc);
     const int D = e->D, T = e->T, R = p.R, n_img = p.n_img;
     const BlockW& w = e->blocks[i];
-    const bool text = e->tower == HMM_TOWER_TEXT;     // the selected (EOS) row differs per sample: no cls-only shortcut
+    const bool packed = c.pk_off != nullptr;          // text tower, questions at their own lengths: the EOS row is each sample's last
+    const bool text = e->tower == HMM_TOWER_TEXT && !packed;   // padded: the selected (EOS) row differs per sample, no cls-only shortcut
     const bool fused = e->fused_attention && c.fuse && e->tower == HMM_TOWER_VISION && D == 1280 && e->heads == 16 && T == 257;
     float* part = reinterpret_cast<float*>(c.ws + p.off_part);
     const size_t part_stride = (size_t)R * D;
@@ -484,7 +493,8 @@ static int chain_block(hmm_encoder* e, const Chain& c, int i) {
         HMM_TRY(gemm_bf16(big, w.fc2_w, w.fc2_b, x, R, D, e->mlp, HMM_EPI_BIAS_RESID_F32, c.tile, c.small_tiles, st));
     } else if (i + 1 < e->depth || text) {
         HMM_TRY(gemm_bf16(a, w.qkv_w, w.qkv_b, big, R, 3 * D, D, HMM_EPI_BIAS_BF16, c.tile, c.small_tiles, st));
-        HMM_TRY(attention_bf16(big, a, n_img, T, e->heads, D / e->heads, w.bias_k, w.bias_v, st, text));
+        if (packed) HMM_TRY(attention_causal_packed_bf16(big, a, c.pk_off, n_img, R, e->heads, D / e->heads, st));
+        else        HMM_TRY(attention_bf16(big, a, n_img, T, e->heads, D / e->heads, w.bias_k, w.bias_v, st, text));
         if (c.sk_mode == 1 && g_enc_splitk_out > 1) {
             HMM_TRY(gemm_bf16_splitk(a, w.out_w, part, R, D, D, g_enc_splitk_out, -1, st));
             HMM_TRY(launch_layernorm_reduce_bf16(x, part, part_stride, g_enc_splitk_out, w.out_b, w.ln2_g, w.ln2_b, a, R, D, 1e-6f, st));
@@ -504,10 +514,15 @@ static int chain_block(hmm_encoder* e, const Chain& c, int i) {
         // token but Q, attention output, out-proj and the MLP for the cls row of each image only.
         // K|V projection of all rows (in_proj rows D..3D), Q projection of the cls rows (rows 0..D).
         HMM_TRY(gemm_bf16(a, w.qkv_w + (size_t)D * D, w.qkv_b + D, big, R, 2 * D, D, HMM_EPI_BIAS_BF16, c.tile, c.small_tiles, st));
-        HMM_TRY(launch_gather_rows(a, (size_t)T * D * 2, ac, n_img, D * 2, st));
+        // Packed text rows: the same with each question's LAST row (its EOS row, which under the causal mask sees all of the
+        // question's keys, so the one-query kernel needs no mask) and per-sample key counts from the table.
+        if (packed) HMM_TRY(launch_gather_last_rows(a, c.pk_off, ac, n_img, R, D * 2, st));
+        else        HMM_TRY(launch_gather_rows(a, (size_t)T * D * 2, ac, n_img, D * 2, st));
         HMM_TRY(gemm_bf16(ac, w.qkv_w, w.qkv_b, qc, n_img, D, D, HMM_EPI_BIAS_BF16, c.tile, c.small_tiles, st));
-        HMM_TRY(attention_cls_bf16(qc, big, ac, n_img, T, e->heads, D / e->heads, w.bias_k, w.bias_v, st));
-        HMM_TRY(launch_gather_rows(x, (size_t)T * D * 4, xc, n_img, D * 4, st));
+        if (packed) HMM_TRY(attention_last_packed_bf16(qc, big, ac, c.pk_off, n_img, R, e->heads, D / e->heads, st));
+        else        HMM_TRY(attention_cls_bf16(qc, big, ac, n_img, T, e->heads, D / e->heads, w.bias_k, w.bias_v, st));
+        if (packed) HMM_TRY(launch_gather_last_rows(x, c.pk_off, xc, n_img, R, D * 4, st));
+        else        HMM_TRY(launch_gather_rows(x, (size_t)T * D * 4, xc, n_img, D * 4, st));
         HMM_TRY(gemm_bf16(ac, w.out_w, w.out_b, xc, n_img, D, D, HMM_EPI_BIAS_RESID_F32, c.tile, c.small_tiles, st));
         HMM_TRY(launch_layernorm_bf16(xc, (size_t)D, w.ln2_g, w.ln2_b, ac, n_img, D, 1e-6f, st));
         HMM_TRY(gemm_bf16(ac, w.fc1_w, w.fc1_b, hc, n_img, e->mlp, D, HMM_EPI_BIAS_GELU_BF16, c.tile, c.small_tiles, st));
@@ -522,12 +537,12 @@ static int chain_head(hmm_encoder* e, const Chain& c) {
     float* xc = reinterpret_cast<float*>(c.ws + p.off_xc);
     bf16_t* hl = reinterpret_cast<bf16_t*>(c.ws + p.off_hl);
     float* hv = reinterpret_cast<float*>(c.ws + p.off_hv);
-    if (e->tower == HMM_TOWER_TEXT && g_enc_text_head_fused) {
+    if (e->tower == HMM_TOWER_TEXT && g_enc_text_head_fused && !c.pk_off) {
         // SelectEOSAndProject: the row at the EOS position of each sample, LayerNormed -- one launch instead of three
         HMM_TRY(launch_layernorm_eos_bf16(chain_x(c), static_cast<const int64_t*>(c.input), e->T, e->head_g, e->head_b, hl, p.n_img, e->D,
                                           1e-6f, c.st));
     } else {
-        if (e->tower == HMM_TOWER_TEXT)
+        if (e->tower == HMM_TOWER_TEXT && !c.pk_off)     // packed: the last block left each question's EOS row in xc, like a cls row
             HMM_TRY(launch_gather_selected_rows(chain_x(c), reinterpret_cast<const int32_t*>(c.ws + p.off_sel), e->T, xc,
                                                 p.n_img, e->D * 4, c.st));
         HMM_TRY(launch_layernorm_bf16(xc, (size_t)e->D, e->head_g, e->head_b, hl, p.n_img, e->D, 1e-6f, c.st));
@@ -618,6 +633,63 @@ extern "C" int hmm_encoder_forward(hmm_encoder* e, const void* input_dev, int ba
             }
         }
     }
+    return rc;
+}
+
+// ---- text tower on packed rows: every question at its own length ----------------------------------------------------------
+// One chain on the caller's stream (capturable).  Regime and GEMM dispatch by the existing rules, keyed by the rows that exist:
+// split-K fc2 up to g_enc_splitk_rows rows, the sliver kernel up to g_enc_sliver_rows.
+static int packed_rows(const int32_t* lengths_host, int batch, int T, int64_t* rows, int* max_len) {
+    int64_t r = 0;
+    int m = 0;
+    for (int b = 0; b < batch; ++b) {
+        const int len = lengths_host[b];
+        HMM_REQUIRE(len >= 1 && len <= T, HMM_E_INVALID, "encoder_forward_text_packed: length %d of sample %d is outside 1 .. %d", len, b, T);
+        r += len;
+        if (len > m) m = len;
+    }
+    *rows = r;
+    *max_len = m;
+    return HMM_OK;
+}
+
+extern "C" size_t hmm_encoder_text_packed_workspace_bytes(const hmm_encoder* e, int batch, int64_t total_rows) {
+    if (!e || e->tower != HMM_TOWER_TEXT || batch < 1 || total_rows < batch || total_rows > (int64_t)batch * e->T) return 0;
+    return ws_plan_rows(e, batch, (int)total_rows, splitk_mode_rows(e, total_rows), true).total;
+}
+
+extern "C" int hmm_encoder_forward_text_packed(hmm_encoder* e, const int64_t* ids_dev, const int32_t* lengths_host,
+                                               const int32_t* offsets_dev, int batch, float* out_dev, void* workspace_dev,
+                                               size_t workspace_bytes, hmm_stream_t stream) {
+    constexpr int kTextTokens = 77;                   // checked against the handle below; lets the lengths be judged before it is read
+    HMM_REQUIRE(e && ids_dev && lengths_host && offsets_dev && out_dev && workspace_dev, HMM_E_INVALID,
+                "encoder_forward_text_packed: null argument");
+    HMM_REQUIRE(batch >= 1 && batch <= 65535, HMM_E_INVALID, "encoder_forward_text_packed: batch=%d (1 .. 65535)", batch);
+    HMM_REQUIRE(reinterpret_cast<uintptr_t>(offsets_dev) % 4 == 0 && reinterpret_cast<uintptr_t>(ids_dev) % 8 == 0, HMM_E_INVALID,
+                "encoder_forward_text_packed: ids / offsets table not aligned");
+    int64_t rows = 0;
+    int max_len = 0;
+    { const int rc = packed_rows(lengths_host, batch, kTextTokens, &rows, &max_len); if (rc != HMM_OK) return rc; }
+    HMM_REQUIRE(e->tower == HMM_TOWER_TEXT && e->T == kTextTokens, HMM_E_INVALID, "encoder_forward_text_packed: not a text tower handle");
+    int cur_dev = -1;
+    HMM_HIP_CHECK(hipGetDevice(&cur_dev));
+    HMM_REQUIRE(cur_dev == e->device, HMM_E_STATE, "encoder_forward_text_packed: handle lives on device %d, current device is %d",
+                e->device, cur_dev);
+    if (!e->ready) {
+        HMM_REQUIRE(hmm_encoder_missing_params(e) == 0, HMM_E_STATE, "encoder_forward_text_packed: %s", hmm_last_error());
+        e->ready = true;
+    }
+    const size_t need = hmm_encoder_text_packed_workspace_bytes(e, batch, rows);
+    HMM_REQUIRE(workspace_bytes >= need, HMM_E_WORKSPACE, "encoder_forward_text_packed: workspace %zu < required %zu",
+                workspace_bytes, need);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int sk = splitk_mode_rows(e, rows);
+    const int tile = rows <= g_enc_sliver_rows ? HMM_GEMM_TILE_AUTO : HMM_GEMM_TILE_AUTO_TILED;
+    Chain c{ids_dev, out_dev, static_cast<char*>(workspace_dev), ws_plan_rows(e, batch, (int)rows, sk, true), st, batch,
+            e->cls_stream[0], e->ev_x[0], e->ev_cls[0], tile, kGemmSmallTiles, false, sk, nullptr, offsets_dev, max_len};
+    int rc = chain_tokens(e, c);
+    for (int i = 0; i < e->depth && rc == HMM_OK; ++i) rc = chain_block(e, c, i);
+    if (rc == HMM_OK) rc = chain_head(e, c);
     return rc;
 }
 

@@ -30,6 +30,13 @@ int launch_l2norm_rows(const float* v, float* out, int n_out, int clips, const f
 int launch_gather_rows(const void* src, size_t src_row_stride_bytes, void* dst, int n_rows, int row_bytes, hipStream_t st);
 int launch_embed_tokens(const int64_t* ids, const float* table, const float* pos, float* x, int n_rows, int T, int vocab,
                         hipStream_t st);
+// Packed text rows (questions at their own lengths): sample b owns rows off[b] .. off[b+1]-1, off = int32[batch + 1], the exclusive
+// prefix sum of the lengths with the total behind it.  Kernels skip a sample whose table entry is not 1 .. T rows inside
+// [0, total_rows].  x[off[b] + t] = table[ids[b*T + t]] + pos[t] for t < len[b]; max_len (host) sizes the launch.
+int launch_embed_tokens_packed(const int64_t* ids, const int32_t* off, const float* table, const float* pos, float* x, int batch, int T,
+                               int max_len, int total_rows, int vocab, hipStream_t st);
+// dst[b] = src row off[b+1] - 1 (each question's last row), rows of row_bytes (16-B pieces)
+int launch_gather_last_rows(const void* src, const int32_t* off, void* dst, int batch, int total_rows, int row_bytes, hipStream_t st);
 int launch_select_eos(const int64_t* ids, int32_t* sel, int batch, int T, hipStream_t st);
 // y_bf16[b] = LN(x[b*T + first position of the largest id of sample b]): the text head's select + gather + LayerNorm in one launch
 int launch_layernorm_eos_bf16(const float* x, const int64_t* ids, int T, const float* g, const float* b, bf16_t* y, int batch, int D,
@@ -42,6 +49,13 @@ int launch_fold_conv3d(const float* w, bf16_t* dst, int D, hipStream_t st);
 
 int attention_bf16(const bf16_t* qkv, bf16_t* out, int batch, int tokens, int heads, int head_dim,
                    const float* bias_k, const float* bias_v, hipStream_t st, bool causal = false);
+
+// text tower, packed rows: causal attention per sample with T = Lk = off[b+1] - off[b] <= 96 (head_dim 64), and the last block's
+// one query per sample (its last row, which sees all of its keys); kv is [total_rows][2D], q_last / out [batch][D]
+int attention_causal_packed_bf16(const bf16_t* qkv, bf16_t* out, const int32_t* offsets, int batch, int total_rows, int heads,
+                                 int head_dim, hipStream_t st);
+int attention_last_packed_bf16(const bf16_t* q_last, const bf16_t* kv, bf16_t* out, const int32_t* offsets, int batch, int total_rows,
+                               int heads, int head_dim, hipStream_t st);
 
 // vision tower only (D 1280, 16 heads, 257 tokens): in_proj + attention in one kernel (qkv_attention.hip); qkv_cls is the
 // [n_img][3D] projection of the cls rows, out is [n_img*257][D]

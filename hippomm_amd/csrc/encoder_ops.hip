@@ -251,6 +251,42 @@ __global__ __launch_bounds__(256) void embed_tokens_kernel(const int64_t* __rest
     }
 }
 
+// text tower, packed rows: x[off[b] + t] = token_embedding[ids[b][t]] + pos_embed[t] for t < off[b+1] - off[b]   (D = 1024; one
+// wave per token row, grid (ceil(max_len / 4), batch)); the tokens behind a question's length are never read
+__global__ __launch_bounds__(256) void embed_tokens_packed_kernel(const int64_t* __restrict__ ids, const int32_t* __restrict__ off,
+                                                                  const float* __restrict__ table, const float* __restrict__ pos,
+                                                                  float* __restrict__ x, int T, int total_rows, int vocab) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.y;
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int r0 = off[b], len = off[b + 1] - r0;
+    if (r0 < 0 || len < 1 || len > T || len > total_rows - r0 || t >= len) return;
+    int64_t id = ids[(size_t)b * T + t];
+    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+    const float* src = table + (size_t)id * 1024;
+    const float* pr = pos + (size_t)t * 1024;
+    float* dst = x + (size_t)(r0 + t) * 1024;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float4 a = *reinterpret_cast<const float4*>(src + 4 * (64 * j + lane));
+        const float4 p = *reinterpret_cast<const float4*>(pr + 4 * (64 * j + lane));
+        *reinterpret_cast<float4*>(dst + 4 * (64 * j + lane)) = make_float4(a.x + p.x, a.y + p.y, a.z + p.z, a.w + p.w);
+    }
+}
+
+// dst[b] = src[off[b+1] - 1]   rows of row_bytes (16-B pieces): each packed question's last row
+__global__ void gather_last_rows_kernel(const char* __restrict__ src, const int32_t* __restrict__ off, char* __restrict__ dst,
+                                        int n_rows, int total_rows, int row_bytes) {
+    const int per_row = row_bytes / 16;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)n_rows * per_row) return;
+    const int r = (int)(i / per_row), c = (int)(i % per_row);
+    const int last = off[r + 1] - 1;
+    if (last < 0 || last >= total_rows) return;
+    *reinterpret_cast<uint4*>(dst + (size_t)r * row_bytes + c * 16) =
+        *reinterpret_cast<const uint4*>(src + (size_t)last * row_bytes + c * 16);
+}
+
 // sel[b] = first position of the largest token id of sample b (the EOS token has the largest id)
 __global__ __launch_bounds__(64) void select_eos_kernel(const int64_t* __restrict__ ids, int32_t* __restrict__ sel, int T) {
     const int b = blockIdx.x, lane = threadIdx.x;
@@ -407,6 +443,21 @@ int launch_gather_rows(const void* src, size_t src_row_stride_bytes, void* dst, 
 int launch_embed_tokens(const int64_t* ids, const float* table, const float* pos, float* x, int n_rows, int T, int vocab,
                         hipStream_t st) {
     embed_tokens_kernel<<<(n_rows + 3) / 4, 256, 0, st>>>(ids, table, pos, x, n_rows, T, vocab);
+    HMM_LAUNCH_CHECK();
+    return HMM_OK;
+}
+int launch_embed_tokens_packed(const int64_t* ids, const int32_t* off, const float* table, const float* pos, float* x, int batch, int T,
+                               int max_len, int total_rows, int vocab, hipStream_t st) {
+    HMM_REQUIRE(batch >= 1 && batch <= 65535 && max_len >= 1 && max_len <= T, HMM_E_INVALID,
+                "embed_tokens_packed: batch %d (1 .. 65535), max_len %d (1 .. %d)", batch, max_len, T);
+    embed_tokens_packed_kernel<<<dim3((max_len + 3) / 4, batch), 256, 0, st>>>(ids, off, table, pos, x, T, total_rows, vocab);
+    HMM_LAUNCH_CHECK();
+    return HMM_OK;
+}
+int launch_gather_last_rows(const void* src, const int32_t* off, void* dst, int batch, int total_rows, int row_bytes, hipStream_t st) {
+    const int64_t n = (int64_t)batch * (row_bytes / 16);
+    gather_last_rows_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(static_cast<const char*>(src), off, static_cast<char*>(dst),
+                                                                        batch, total_rows, row_bytes);
     HMM_LAUNCH_CHECK();
     return HMM_OK;
 }

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, _pinned
 
 logger = logging.getLogger(__name__)
 
@@ -44,6 +44,30 @@ _PREFIXES = {
 }
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+
+
+TEXT_TOKENS = 77
+
+
+def text_lengths(ids) -> np.ndarray:
+    """(B,77) token ids on the host (tensor, array or nested list) -> int32 (B,) lengths for the packed text route:
+    len[b] = (first index of the row's largest id) + 1, the EOS rule of the tower's head (the EOS token has the largest id
+    of the CLIP vocabulary), so 1 <= len <= 77 and a row of equal ids has length 1.  Pure host function, no GPU."""
+    a = ids.detach().cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
+    if a.ndim != 2 or a.shape[1] != TEXT_TOKENS:
+        raise ValueError(f"text ids must be (B,{TEXT_TOKENS}), got {tuple(a.shape)}")
+    return (np.argmax(a, axis=1) + 1).astype(np.int32)            # numpy's argmax returns the first of equal maxima
+
+
+def text_offsets(lengths) -> np.ndarray:
+    """int32 (B+1,): the exclusive prefix sum of the lengths with the total behind it -- sample b owns rows
+    off[b] .. off[b+1]-1 of the packed residual stream (the device table of hmm_encoder_forward_text_packed)."""
+    n = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    if n.size and (n.min() < 1 or n.max() > TEXT_TOKENS):
+        raise ValueError(f"text lengths must be 1 .. {TEXT_TOKENS}, got {int(n.min())} .. {int(n.max())}")
+    off = np.zeros(n.size + 1, dtype=np.int32)
+    np.cumsum(n, out=off[1:])
+    return off
 
 
 class ModalityType:
@@ -68,6 +92,8 @@ class HipTower:
             self._h = handle
             self._load(state_dict)
         self._ws = None
+        self._table_stage = {}                        # text tower, packed route: pinned staging of the offsets table
+        self.text_stats = None                        # text tower: the last call's {"route", "rows_padded", "rows_packed"}
 
     def _load(self, state_dict):
         used = 0
@@ -138,14 +164,66 @@ class HipTower:
             _lib.check(self._lib.hmm_encoder_forward(self._h, x.data_ptr(), b, out.data_ptr(), ws.data_ptr(), ws.numel(),
                                                      _lib.stream_ptr()), "hmm_encoder_forward")
 
-    def __call__(self, x: torch.Tensor, max_batch: int = 256) -> torch.Tensor:
+    def upload_text_table(self, lengths) -> torch.Tensor:
+        """Host lengths (text_lengths) -> the int32 (B+1,) offsets table on the device, through pinned staging; asynchronous."""
+        off = text_offsets(lengths)
+        with torch.cuda.device(self.device):
+            st = _pinned.stage(self._table_stage, self.device.index, (max(off.size, 64),), torch.int32)
+            st.wait()
+            st.host[:off.size] = off
+            dev = torch.empty(off.size, dtype=torch.int32, device=self.device)
+            dev.copy_(st.pinned[:off.size], non_blocking=True)
+            st.mark()
+        return dev
+
+    def forward_text_packed_into(self, ids: torch.Tensor, lengths: np.ndarray, offsets_dev: torch.Tensor, out: torch.Tensor):
+        """Text tower on packed rows (hmm_encoder_forward_text_packed).  ids: (b,77) int64 contiguous CUDA; lengths: int32 (b,)
+        on the host (text_lengths); offsets_dev: upload_text_table(lengths); out: (b,1024) fp32 CUDA.  Asynchronous, capturable."""
+        if self.name != "text":
+            raise ValueError(f"the packed route belongs to the text tower, this is the {self.name} tower")
+        b = ids.shape[0]
+        lengths = np.ascontiguousarray(lengths, dtype=np.int32)
+        if lengths.shape != (b,) or tuple(offsets_dev.shape) != (b + 1,) or offsets_dev.dtype != torch.int32:
+            raise ValueError(f"{b} questions need {b} lengths and an int32 table of {b + 1}")
+        rows = int(lengths.sum(dtype=np.int64))
+        with torch.cuda.device(self.device):
+            need = self._lib.hmm_encoder_text_packed_workspace_bytes(self._h, b, rows)
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = None
+                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            _lib.check(self._lib.hmm_encoder_forward_text_packed(self._h, ids.data_ptr(), lengths.ctypes.data, offsets_dev.data_ptr(),
+                                                                 b, out.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
+                                                                 _lib.stream_ptr()), "hmm_encoder_forward_text_packed")
+
+    def _eos_lengths_from_device(self, x: torch.Tensor) -> np.ndarray:
+        """One small read-back: the first position of each row's largest id, + 1 (ties resolved as text_lengths resolves them)."""
+        top = x.max(dim=1, keepdim=True).values
+        where = torch.where(x == top, torch.arange(x.shape[1], device=x.device).expand_as(x), x.shape[1])
+        return (where.min(dim=1).values + 1).to(torch.int32).cpu().numpy()
+
+    def __call__(self, x: torch.Tensor, max_batch: int = 256, pack: bool = False, lengths=None) -> torch.Tensor:
+        """pack (text tower only): every question at its own length (lengths: text_lengths of the host ids; None: read back
+        from x).  Off: the padded forward, unchanged."""
         if tuple(x.shape[1:]) != INPUT_SHAPE[self.name]:
             raise ValueError(f"{self.name} input must be (B,{','.join(map(str, INPUT_SHAPE[self.name]))}), "
                              f"got {tuple(x.shape)}")
+        if pack and self.name != "text":
+            raise ValueError(f"the packed route belongs to the text tower, this is the {self.name} tower")
+        if pack and lengths is None and not x.is_cuda:
+            lengths = text_lengths(x)
         x = x.to(device=self.device, dtype=INPUT_DTYPE[self.name]).contiguous()
         out = torch.empty(x.shape[0], 1024, dtype=torch.float32, device=self.device)
+        if pack and x.shape[0]:
+            lengths = self._eos_lengths_from_device(x) if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
+            for s in range(0, x.shape[0], max_batch):
+                part = lengths[s:s + max_batch]
+                self.forward_text_packed_into(x[s:s + max_batch], part, self.upload_text_table(part), out[s:s + max_batch])
+            self.text_stats = {"route": "packed", "rows_padded": int(x.shape[0]) * TEXT_TOKENS, "rows_packed": int(lengths.sum())}
+            return out
         for s in range(0, x.shape[0], max_batch):
             self.forward_into(x[s:s + max_batch], out[s:s + max_batch])
+        if self.name == "text":
+            self.text_stats = {"route": "padded", "rows_padded": int(x.shape[0]) * TEXT_TOKENS, "rows_packed": None}
         return out
 
 
@@ -157,13 +235,19 @@ class HipImageBindModel(nn.Module):
         super().__init__()
         self.towers = towers
         self.max_batch = max_batch
+        self.pack_text = False                        # 'text': every question at its own length (HipTower.__call__(pack=True))
 
     def forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         out = {}
         for key, value in inputs.items():
             if key not in self.towers:
                 raise KeyError(f"modality {key!r} is not built on this device (have {list(self.towers)})")
-            out[key] = self.towers[key](value, self.max_batch.get(key, 256))
+            if key == ModalityType.TEXT and self.pack_text:
+                # the lengths ImageBind.load_data took from the tokenizer's host ids ride on the tensor; without them: one read-back
+                out[key] = self.towers[key](value, self.max_batch.get(key, 256), pack=True,
+                                            lengths=getattr(value, "_hmm_text_lengths", None))
+            else:
+                out[key] = self.towers[key](value, self.max_batch.get(key, 256))
         return out
 
 
@@ -265,7 +349,7 @@ class ImageBind(nn.Module):
                  towers: Iterable[str] = ("vision", "audio"),
                  depth: Optional[Dict[str, int]] = None,
                  max_batch: Optional[Dict[str, int]] = None,
-                 tokenizer=None, tower_inputs=None):
+                 tokenizer=None, tower_inputs=None, pack_text: bool = False):
         super().__init__()
         self.tower_inputs = tower_inputs            # a preprocess.TowerInputCache (or None; may be set later): _vision_from_files
         self.tokenizer = tokenizer                  # str list -> (B,77) int64 (imagebind.data.load_and_transform_text)
@@ -277,6 +361,24 @@ class ImageBind(nn.Module):
         self.device = _lib.require_gpu()            # reference :26 falls back to cpu then calls .cuda() anyway (:33)
         self.model = self._load_model(model_path, state_dict, tuple(towers), depth or {},
                                       max_batch or {"vision": 256, "audio": 128})
+        self.pack_text = pack_text
+
+    @property
+    def pack_text(self) -> bool:
+        """'text' through the packed route: every question at its own length (causal tower, the head reads the EOS row: the
+        rows behind EOS cannot change the result and are not computed).  Off by default; other bits than the padded route,
+        the same stated tolerance.  May be set at any time."""
+        return self.model.pack_text
+
+    @pack_text.setter
+    def pack_text(self, on: bool):
+        self.model.pack_text = bool(on)
+
+    @property
+    def text_stats(self):
+        """The last 'text' forward: {"route": "packed" | "padded", "rows_padded": 77 B, "rows_packed": sum of lengths | None}."""
+        tower = self.model.towers.get(ModalityType.TEXT)
+        return None if tower is None else tower.text_stats
 
     def _load_model(self, model_path, state_dict, towers, depth, max_batch) -> nn.Module:
         """Build the HIP towers from upstream-named weights (reference :31-35)."""
@@ -330,7 +432,10 @@ class ImageBind(nn.Module):
                         raise NotImplementedError("text needs the CLIP merge table bpe_simple_vocab_16e6.txt.gz (under "
                                                   "model_path, .checkpoints/, bpe/ or $IMAGEBIND_BPE), a tokenizer= "
                                                   "callable, or a (B,77) int64 token tensor")
-                    transformed[modality] = self.tokenizer(list(value)).to(self.device)
+                    tokens = self.tokenizer(list(value))
+                    transformed[modality] = tokens.to(self.device)
+                    if self.pack_text:                             # lengths from the HOST ids: no read-back of the EOS positions
+                        transformed[modality]._hmm_text_lengths = text_lengths(tokens)
                 else:
                     raise NotImplementedError(f"modality {modality!r} is not built")
             except Exception as e:  # noqa: BLE001 - mirror of the reference's catch-all
@@ -338,10 +443,13 @@ class ImageBind(nn.Module):
                 continue
         return transformed
 
-    def forward(self, inputs):
-        """{modality: tensor} -> {modality: (B,1024) fp32} (reference :116-133)."""
+    def forward(self, inputs, stats: Optional[dict] = None):
+        """{modality: tensor} -> {modality: (B,1024) fp32} (reference :116-133).  stats: a dict that receives text_stats when
+        the call embeds 'text'."""
         with torch.no_grad():
             embeddings = self.model(inputs)
+        if stats is not None and ModalityType.TEXT in embeddings:
+            stats.update(self.text_stats)
         return embeddings
 
     def _vision_from_files(self, images) -> torch.Tensor:
@@ -404,7 +512,7 @@ class ImageBind(nn.Module):
         with torch.no_grad():
             return self.model.towers[a](track.melspec(spans), self.model.max_batch.get(a, 256))
 
-    def extract_features(self, inputs, modalities):
+    def extract_features(self, inputs, modalities, stats: Optional[dict] = None):
         """load_data + forward (reference :135-151).  Vision given as files (the reference's formation calls,
         hippocampal_memory.py:1180-1186, :1328-1335) runs decode, upload, resize and the tower as one overlapped pipeline;
         a failure is logged and the modality left out, exactly as load_data does (:110-112)."""
@@ -418,5 +526,5 @@ class ImageBind(nn.Module):
                     fused[v] = self._vision_from_files(inputs[v])
             except Exception as e:  # noqa: BLE001 - mirror of the reference's catch-all
                 logger.error(f"Error processing {v}: {str(e)}")
-        out = self.forward(self.load_data(inputs, rest)) if rest else {}
+        out = self.forward(self.load_data(inputs, rest), stats=stats) if rest else {}
         return {m: (fused[m] if m in fused else out[m]) for m in modalities if m in fused or m in out}

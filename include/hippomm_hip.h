@@ -385,6 +385,33 @@ int  hmm_encoder_set_streams(hmm_encoder* enc, int n_streams);
  * per sample. */
 int  hmm_encoder_set_fused_attention(hmm_encoder* enc, int on);
 
+/* Text tower on PACKED rows: every question at its own length instead of 77 rows (opt-in; hmm_encoder_forward is untouched).
+ * The tower is causal and the head reads only the row at the EOS position, so no row behind EOS can change the result; this
+ * entry does not compute them.  len[b] = (first index of the largest id of row b) + 1, 1 <= len[b] <= 77: the EOS rule of
+ * hmm_encoder_forward.  Sample b owns rows off[b] .. off[b] + len[b] - 1 of one dense [R][1024] residual stream, R = sum len.
+ *   ids_dev       (batch,77) int64, as for hmm_encoder_forward; ids behind a row's length are never read; never written
+ *   lengths_host  int32[batch] on the HOST: validated here (a length outside 1 .. 77: HMM_E_INVALID) and used for launch sizes,
+ *                 the regime and the workspace layout; not read after the call returns
+ *   offsets_dev   int32[batch + 1] on the DEVICE: the exclusive prefix sum of lengths_host, the total R behind it.  The library
+ *                 derives the same table from lengths_host for its own sizes and never reads offsets_dev on the host (no
+ *                 synchronisation); kernels read only offsets_dev.  A device table that differs from that prefix sum breaks a
+ *                 precondition: the kernels skip every sample whose entry does not describe 1 .. 77 rows inside [0, R], so no
+ *                 byte outside the documented extents is touched, but the embeddings of that call are undefined.
+ *   Lengths that do not match the EOS positions of ids_dev are a precondition too, not checked: the embedding is then that
+ *   of the row at len[b] - 1.
+ *   out_dev       (batch,1024) fp32
+ * Workspace: exactly hmm_encoder_text_packed_workspace_bytes(enc, batch, R), a function of (batch, R) alone (0 for a handle
+ * that is not a text tower, batch < 1 or R outside batch .. 77 batch); fewer bytes are refused with HMM_E_WORKSPACE before
+ * anything is written.  One chain on the caller's stream, no synchronisation, capturable.  Regime and GEMM dispatch follow the
+ * rules of hmm_encoder_forward keyed by R (few-row regime: R <= 700); within a regime a question's embedding does not depend on
+ * its position in the batch or on its batch-mates, bit for bit.  The last block computes Q, attention, out-proj and the MLP
+ * for the EOS rows only.  Bits differ from hmm_encoder_forward's (other row counts, the one-query last block); both meet the
+ * stated tolerance against the fp32 oracle. */
+size_t hmm_encoder_text_packed_workspace_bytes(const hmm_encoder* enc, int batch, int64_t total_rows);
+int  hmm_encoder_forward_text_packed(hmm_encoder* enc, const int64_t* ids_dev, const int32_t* lengths_host,
+                                     const int32_t* offsets_dev, int batch, float* out_dev,
+                                     void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Device-side vision preprocessing.  Replaces, for already decoded frames, the transform chain of
  * imagebind.data.load_and_transform_vision_data (torchvision Resize(224, BICUBIC) -> CenterCrop(224) ->
@@ -745,6 +772,13 @@ int hmm_op_qkv_attention_audio_bf16(const uint16_t* a_dev, const uint16_t* w_dev
 /* Causal variant (text tower): key j is visible to query i iff j <= i; no bias_kv. */
 int hmm_op_attention_causal_bf16(const uint16_t* qkv_dev, uint16_t* out_dev, int batch, int tokens,
                                  int heads, int head_dim, hmm_stream_t stream);
+/* Causal attention over packed sequences: sample b owns rows offsets_dev[b] .. offsets_dev[b+1]-1 (int32[batch + 1] on the
+ * device, non-decreasing, offsets_dev[batch] = total_rows) of qkv_dev [total_rows][3D] and out_dev [total_rows][D], with as many
+ * keys as queries.  head_dim 64 and at most 96 rows per sample; a sample whose table entry is outside 1 .. 96 rows or outside
+ * [0, total_rows] is skipped (its output rows keep their bytes).  A sample of T rows gets the bits hmm_op_attention_causal_bf16
+ * gives a sample of T tokens. */
+int hmm_op_attention_causal_packed_bf16(const uint16_t* qkv_dev, uint16_t* out_dev, const int32_t* offsets_dev, int batch,
+                                        int total_rows, int heads, int head_dim, hmm_stream_t stream);
 
 /* ---- the tower stages that are neither a GEMM nor the attention core, each on its own (tests/test_gpu_stage_ops.py) ----
  * Thin entry points over the launchers hmm_encoder_forward uses.  Every one refuses null required pointers and
