@@ -36,8 +36,16 @@ and the callers' retrieval step with the reference's row and fallback rules appl
 
     hippomm_amd.find_relevant_video_segments         <- hippomm/core/hippocampal_memory.py:3127-3279
     hippomm_amd.find_relevant_audio_segments         <- hippomm/core/hippocampal_memory.py:3281-3383
+
+and the step right after it, the frame windows read around every frame_time of the relevant segments: cv2.resize's 8-bit
+INTER_LINEAR for targets no larger than the source (hippomm_amd/csrc/resize.hip), the JPEG and the SSIM dedup in one pass, without
+a file round-trip (video decoding stays with the caller; the time of a question is the caller's seeks and the captioner, not this):
+
+    hippomm_amd.recall_window_frames                 <- hippomm/core/hippocampal_memory.py:2226-2249, :2789-2812
+    hippomm_amd.segmentation.resize_frames           <- cv2.resize(frame, (320, 180))
 """
 __version__ = "0.1.0"
 
 from .jpeg import decode_jpeg, encode_jpeg  # noqa: E402,F401
-from .retrieval import feature_entries, find_relevant_audio_segments, find_relevant_video_segments  # noqa: E402,F401
+from .retrieval import (feature_entries, find_relevant_audio_segments, find_relevant_video_segments,  # noqa: E402,F401
+                        recall_window_frames)

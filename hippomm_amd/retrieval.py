@@ -13,16 +13,27 @@ callables' entries; a feature hit among the final ``keep`` is among the best ``k
 
 Limits: where NaN similarities sort is this library's rule (first), not Python's; a store converted from fp64 holds fp32
 similarities widened, so a 0.4 decision within 2e-6 of the threshold can differ from the reference.
+
+``recall_window_frames`` is the step the reference takes next (:2210-2251 in ``_process_video_query``, :2773-2815 in
+``_process_multimodal_query``, the same text): the frames of a +-1 s window around every frame_time of the segments found are
+shrunk with ``cv2.resize(frame, (320, 180))``, written as JPEG and dropped when their SSIM with the last kept file of the window
+is above 0.3.  Here the shrink, the files, their decoded pixels, the gray frames and the scores of all windows of a question are
+made on the device in one pass; the walk is a host function of the scores.  A question's wall time is the caller's video seeks
+and the captioner, not this arithmetic: the point is that no numeric step of the retrieval path is left on the host.
 """
 from __future__ import annotations
 
 import logging
+from dataclasses import dataclass
+from pathlib import Path
 from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from .segmentation import SequenceSegment
+from . import _lib, jpeg
+from .segmentation import (RECALL_SIMILARITY_CUT, RECALL_SIZE, SAVE_QUALITY, SAVE_SUBSAMPLING, WIN, FrameCache, SequenceSegment,
+                           _ssim_launch, _upload_frames, gray_frames, resize_frames, resize_mode, walk_recall_window)
 from .vector_ops import FEATURE_DIM, EventStore
 
 logger = logging.getLogger(__name__)
@@ -121,3 +132,115 @@ def find_relevant_audio_segments(events, query_features, *, store: Optional[Even
     """``_find_relevant_audio_segments`` (:3281-3383); see ``find_relevant_video_segments`` (the store holds the audio matrices,
     the row limit is ``len(event.feature_times['audio_times'])``, the flag is ``holistic_audio_transcription``)."""
     return _find("audio", events, query_features, store, deferred, k, keep, min_similarity, prefilter)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the recall frame windows: shrink, JPEG and SSIM dedup of the frames read around every frame_time of the relevant segments
+# ---------------------------------------------------------------------------------------------------------------------------------
+MAX_WINDOW_FRAMES = 8                      # the reference's +-1 s windows at 1 fps hold at most 3
+
+
+@dataclass
+class RecallWindowFrames:
+    """What ``recall_window_frames`` returns.  Per window, in the order given: ``kept`` the indices of the frames that survive
+    the dedup walk, ``times`` their times, ``files`` their JPEG files (bytes).  Flat, window after window -- the order in which the
+    reference appends to all_segment_frames / all_segment_times: ``all_segment_times``, ``all_segment_files`` and, when ``paths``
+    were given, ``all_segment_frames`` (the paths the kept files were written to; else None)."""
+    kept: List[List[int]]
+    times: List[List[float]]
+    files: List[List[bytes]]
+    all_segment_times: List[float]
+    all_segment_files: List[bytes]
+    all_segment_frames: Optional[List[str]] = None
+
+
+def recall_window_frames(windows, size: Tuple[int, int] = RECALL_SIZE, similarity_cut: float = RECALL_SIMILARITY_CUT,
+                         quality: int = SAVE_QUALITY, paths=None, cache: Optional[FrameCache] = None) -> RecallWindowFrames:
+    """The numeric work of the frame loop that follows retrieval in ``_process_video_query`` / ``_process_multimodal_query``
+    (:2226-2249, :2789-2812) for all windows of a question in one pass.  ``windows``: one list per (segment, frame_time) of
+    ``(time, frame)`` in read order, the frames BGR uint8 (H, W, 3) arrays as ``cap.read()`` returns them; video decoding stays
+    with the caller.  At most ``MAX_WINDOW_FRAMES`` frames per window (``ValueError``).
+
+    Per call: one pinned upload and one resize launch per source geometry (``cv2.resize(frame, size)``, ``size`` = (width,
+    height): ``segmentation.resize_frames``); one ``encode_jpeg(..., "BGR", return_decoded=True)`` at ``quality`` and 4:2:0 (the
+    files of ``cv2.imwrite``'s defaults, and their decoded pixels without a file round-trip); one gray pass with min / max; one
+    ``hmm_ssim_pairs`` over all (i < j) pairs inside each window, the earlier frame in the im1 role (data_range = max - min of
+    it, as ``_compute_frame_similarity`` passes); one read-back of the scores; then ``segmentation.walk_recall_window`` per window
+    on the host: frame 0 is kept, a frame is dropped iff its SSIM with the last kept frame is ``> similarity_cut``.
+
+    ``paths``: one path per frame, nested as ``windows``; the kept frames' files are written there (parents are created), dropped
+    frames write nothing.  The reference's ``/tmp/frame_<ms>.jpg`` names collide across segments, so naming stays with the
+    caller.  ``cache``: a ``FrameCache`` that receives the gray frame of every file written (needs ``paths``).
+
+    The source may not be smaller than ``size`` on either axis, and ``size`` not under 7 x 7 (``ValueError``).  The file bytes are
+    Pillow's for the shrunk frame (``encode_jpeg``); they are not claimed to equal OpenCV's file."""
+    windows = [list(w) for w in windows]
+    for w, window in enumerate(windows):
+        if len(window) > MAX_WINDOW_FRAMES:
+            raise ValueError(f"recall_window_frames: window {w} holds {len(window)} frames; at most {MAX_WINDOW_FRAMES} are taken")
+        for _, frame in window:
+            if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
+                raise TypeError(f"recall_window_frames: window {w} holds a frame that is not a uint8 (H, W, 3) BGR array")
+    if paths is not None:
+        paths = [[str(p) for p in ps] for ps in paths]
+        if [len(ps) for ps in paths] != [len(w) for w in windows]:
+            raise ValueError("recall_window_frames: paths must hold one path per frame, nested as windows")
+    elif cache is not None:
+        raise ValueError("recall_window_frames: cache= keys frames by the path of their file; give paths= too")
+    dw, dh = (int(v) for v in size)
+    if dw < WIN or dh < WIN:
+        raise ValueError(f"recall_window_frames: size {dw} x {dh} is under the {WIN} x {WIN} SSIM window")
+    flat = [frame for window in windows for _, frame in window]
+    base = np.cumsum([0] + [len(window) for window in windows])
+    groups = {}
+    for i, frame in enumerate(flat):
+        resize_mode(frame.shape[:2], (dh, dw))                            # an enlargement raises before anything is uploaded
+        groups.setdefault(frame.shape[:2], []).append(i)
+    scores = np.empty(0)
+    files: List[bytes] = []
+    pairs = [(int(base[w]) + i, int(base[w]) + j) for w, window in enumerate(windows)
+             for i in range(len(window)) for j in range(i + 1, len(window))]
+    if flat:
+        dev = _lib.require_gpu()
+        small = None
+        for members in groups.values():
+            shrunk = resize_frames(_upload_frames([flat[i] for i in members], dev), (dw, dh))
+            if len(groups) == 1:
+                small = shrunk
+            else:
+                if small is None:
+                    small = torch.empty((len(flat), dh, dw, 3), dtype=torch.uint8, device=dev)
+                small.index_copy_(0, torch.tensor(members, dtype=torch.int64).to(dev), shrunk)
+        files, decoded = jpeg.encode_jpeg(small, quality=quality, subsampling=SAVE_SUBSAMPLING, channel_order="BGR",
+                                          return_decoded=True)
+        if pairs:
+            gray, minmax = gray_frames(decoded, "RGB", return_minmax=True)
+            scores = _ssim_launch(gray, np.array(pairs, dtype=np.int32), -1.0, minmax).cpu().numpy()
+    out = RecallWindowFrames([], [], [], [], [], None if paths is None else [])
+    at = 0
+    for w, window in enumerate(windows):
+        m = len(window)
+        table = np.full((m, m), np.nan)
+        for i in range(m):
+            for j in range(i + 1, m):
+                table[i, j] = scores[at]
+                at += 1
+        kept = walk_recall_window(table, similarity_cut)
+        out.kept.append(kept)
+        out.times.append([window[i][0] for i in kept])
+        out.files.append([files[int(base[w]) + i] for i in kept])
+        out.all_segment_times.extend(out.times[-1])
+        out.all_segment_files.extend(out.files[-1])
+        if paths is not None:
+            out.all_segment_frames.extend(paths[w][i] for i in kept)
+    if paths is not None:
+        written = []
+        for w, kept in enumerate(out.kept):
+            for i, data in zip(kept, out.files[w]):
+                Path(paths[w][i]).parent.mkdir(parents=True, exist_ok=True)
+                Path(paths[w][i]).write_bytes(data)
+                written.append((paths[w][i], int(base[w]) + i))
+        if cache is not None and written:
+            last = {p: k for p, k in written}                             # a path written twice holds its last frame
+            cache.put(list(last), decoded[torch.tensor(list(last.values()), dtype=torch.int64).to(decoded.device)])
+    return out

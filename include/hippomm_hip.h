@@ -544,6 +544,31 @@ int    hmm_ssim_pairs(const uint8_t* gray_dev, int n_frames, int H, int W, const
                       void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * cv2.resize of 8-bit frames to a target no larger than the source, as the reference shrinks every recalled frame
+ * (hippomm/core/hippocampal_memory.py:2232, :2795: cv2.resize(frame, (320, 180))).  The arithmetic is OpenCV's 8-bit INTER_LINEAR,
+ * restated from its published source (imgproc/src/resize.cpp); a build that routes 8-bit resize through another back end may differ.
+ *
+ * hmm_resize_linear_u8: src_dev (n, src_h, src_w, channels) u8 dense -> dst_dev (n, dst_h, dst_w, channels) u8 dense; channels 1
+ *   or 3; dst_h <= src_h and dst_w <= src_w (an enlargement is HMM_E_INVALID: OpenCV's border rules there are not built).
+ *   mode HMM_RESIZE_LINEAR: xofs_dev int32[dst_w] and yofs_dev int32[dst_h] are the first of the two source indices of an output
+ *     index, xcoef_dev int16[dst_w][2] and ycoef_dev int16[dst_h][2] its weights on the 2048 scale (for output index d at scale
+ *     src / dst in double: f = (float)((d + 0.5) * scale - 0.5), s = floor(f), f -= s in float, weights (short)rint((1.f - f) * 2048)
+ *     and (short)rint(f * 2048), half to even; a pair need not sum to 2048).  Per channel, in int32:
+ *       h = S[s] * a0 + S[s + 1] * a1 along x (S[s] * 2048 where s + 1 would leave the row), for the rows sy and sy + 1, then
+ *       d = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2.
+ *     Offsets are clamped to the frame: a wrong table gives wrong pixels, never a read outside src_dev.
+ *   mode HMM_RESIZE_AREA2X (src exactly twice dst on both axes, where OpenCV turns INTER_LINEAR into its 2 x 2 area path):
+ *     d = (s00 + s01 + s10 + s11 + 2) >> 2; the tables are not read and may be null.
+ *   One launch for all n frames (n <= 65535; n == 0: HMM_OK, nothing launched); no workspace, no allocation, no
+ *   synchronisation.  Offsets aligned to 4 bytes, coefficients to 2.
+ * ---------------------------------------------------------------------------------------- */
+#define HMM_RESIZE_LINEAR  0
+#define HMM_RESIZE_AREA2X  1
+int hmm_resize_linear_u8(const uint8_t* src_dev, int n, int src_h, int src_w, int channels, uint8_t* dst_dev, int dst_h, int dst_w,
+                         const int32_t* xofs_dev, const int16_t* xcoef_dev, const int32_t* yofs_dev, const int16_t* ycoef_dev,
+                         int mode, hmm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Baseline JPEG decoding, split between host and GPU.  Replaces the libjpeg decode inside Image.open(path).convert("RGB") of
  * imagebind.data.load_and_transform_vision_data [upstream, recalled] (hippomm/models/foundation_models.py:87-90) and of the
  * frame reads of _segment_sequence (hippomm/core/hippocampal_memory.py:1002-1114), with Pillow's pixels to the bit: libjpeg-turbo's
