@@ -43,6 +43,10 @@ a file round-trip (video decoding stays with the caller; the time of a question 
 
     hippomm_amd.recall_window_frames                 <- hippomm/core/hippocampal_memory.py:2226-2249, :2789-2812
     hippomm_amd.segmentation.resize_frames           <- cv2.resize(frame, (320, 180))
+
+and, opt-in, the feature matrices of an event file written as JSON text on the device, byte for byte json.dump's (hippomm_amd/csrc/event_json.hip):
+
+    hippomm_amd.event_store.save_event(..., matrices="device"), event_json_bytes, matrix_json_bytes  <- hippomm/core/hippocampal_memory.py:331-335
 """
 __version__ = "0.1.0"
 

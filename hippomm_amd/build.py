@@ -58,8 +58,10 @@ def _compile(src: Path, obj: Path, extra):
 def _build(srcs, obj_dir: Path, lib: Path, force: bool, jobs: int, extra) -> Path:
     obj_dir.mkdir(parents=True, exist_ok=True)
     todo, objs = [], []
+    stems = [src.stem for src in srcs]
     for src in srcs:
-        obj = obj_dir / (src.stem + ".o")
+        # event_json.cpp (host) and event_json.hip (kernels) share a stem: such objects carry the suffix as well
+        obj = obj_dir / (src.stem + ("" if stems.count(src.stem) == 1 else "_" + src.suffix[1:]) + ".o")
         objs.append(obj)
         if force or _stale(src, obj):
             todo.append((src, obj))

@@ -881,6 +881,36 @@ int hmm_json_parse_matrix_f32(const char* text, size_t begin, size_t end, size_t
 size_t hmm_json_matrix_text_bound(size_t rows, size_t cols, int close_indent);
 int hmm_json_write_matrix_f64(const double* m_host, size_t rows, size_t cols, int close_indent, char* out_text, size_t cap, size_t* written);
 
+/* ---- the same text, written on the device (csrc/event_json.hip, csrc/event_json_core.h) ----
+ * hmm_json_write_matrix_device: a rows x cols row-major matrix ON THE DEVICE, fp32 (dtype HMM_JSON_DTYPE_F32; every value is
+ * widened to double first, which is what np.asarray(f32).tolist() hands to json) or fp64 (HMM_JSON_DTYPE_F64) -> exactly the bytes
+ * hmm_json_write_matrix_f64 writes for those values at the same close_indent, into out_text_dev[0, *written_dev); *written_dev is a
+ * uint64 on the device.  Not one byte of out_text_dev behind *written_dev is written, nor one of the workspace behind
+ * hmm_json_write_matrix_device_workspace_bytes(rows, cols); the matrix is only read.  out_text_dev needs no alignment; the
+ * workspace and written_dev are 8-byte aligned, the matrix aligned to its element.  Three launches on `stream` (item lengths summed
+ * per workgroup of HMM_JSON_VALUES_PER_GROUP values; those sums scanned by one workgroup, HMM_JSON_SCAN_SUMS_PER_ROUND of them per
+ * round, i.e. HMM_JSON_VALUES_PER_SCAN_ROUND values; the text formed again, placed in LDS and stored in whole dwords): nothing
+ * synchronises or allocates, no workgroup waits for another, the call can be captured into a graph.
+ *   HMM_E_INVALID with a message, before any launch and without needing a GPU, for: a null pointer, an unknown dtype, rows or
+ *   cols < 1, rows * cols > HMM_JSON_MAX_VALUES, close_indent outside 0 .. HMM_JSON_MAX_INDENT (a workgroup stages its longest
+ *   possible round in LDS), cap < hmm_json_matrix_text_bound(rows, cols, close_indent), workspace_bytes below the query's answer
+ *   (the query answers 0 for a shape the call refuses), a misaligned matrix, workspace or written_dev.
+ * hmm_json_float_repr: HOST only, no GPU call -- the device's float printer run on the host: values[i] -> the characters
+ * json.dumps writes for that double (float.__repr__; NaN, Infinity, -Infinity) at out_chars + HMM_JSON_REPR_BYTES * i, their count
+ * (at most HMM_JSON_REPR_BYTES, no terminator) in out_lengths[i].  Correct for every double. */
+#define HMM_JSON_DTYPE_F32 0
+#define HMM_JSON_DTYPE_F64 1
+#define HMM_JSON_REPR_BYTES 24
+#define HMM_JSON_VALUES_PER_GROUP 1024
+#define HMM_JSON_SCAN_SUMS_PER_ROUND 256
+#define HMM_JSON_VALUES_PER_SCAN_ROUND (HMM_JSON_VALUES_PER_GROUP * HMM_JSON_SCAN_SUMS_PER_ROUND)
+#define HMM_JSON_MAX_VALUES 2147483648ull
+#define HMM_JSON_MAX_INDENT 32
+size_t hmm_json_write_matrix_device_workspace_bytes(size_t rows, size_t cols);
+int hmm_json_write_matrix_device(const void* m_dev, int dtype, size_t rows, size_t cols, int close_indent, char* out_text_dev, size_t cap,
+                                 uint64_t* written_dev, void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
+int hmm_json_float_repr(const double* values, size_t n, char* out_chars, int* out_lengths);
+
 #ifdef __cplusplus
 }
 #endif
