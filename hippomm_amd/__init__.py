@@ -47,6 +47,11 @@ a file round-trip (video decoding stays with the caller; the time of a question 
 and, opt-in, the feature matrices of an event file written as JSON text on the device, byte for byte json.dump's (hippomm_amd/csrc/event_json.hip):
 
     hippomm_amd.event_store.save_event(..., matrices="device"), event_json_bytes, matrix_json_bytes  <- hippomm/core/hippocampal_memory.py:331-335
+
+and, opt-in too, read back from that text on the device, the bits of np.array(json.load(f)) (hippomm_amd/csrc/event_json_parse.hip):
+
+    hippomm_amd.event_store.parse_matrix_device, parse_event_features(..., matrices="device"),
+    build_event_store / refresh_event_store(..., parse="device")                                   <- hippomm/core/hippocampal_memory.py:369-395
 """
 __version__ = "0.1.0"
 

@@ -145,6 +145,10 @@ _SIGNATURES = {
     "hmm_json_write_matrix_device": (C.c_int, [c_ptr, C.c_int, C.c_size_t, C.c_size_t, C.c_int, c_ptr, C.c_size_t, c_ptr, c_ptr,
                                                C.c_size_t, c_ptr]),
     "hmm_json_float_repr": (C.c_int, [c_ptr, C.c_size_t, c_ptr, c_ptr]),
+    "hmm_json_parse_matrix_device_workspace_bytes": (C.c_size_t, [C.c_size_t]),
+    "hmm_json_parse_matrix_device": (C.c_int, [c_ptr, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, c_ptr, c_ptr, c_ptr,
+                                               C.c_int64, c_ptr, C.c_size_t, c_ptr]),
+    "hmm_json_float_parse": (C.c_int, [c_ptr, c_ptr, C.c_size_t, c_ptr, c_ptr, c_ptr]),
 }
 
 

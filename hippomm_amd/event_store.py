@@ -20,13 +20,18 @@ stored fp32, float64 arrays after loading.  That file format is the contract wit
                      GPU (opt-in; the same bytes), so that embeddings that are still on the device reach the file without
                      becoming Python floats.
 
-Nothing here touches the GPU except ``build_event_store``, ``refresh_event_store`` and the ``matrices="device"`` route.
+* ``parse_matrix_device`` / ``parse_event_features(matrices="device")`` / ``build_event_store(parse="device")``  read the feature
+                     matrices back from that text ON THE GPU (opt-in; the same bits), so that a cold store without sidecars
+                     reaches HBM without a host fp32 matrix in between.
+
+Nothing here touches the GPU except ``build_event_store``, ``refresh_event_store`` and the ``matrices="device"`` / ``parse="device"`` routes.
 """
 from __future__ import annotations
 
 import json
 import logging
 import os
+import re
 import sys
 import threading
 import uuid
@@ -125,6 +130,11 @@ def _sidecar_paths(json_path: Path, modality: str) -> Tuple[Path, Path]:
 def _as_feature_matrix(a) -> np.ndarray:
     """One rule for both paths (JSON parse and sidecar): fp32, C-contiguous, and the reference's shape fix-up when a
     matrix arrives as (1024, N) (:413-417) -- so that an event loads with the same shape whichever path serves it."""
+    if _cuda_tensor(a):                                  # a matrix the device parser left in HBM: the same rule, no host trip
+        import torch
+        if a.dim() > 1 and a.shape[1] != 1024 and a.shape[0] == 1024:
+            a = a.T
+        return a.to(torch.float32).contiguous()
     a = np.asarray(a)
     if a.ndim > 1 and a.shape[1] != 1024 and a.shape[0] == 1024:
         a = a.T
@@ -392,6 +402,211 @@ def _fresh_manifest(json_path: Path) -> Optional[dict]:
     return None
 
 
+# ---- the feature matrices read back from JSON text on the device (csrc/event_json_parse.hip) ----
+FLAGGED_CAP = 256                    # entries of the flagged list a call brings; more flagged values than that: the host route
+_PARSE_OK, _FLAG_RANGE = 0, 2        # HMM_JSON_PARSE_OK, HMM_JSON_FLAG_RANGE
+_JSON_NUMBER = re.compile(rb"-?(?:0|[1-9][0-9]*)(?:\.[0-9]+)?(?:[eE][+-]?[0-9]+)?")
+_parse_route = {"on": True}          # False: every matrix is parsed by the host route
+_parse_check = {"ok": None}          # None: not compared yet in this process; False: the comparison failed, the route is off
+_parse_counts = {"device": 0, "host": 0, "json": 0}
+
+
+def matrix_parse_stats() -> dict:
+    """Matrices read per route by ``parse_matrix_device`` and ``parse_event_features(matrices="device")`` since the process
+    started: "device", "host" (``hmm_json_parse_matrix_f32``, then uploaded) and "json" (``json.loads``)."""
+    return dict(_parse_counts)
+
+
+class _EventText:
+    """The text of one event file for the device route: the bytes, the uint8 tensor, or both -- each made from the other at most
+    once (bytes go up through pinned staging in one copy; a tensor comes down only when the host route needs the characters)."""
+
+    def __init__(self, raw, dev):
+        self.dev = dev
+        self.host = raw if isinstance(raw, (bytes, bytearray, memoryview)) else None
+        self.tensor = None if self.host is not None else raw
+
+    def __len__(self):
+        return len(self.host) if self.host is not None else int(self.tensor.numel())
+
+    def on_device(self):
+        """Call with ``_device_lock`` held."""
+        if self.tensor is None:
+            import torch
+            from ._pinned import stage
+            n = len(self.host)
+            up = stage(_device_stages, ("text", self.dev.index), (n,))
+            up.wait()
+            up.host[:n] = np.frombuffer(self.host, np.uint8)
+            self.tensor = torch.empty(n, dtype=torch.uint8, device=self.dev)
+            self.tensor.copy_(up.pinned[:n], non_blocking=True)
+            up.mark()
+        return self.tensor
+
+    def bytes_of(self, begin: int, end: int) -> bytes:
+        if self.host is not None:
+            return bytes(self.host[begin:end])
+        return self.tensor[begin:end].cpu().numpy().tobytes()
+
+
+def _span4(span) -> Tuple[int, int, int, int]:
+    """(begin, end, rows, cols) of a span given as such a tuple or as an ``hmm_json_matrix``."""
+    if isinstance(span, (tuple, list)) and len(span) == 4:
+        return tuple(int(v) for v in span)
+    return int(span.begin), int(span.end), int(span.rows), int(span.cols)
+
+
+def _matrix_by_host(span_text: bytes, rows: int, cols: int) -> Optional[np.ndarray]:
+    """``hmm_json_parse_matrix_f32`` on a span that is the whole of `span_text`; None when it declines."""
+    from . import _lib as L
+    a = np.empty((rows, cols), np.float32)
+    if L.load().hmm_json_parse_matrix_f32(span_text, 0, len(span_text), rows, cols, a.ctypes.data) != 0:
+        return None
+    return a
+
+
+def _matrix_on_device(text: _EventText, begin: int, end: int, rows: int, cols: int, f64: bool):
+    """One launch sequence and one read-back of the report (with the flagged list behind it, one copy); flagged values are
+    converted by ``float(token)`` and patched in with one small copy.  -> (tensor, report words) or (None, report words) when the
+    matrix must go to the host route.  Call with ``_device_lock`` held, inside ``torch.cuda.device``."""
+    import torch
+    from . import _lib as L
+    from ._pinned import stage
+    lib, dev = L.load(), text.dev
+    t = text.on_device()
+    out = torch.empty((rows, cols), dtype=torch.float64 if f64 else torch.float32, device=dev)
+    ws_bytes = lib.hmm_json_parse_matrix_device_workspace_bytes(end - begin)
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+    report = torch.empty(4 + 4 * FLAGGED_CAP, dtype=torch.int64, device=dev)          # hmm_json_parse_report, then hmm_json_flagged[]
+    L.check(lib.hmm_json_parse_matrix_device(t.data_ptr(), begin, end, rows, cols, 1 if f64 else 0, out.data_ptr(), report.data_ptr(),
+                                             report.data_ptr() + 32, FLAGGED_CAP, ws.data_ptr(), ws_bytes, L.stream_ptr()),
+            "hmm_json_parse_matrix_device")
+    nbytes = report.numel() * 8
+    down = stage(_device_stages, ("report", dev.index), (nbytes,))
+    down.pinned[:nbytes].view(torch.int64).copy_(report, non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    words = down.host[:nbytes].view(np.uint64).copy()
+    n_flagged, status = int(words[1]), int(words[3])
+    if status != _PARSE_OK or n_flagged > FLAGGED_CAP:
+        return None, words
+    if n_flagged:
+        entries = words[4:4 + 4 * n_flagged].reshape(-1, 4)
+        values = []
+        for _, b, e, flag in entries.tolist():
+            token = text.bytes_of(b, e)
+            # a literal outside the double range is the host parser's to decline; a token too long for the device was not checked
+            # against the grammar there
+            if flag == _FLAG_RANGE or _JSON_NUMBER.fullmatch(token) is None:
+                return None, words
+            v = float(token)
+            if v == 0.0 or v in (float("inf"), float("-inf")):
+                return None, words
+            values.append(v)
+        packed = np.stack([entries[:, 0].astype(np.int64), np.array(values, np.float64).view(np.int64)])
+        packed = torch.from_numpy(packed).to(dev)
+        out.view(-1).index_copy_(0, packed[0], packed[1].view(torch.float64).to(out.dtype))      # narrowed as (float)(double)
+    return out, words
+
+
+def _edge_rows_agree(text: _EventText, begin: int, end: int, cols: int, out) -> bool:
+    """The self-check's comparison: the first and the last row of `out`, as bits, against the host parser's (fp32;
+    ``json.loads`` for fp64 and where the host parser declines)."""
+    import torch
+    span = text.bytes_of(begin, end)
+    first_open = span.index(b"[", 1)
+    last_open = span.rindex(b"[")
+    for open_at, got in ((first_open, out[0]), (last_open, out[-1])):
+        row = b"[" + span[open_at:span.index(b"]", open_at) + 1] + b"]"
+        want = _matrix_by_host(row, 1, cols) if out.dtype == torch.float32 else None
+        if want is None:
+            want = np.array(json.loads(row), np.float64).astype(np.float32 if out.dtype == torch.float32 else np.float64)
+        if got.cpu().numpy().tobytes() != want.reshape(-1).tobytes():
+            return False
+    return True
+
+
+def _parse_matrix_routes(text: _EventText, span, dtype, report: dict = None):
+    """One matrix of `text` as a tensor on ``text.dev`` -> (tensor, "device" | "host"), or (None, None) when the device route and
+    the host route both decline it (the caller then asks ``json``).  `report`, when given, receives the device's report."""
+    import torch
+    begin, end, rows, cols = span
+    f64 = np.dtype(dtype) == np.float64
+    if _parse_route["on"] and _parse_check["ok"] is not False:
+        with torch.cuda.device(text.dev), _device_lock:
+            out, words = _matrix_on_device(text, begin, end, rows, cols, f64)
+            if report is not None:
+                report.update(n_tokens=int(words[0]), n_flagged=int(words[1]), first_bad=int(words[2]), status=int(words[3]))
+            if out is not None and _parse_check["ok"] is None:
+                ok = _edge_rows_agree(text, begin, end, cols, out)
+                if not ok:
+                    _log.warning("hippomm_amd.event_store: the device JSON parser disagrees with the host parser; "
+                                 "every matrix is parsed by the host route in this process")
+                _parse_check["ok"] = ok
+        if out is not None and _parse_check["ok"]:
+            return out, "device"
+    if f64:
+        return None, None                                        # fp64 has no host parser: json.loads is its other route
+    a = _matrix_by_host(text.bytes_of(begin, end), rows, cols)
+    if a is None:
+        return None, None
+    return torch.from_numpy(a).to(text.dev), "host"
+
+
+def _parse_device_of(raw, device):
+    import torch
+    from . import _lib as L
+    dev = raw.device if _cuda_tensor(raw) else (torch.device(device) if device is not None else L.require_gpu())
+    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+
+
+def parse_matrix_device(raw, span, dtype=np.float32, device=None, stats: dict = None):
+    """One feature matrix of an event file, from its JSON text to a CUDA tensor of rows x cols, converted ON THE GPU
+    (``hmm_json_parse_matrix_device``: token starts counted per 4 KiB of text, a prefix sum, every token converted with integer
+    arithmetic -- Eisel-Lemire on its first 19 significant digits, exact for every such literal).  fp32 gives the bits of
+    ``hmm_json_parse_matrix_f32``, i.e. ``np.array(json.load(f)).astype(np.float32)``; fp64 the bits of ``np.array(json.loads(span))``.
+
+    raw: the file as ``bytes`` (uploaded once, through pinned staging) or as a 1-D uint8 CUDA tensor that already holds it.
+    span: (begin, end, rows, cols) as ``hmm_json_find_matrices`` reports a matrix (its struct is taken as well).  One launch
+    sequence and one read-back of the report.  Values the device flags (a literal of more than 19 significant digits whose two
+    candidates round differently, a token above 64 bytes; at most ``FLAGGED_CAP``) are converted by ``float(token)`` on the host
+    and patched in with one small copy.  Any other status -- a token count that is not rows x cols, a foreign byte, a token that is
+    no JSON number --, more flagged values than that, or a literal outside the double range hands the whole matrix to the host
+    route: ``hmm_json_parse_matrix_f32``, then one upload (fp32 only).  Where that declines as well, ``json.loads`` of the span
+    answers, with whatever shape it finds, or raises as it does.  `stats`, when given, receives "route": "device", "host" or
+    "json", and the device's report ("status", "n_tokens", "n_flagged", "first_bad") when the device ran.
+
+    The first matrix a process parses this way has its first and last row compared, as bits, with the host parser's; on a
+    mismatch a warning is logged and the host route answers, as it does from then on.
+
+    Measured on one MI355X (profiles/event_json_parse.json): the kernels take 68 us for 600 x 1024 values
+    (18.5 MB of text) and 336 us for 3600 x 1024; ``parse_event_features`` 23.4 -> 9.7 ms and 163.8 -> 79.3 ms against the host
+    route -- what is left is the host's span finder (7.5 / 46 ms), the file read and the upload.  The route is opt-in."""
+    if not (_cuda_tensor(raw) or isinstance(raw, (bytes, bytearray, memoryview))):
+        raise TypeError(f"parse_matrix_device takes bytes or a uint8 CUDA tensor, got {type(raw).__name__}")
+    if np.dtype(dtype) not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError(f"parse_matrix_device gives fp32 or fp64, not {np.dtype(dtype)}")
+    if _cuda_tensor(raw):
+        import torch
+        if raw.dtype != torch.uint8 or raw.dim() != 1 or not raw.is_contiguous():
+            raise TypeError("parse_matrix_device takes a contiguous 1-D uint8 tensor")
+    begin, end, rows, cols = span = _span4(span)
+    if not 0 <= begin < end <= len(raw) or rows < 1 or cols < 1:
+        raise ValueError(f"parse_matrix_device: span [{begin}, {end}) of {rows} x {cols} values in a text of {len(raw)} bytes")
+    import torch
+    text = _EventText(raw, _parse_device_of(raw, device))
+    report = {}
+    out, route = _parse_matrix_routes(text, span, dtype, report)
+    if stats is not None:
+        stats.update(report)                                     # before json is asked: it may raise
+    if out is None:
+        a = np.array(json.loads(text.bytes_of(begin, end))).astype(dtype)
+        out, route = torch.from_numpy(np.ascontiguousarray(a)).to(text.dev), "json"
+    _parse_counts[route] += 1
+    if stats is not None:
+        stats["route"] = route
+    return out
+
+
 NATIVE_MIN_VALUES = 1024        # 2-D arrays of at least this many numbers are parsed by the library, the rest by json
 
 
@@ -403,14 +618,16 @@ class _NativeMatrix:
         self.array = array
 
 
-def _load_json_native(raw: bytes):
+def _load_json_native(raw: bytes, matrices: str = "host", device=None, counts: dict = None):
     """``json.loads(raw)`` with every large 2-D array of numbers parsed by the library (``hmm_json_find_matrices`` /
     ``hmm_json_parse_matrix_f32``: fp32, the value ``np.array(list).astype(float32)`` has) and left in the result as a
     ``_NativeMatrix``.  None when the library declines (a literal outside the double range) or a matrix sits where this module
-    does not expect one -- the caller then uses plain ``json.loads``."""
+    does not expect one -- the caller then uses plain ``json.loads``.  matrices="device": the text goes to `device` once and the
+    spans are converted there (``_parse_matrix_routes``), each ``_NativeMatrix`` then holds a CUDA fp32 tensor.  `counts`, when
+    given, counts the matrices per route."""
     import ctypes as C
     from . import _lib as L
-    lib = _host_library()
+    lib = _host_library() if matrices == "host" else L.load()       # the device route has no fallback: a missing library raises
     if lib is None:
         return None
 
@@ -429,11 +646,19 @@ def _load_json_native(raw: bytes):
         return json.loads(raw)
     salt = uuid.uuid4().hex
     pieces, mats, pos = [], {}, 0
+    text = _EventText(raw, _parse_device_of(raw, device)) if matrices == "device" else None
     for i in range(n.value):
         sp = spans[i]
-        a = np.empty((sp.rows, sp.cols), np.float32)
-        if lib.hmm_json_parse_matrix_f32(raw, sp.begin, sp.end, sp.rows, sp.cols, a.ctypes.data_as(C.c_void_p)) != 0:
-            return None
+        if text is not None:
+            a, route = _parse_matrix_routes(text, _span4(sp), np.float32)
+            if a is None:
+                return None
+        else:
+            a, route = np.empty((sp.rows, sp.cols), np.float32), "host"
+            if lib.hmm_json_parse_matrix_f32(raw, sp.begin, sp.end, sp.rows, sp.cols, a.ctypes.data_as(C.c_void_p)) != 0:
+                return None
+        if counts is not None:
+            counts[route] += 1
         token = f"@@hmm_matrix_{i}_{salt}@@"
         mats[token] = a
         pieces += [raw[pos:sp.begin], b'"' + token.encode() + b'"']
@@ -454,13 +679,25 @@ def _load_json_native(raw: bytes):
     return put_back(json.loads(reduced))
 
 
-def parse_event_features(json_path, native: bool = True) -> Tuple[Dict[str, np.ndarray], Dict[str, np.ndarray]]:
+def parse_event_features(json_path, native: bool = True, matrices: str = "host", device=None,
+                         stats: dict = None) -> Tuple[Dict[str, np.ndarray], Dict[str, np.ndarray]]:
     """An event file without sidecars, by the reference's own reading rules (:369-408): new format with ``feature_times``, and
     the old format where a modality maps to ``{'features': ..., 'times': ...}``.  Features come back as fp32.  With ``native`` the
     feature matrices -- 99.9 % of the text -- are converted by the library instead of ``json.load`` + ``np.array(list)`` (~10x
-    faster, same values: tests/test_cpu_event_store.py); ``native=False`` is the reference's path as it stands."""
+    faster, same values: tests/test_cpu_event_store.py); ``native=False`` is the reference's path as it stands.
+
+    matrices="device" (opt-in, with ``native``): the file is uploaded once and every matrix the library finds among the feature
+    values is converted ON THE GPU (``parse_matrix_device``) and comes back as a CUDA fp32 tensor on `device` -- the same bits;
+    where the device declines a matrix the host parser converts it and it is uploaded.  The same rule says which matrices are
+    taken (feature values only); times and metadata keep ``json``'s float64 lists, and features the library does not report
+    (fewer than 1024 values, 1-D) stay numpy arrays.  Where the host parser declines as well, or a matrix is a stray, the whole
+    file goes through ``json.loads`` exactly as on the host route, and every feature is a numpy array.
+    `stats`, when given, receives "device", "host" and "json": the feature matrices each route read."""
+    if matrices not in ("host", "device"):
+        raise ValueError(f"matrices must be 'host' or 'device', not {matrices!r}")
     raw = Path(json_path).read_bytes()
-    data = _load_json_native(raw) if native else None
+    counts = {"device": 0, "host": 0, "json": 0}
+    data = _load_json_native(raw, matrices, device, counts) if native else None
     if data is not None:
         # matrices are expected as feature values only; anywhere else (times, metadata) keeps the reference's float64 lists
         feats_in = data.get("features") if isinstance(data, dict) else None
@@ -482,7 +719,8 @@ def parse_event_features(json_path, native: bool = True) -> Tuple[Dict[str, np.n
             return False
         if stray(data):
             data = None
-    if data is None:
+    by_json = data is None
+    if by_json:
         data = json.loads(raw)
     unwrap = lambda v: v.array if isinstance(v, _NativeMatrix) else np.array(v)     # noqa: E731
     feats, times = {}, {}
@@ -500,6 +738,13 @@ def parse_event_features(json_path, native: bool = True) -> Tuple[Dict[str, np.n
                     times[modality] = np.array(d["times"])
             else:
                 feats[modality] = unwrap(d)
+    if by_json:                                                  # whatever the routes had read before one of them declined is dropped
+        counts = {"device": 0, "host": 0, "json": sum(1 for a in feats.values() if a.ndim == 2)}
+    if matrices == "device":
+        for route, n in counts.items():
+            _parse_counts[route] += n
+    if stats is not None:
+        stats.update(counts)
     return {modality: _as_feature_matrix(a) for modality, a in feats.items()}, times
 
 
@@ -540,31 +785,62 @@ def iter_event_files(memory_store_dir) -> Iterable[Tuple[str, Path]]:
         yield event_id, p
 
 
-def build_event_store(memory_store_dir, modality: str = "vision", device=None, workers: Optional[int] = None):
+def _check_parse(parse: str) -> None:
+    if parse not in ("host", "device"):
+        raise ValueError(f"parse must be 'host' or 'device', not {parse!r}")
+
+
+def _event_segment_device(json_path: Path, modality: str, device, write_sidecar: bool):
+    """One event without fresh sidecars on the parse="device" route: its matrices are converted on the GPU and the ``modality``
+    one stays there; the sidecars come from one read-back of each fp32 matrix."""
+    feats, _ = parse_event_features(json_path, matrices="device", device=device)
+    if write_sidecar:
+        try:
+            _write_sidecars(json_path, {m: _on_host(f, fp32=True) for m, f in feats.items()})
+        except OSError:
+            pass                                    # read-only store: keep working from the JSON
+    return _modality_matrix(feats, modality)
+
+
+def build_event_store(memory_store_dir, modality: str = "vision", device=None, workers: Optional[int] = None, parse: str = "host",
+                      write_sidecar: bool = True):
     """All events' ``modality`` matrices of a memory_store, resident in HBM.  Returns (EventStore, event_ids);
     events that lack the modality or whose width is not 1024 get an empty segment (the reference skips them
     with a warning, :3135-3137).  Event files are read by ``workers`` threads (default: min(16, cores)): the sidecar reads and
-    the library's matrix parser run outside the GIL, so a cold store loads in parallel; the order of the events is the index's."""
+    the library's matrix parser run outside the GIL, so a cold store loads in parallel; the order of the events is the index's.
+
+    parse="device" (opt-in): events with fresh sidecars load as above; the others are read one after the other, their text
+    converted on the GPU (``parse_event_features(matrices="device")``), and enter the store through ``EventStore.extend`` from
+    the device tensors -- no host fp32 matrix, no second upload; the same rows, offsets and search results.  Their sidecars are
+    still written, from one read-back of each fp32 matrix, unless ``write_sidecar=False``."""
     from concurrent.futures import ThreadPoolExecutor
     from .vector_ops import EventStore
+    _check_parse(parse)
     files = list(iter_event_files(memory_store_dir))
     if workers is None:
         workers = min(16, os.cpu_count() or 1)
-    if workers > 1 and len(files) > 1:
+    cold = {i for i, (_, path) in enumerate(files) if _fresh_manifest(path) is None} if parse == "device" else set()
+    warm = [f for i, f in enumerate(files) if i not in cold]
+    if workers > 1 and len(warm) > 1:
         with ThreadPoolExecutor(max_workers=workers) as pool:
-            loaded = list(pool.map(lambda f: load_event_features(f[1]), files))
+            loaded = list(pool.map(lambda f: load_event_features(f[1]), warm))
     else:
-        loaded = [load_event_features(path) for _, path in files]
+        loaded = [load_event_features(path) for _, path in warm]
+    loaded = iter(loaded)
     ids, mats = [], []
-    for (event_id, path), feats in zip(files, loaded):
+    for i, (event_id, path) in enumerate(files):
         ids.append(event_id)
-        mats.append(_modality_matrix(feats, modality))
-    return EventStore(mats, device), ids
+        mats.append(_event_segment_device(path, modality, device, write_sidecar) if i in cold else _modality_matrix(next(loaded), modality))
+    if parse == "host":
+        return EventStore(mats, device), ids
+    store = EventStore([], device)
+    store.extend(mats)
+    return store, ids
 
 
 def _modality_matrix(feats: Mapping[str, np.ndarray], modality: str) -> np.ndarray:
-    """One event's segment of an EventStore: its ``modality`` matrix, a 1-D feature as one row, and an empty segment when the
-    modality is missing or its width is not 1024."""
+    """One event's segment of an EventStore: its ``modality`` matrix (a numpy array, or a CUDA tensor from the device parser), a
+    1-D feature as one row, and an empty segment when the modality is missing or its width is not 1024."""
     a = feats.get(modality)
     if a is not None and a.ndim == 1 and a.shape[0] == 1024:
         a = a.reshape(1, 1024)                       # top_k_cosine_similarity treats a 1-D feature as one row (vector_ops.py:173-174)
@@ -573,14 +849,16 @@ def _modality_matrix(feats: Mapping[str, np.ndarray], modality: str) -> np.ndarr
     return a
 
 
-def refresh_event_store(store, ids, memory_store_dir, modality: str = "vision"):
+def refresh_event_store(store, ids, memory_store_dir, modality: str = "vision", parse: str = "host", write_sidecar: bool = True):
     """Bring a resident EventStore up to date with ``event_index.json`` after ``save_theta_event`` wrote new events: the events
     of the index that are not in ``ids`` yet are appended on the device (``EventStore.extend``: the rows already resident are
     neither re-read nor re-uploaded, a shadow is kept current), events that vanished from the index are removed
     (``EventStore.remove_events``).  Returns the new id list; ``store`` and the list equal what ``build_event_store`` returns
     for the same index as long as the index only grew at its end or lost entries, which is how the reference writes it
     (hippocampal_memory.py:338-346).  A missing modality, a 1-D feature and a wrong width are handled as there.  An event whose
-    file changed under an id that stays is not noticed: use ``EventStore.replace_event``."""
+    file changed under an id that stays is not noticed: use ``EventStore.replace_event``.  parse="device" and ``write_sidecar``:
+    as in ``build_event_store``, on the store's own device."""
+    _check_parse(parse)
     files = list(iter_event_files(memory_store_dir))
     in_index = {event_id for event_id, _ in files}
     gone = [pos for pos, event_id in enumerate(ids) if event_id not in in_index]
@@ -590,6 +868,8 @@ def refresh_event_store(store, ids, memory_store_dir, modality: str = "vision"):
     have = set(new_ids)
     fresh = [(event_id, path) for event_id, path in files if event_id not in have]
     if fresh:
-        store.extend([_modality_matrix(load_event_features(path), modality) for _, path in fresh])
+        store.extend([_event_segment_device(path, modality, store.rows.device, write_sidecar)
+                      if parse == "device" and _fresh_manifest(path) is None else _modality_matrix(load_event_features(path), modality)
+                      for _, path in fresh])
         new_ids += [event_id for event_id, _ in fresh]
     return new_ids

@@ -911,6 +911,63 @@ int hmm_json_write_matrix_device(const void* m_dev, int dtype, size_t rows, size
                                  uint64_t* written_dev, void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
 int hmm_json_float_repr(const double* values, size_t n, char* out_chars, int* out_lengths);
 
+/* ---- and read back on the device (csrc/event_json_parse.hip, csrc/event_json_parse_core.h) ----
+ * hmm_json_parse_matrix_device: text_dev[begin, end) ON THE DEVICE is one matrix as hmm_json_find_matrices reported it (its first
+ * byte is the outer '['; no string literal inside) -> rows x cols row-major values in out_dev: fp32 (HMM_JSON_DTYPE_F32) with the
+ * bits hmm_json_parse_matrix_f32 gives, out = (float)(double)literal, or fp64 (HMM_JSON_DTYPE_F64) with the bits of Python's
+ * float(literal), the reference's own in-memory dtype.  NaN is 0x7fc00000 / 0x7ff8000000000000; "-0.0" and "-0e0" keep their sign,
+ * "-0" is +0.0 (an int to json.load).  A token is a run of number bytes (digits + - . e E and the letters of NaN and Infinity) behind
+ * a separator (space \n \r \t , [ ]); the token with ordinal k is checked against JSON's number grammar (as hmm_json_find_matrices
+ * does), converted with integer arithmetic only (Eisel-Lemire on the first 19 significant digits, exact for every such literal) and
+ * stored to out[k].  The brackets and commas between the tokens are NOT checked again: the span finder is their authority.
+ *   report_dev (32 bytes, 8-byte aligned) is written by every call: n_tokens; n_flagged; first_bad, the lowest byte offset in
+ *   text_dev of a wrong byte or token (HMM_JSON_PARSE_NO_OFFSET: none); status, the highest of
+ *     HMM_JSON_PARSE_OK;
+ *     HMM_JSON_PARSE_COUNT      n_tokens != rows x cols: out[k] is written for k < min(n_tokens, rows x cols) only;
+ *     HMM_JSON_PARSE_BAD_BYTE   a byte that is neither a separator nor a number byte;
+ *     HMM_JSON_PARSE_BAD_TOKEN  a token that fails the grammar ("1.", ".5", "+1", "01", "nan"); its slot of out holds zero.
+ *   FLAGGED values are tokens this call does not convert; their slots of out hold +0.0, so that out is fully defined, and
+ *   flagged_dev[0 .. min(n_flagged, flagged_cap)) names them in no particular order: ordinal, byte span [begin, end) in text_dev,
+ *   and why -- HMM_JSON_FLAG_UNDECIDED (more than 19 significant digits, counted from the first non-zero digit of the mantissa, and
+ *   the first 19 as an integer and that integer plus one round to different doubles), HMM_JSON_FLAG_RANGE (a non-zero literal that
+ *   rounds to infinity or to zero, or a decimal exponent above 9999: hmm_json_parse_matrix_f32 declines such a file) or
+ *   HMM_JSON_FLAG_TOO_LONG (a token of more than HMM_JSON_TOKEN_MAX bytes).  n_flagged counts all of them; entries behind
+ *   flagged_cap are not written, nor is anything of flagged_dev behind min(n_flagged, flagged_cap).  A literal of at most 19
+ *   significant digits inside the double range is never flagged.
+ * Text of any alignment: it is read as aligned 16-byte words where those lie inside [begin, end) and byte by byte at the two ends;
+ * no byte outside the span is read.  out_dev is aligned to its element; report_dev, flagged_dev and the workspace
+ * (hmm_json_parse_matrix_device_workspace_bytes(end - begin): one 64-bit count per HMM_JSON_PARSE_GROUP_BYTES bytes of the span; no
+ * initialisation) to 8 bytes.  Three launches on `stream` (token starts counted per group; the counts scanned by one workgroup,
+ * HMM_JSON_PARSE_SCAN_GROUPS_PER_ROUND per round; the tokens found again and converted): nothing synchronises or allocates, no
+ * workgroup waits for another, the call can be captured into a graph.
+ *   HMM_E_INVALID with a message, before any launch and without needing a GPU, for: a null pointer (flagged_dev may be null when
+ *   flagged_cap is 0), begin >= end, a span above HMM_JSON_PARSE_MAX_SPAN_BYTES, an unknown dtype, rows or cols < 1, rows * cols >
+ *   HMM_JSON_MAX_VALUES, flagged_cap < 0, workspace_bytes below the query's answer (0 for a span the call refuses), a misaligned
+ *   out_dev, report_dev, flagged_dev or workspace.
+ * hmm_json_float_parse: HOST only, no GPU call -- the device's number parser run on the host: token i is text[spans[2 i],
+ * spans[2 i + 1]) -> out_f64_bits[i] (Python's float(token)), out_f32_bits[i] ((float)(double)) and out_flags[i]: 0 for a
+ * converted token, else one of HMM_JSON_FLAG_* with both values zero (HMM_JSON_FLAG_BAD_TOKEN: not a number by the grammar). */
+#define HMM_JSON_TOKEN_MAX 64
+#define HMM_JSON_PARSE_GROUP_BYTES 4096
+#define HMM_JSON_PARSE_SCAN_GROUPS_PER_ROUND 256
+#define HMM_JSON_PARSE_MAX_SPAN_BYTES 1099511627776ull
+#define HMM_JSON_PARSE_OK 0
+#define HMM_JSON_PARSE_COUNT 1
+#define HMM_JSON_PARSE_BAD_BYTE 2
+#define HMM_JSON_PARSE_BAD_TOKEN 3
+#define HMM_JSON_PARSE_NO_OFFSET 0xFFFFFFFFFFFFFFFFull
+#define HMM_JSON_FLAG_UNDECIDED 1
+#define HMM_JSON_FLAG_RANGE 2
+#define HMM_JSON_FLAG_TOO_LONG 3
+#define HMM_JSON_FLAG_BAD_TOKEN 4
+typedef struct hmm_json_parse_report { uint64_t n_tokens, n_flagged, first_bad, status; } hmm_json_parse_report;
+typedef struct hmm_json_flagged { uint64_t ordinal, begin, end, flag; } hmm_json_flagged;
+size_t hmm_json_parse_matrix_device_workspace_bytes(size_t span_bytes);
+int hmm_json_parse_matrix_device(const char* text_dev, size_t begin, size_t end, size_t rows, size_t cols, int dtype, void* out_dev,
+                                 hmm_json_parse_report* report_dev, hmm_json_flagged* flagged_dev, int64_t flagged_cap,
+                                 void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
+int hmm_json_float_parse(const char* text, const uint64_t* spans, size_t n, uint64_t* out_f64_bits, uint32_t* out_f32_bits, int* out_flags);
+
 #ifdef __cplusplus
 }
 #endif
