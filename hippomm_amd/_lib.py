@@ -149,6 +149,9 @@ _SIGNATURES = {
     "hmm_json_parse_matrix_device": (C.c_int, [c_ptr, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, c_ptr, c_ptr, c_ptr,
                                                C.c_int64, c_ptr, C.c_size_t, c_ptr]),
     "hmm_json_float_parse": (C.c_int, [c_ptr, c_ptr, C.c_size_t, c_ptr, c_ptr, c_ptr]),
+    "hmm_json_find_matrices_device_workspace_bytes": (C.c_size_t, [C.c_size_t]),
+    "hmm_json_find_matrices_device": (C.c_int, [c_ptr, C.c_size_t, C.c_size_t, c_ptr, C.c_int, c_ptr, c_ptr, C.c_size_t, c_ptr]),
+    "hmm_json_find_matrices_blocks": (C.c_int, [c_ptr, C.c_size_t, C.c_size_t, c_ptr, C.c_int, c_ptr]),
 }
 
 

@@ -24,6 +24,10 @@ stored fp32, float64 arrays after loading.  That file format is the contract wit
                      matrices back from that text ON THE GPU (opt-in; the same bits), so that a cold store without sidecars
                      reaches HBM without a host fp32 matrix in between.
 
+* ``find_matrices_device`` / ``parse_event_features(matrices="device", find="device")`` / ``build_event_store(parse="device",
+                     find="device")``  also decide ON THE GPU where those matrices lie in the text (opt-in; the same spans), so
+                     that the host no longer walks the file before the parser's kernels start.
+
 Nothing here touches the GPU except ``build_event_store``, ``refresh_event_store`` and the ``matrices="device"`` / ``parse="device"`` routes.
 """
 from __future__ import annotations
@@ -448,6 +452,12 @@ class _EventText:
             return bytes(self.host[begin:end])
         return self.tensor[begin:end].cpu().numpy().tobytes()
 
+    def all_bytes(self) -> bytes:
+        """The whole text on the host; a tensor is brought down once and kept."""
+        if self.host is None:
+            self.host = self.tensor.cpu().numpy().tobytes()
+        return self.host if isinstance(self.host, bytes) else bytes(self.host)
+
 
 def _span4(span) -> Tuple[int, int, int, int]:
     """(begin, end, rows, cols) of a span given as such a tuple or as an ``hmm_json_matrix``."""
@@ -610,6 +620,127 @@ def parse_matrix_device(raw, span, dtype=np.float32, device=None, stats: dict = 
 NATIVE_MIN_VALUES = 1024        # 2-D arrays of at least this many numbers are parsed by the library, the rest by json
 
 
+# ---- where the matrices lie, found in the text on the device (csrc/event_json_find.hip) ----
+FIND_FIRST = 16                      # entries of the list that come back with the report, in the one read-back
+FIND_CAP = 4096                      # entries the device list holds; a text with more matrices is asked again with room for all
+_FIND_OK = 0                         # HMM_JSON_FIND_OK
+_find_route = {"on": True}           # False: the host finder answers
+_find_check = {"ok": None}           # None: not compared yet in this process; False: the comparison failed, the route is off
+_find_counts = {"device": 0, "declined": 0, "host": 0}
+
+
+def matrix_find_stats() -> dict:
+    """Texts searched per route by ``find_matrices_device`` and ``parse_event_features(find="device")`` since the process
+    started: "device", "declined" (the device declined and the host finder answered) and "host" (the route is off)."""
+    return dict(_find_counts)
+
+
+def _find_by_host(raw, min_values: int):
+    """``hmm_json_find_matrices`` -> [(begin, end, rows, cols)] in document order."""
+    import ctypes as C
+    from . import _lib as L
+    lib = L.load()
+    n, cap = C.c_int(0), FIND_FIRST
+    while True:
+        spans = (C.c_size_t * (4 * cap))()
+        L.check(lib.hmm_json_find_matrices(bytes(raw), len(raw), min_values, C.cast(spans, C.c_void_p), cap, C.byref(n)), "hmm_json_find_matrices")
+        if n.value <= cap:
+            break
+        cap = n.value
+    return [tuple(spans[4 * i:4 * i + 4]) for i in range(n.value)]
+
+
+def _find_on_device(text: _EventText, min_values: int):
+    """One launch sequence and one read-back: the report with the first ``FIND_FIRST`` entries behind it; a second copy only when
+    there are more.  -> (list or None when the device declined, report words).  Call with ``_device_lock`` held, inside
+    ``torch.cuda.device``."""
+    import torch
+    from . import _lib as L
+    from ._pinned import stage
+    lib, dev = L.load(), text.dev
+    t = text.on_device()
+    ws_bytes = lib.hmm_json_find_matrices_device_workspace_bytes(len(text))
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+    cap = FIND_CAP
+    while True:
+        out = torch.empty(4 + 4 * cap, dtype=torch.int64, device=dev)                 # hmm_json_find_report, then hmm_json_matrix[]
+        L.check(lib.hmm_json_find_matrices_device(t.data_ptr(), len(text), min_values, out.data_ptr() + 32, cap, out.data_ptr(), ws.data_ptr(),
+                                                  ws_bytes, L.stream_ptr()), "hmm_json_find_matrices_device")
+        nbytes = 8 * (4 + 4 * FIND_FIRST)
+        down = stage(_device_stages, ("find", dev.index), (nbytes,))
+        down.pinned[:nbytes].view(torch.int64).copy_(out[:4 + 4 * FIND_FIRST], non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        words = down.host[:nbytes].view(np.uint64).copy()
+        n_found, status = int(words[0]), int(words[2])
+        if status != _FIND_OK:
+            return None, words
+        if n_found <= cap:
+            break
+        cap = n_found
+    entries = words[4:4 + 4 * min(n_found, FIND_FIRST)]
+    if n_found > FIND_FIRST:
+        entries = np.concatenate([entries, out[4 + 4 * FIND_FIRST:4 + 4 * n_found].cpu().numpy().view(np.uint64)])
+    return [tuple(int(v) for v in e) for e in entries.reshape(-1, 4)], words
+
+
+def _find_routes(text: _EventText, min_values: int, report: dict = None):
+    """Where the matrices of `text` lie -> (list, "device" | "host").  `report`, when given, receives the device's report."""
+    import torch
+    if len(text) == 0:
+        return [], "host"
+    if _find_route["on"] and _find_check["ok"] is not False:
+        with torch.cuda.device(text.dev), _device_lock:
+            found, words = _find_on_device(text, min_values)
+            if report is not None:
+                report.update(n_found=int(words[0]), n_candidates=int(words[1]), status=int(words[2]), first_declined=int(words[3]))
+            if found is not None and _find_check["ok"] is None:
+                ok = found == _find_by_host(text.all_bytes(), min_values)
+                if not ok:
+                    _log.warning("hippomm_amd.event_store: the device span finder disagrees with the host finder; "
+                                 "every text is searched by the host finder in this process")
+                _find_check["ok"] = ok
+        if found is not None and _find_check["ok"]:
+            _find_counts["device"] += 1
+            return found, "device"
+        _find_counts["declined" if found is None else "host"] += 1
+    else:
+        _find_counts["host"] += 1
+    return _find_by_host(text.all_bytes(), min_values), "host"
+
+
+def find_matrices_device(raw, min_values: int = NATIVE_MIN_VALUES, device=None, stats: dict = None):
+    """Where the feature matrices of an event file lie, found ON THE GPU (``hmm_json_find_matrices_device``): every
+    ``[[numbers], ...]`` with equally long rows and at least `min_values` numbers outside string literals, as
+    [(begin, end, rows, cols)] in document order -- the list ``hmm_json_find_matrices`` gives for the same bytes, whatever they are.
+
+    raw: the file as ``bytes`` (uploaded once, through pinned staging) or as a 1-D uint8 CUDA tensor that already holds it.  One
+    launch sequence and one read-back: the report with the first 16 entries behind it; a second copy only for a text with more
+    matrices.  The string state, the class of the last non-whitespace byte and the counts of tokens, rows and illegal bytes are
+    prefix scans over groups of 4 KiB; a candidate ``[[`` is a matrix when the next ``]]``-or-``[[`` behind it is a ``]]`` with no
+    illegal byte between and every row starts where equal rows put it.  The device declines -- and the host finder answers, on the
+    bytes or on the tensor brought down -- for two reasons only: a candidate holds a number token above 64 bytes, or the text has
+    more than 16384 candidates.  `stats`, when given, receives "route" ("device" or "host") and the device's report ("n_found",
+    "n_candidates", "status", "first_declined") when the device ran.
+
+    The first text a process searches this way has its list compared with the host finder's; on a mismatch a warning is logged
+    and the host finder answers, as it does from then on.  Timings: profiles/event_json_find.json, DESIGN.md section 8.  Opt-in."""
+    if not (_cuda_tensor(raw) or isinstance(raw, (bytes, bytearray, memoryview))):
+        raise TypeError(f"find_matrices_device takes bytes or a uint8 CUDA tensor, got {type(raw).__name__}")
+    if _cuda_tensor(raw):
+        import torch
+        if raw.dtype != torch.uint8 or raw.dim() != 1 or not raw.is_contiguous():
+            raise TypeError("find_matrices_device takes a contiguous 1-D uint8 tensor")
+    if int(min_values) < 0:
+        raise ValueError(f"find_matrices_device: min_values {min_values!r} is negative")
+    text = _EventText(raw, _parse_device_of(raw, device))
+    report = {}
+    found, route = _find_routes(text, int(min_values), report)
+    if stats is not None:
+        stats.update(report)
+        stats["route"] = route
+    return found
+
+
 class _NativeMatrix:
     """Placeholder json.loads leaves where the library parsed a matrix."""
     __slots__ = ("array",)
@@ -618,13 +749,14 @@ class _NativeMatrix:
         self.array = array
 
 
-def _load_json_native(raw: bytes, matrices: str = "host", device=None, counts: dict = None):
+def _load_json_native(raw: bytes, matrices: str = "host", device=None, counts: dict = None, find: str = "host"):
     """``json.loads(raw)`` with every large 2-D array of numbers parsed by the library (``hmm_json_find_matrices`` /
     ``hmm_json_parse_matrix_f32``: fp32, the value ``np.array(list).astype(float32)`` has) and left in the result as a
     ``_NativeMatrix``.  None when the library declines (a literal outside the double range) or a matrix sits where this module
     does not expect one -- the caller then uses plain ``json.loads``.  matrices="device": the text goes to `device` once and the
     spans are converted there (``_parse_matrix_routes``), each ``_NativeMatrix`` then holds a CUDA fp32 tensor.  `counts`, when
-    given, counts the matrices per route."""
+    given, counts the matrices per route.  find="device" (with matrices="device"): the spans are found in that same uploaded text
+    on the device (``_find_routes``) instead of by ``hmm_json_find_matrices`` on the host."""
     import ctypes as C
     from . import _lib as L
     lib = _host_library() if matrices == "host" else L.load()       # the device route has no fallback: a missing library raises
@@ -634,19 +766,23 @@ def _load_json_native(raw: bytes, matrices: str = "host", device=None, counts: d
     class Span(C.Structure):
         _fields_ = [("begin", C.c_size_t), ("end", C.c_size_t), ("rows", C.c_size_t), ("cols", C.c_size_t)]
 
-    n = C.c_int(0)
-    cap = 16
-    while True:
-        spans = (Span * cap)()
-        L.check(lib.hmm_json_find_matrices(raw, len(raw), NATIVE_MIN_VALUES, C.cast(spans, C.c_void_p), cap, C.byref(n)), "hmm_json_find_matrices")
-        if n.value <= cap:
-            break
-        cap = n.value
+    text = _EventText(raw, _parse_device_of(raw, device)) if matrices == "device" else None
+    if find == "device":
+        spans = [Span(*sp) for sp in _find_routes(text, NATIVE_MIN_VALUES)[0]]
+        n = C.c_int(len(spans))
+    else:
+        n = C.c_int(0)
+        cap = 16
+        while True:
+            spans = (Span * cap)()
+            L.check(lib.hmm_json_find_matrices(raw, len(raw), NATIVE_MIN_VALUES, C.cast(spans, C.c_void_p), cap, C.byref(n)), "hmm_json_find_matrices")
+            if n.value <= cap:
+                break
+            cap = n.value
     if n.value == 0:
         return json.loads(raw)
     salt = uuid.uuid4().hex
     pieces, mats, pos = [], {}, 0
-    text = _EventText(raw, _parse_device_of(raw, device)) if matrices == "device" else None
     for i in range(n.value):
         sp = spans[i]
         if text is not None:
@@ -679,8 +815,15 @@ def _load_json_native(raw: bytes, matrices: str = "host", device=None, counts: d
     return put_back(json.loads(reduced))
 
 
+def _check_find(find: str, device_route: bool, needs: str) -> None:
+    if find not in ("host", "device"):
+        raise ValueError(f"find must be 'host' or 'device', not {find!r}")
+    if find == "device" and not device_route:
+        raise ValueError(f"find='device' searches the text the device parses: it needs {needs}")
+
+
 def parse_event_features(json_path, native: bool = True, matrices: str = "host", device=None,
-                         stats: dict = None) -> Tuple[Dict[str, np.ndarray], Dict[str, np.ndarray]]:
+                         stats: dict = None, find: str = "host") -> Tuple[Dict[str, np.ndarray], Dict[str, np.ndarray]]:
     """An event file without sidecars, by the reference's own reading rules (:369-408): new format with ``feature_times``, and
     the old format where a modality maps to ``{'features': ..., 'times': ...}``.  Features come back as fp32.  With ``native`` the
     feature matrices -- 99.9 % of the text -- are converted by the library instead of ``json.load`` + ``np.array(list)`` (~10x
@@ -692,12 +835,18 @@ def parse_event_features(json_path, native: bool = True, matrices: str = "host",
     taken (feature values only); times and metadata keep ``json``'s float64 lists, and features the library does not report
     (fewer than 1024 values, 1-D) stay numpy arrays.  Where the host parser declines as well, or a matrix is a stray, the whole
     file goes through ``json.loads`` exactly as on the host route, and every feature is a numpy array.
-    `stats`, when given, receives "device", "host" and "json": the feature matrices each route read."""
+    `stats`, when given, receives "device", "host" and "json": the feature matrices each route read.
+
+    find="device" (opt-in, with matrices="device" only): where the matrices lie is decided on the GPU as well
+    (``find_matrices_device``), on the text that was uploaded for the parser -- the host no longer walks the file; it keeps the
+    file read, one read-back of the span list and ``json.loads`` of the few KB around the matrices.  The same spans, so the same
+    result; where the device declines a text the host finder answers."""
     if matrices not in ("host", "device"):
         raise ValueError(f"matrices must be 'host' or 'device', not {matrices!r}")
+    _check_find(find, matrices == "device", "matrices='device'")
     raw = Path(json_path).read_bytes()
     counts = {"device": 0, "host": 0, "json": 0}
-    data = _load_json_native(raw, matrices, device, counts) if native else None
+    data = _load_json_native(raw, matrices, device, counts, find) if native else None
     if data is not None:
         # matrices are expected as feature values only; anywhere else (times, metadata) keeps the reference's float64 lists
         feats_in = data.get("features") if isinstance(data, dict) else None
@@ -790,10 +939,10 @@ def _check_parse(parse: str) -> None:
         raise ValueError(f"parse must be 'host' or 'device', not {parse!r}")
 
 
-def _event_segment_device(json_path: Path, modality: str, device, write_sidecar: bool):
+def _event_segment_device(json_path: Path, modality: str, device, write_sidecar: bool, find: str = "host"):
     """One event without fresh sidecars on the parse="device" route: its matrices are converted on the GPU and the ``modality``
     one stays there; the sidecars come from one read-back of each fp32 matrix."""
-    feats, _ = parse_event_features(json_path, matrices="device", device=device)
+    feats, _ = parse_event_features(json_path, matrices="device", device=device, find=find)
     if write_sidecar:
         try:
             _write_sidecars(json_path, {m: _on_host(f, fp32=True) for m, f in feats.items()})
@@ -803,7 +952,7 @@ def _event_segment_device(json_path: Path, modality: str, device, write_sidecar:
 
 
 def build_event_store(memory_store_dir, modality: str = "vision", device=None, workers: Optional[int] = None, parse: str = "host",
-                      write_sidecar: bool = True):
+                      write_sidecar: bool = True, find: str = "host"):
     """All events' ``modality`` matrices of a memory_store, resident in HBM.  Returns (EventStore, event_ids);
     events that lack the modality or whose width is not 1024 get an empty segment (the reference skips them
     with a warning, :3135-3137).  Event files are read by ``workers`` threads (default: min(16, cores)): the sidecar reads and
@@ -812,10 +961,12 @@ def build_event_store(memory_store_dir, modality: str = "vision", device=None, w
     parse="device" (opt-in): events with fresh sidecars load as above; the others are read one after the other, their text
     converted on the GPU (``parse_event_features(matrices="device")``), and enter the store through ``EventStore.extend`` from
     the device tensors -- no host fp32 matrix, no second upload; the same rows, offsets and search results.  Their sidecars are
-    still written, from one read-back of each fp32 matrix, unless ``write_sidecar=False``."""
+    still written, from one read-back of each fp32 matrix, unless ``write_sidecar=False``.  find="device" (opt-in, with
+    parse="device" only): those texts are searched for their matrices on the GPU too (``parse_event_features(find="device")``)."""
     from concurrent.futures import ThreadPoolExecutor
     from .vector_ops import EventStore
     _check_parse(parse)
+    _check_find(find, parse == "device", "parse='device'")
     files = list(iter_event_files(memory_store_dir))
     if workers is None:
         workers = min(16, os.cpu_count() or 1)
@@ -830,7 +981,7 @@ def build_event_store(memory_store_dir, modality: str = "vision", device=None, w
     ids, mats = [], []
     for i, (event_id, path) in enumerate(files):
         ids.append(event_id)
-        mats.append(_event_segment_device(path, modality, device, write_sidecar) if i in cold else _modality_matrix(next(loaded), modality))
+        mats.append(_event_segment_device(path, modality, device, write_sidecar, find) if i in cold else _modality_matrix(next(loaded), modality))
     if parse == "host":
         return EventStore(mats, device), ids
     store = EventStore([], device)
@@ -849,7 +1000,8 @@ def _modality_matrix(feats: Mapping[str, np.ndarray], modality: str) -> np.ndarr
     return a
 
 
-def refresh_event_store(store, ids, memory_store_dir, modality: str = "vision", parse: str = "host", write_sidecar: bool = True):
+def refresh_event_store(store, ids, memory_store_dir, modality: str = "vision", parse: str = "host", write_sidecar: bool = True,
+                        find: str = "host"):
     """Bring a resident EventStore up to date with ``event_index.json`` after ``save_theta_event`` wrote new events: the events
     of the index that are not in ``ids`` yet are appended on the device (``EventStore.extend``: the rows already resident are
     neither re-read nor re-uploaded, a shadow is kept current), events that vanished from the index are removed
@@ -857,8 +1009,9 @@ def refresh_event_store(store, ids, memory_store_dir, modality: str = "vision", 
     for the same index as long as the index only grew at its end or lost entries, which is how the reference writes it
     (hippocampal_memory.py:338-346).  A missing modality, a 1-D feature and a wrong width are handled as there.  An event whose
     file changed under an id that stays is not noticed: use ``EventStore.replace_event``.  parse="device" and ``write_sidecar``:
-    as in ``build_event_store``, on the store's own device."""
+    and ``find``: as in ``build_event_store``, on the store's own device."""
     _check_parse(parse)
+    _check_find(find, parse == "device", "parse='device'")
     files = list(iter_event_files(memory_store_dir))
     in_index = {event_id for event_id, _ in files}
     gone = [pos for pos, event_id in enumerate(ids) if event_id not in in_index]
@@ -868,7 +1021,7 @@ def refresh_event_store(store, ids, memory_store_dir, modality: str = "vision", 
     have = set(new_ids)
     fresh = [(event_id, path) for event_id, path in files if event_id not in have]
     if fresh:
-        store.extend([_event_segment_device(path, modality, store.rows.device, write_sidecar)
+        store.extend([_event_segment_device(path, modality, store.rows.device, write_sidecar, find)
                       if parse == "device" and _fresh_manifest(path) is None else _modality_matrix(load_event_features(path), modality)
                       for _, path in fresh])
         new_ids += [event_id for event_id, _ in fresh]

@@ -968,6 +968,40 @@ int hmm_json_parse_matrix_device(const char* text_dev, size_t begin, size_t end,
                                  void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
 int hmm_json_float_parse(const char* text, const uint64_t* spans, size_t n, uint64_t* out_f64_bits, uint32_t* out_f32_bits, int* out_flags);
 
+/* ---- and found in the text on the device (csrc/event_json_find.hip, csrc/event_json_find_core.h) ----
+ * hmm_json_find_matrices_device: hmm_json_find_matrices for a text ON THE DEVICE.  text_dev[0, len) may have any alignment and is
+ * only read; no byte outside it is dereferenced.  *report_dev (device, 8-byte aligned) receives
+ *   n_found         all matrices, as the host's *n_found; out_dev[0 .. min(n_found, cap)) (device, 8-byte aligned; may be null when
+ *                   cap is 0) is the host finder's list, field for field, in document order; nothing behind it is written;
+ *   n_candidates    the `[` outside string literals whose next byte that is not whitespace is another `[`;
+ *   status          HMM_JSON_FIND_OK: the list equals hmm_json_find_matrices(text, len, min_values, ...) for every byte string --
+ *                   malformed JSON, unbalanced quotes and texts that end inside a string included;
+ *                   HMM_JSON_FIND_DECLINED: n_found is 0, nothing is listed and the caller runs the host finder.  Two reasons only:
+ *                   a candidate that is otherwise a matrix holds a number token of more than HMM_JSON_TOKEN_MAX bytes, or the text
+ *                   has more than HMM_JSON_FIND_MAX_CANDIDATES candidates (each takes at most two entries of the workspace's event
+ *                   list; the call declines when the list overflows);
+ *   first_declined  the text offset of the first candidate that made the call decline (HMM_JSON_PARSE_NO_OFFSET: none).
+ * Whitespace runs, backslash runs and nesting of any length and depth and a matrix larger than any group are handled.  The
+ * workspace (hmm_json_find_matrices_device_workspace_bytes(len), 8-byte aligned) needs no initialisation and nothing behind the
+ * query's answer is written.  Eight launches on `stream` (per group of HMM_JSON_PARSE_GROUP_BYTES bytes: the string-state map and
+ * the last non-whitespace byte under each incoming state; one workgroup scans them; the groups count their tokens, rows, illegal
+ * bytes and events; one workgroup scans the counts; the groups list candidates and closers; one workgroup pairs them; the groups
+ * check every row's place; one workgroup writes the list): nothing synchronises or allocates, no workgroup waits for another, the
+ * sequence may be captured into a graph.
+ * HMM_E_INVALID before any launch (no GPU needed): a null pointer (out_dev may be null when cap is 0), cap < 0, len of 0 or above
+ *   HMM_JSON_PARSE_MAX_SPAN_BYTES, workspace_bytes below the query's answer (0 for a len the call refuses), a misaligned out_dev,
+ *   report or workspace.
+ * hmm_json_find_matrices_blocks: HOST only, no GPU call -- the same block algorithm (the same per-byte rules, summaries and
+ * compositions, the same group size and decline rules) run on host memory; `out` and `report` are host pointers. */
+#define HMM_JSON_FIND_OK 0
+#define HMM_JSON_FIND_DECLINED 1
+#define HMM_JSON_FIND_MAX_CANDIDATES 16384
+typedef struct hmm_json_find_report { uint64_t n_found, n_candidates, status, first_declined; } hmm_json_find_report;
+size_t hmm_json_find_matrices_device_workspace_bytes(size_t len);
+int hmm_json_find_matrices_device(const char* text_dev, size_t len, size_t min_values, hmm_json_matrix* out_dev, int cap,
+                                  hmm_json_find_report* report_dev, void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
+int hmm_json_find_matrices_blocks(const char* text, size_t len, size_t min_values, hmm_json_matrix* out, int cap, hmm_json_find_report* report);
+
 #ifdef __cplusplus
 }
 #endif
