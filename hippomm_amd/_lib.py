@@ -152,6 +152,11 @@ _SIGNATURES = {
     "hmm_json_find_matrices_device_workspace_bytes": (C.c_size_t, [C.c_size_t]),
     "hmm_json_find_matrices_device": (C.c_int, [c_ptr, C.c_size_t, C.c_size_t, c_ptr, C.c_int, c_ptr, c_ptr, C.c_size_t, c_ptr]),
     "hmm_json_find_matrices_blocks": (C.c_int, [c_ptr, C.c_size_t, C.c_size_t, c_ptr, C.c_int, c_ptr]),
+    "hmm_base64_encoded_length": (C.c_size_t, [C.c_size_t]),
+    "hmm_base64_encode_device": (C.c_int, [c_ptr, C.c_int, C.c_size_t, c_ptr, C.c_size_t, c_ptr]),
+    "hmm_base64_decode_device": (C.c_int, [c_ptr, C.c_size_t, C.c_int, c_ptr, C.c_size_t, c_ptr, c_ptr]),
+    "hmm_base64_encode_host": (C.c_int, [c_ptr, C.c_int, C.c_size_t, c_ptr, C.c_size_t]),
+    "hmm_base64_decode_host": (C.c_int, [c_ptr, C.c_size_t, C.c_int, c_ptr, C.c_size_t, c_ptr]),
 }
 
 

@@ -147,6 +147,7 @@ class AudioTrack:
             audio_data = audio_data.detach().cpu().numpy()
         x = np.asarray(audio_data)
         self.source_dtype = x.dtype                 # window_levels refuses a track that was not float32 / float64 at its source
+        self.source_shape = tuple(x.shape)          # checkpoint.py writes a memory's waveform from the track only if this is (n,) / (n, 1)
         if x.dtype not in (np.float32, np.float64):
             x = x.astype(np.float32)
         if x.ndim == 2:

@@ -1002,6 +1002,68 @@ int hmm_json_find_matrices_device(const char* text_dev, size_t len, size_t min_v
                                   hmm_json_find_report* report_dev, void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
 int hmm_json_find_matrices_blocks(const char* text, size_t len, size_t min_values, hmm_json_matrix* out, int cap, hmm_json_find_report* report);
 
+/* ---- base64, for the checkpoint file (csrc/base64.hip, csrc/base64_core.h) ----
+ * The reference writes every feature block of a checkpoint as base64(np.array(v.tolist()).tobytes()) (hippocampal_memory.py:308-310,
+ * :1506): the block as float64, standard alphabet, '=' padding -- the bytes of Python's base64.b64encode.
+ * hmm_base64_encoded_length: 4 * ceil(n_bytes / 3).
+ * hmm_base64_encode_device: n_values values at src_dev ON THE DEVICE -> out_dev[0, hmm_base64_encoded_length(bytes)), where bytes is
+ *   8 * n_values for HMM_BASE64_DTYPE_F32 (each value widened to double first, as np.array(v.tolist()) does) and for
+ *   HMM_BASE64_DTYPE_F64, and n_values for HMM_BASE64_DTYPE_U8 (raw bytes).  One launch on `stream`: a thread encodes
+ *   HMM_BASE64_BYTES_PER_THREAD source bytes into 32 characters (two 16-byte stores), a workgroup HMM_BASE64_BYTES_PER_GROUP; the
+ *   last, partial unit writes the padding.  Nothing allocates or synchronises, there is no workspace and no count to read back; not a
+ *   byte behind the encoded length is written and the source is only read.  n_values == 0 launches nothing.  Quiet NaNs of any
+ *   payload pass bit for bit; a SIGNALLING NaN in an fp32 source is outside the contract (widening quiets it, here and in numpy, but
+ *   nothing pins the two to the same bits).
+ *   Alignment: src_dev to its element (4 / 8 bytes; none for bytes), out_dev to 16 bytes.
+ * hmm_base64_decode_device: STRICT.  text_dev[0, n_chars) is accepted only if n_chars is a multiple of 4, every character is of the
+ *   alphabet, and padding stands at the very end only ("xxx=" or "xx==") in canonical form (the bits the padding cuts off are zero).
+ *   Whitespace and stray characters, which Python's lenient b64decode skips, are refused: the caller then decodes on the host.
+ *   report_dev (HMM_BASE64_REPORT_WORDS uint64, 8-byte aligned) is written by every call:
+ *     [0] status   HMM_BASE64_OK, or why the text is refused:
+ *                  HMM_BASE64_BAD_LENGTH     n_chars % 4 != 0; the offset is where the incomplete quad begins;
+ *                  HMM_BASE64_BAD_CHAR       a byte outside the alphabet that is not '=';
+ *                  HMM_BASE64_BAD_PADDING    '=' anywhere but in the last two places, or "xx=x";
+ *                  HMM_BASE64_NONCANONICAL   the character in front of the padding carries bits the padding cuts off;
+ *                  HMM_BASE64_PARTIAL_VALUE  a float dtype_out and the bytes are not whole doubles (offset: the last quad);
+ *                  HMM_BASE64_CAPACITY       more values than cap_values (bytes only, see below; offset: the last quad);
+ *     [1] offset   the LOWEST offending text offset, with its status in [0]; 0 when the status is OK;
+ *     [2] inexact  HMM_BASE64_DTYPE_F32 only: the values v for which (double)(float)v does not have v's 64 bits;
+ *     [3] values   the values written (0 on a refusal);
+ *     [4] reserved (the call's working word).
+ *   On a refusal NOT ONE byte of out_dev is written.  dtype_out: HMM_BASE64_DTYPE_U8, the bytes; HMM_BASE64_DTYPE_F64, the bytes as
+ *   they are, which must be whole doubles; HMM_BASE64_DTYPE_F32, each double narrowed (round to nearest even).  Three launches on
+ *   `stream` (the report's start values; every quad checked, the lowest offending offset kept by a 64-bit atomic minimum; the
+ *   groups decoded unless something was found): nothing allocates or synchronises, no workgroup waits for another.
+ *   cap_values: a float dtype_out needs floor(3 (n_chars / 4) / 8), which is the exact count of an accepted text; bytes need
+ *   3 (n_chars / 4) - 2, the count under the longest padding, and a text that decodes to more than cap_values is refused on the
+ *   device (HMM_BASE64_CAPACITY).  Alignment: text_dev to 16 bytes, out_dev to its element, report_dev to 8.
+ * hmm_base64_encode_host / hmm_base64_decode_host: HOST only, no GPU call -- the same core on host memory (no alignment beyond the
+ *   element's; `report` as above).
+ * HMM_E_INVALID with a message, before any launch and without needing a GPU, for: a null pointer (src / out may be null when
+ *   there is nothing to read or write), an unknown dtype, more than HMM_BASE64_MAX_BYTES, a cap below the need, a misaligned
+ *   pointer. */
+#define HMM_BASE64_DTYPE_F32 0
+#define HMM_BASE64_DTYPE_F64 1
+#define HMM_BASE64_DTYPE_U8 2
+#define HMM_BASE64_BYTES_PER_THREAD 24
+#define HMM_BASE64_THREADS_PER_GROUP 256
+#define HMM_BASE64_BYTES_PER_GROUP (HMM_BASE64_BYTES_PER_THREAD * HMM_BASE64_THREADS_PER_GROUP)
+#define HMM_BASE64_MAX_BYTES 1099511627776ull
+#define HMM_BASE64_REPORT_WORDS 5
+#define HMM_BASE64_OK 0
+#define HMM_BASE64_BAD_LENGTH 1
+#define HMM_BASE64_BAD_CHAR 2
+#define HMM_BASE64_BAD_PADDING 3
+#define HMM_BASE64_NONCANONICAL 4
+#define HMM_BASE64_PARTIAL_VALUE 5
+#define HMM_BASE64_CAPACITY 6
+size_t hmm_base64_encoded_length(size_t n_bytes);
+int hmm_base64_encode_device(const void* src_dev, int dtype, size_t n_values, char* out_dev, size_t cap, hmm_stream_t stream);
+int hmm_base64_decode_device(const char* text_dev, size_t n_chars, int dtype_out, void* out_dev, size_t cap_values, uint64_t* report_dev,
+                             hmm_stream_t stream);
+int hmm_base64_encode_host(const void* src, int dtype, size_t n_values, char* out, size_t cap);
+int hmm_base64_decode_host(const char* text, size_t n_chars, int dtype_out, void* out, size_t cap_values, uint64_t* report);
+
 #ifdef __cplusplus
 }
 #endif
