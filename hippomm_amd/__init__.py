@@ -52,9 +52,15 @@ and, opt-in too, read back from that text on the device, the bits of np.array(js
 
     hippomm_amd.event_store.parse_matrix_device, parse_event_features(..., matrices="device"),
     build_event_store / refresh_event_store(..., parse="device")                                   <- hippomm/core/hippocampal_memory.py:369-395
+
+and the decision loop of frame extraction with the last saved frame, the cumulative difference and the time of the last save on the
+device: each frame uploaded once, one read-back per batch of candidates (hippomm_amd/csrc/extract_walk.hip):
+
+    hippomm_amd.extract_frames, FrameExtractor, extraction_records  <- hippomm/core/batch_process.py:179-228
 """
 __version__ = "0.1.0"
 
 from .jpeg import decode_jpeg, encode_jpeg  # noqa: E402,F401
+from .segmentation import FrameExtractor, extract_frames, extraction_records  # noqa: E402,F401
 from .retrieval import (feature_entries, find_relevant_audio_segments, find_relevant_video_segments,  # noqa: E402,F401
                         recall_window_frames)

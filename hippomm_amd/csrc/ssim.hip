@@ -11,6 +11,7 @@
 //
 // Gray conversion is OpenCV's 8-bit BGR2GRAY rule (CV_DESCALE with yuv_shift 14): g = (1868 B + 9617 G + 4899 R + 8192) >> 14.
 #include "hmm_common.h"
+#include "ssim_core.h"
 
 #pragma clang fp contract(off)
 
@@ -19,12 +20,7 @@ namespace hmm {
 constexpr int kGrayThreads = 256;
 constexpr int kGrayBlocksPerFrame = 512;          // grid-stride inside a frame: at most 512 x 2 atomics per frame
 
-constexpr int kSsimTW = 256;                      // output columns of a tile: one per thread
-constexpr int kSsimTH = 36;                       // output rows of a tile: TH + 6 = 42 input rows = 6 turns of the 7-row ring
-constexpr int kSsimIn = kSsimTH + 6;
-constexpr int kSsimLdsW = kSsimTW + 8;            // 262 staged bytes per row, padded
 constexpr int kSsimChunk = 128;                   // pairs per launch, carried in the kernel arguments (1 KiB)
-constexpr int kFinishThreads = 256;
 
 struct PairChunk {
     int32_t a[kSsimChunk];
@@ -84,116 +80,28 @@ __global__ __launch_bounds__(kGrayThreads) void gray_kernel(const uint8_t* __res
     }
 }
 
-// One workgroup per (pair, tile of 256 x 36 output positions).  Both frames' (36 + 6) x (256 + 6) input block is staged in LDS;
-// each thread owns one output column and walks down it: the five horizontal 7-sums of every input row go through a 7-deep ring
-// in registers (the loop over a turn of the ring is unrolled, so the ring is indexed by constants), and the vertical sums slide by
-// adding the new row and subtracting the one that left.  Output (ox, oy) is the window whose top-left pixel is (ox, oy).
+// One workgroup per (pair, tile of 256 x 36 output positions): the tile body is ssim_tile_partial (ssim_core.h).
 __global__ __launch_bounds__(kSsimTW) void ssim_tile_kernel(const uint8_t* __restrict__ gray, int H, int W, PairChunk pairs,
                                                             int pair0, int range_from_a, double data_range,
                                                             const int32_t* __restrict__ minmax, int tiles_x, int n_tiles,
                                                             double* __restrict__ partial) {
-    __shared__ uint8_t s_a[kSsimIn][kSsimLdsW];
-    __shared__ uint8_t s_b[kSsimIn][kSsimLdsW];
-    __shared__ double s_wave[kSsimTW / kWave];
-
+    __shared__ SsimTileLds s;
     const int tile = blockIdx.x;
     const int x0 = (tile % tiles_x) * kSsimTW, y0 = (tile / tiles_x) * kSsimTH;
     const int ia = pairs.a[blockIdx.y], ib = pairs.b[blockIdx.y];
     const int64_t hw = (int64_t)H * W;
-    const uint8_t* A = gray + ia * hw;
-    const uint8_t* B = gray + ib * hw;
-
-    for (int i = threadIdx.x; i < kSsimIn * (kSsimTW + 6); i += kSsimTW) {
-        const int r = i / (kSsimTW + 6), c = i % (kSsimTW + 6);
-        const int y = y0 + r, x = x0 + c;
-        const bool in = y < H && x < W;
-        const int64_t o = (int64_t)y * W + x;
-        s_a[r][c] = in ? A[o] : 0;
-        s_b[r][c] = in ? B[o] : 0;
-    }
-    __syncthreads();
-
     double R = data_range;
     if (range_from_a) R = (double)(minmax[2 * ia + 1] - minmax[2 * ia]);
-    const double k1r = 0.01 * R, k2r = 0.03 * R;
-    const double C1 = k1r * k1r, C2 = k2r * k2r;
-    const double cov_norm = 49.0 / 48.0;
-
-    const int tx = threadIdx.x;
-    const bool col_ok = x0 + tx < W - 6;
-    const int rows_out = min(kSsimTH, H - 6 - y0);
-    int ring[7][5] = {};
-    int vx = 0, vy = 0, vxx = 0, vyy = 0, vxy = 0;
-    double acc = 0.0;
-    for (int r0 = 0; r0 < kSsimIn; r0 += 7) {
-#pragma unroll
-        for (int k = 0; k < 7; ++k) {
-            const int r = r0 + k;
-            int hx = 0, hy = 0, hxx = 0, hyy = 0, hxy = 0;
-#pragma unroll
-            for (int j = 0; j < 7; ++j) {
-                const int a = s_a[r][tx + j], b = s_b[r][tx + j];
-                hx += a;
-                hy += b;
-                hxx += a * a;
-                hyy += b * b;
-                hxy += a * b;
-            }
-            vx += hx - ring[k][0];
-            vy += hy - ring[k][1];
-            vxx += hxx - ring[k][2];
-            vyy += hyy - ring[k][3];
-            vxy += hxy - ring[k][4];
-            ring[k][0] = hx;
-            ring[k][1] = hy;
-            ring[k][2] = hxx;
-            ring[k][3] = hyy;
-            ring[k][4] = hxy;
-            if (r >= 6 && r - 6 < rows_out && col_ok) {
-                const double ux = (double)vx / 49.0, uy = (double)vy / 49.0;
-                const double uxx = (double)vxx / 49.0, uyy = (double)vyy / 49.0, uxy = (double)vxy / 49.0;
-                const double sx = cov_norm * (uxx - ux * ux);
-                const double sy = cov_norm * (uyy - uy * uy);
-                const double sxy = cov_norm * (uxy - ux * uy);
-                const double a1 = 2.0 * ux * uy + C1, a2 = 2.0 * sxy + C2;
-                const double b1 = ux * ux + uy * uy + C1, b2 = sx + sy + C2;
-                acc += (a1 * a2) / (b1 * b2);
-            }
-        }
-    }
-    acc = wave_sum(acc);
-    if ((tx & (kWave - 1)) == 0) s_wave[tx / kWave] = acc;
-    __syncthreads();
-    if (tx == 0) {
-        double s = s_wave[0];
-#pragma unroll
-        for (int i = 1; i < kSsimTW / kWave; ++i) s += s_wave[i];
-        partial[(int64_t)(pair0 + blockIdx.y) * n_tiles + tile] = s;
-    }
+    ssim_tile_partial(gray + ia * hw, gray + ib * hw, H, W, x0, y0, R, s,
+                      partial + (int64_t)(pair0 + blockIdx.y) * n_tiles + tile);
 }
 
-// score[p] = (sum of pair p's tile partials, in a fixed order) / count.  blockIdx.x = pair.
+// score[p] = (sum of pair p's tile partials, in a fixed order: ssim_partials_sum) / count.  blockIdx.x = pair.
 __global__ __launch_bounds__(kFinishThreads) void ssim_finish_kernel(const double* __restrict__ partial, int n_tiles, double count,
                                                                      double* __restrict__ scores) {
     __shared__ double s_wave[kFinishThreads / kWave];
-    const double* p = partial + (int64_t)blockIdx.x * n_tiles;
-    double acc = 0.0;
-    for (int t = threadIdx.x; t < n_tiles; t += kFinishThreads) acc += p[t];
-    acc = wave_sum(acc);
-    if ((threadIdx.x & (kWave - 1)) == 0) s_wave[threadIdx.x / kWave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = s_wave[0];
-#pragma unroll
-        for (int i = 1; i < kFinishThreads / kWave; ++i) s += s_wave[i];
-        scores[blockIdx.x] = s / count;
-    }
-}
-
-static int ssim_tiles(int H, int W, int* tiles_x) {
-    const int tx = (W - 6 + kSsimTW - 1) / kSsimTW, ty = (H - 6 + kSsimTH - 1) / kSsimTH;
-    if (tiles_x) *tiles_x = tx;
-    return tx * ty;
+    const double s = ssim_partials_sum(partial + (int64_t)blockIdx.x * n_tiles, n_tiles, s_wave);
+    if (threadIdx.x == 0) scores[blockIdx.x] = s / count;
 }
 
 }  // namespace hmm

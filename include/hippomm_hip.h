@@ -544,6 +544,58 @@ int    hmm_ssim_pairs(const uint8_t* gray_dev, int n_frames, int H, int W, const
                       void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The decision loop of extract_frames_from_video (hippomm/core/batch_process.py:179-228) with its state on the device: the last
+ * saved frame (the anchor), the running cumulative difference and the time of the last save.
+ *
+ * Slots: gray_slots_dev is (n_slots, H, W) u8, owned by the caller.  Slot 0 holds the anchor carried over from the previous call,
+ * slots 1 .. n_slots - 1 this batch's candidates (hmm_gray_u8 fills them in one launch).  hmm_extract_state is the whole state; the
+ * caller creates it zeroed (no anchor), may copy it out and back to snapshot and restore it, and never needs to look inside between
+ * calls.
+ *
+ * hmm_extract_walk: for the candidates in slots first_slot .. first_slot + count - 1, in order, with times_host[i], check_host[i] and
+ *   deny_host[i] (HOST arrays of count entries, passed to the kernels by value) for the candidate in slot first_slot + i:
+ *     compared = has_anchor && check_i && (time_i - last_save_time >= min_gap)
+ *     compared:    diff = 1.0 - SSIM(candidate, gray[anchor_slot]) with R = 255, the candidate in skimage's im1 role -- bit for
+ *                  bit 1.0 - hmm_ssim_pairs' score of that pair --, cumulative_diff += diff,
+ *                  save = diff > max_diff_threshold || cumulative_diff > max_diff_threshold
+ *     no anchor:   save = true without a comparison;  otherwise save = false, diff = 0
+ *     save && !deny_i:  anchor_slot = the candidate's slot, has_anchor = 1, last_save_time = time_i, cumulative_diff = 0
+ *     a denied save leaves the four as they are (the reference when save_frame returns False).
+ *   records_out_dev[i] describes candidate i and the state after it; only records_out_dev[0 .. count) is written.  Two launches per
+ *   candidate on `stream`, which must execute in order; no host synchronisation, no workgroup waits for another one.  The anchor slot
+ *   is the only index read from device memory and is clamped to [0, n_slots) before use.  The inputs are not written.
+ *   HMM_E_INVALID before anything is launched (no GPU needed): a null pointer, H or W under 7, n_slots < 2, count < 1,
+ *   first_slot < 1 or first_slot + count > n_slots, state / records / workspace not 8-byte aligned, a time that is not finite,
+ *   max_diff_threshold or min_gap NaN.  HMM_E_WORKSPACE: workspace_bytes below hmm_extract_walk_workspace_bytes(H, W).
+ *
+ * hmm_extract_carry: gray[0] = gray[anchor_slot] and anchor_slot = 0, the indirection on the device with the same clamp; nothing
+ *   happens without an anchor or with the anchor in slot 0 already.  Afterwards slots 1 .. may be overwritten with the next batch.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t has_anchor;
+    int32_t anchor_slot;
+    double  cumulative_diff;
+    double  last_save_time;
+} hmm_extract_state;
+
+typedef struct {
+    int32_t compared;               /* 1: the candidate was scored against the anchor */
+    int32_t saved;                  /* 1: the candidate became the anchor (save && !deny) */
+    int32_t anchor_slot_after;
+    int32_t has_anchor_after;
+    double  diff;                   /* 0 where nothing was compared */
+    double  cumulative_after;
+    double  last_save_time_after;
+} hmm_extract_record;
+
+size_t hmm_extract_walk_workspace_bytes(int H, int W);
+int    hmm_extract_walk(const uint8_t* gray_slots_dev, int n_slots, int H, int W, int first_slot, int count,
+                        const double* times_host, const int32_t* check_host, const int32_t* deny_host,
+                        double max_diff_threshold, double min_gap, hmm_extract_state* state_dev,
+                        hmm_extract_record* records_out_dev, void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
+int    hmm_extract_carry(uint8_t* gray_slots_dev, int n_slots, int H, int W, hmm_extract_state* state_dev, hmm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * cv2.resize of 8-bit frames to a target no larger than the source, as the reference shrinks every recalled frame
  * (hippomm/core/hippocampal_memory.py:2232, :2795: cv2.resize(frame, (320, 180))).  The arithmetic is OpenCV's 8-bit INTER_LINEAR,
  * restated from its published source (imgproc/src/resize.cpp); a build that routes 8-bit resize through another back end may differ.
