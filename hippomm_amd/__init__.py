@@ -57,9 +57,16 @@ and the decision loop of frame extraction with the last saved frame, the cumulat
 device: each frame uploaded once, one read-back per batch of candidates (hippomm_amd/csrc/extract_walk.hip):
 
     hippomm_amd.extract_frames, FrameExtractor, extraction_records  <- hippomm/core/batch_process.py:179-228
+
+and the step that joins formation to the stored event, a video's segment memories consolidated into one: the stacked, time-ordered
+matrix gathered on the device from the segments' blocks where they lie (hippomm_amd/csrc/rows_gather.hip), the selection on it,
+nothing read back but the kept list, and a result that can stay a device tensor:
+
+    hippomm_amd.consolidate_short_term_memory        <- hippomm/core/hippocampal_memory.py:754-927
 """
 __version__ = "0.1.0"
 
+from .consolidation import consolidate_short_term_memory  # noqa: E402,F401
 from .jpeg import decode_jpeg, encode_jpeg  # noqa: E402,F401
 from .segmentation import FrameExtractor, extract_frames, extraction_records  # noqa: E402,F401
 from .retrieval import (feature_entries, find_relevant_audio_segments, find_relevant_video_segments,  # noqa: E402,F401

@@ -30,6 +30,7 @@ _SIGNATURES = {
     "hmm_store_ingest_rows": (C.c_int, [c_ptr, C.c_int, C.c_int64, C.c_int, c_ptr, c_ptr, C.c_int64, C.c_int64, c_ptr]),
     "hmm_store_gather_segments": (C.c_int, [c_ptr, c_ptr, C.c_int64, c_ptr, C.c_int, c_ptr, c_ptr, C.c_int, C.c_int, c_ptr, c_ptr,
                                             C.c_int64, C.c_int64, c_ptr]),
+    "hmm_rows_gather": (C.c_int, [c_ptr, C.c_int64, C.c_int, c_ptr, c_ptr]),
     "hmm_cosine_topk_prefilter_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "hmm_cosine_topk_prefilter": (C.c_int, [c_ptr, c_ptr, C.c_int64, C.c_int, c_ptr, C.c_int, c_ptr, c_ptr, c_ptr, c_ptr,
                                             c_ptr, C.c_size_t, c_ptr]),

@@ -2,6 +2,8 @@
 ``HippocampalMemory._select_key_frames`` (hippomm/core/hippocampal_memory.py:944-967),
 bound to ``hmm_gram_select`` (fp32 normalise, fp64-accumulated gram via f64 MFMA, greedy scan).  ``KeyFrameSelector`` is the
 same selection grown batch by batch (``hmm_keyframe_extend``): each frame is decided when its embedding arrives.
+``consolidate_short_term_memory`` is the caller around the selection (:754-927): the rows of every segment's block stacked in time
+order by one gather launch on the device (``hmm_rows_gather``), selected there, and returned as numpy or as device tensors.
 """
 from __future__ import annotations
 
@@ -200,3 +202,263 @@ class KeyFrameSelector:
         count = min(max(int(host[0]), 0), self._bound)
         self._bound = count
         return host[1: 1 + count].copy()
+
+
+# ---- the caller around the selection: consolidate_short_term_memory and its two helpers (hippocampal_memory.py:754-927) ----
+#
+# The reference walks every segment's memory, picks one row per frame out of the segment's own feature block
+# (_extract_frame_feature, :929-942 -- with tensor features a .cpu() of the whole block per frame), sorts the rows by time, stacks
+# them on the host (:842) and selects.  Here the walk is a PLAN on the host (which row of which block goes where: shapes and times
+# only, no feature value is touched) and the stack is one launch of hmm_rows_gather over the blocks where they lie on the device.
+
+def _is_block(a) -> bool:
+    return isinstance(a, (np.ndarray, torch.Tensor))
+
+
+def _flat_width(shape) -> int:
+    """``feature.flatten().shape[0]`` for more than one dimension, ``feature.shape[0]`` otherwise (:827-829, :885-887)."""
+    return int(np.prod(shape)) if len(shape) > 1 else shape[0]
+
+
+def plan_vision_rows(memories):
+    """The loop of ``_process_vision_features`` (:818-838) without the features: -> (entries, skipped).  ``entries`` has one
+    ``(memory index, row index or None, frame, frame_time)`` per row the reference stacks, in the order it stacks them; a row index
+    of None means "the whole block, flattened".  ``skipped`` counts the rows the reference drops with its warning.  Pure host.
+
+    ``_extract_frame_feature``'s rules (:929-942): a block with more than one row and ``idx < rows`` gives row ``idx``; a block of
+    one row, or a 1-D block, gives itself to every frame of its memory; ``idx >= rows`` on a block of several rows gives the whole
+    matrix, whose flattened width is wrong, so it is skipped; frames beyond ``len(frame_times)`` are ignored; a block that is
+    neither an array nor a tensor gives nothing.  The order is Python's own stable ``sort(key=time)`` on the collected list, as
+    :838 -- ties stay in collection order, and a ``None`` time raises the ``TypeError`` it raises there."""
+    entries, skipped = [], 0
+    for mi, memory in enumerate(memories):
+        if 'vision' in memory.modalities and 'frames' in memory.content:
+            for idx, frame in enumerate(memory.content['frames']):
+                if idx < len(memory.content.get('frame_times', [])):
+                    frame_time = memory.content['frame_times'][idx]
+                    block = memory.features.get('vision')
+                    if not _is_block(block):                                  # None, or a type :937 does not know
+                        continue
+                    shape, row = tuple(block.shape), None
+                    if len(shape) > 1 and shape[0] > 1 and idx < shape[0]:    # :938
+                        shape, row = shape[1:], idx
+                    if _flat_width(shape) != FEATURE_DIM:                     # :829
+                        skipped += 1
+                        continue
+                    entries.append((mi, row, frame, frame_time))
+    entries.sort(key=lambda e: e[3])                                          # :838
+    return entries, skipped
+
+
+def _walk_audio(memories):
+    entries, skipped, transcriptions = [], 0, []
+    for mi, memory in enumerate(memories):
+        if 'audio' in memory.modalities and 'audio' in memory.content:
+            if 'audio' in memory.features:
+                start = memory.content['audio'].get('start_time')
+                block = memory.features['audio']
+                if _flat_width(tuple(block.shape)) != FEATURE_DIM:            # :887: the memory's transcription is dropped with it
+                    skipped += 1
+                    continue
+                if _is_block(block):                                          # :903
+                    entries.append((mi, None, None, start))
+            if memory.transcription:
+                transcriptions.extend(memory.transcription)
+    return entries, skipped, transcriptions
+
+
+def plan_audio_rows(memories):
+    """The loop of ``_process_audio_features`` (:875-905) without the features: -> (entries, skipped), entries as
+    ``plan_vision_rows`` gives them with ``(memory index, None, None, start_time)``.  Memory order is kept (the reference does not
+    sort here), a tensor or a 2-D (1,1024) block counts flattened, a block of another width is skipped with the reference's
+    warning, and the times are the ``start_time`` values of ``content['audio']`` as they are (None when absent).  Pure host."""
+    entries, skipped, _ = _walk_audio(memories)
+    return entries, skipped
+
+
+def _f32(block) -> bool:
+    return block.dtype == (torch.float32 if isinstance(block, torch.Tensor) else np.float32)
+
+
+def _stack_host(blocks, entries) -> np.ndarray:
+    """The reference's own expression (:824-842): every block on the host (one read-back per block, where the reference makes one
+    per frame), the row or the flattened block per entry, ``np.stack``."""
+    host = {mi: b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else b for mi, b in blocks.items()}
+    return np.stack([(host[mi] if row is None else host[mi][row]).reshape(-1) for mi, row, _, _ in entries])
+
+
+def _gather_device(blocks, entries, dev, stat) -> torch.Tensor:
+    """(n,1024) fp32 on `dev`: row i is what entry i names.  Resident blocks are read where they lie (a row of a 2-D view with
+    unit column stride at its own address, whatever the row stride; anything else through a contiguous copy on the device); host
+    blocks travel once each, together with the address table, in ONE pinned buffer and one copy; one ``hmm_rows_gather`` launch."""
+    from ._pinned import stage
+    from .event_store import _device_lock, _device_stages
+    lib, n = _lib.load(), len(entries)
+    table_bytes = (8 * n + 255) // 256 * 256
+    resident, host, at, total = {}, {}, {}, table_bytes
+    for mi, b in blocks.items():
+        if isinstance(b, torch.Tensor) and b.is_cuda:
+            resident[mi] = b.detach() if b.device == dev else b.detach().to(dev)
+        else:
+            host[mi] = np.ascontiguousarray(b.detach().numpy() if isinstance(b, torch.Tensor) else b)
+            at[mi], total = total, total + (host[mi].nbytes + 255) // 256 * 256
+    stat["resident"], stat["uploaded"] = len(resident), len(host)
+
+    def address(mi, row) -> int:
+        if mi in host:
+            return raw.data_ptr() + at[mi] + (0 if row is None else row * 4 * FEATURE_DIM)
+        t = resident[mi]
+        if row is not None and t.dim() == 2 and t.stride(1) == 1:
+            return t.data_ptr() + row * t.stride(0) * 4
+        if not t.is_contiguous():
+            t = resident[mi] = t.contiguous()
+        return t.data_ptr() + (0 if row is None else row * 4 * FEATURE_DIM)
+
+    with torch.cuda.device(dev), _device_lock:
+        raw = torch.empty(total, dtype=torch.uint8, device=dev)
+        up = stage(_device_stages, ("up", dev.index), (total,))
+        up.wait()
+        up.host[: 8 * n].view(np.int64)[:] = [address(mi, row) for mi, row, _, _ in entries]
+        for mi, a in host.items():
+            up.host[at[mi]: at[mi] + a.nbytes] = a.reshape(-1).view(np.uint8)
+        raw.copy_(up.pinned[:total], non_blocking=True)
+        up.mark()
+        out = torch.empty(n, FEATURE_DIM, dtype=torch.float32, device=dev)
+        _lib.check(lib.hmm_rows_gather(raw.data_ptr(), n, FEATURE_DIM, out.data_ptr(), _lib.stream_ptr()), "hmm_rows_gather")
+    # `raw` and `resident` (the contiguous copies among them) have lived until here: the gather is on the stream, and what the
+    # allocator hands out again from now on is ordered behind it on that stream
+    return out
+
+
+def _kept_device(matrix: torch.Tensor, similarity_threshold: float) -> np.ndarray:
+    """``hmm_gram_select`` on the gathered matrix; the count and the indices come back in one copy: the call's only read-back."""
+    n = matrix.shape[0]
+    if n <= 2:                                                                # :947-948
+        return np.arange(n)
+    lib = _lib.load()
+    with torch.cuda.device(matrix.device):
+        meta = torch.zeros(1 + n, dtype=torch.int64, device=matrix.device)    # the count (an int32 in the low half), then the indices
+        ws = torch.empty(max(lib.hmm_gram_select_workspace_bytes(n), 256), dtype=torch.uint8, device=matrix.device)
+        thr = float(np.float32(similarity_threshold))                         # the reference compares in float32 (:960)
+        _lib.check(lib.hmm_gram_select(matrix.data_ptr(), n, FEATURE_DIM, thr, meta.data_ptr() + 8, meta.data_ptr(), ws.data_ptr(),
+                                       ws.numel(), _lib.stream_ptr()), "hmm_gram_select")
+        host = meta.cpu().numpy()
+    return host[1: 1 + min(max(int(host[0]), 0), n)].copy()
+
+
+def _stacked(memories, key, entries, features, device, stat, select, similarity_threshold):
+    """-> (the stacked matrix as `features` asks for it, the kept indices or None when `select` is off)."""
+    blocks = {mi: memories[mi].features[key] for mi, _, _, _ in entries}
+    if all(_f32(b) for b in blocks.values()):
+        stat["route"] = "device"
+        matrix = _gather_device(blocks, entries, _target_device(device), stat)
+        kept = _kept_device(matrix, similarity_threshold) if select else None
+        return (matrix if features == "device" else matrix.cpu().numpy()), kept
+    stat["route"] = "host"
+    matrix = _stack_host(blocks, entries)
+    kept = select_key_frames(matrix, None, similarity_threshold) if select else None
+    if features == "device":
+        matrix = torch.from_numpy(matrix).to(_target_device(device))
+    return matrix, kept
+
+
+def _target_device(device) -> torch.device:
+    """`device` with an index (None, or "cuda" without one: the current device), once the GPU has been checked."""
+    current = _lib.require_gpu()
+    dev = current if device is None else torch.device(device)
+    return dev if dev.index is not None else current
+
+
+_EMPTY = {"route": None, "rows": 0, "skipped": 0, "resident": 0, "uploaded": 0}
+
+
+def _vision_part(memories, similarity_threshold=0.9, features="host", device=None, stat=None):
+    stat = {} if stat is None else stat
+    entries, skipped = plan_vision_rows(memories)
+    stat.update(_EMPTY, rows=len(entries), skipped=skipped)
+    if not entries:
+        return {'features': {}, 'content': {}}
+    times = np.array([e[3] for e in entries])                                 # :843
+    matrix, kept = _stacked(memories, 'vision', entries, features, device, stat, True, similarity_threshold)
+    return {'features': {'vision': matrix, 'vision_times': times},
+            'content': {'frames': [entries[i][2] for i in kept], 'frame_times': times[kept].tolist()}}
+
+
+def _audio_part(memories, features="host", device=None, stat=None):
+    stat = {} if stat is None else stat
+    entries, skipped, transcriptions = _walk_audio(memories)
+    stat.update(_EMPTY, rows=len(entries), skipped=skipped)
+    if not entries:
+        return {'features': {}, 'content': {}}
+    times = np.array([e[3] for e in entries])                                 # :909
+    matrix, _ = _stacked(memories, 'audio', entries, features, device, stat, False, None)
+    return {'features': {'audio': matrix, 'audio_times': times},
+            'content': {'audio_times': times.tolist(), 'transcription': transcriptions if transcriptions else None}}
+
+
+def consolidate_short_term_memory(memories, similarity_threshold: float = 0.9, *, features: str = "host", device=None,
+                                  stats: Optional[dict] = None):
+    """``HippocampalMemory.consolidate_short_term_memory`` (:754-813) with its two helpers (:815-927): all short-term memories of a
+    video combined into one ``checkpoint.ShortTermMemory``, filled as :773-802 fills it.  ``memories`` is sorted in place by
+    ``segment_info.start_time`` (the reference sorts the caller's list); ``timestamp`` and ``source_time`` come from the first
+    memory, ``segment_info`` is ``SequenceSegment(first.timestamp, last.timestamp)``, ``transcription`` is ``[]``; ``features`` holds
+    'vision', 'vision_times', 'audio', 'audio_times' and ``content`` 'frames', 'frame_times', 'audio_times', 'transcription', in
+    that order, each pair only when its modality has rows to stack.  An empty list returns None.  The times arrays are
+    ``np.array(list)`` on the host, as in the reference.
+
+    Device route, per modality, when every block the plan names (``plan_vision_rows`` / ``plan_audio_rows``) is float32, a numpy
+    array or a tensor alike: blocks on the device are read where they lie, host blocks are uploaded once each -- all of them and
+    the table of row addresses in one pinned buffer and one copy --, ``hmm_rows_gather`` builds the stacked, time-ordered matrix
+    in one launch, ``hmm_gram_select`` runs on it, and the kept indices are the only read-back (one synchronisation; ``n <= 2``
+    keeps all rows without any, :947-948).  ``features="device"`` returns the gathered CUDA tensors themselves, which
+    ``event_store.event_json_bytes(..., matrices="device")``, ``EventStore.append_event`` and ``top_k_cosine_similarity`` take as
+    they are; ``features="host"`` (the default, and what the drop-ins use) reads them back into numpy matrices, as the reference
+    returns.  The stacked bytes are the blocks' bytes either way.
+
+    Host route, per modality, when any named block has another dtype: the reference's numpy expression (``np.stack`` of the rows,
+    numpy's own dtype promotion) followed by ``select_key_frames``; ``features="device"`` then uploads that matrix as it is.
+
+    ``stats``, when given, receives per modality ('vision', 'audio') a dict: "route" ("device", "host", or None when nothing was
+    stacked), "rows", "skipped" (rows dropped with the reference's wrong-width rule), "resident" and "uploaded" (blocks read where
+    they lay / uploaded on the device route).
+
+    One deviation: ``modalities`` is 'vision', then 'audio', then any other name in sorted order, each when some memory has it.
+    The reference's ``list(set().union(...))`` has the iteration order of a set of strings, which varies between processes."""
+    if features not in ("host", "device"):
+        raise ValueError(f"features must be 'host' or 'device', not {features!r}")
+    if not memories:
+        return None
+    from .checkpoint import SequenceSegment, ShortTermMemory
+    memories.sort(key=lambda x: x.segment_info.start_time)                    # :769
+    present = set().union(*(memory.modalities for memory in memories))        # :787
+    out = ShortTermMemory(features={}, content={}, timestamp=memories[0].timestamp, source_time=memories[0].source_time,
+                          modalities=[m for m in ('vision', 'audio') if m in present] + sorted(present - {'vision', 'audio'}),
+                          segment_info=SequenceSegment(start_time=memories[0].timestamp, end_time=memories[-1].timestamp),
+                          transcription=[])
+    stats = {} if stats is None else stats
+    if 'vision' in present:
+        part = _vision_part(memories, similarity_threshold, features, device, stats.setdefault('vision', {}))
+        out.features.update(part['features'])
+        out.content.update(part['content'])
+    if 'audio' in present:
+        part = _audio_part(memories, features, device, stats.setdefault('audio', {}))
+        out.features.update(part['features'])
+        out.content.update(part['content'])
+    return out
+
+
+def _process_vision_features(self, memories, pool=None):
+    """Drop-in for ``HippocampalMemory._process_vision_features`` (assign it on the class; ``self`` and ``pool`` are unused, the
+    pool there as well): the reference's dict, ``{'features': {}, 'content': {}}`` when nothing can be stacked."""
+    return _vision_part(memories)
+
+
+def _process_audio_features(self, memories, pool=None):
+    """Drop-in for ``HippocampalMemory._process_audio_features`` (assign it on the class)."""
+    return _audio_part(memories)
+
+
+def _consolidate_short_term_memory(self, memories):
+    """Drop-in for ``HippocampalMemory.consolidate_short_term_memory`` (assign it on the class under that name; it starts no
+    process pool -- the reference's two helpers never use theirs)."""
+    return consolidate_short_term_memory(memories)

@@ -150,6 +150,27 @@ int    hmm_store_gather_segments(const float* src_store_dev, const void* src_sha
                                  int n_dst, int dim, float* dst_store_dev, void* dst_shadow_dev, int64_t dst_rows,
                                  int64_t dst_capacity_rows, hmm_stream_t stream);
 
+/* The stack behind consolidate_short_term_memory (hippocampal_memory.py:842: one row per frame out of every segment's own feature
+ * block, in time order), built on the device from the blocks where they lie.
+ *
+ * hmm_rows_gather: src_row_ptrs_dev is a device table of n device addresses; src_row_ptrs_dev[i] is the address of 1024
+ * contiguous fp32 values, and row i of out_dev (contiguous (n,1024)) receives them bit for bit.  Unlike
+ * hmm_store_gather_segments the sources are independent allocations, addressed row by row: the same source row may be named any
+ * number of times and the sources may lie in any order.  Writes exactly n * 4096 bytes of out_dev; reads exactly the named rows
+ * and the n table entries.  One wave copies one row with 16-byte loads and stores; a source row that is only 4-byte aligned (a
+ * view into a wider matrix at an odd column offset) takes a dword path, chosen per row on its address.  out_dev must be 16-byte
+ * aligned, the table 8-byte aligned.
+ *
+ * The host cannot see the addresses in the table.  THE CALLER GUARANTEES that every one of them is the address of a readable
+ * fp32 row of 1024 values on the stream's device, aligned to 4 bytes at least, that stays valid until the launch has run, and
+ * that no source row overlaps the n * 4096 bytes of out_dev.  Nothing of this can be checked here; a wrong address is a wild read.
+ *
+ * n == 0 returns HMM_OK without a launch and without looking at a pointer.  Otherwise HMM_E_INVALID, before anything is launched,
+ * for dim != 1024, n < 0, a null table or output, or a misaligned table or output.  No workspace; nothing is allocated, copied
+ * or synchronised. */
+int    hmm_rows_gather(const uint64_t* src_row_ptrs_dev /* [n] */, int64_t n, int dim, float* out_dev /* (n,1024) */,
+                       hmm_stream_t stream);
+
 /* Batched feature_search: the top-k of n_queries queries against the same store in ONE pass over it
  * (16 queries per pass; the Q x rows similarity block runs on the fp32 matrix cores, so a row is still read once from
  * HBM).  The reference calls top_k_cosine_similarity once per question (hippomm/utils/vector_ops.py:151-188 via
