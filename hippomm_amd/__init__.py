@@ -63,6 +63,11 @@ matrix gathered on the device from the segments' blocks where they lie (hippomm_
 nothing read back but the kept list, and a result that can stay a device tensor:
 
     hippomm_amd.consolidate_short_term_memory        <- hippomm/core/hippocampal_memory.py:754-927
+
+and, opt-in, the window walk of sequence segmentation itself on the device over resident pair scores, frame times and the audio
+track, the segment list the one read-back (hippomm_amd/csrc/segment_walk.hip):
+
+    hippomm_amd.segmentation.segment_sequence(..., walk="device"), PathScorer.score_adjacent  <- hippomm/core/hippocampal_memory.py:1002-1114
 """
 __version__ = "0.1.0"
 

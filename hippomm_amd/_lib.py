@@ -85,6 +85,10 @@ _SIGNATURES = {
     "hmm_extract_walk": (C.c_int, [c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr, c_ptr, C.c_double, C.c_double,
                                    c_ptr, c_ptr, c_ptr, C.c_size_t, c_ptr]),
     "hmm_extract_carry": (C.c_int, [c_ptr, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr]),
+    "hmm_segment_walk_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "hmm_segment_walk": (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, c_ptr, C.c_int, C.c_int64, C.c_int, C.c_double, C.c_double,
+                                   C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr, c_ptr, C.c_size_t,
+                                   c_ptr]),
     "hmm_resize_linear_u8": (C.c_int, [c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr, C.c_int, C.c_int, c_ptr, c_ptr, c_ptr, c_ptr,
                                        C.c_int, c_ptr]),
     "hmm_jpeg_parse": (C.c_int, [c_ptr, C.c_size_t, c_ptr]),

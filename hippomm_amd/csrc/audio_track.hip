@@ -35,7 +35,7 @@
 // All three read their span / clip / window tables from the device and clamp what they find there to the track, so a device table
 // that disagrees with the host copy the entry point has checked reads and writes less, never elsewhere.  No scratch, vector stores
 // only.
-#include "hmm_common.h"
+#include "audio_levels.h"
 
 namespace hmm {
 
@@ -233,6 +233,16 @@ __global__ __launch_bounds__(256) void window_sums_kernel(const T* __restrict__ 
     if (tid == 0) sums[blockIdx.x] = total;
 }
 
+void launch_window_sums(const void* track_dev, int track_dtype, int64_t track_len, const int64_t* windows_dev, int n_windows,
+                        void* sums_dev, hipStream_t stream) {
+    if (track_dtype == 1)
+        window_sums_kernel<double><<<n_windows, 256, 0, stream>>>(static_cast<const double*>(track_dev), track_len, windows_dev,
+                                                                   static_cast<double*>(sums_dev));
+    else
+        window_sums_kernel<float><<<n_windows, 256, 0, stream>>>(static_cast<const float*>(track_dev), track_len, windows_dev,
+                                                                  static_cast<float*>(sums_dev));
+}
+
 static bool track_overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
     const uint64_t x = (uint64_t)(uintptr_t)a, y = (uint64_t)(uintptr_t)b;
     return a_bytes != 0 && b_bytes != 0 && x < y + b_bytes && y < x + a_bytes;
@@ -342,13 +352,7 @@ extern "C" int hmm_audio_window_sums(const void* track_dev, int track_dtype, int
     }
     HMM_REQUIRE(!track_overlap(track_dev, (uint64_t)track_len * elem, sums_out_dev, (uint64_t)n_windows * elem), HMM_E_INVALID,
                 "audio_window_sums: the output overlaps the track");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (track_dtype == 1)
-        window_sums_kernel<double><<<n_windows, 256, 0, st>>>(static_cast<const double*>(track_dev), track_len, windows_dev,
-                                                               static_cast<double*>(sums_out_dev));
-    else
-        window_sums_kernel<float><<<n_windows, 256, 0, st>>>(static_cast<const float*>(track_dev), track_len, windows_dev,
-                                                              static_cast<float*>(sums_out_dev));
+    launch_window_sums(track_dev, track_dtype, track_len, windows_dev, n_windows, sums_out_dev, static_cast<hipStream_t>(stream));
     HMM_LAUNCH_CHECK();
     return HMM_OK;
 }

@@ -36,6 +36,10 @@ segments -- the levels of all windows of a step come from one ``AudioTrack.windo
 sum of squares per window in numpy's own summation order; mean, sqrt and log10 on the host in the track's dtype), bit for bit
 the levels of the host route, so the segment list is the same.
 
+``segment_sequence(..., walk="device")`` takes the walk itself to the device (``hmm_segment_walk``, hippomm_amd/csrc/segment_walk.hip):
+every adjacent pair is scored into one device array (``PathScorer.score_adjacent``), the steps are taken there over the scores, the
+frame times and the resident track, and the segment list is the one read-back.  Opt-in; ``walk="host"`` is the route above.
+
 Deliberate deviations from the reference, all documented on the functions: ``compute_frame_difference`` takes uint8 frames only
 (``TypeError`` otherwise); ``_segment_sequence`` raises ``ValueError`` where the reference would loop forever; an unreadable image
 raises ``OSError`` naming the path where the reference raises ``cv2.error``.
@@ -60,6 +64,7 @@ from . import _lib, jpeg
 WIN = 7                                   # skimage's default win_size
 CACHE_BYTES = 512 << 20                   # device cache of gray frames (1080p: 2 MiB per frame)
 UPLOAD_FRAMES = 32                        # frames per pinned staging round
+ADJACENT_CHUNK = 64                       # frames per load-and-score round of PathScorer.score_adjacent
 
 # the reference's __init__ defaults (hippocampal_memory.py:263-266)
 MAX_SEGMENT_DURATION = 10.0
@@ -114,14 +119,17 @@ def gray_frames(frames_u8: torch.Tensor, channel_order: str = "RGB", return_minm
     return (gray, minmax[:n]) if return_minmax else gray
 
 
-def _ssim_launch(gray: torch.Tensor, pairs: np.ndarray, data_range: float, minmax: Optional[torch.Tensor]) -> torch.Tensor:
-    """gray (n, H, W) uint8 CUDA, pairs (m, 2) int32 host -> (m,) float64 CUDA.  data_range < 0: R of frame a from minmax."""
+def _ssim_launch(gray: torch.Tensor, pairs: np.ndarray, data_range: float, minmax: Optional[torch.Tensor],
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gray (n, H, W) uint8 CUDA, pairs (m, 2) int32 host -> (m,) float64 CUDA.  data_range < 0: R of frame a from minmax.
+    out: a contiguous (m,) float64 view on gray's device to write the scores into."""
     lib = _lib.load()
     n, h, w = gray.shape
     m = len(pairs)
     pairs = np.ascontiguousarray(pairs, dtype=np.int32)
     ws = torch.empty(max(lib.hmm_ssim_pairs_workspace_bytes(h, w, m), 256), dtype=torch.uint8, device=gray.device)
-    out = torch.empty(m, dtype=torch.float64, device=gray.device)
+    if out is None:
+        out = torch.empty(m, dtype=torch.float64, device=gray.device)
     _lib.check(lib.hmm_ssim_pairs(gray.data_ptr(), n, h, w, pairs.ctypes.data, m, float(data_range),
                                   0 if minmax is None else minmax.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(),
                                   _lib.stream_ptr()), "hmm_ssim_pairs")
@@ -560,6 +568,44 @@ class PathScorer:
         if err is not None:
             raise err
 
+    def score_adjacent(self, video_frames: Sequence[str], chunk: int = ADJACENT_CHUNK) -> Tuple[torch.Tensor, List[Optional[Exception]]]:
+        """Every pair the walk of ``_segment_sequence`` can consult, scored without a read-back: -> (scores_dev, problems).
+        scores_dev: float64 [n - 1] on the device, scores_dev[i] the SSIM of (video_frames[i + 1], video_frames[i]) -- the later
+        frame in the im1 role, as ``score`` has it.  problems[i]: the exception ``score`` would raise for pair i, or None; such a
+        pair is not scored (its entry stays NaN) and it is the caller's to flag (``hmm_segment_walk`` takes the flags), so that
+        the error is raised only if the walk consults the pair.  Frames go through the cache ``chunk`` at a time, the last frame
+        of a chunk staying for the first pair of the next; one ``hmm_ssim_pairs`` launch per chunk and frame size.
+
+        This decodes every frame, where the host walk decodes only the frames of pairs it consults (539 of 600 on the "cuts"
+        video of DESIGN.md section 11): the price of taking the walk off the host when the frames are not cached already."""
+        n = len(video_frames)
+        scores = torch.full((max(n - 1, 0),), float("nan"), dtype=torch.float64, device=self.dev)
+        problems: List[Optional[Exception]] = [None] * max(n - 1, 0)
+        chunk = max(int(chunk), 1)
+        with self.cache.lock:
+            for c0 in range(1, n, chunk):                       # frames c0 - 1 .. c1 - 1: pairs c0 - 1 .. c1 - 2
+                c1 = min(c0 + chunk, n)
+                paths = list(video_frames[c0 - 1:c1])
+                loaded = self.cache.load(paths, self.dev)
+                sizes = {}
+                for i in range(c0 - 1, c1 - 1):
+                    later, earlier = paths[i + 1 - (c0 - 1)], paths[i - (c0 - 1)]
+                    problems[i] = self._problem(loaded, later, earlier)
+                    if problems[i] is None:
+                        slab = loaded[later][0]
+                        sizes.setdefault((slab.h, slab.w), []).append((i, loaded[later][1], loaded[earlier][1]))
+                for size, items in sizes.items():
+                    slab = self.cache.slabs[size]               # the current slab of that size (it may have grown meanwhile)
+                    idx = np.array([[a, b] for _, a, b in items], dtype=np.int32)
+                    first, m = items[0][0], len(items)
+                    if items[-1][0] - first + 1 == m:           # one run of pairs: straight into the array
+                        _ssim_launch(slab.gray, idx, -1.0, slab.minmax, out=scores[first:first + m])
+                    else:
+                        where = torch.tensor([i for i, _, _ in items], dtype=torch.int64).to(self.dev)
+                        scores.index_copy_(0, where, _ssim_launch(slab.gray, idx, -1.0, slab.minmax))
+                    self.pairs_scored += m
+        return scores, problems
+
 
 def _compute_frame_similarity(self, frame1_path: str, frame2_path: str) -> float:
     """Drop-in for ``HippocampalMemory._compute_frame_similarity`` (assign it on the class; ``self`` is unused): SSIM of the two
@@ -674,17 +720,179 @@ def _window_scorer(video_frames, scorer: PathScorer):
     return score_window
 
 
+# hmm_segment_record and hmm_segment_walk_state of include/hippomm_hip.h
+SEGMENT_RECORD = np.dtype([("start_time", "<f8"), ("end_time", "<f8"), ("first_frame", "<i4"), ("last_frame", "<i4"),
+                           ("cut_pair", "<i4"), ("cut_window", "<i4"), ("pairs_consulted", "<i4"), ("windows_consulted", "<i4")])
+SEGMENT_STATE = np.dtype([("n_segments", "<i4"), ("status", "<i4"), ("flagged_pair", "<i4"), ("steps", "<i4"),
+                          ("current_start", "<f8")])
+WALK_DONE, WALK_FLAGGED, WALK_BOUND = 1, 2, 3       # HMM_SEGMENT_WALK_*
+MAX_DEVICE_STEPS = 4096                             # two launches per step with audio: beyond this the host walks
+MAX_DEVICE_WINDOWS = 65535                          # windows of one step (one workgroup each)
+
+
+def _silent_on_host(rms, threshold) -> bool:
+    """The host route's decision for a window whose rms is the numpy scalar `rms`: ``audio_level``'s last line, then the walk's
+    comparison, with the very objects the host route compares."""
+    with np.errstate(all="ignore"):
+        return bool((20 * np.log10(rms) if rms > 0 else -100) < threshold)
+
+
+@lru_cache(maxsize=64)
+def _silence_cut(dtype_name: str, threshold, _threshold_type) -> Tuple[float, bool]:
+    T = np.dtype(dtype_name).type
+    U = np.uint32 if T is np.float32 else np.uint64
+    value = lambda bits: U(bits).view(T)                                      # noqa: E731
+    lo, hi = 1, int(T(np.inf).view(U))                                        # positive floats in the order of their bit patterns
+    if _silent_on_host(value(hi), threshold):
+        raise AssertionError(f"silence_cut: an infinite rms is silent under threshold {threshold!r}")
+    while lo < hi:                                                            # the least pattern that is not silent
+        mid = (lo + hi) // 2
+        if _silent_on_host(value(mid), threshold):
+            lo = mid + 1
+        else:
+            hi = mid
+    cut = value(lo)
+    if _silent_on_host(cut, threshold) or (lo > 1 and not _silent_on_host(value(lo - 1), threshold)):
+        raise AssertionError(f"silence_cut: the level is not monotonic around rms = {cut!r} for threshold {threshold!r}")
+    return float(cut), bool(-100 < threshold)
+
+
+def silence_cut(dtype, threshold) -> Tuple[float, bool]:
+    """The silence rule of the walk without a logarithm: -> (rms_cut, silent_without_rms) such that, for an rms of `dtype`
+    (float32 or float64), ``(20 * np.log10(rms) if rms > 0 else -100) < threshold`` is ``rms < rms_cut if rms > 0 else
+    silent_without_rms``.  rms_cut is found by bisection over the bit patterns of the positive floats with this host's own scalar
+    expression, and checked: the float below it is silent, it is not (``AssertionError`` otherwise -- a log10 that is not
+    monotonic there).  Cached per (dtype, threshold)."""
+    return _silence_cut(np.dtype(dtype).name, threshold, type(threshold))
+
+
+def _device_walk(video_frames, frame_times, audio_data, audio_sample_rate, max_segment_duration, min_segment_duration,
+                 frame_similarity_threshold, audio_silence_threshold, scorer, audio_track, stats: dict):
+    """The walk by ``hmm_segment_walk`` -> the segments, or a str: why this call stays on the host route."""
+    has_video = bool(video_frames and frame_times)
+    has_audio = (audio_data is not None or audio_track is not None) and bool(audio_sample_rate)
+    if not has_video and not has_audio:
+        return "nothing to segment"
+    if has_audio and audio_track is None:
+        raise ValueError("walk='device' needs the video's AudioTrack (audio_track=) when there is audio")
+    params = (max_segment_duration, min_segment_duration, frame_similarity_threshold, audio_silence_threshold)
+    if any(p != p for p in params) or not all(np.isfinite(p) for p in params[:2]):
+        return "NaN parameters"
+    if not min_segment_duration > 0:
+        return "min_segment_duration <= 0"
+    times = np.empty(0)
+    if has_video:
+        if len(video_frames) != len(frame_times) or not all(isinstance(t, float) for t in frame_times):
+            return "frame_times are not one float per frame"
+        times = np.asarray(frame_times, dtype=np.float64)
+        if not np.all(np.isfinite(times)) or np.any(times[1:] < times[:-1]):
+            return "unsorted frame_times"
+        total = frame_times[-1] - frame_times[0]
+    rate = 0
+    if has_audio:
+        if audio_track.sample_rate != audio_sample_rate or (audio_data is not None and len(audio_data) != audio_track.n_samples):
+            return "audio_track does not match the call"                       # the host route raises the ValueError
+        if audio_track.source_dtype not in (np.float32, np.float64):
+            return "track not float32 / float64 at its source"
+        rate = int(audio_sample_rate)
+        if rate != audio_sample_rate or rate < 2:
+            return "sample rate not an integer >= 2"
+        if not has_video:
+            total = audio_track.n_samples / audio_sample_rate
+    if not np.isfinite(total) or (has_audio and not total * rate < 2.0 ** 52):
+        return "duration out of range"
+    span = min(max_segment_duration, max(total, 0.0))                          # no step is longer, up to rounding
+    window = int(0.5 * rate)
+    if not total / min_segment_duration < MAX_DEVICE_STEPS or (has_audio and not span * rate / window < MAX_DEVICE_WINDOWS):
+        return "more steps or windows than the device route launches"
+    max_steps = max(int(np.ceil(total / min_segment_duration)), 0) + 2         # a clamped step advances by min, or reaches the end
+    max_windows = int((span * rate + 2) // window) + 1 if has_audio else 0
+
+    lib = _lib.load()
+    dev = audio_track.device if has_audio else scorer.dev
+    rms_cut, silent_without_rms = silence_cut(np.float64 if audio_track.dtype_code else np.float32,
+                                              audio_silence_threshold) if has_audio else (0.0, False)
+    problems: List[Optional[Exception]] = []
+    scores = flags = times_dev = None
+    with torch.cuda.device(dev):
+        if has_video:
+            scores, problems = scorer.score_adjacent(video_frames)
+            scores = scores.to(dev)
+            flags = torch.tensor([p is not None for p in problems], dtype=torch.int32).to(dev)
+            times_dev = torch.from_numpy(times).to(dev)
+        ws = torch.empty(max(lib.hmm_segment_walk_workspace_bytes(max_windows, max_steps), 256), dtype=torch.uint8, device=dev)
+        out = torch.empty(max_steps * SEGMENT_RECORD.itemsize + SEGMENT_STATE.itemsize, dtype=torch.uint8, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None   # noqa: E731
+        _lib.check(lib.hmm_segment_walk(ptr(scores), ptr(flags), ptr(times_dev), times.ctypes.data if has_video else None,
+                                        len(times), audio_track.samples.data_ptr() if has_audio else None,
+                                        audio_track.dtype_code if has_audio else 0, audio_track.n_samples if has_audio else 0, rate,
+                                        float(total), float(max_segment_duration), float(min_segment_duration),
+                                        float(frame_similarity_threshold), rms_cut, int(silent_without_rms), max_windows, max_steps,
+                                        out.data_ptr(), out.data_ptr() + max_steps * SEGMENT_RECORD.itemsize, ws.data_ptr(),
+                                        ws.numel(), _lib.stream_ptr()), "hmm_segment_walk")
+        host = out.cpu().numpy()                                               # the one read-back
+    state = host[max_steps * SEGMENT_RECORD.itemsize:].view(SEGMENT_STATE)[0]
+    records = host[:int(state["n_segments"]) * SEGMENT_RECORD.itemsize].view(SEGMENT_RECORD)
+    stats.update(steps=int(state["steps"]), launches=2 * max_steps + 1 if has_audio else 1, read_backs=1,
+                 pairs_scored=len(problems) - sum(p is not None for p in problems),
+                 pairs_consulted=int(records["pairs_consulted"].sum()), windows_consulted=int(records["windows_consulted"].sum()))
+    if state["status"] == WALK_FLAGGED:
+        raise problems[int(state["flagged_pair"])]
+    if state["status"] != WALK_DONE:
+        return "step bound exhausted"
+    segments = []
+    for rec in records:
+        start, end = float(rec["start_time"]), float(rec["end_time"])
+        seg = SequenceSegment(start_time=start, end_time=end)
+        if has_video:                                                          # the frames with start <= t <= end: one index range
+            inside = slice(int(rec["first_frame"]), int(rec["last_frame"]) + 1)
+            seg.frames = list(video_frames[inside])
+            seg.frame_times = list(frame_times[inside])
+        if has_audio and audio_data is not None:
+            seg.audio_data = audio_data[int(start * audio_sample_rate):int(end * audio_sample_rate)]
+        segments.append(seg)
+    return segments
+
+
 def segment_sequence(video_frames: Optional[List[str]] = None, frame_times: Optional[List[float]] = None,
                      audio_data: Optional[np.ndarray] = None, audio_sample_rate: Optional[int] = None, *,
                      max_segment_duration: float = MAX_SEGMENT_DURATION, min_segment_duration: float = MIN_SEGMENT_DURATION,
                      frame_similarity_threshold: float = FRAME_SIMILARITY_THRESHOLD,
                      audio_silence_threshold: float = AUDIO_SILENCE_THRESHOLD,
-                     scorer: Optional[PathScorer] = None, audio_track=None) -> List[SequenceSegment]:
+                     scorer: Optional[PathScorer] = None, audio_track=None, walk: str = "host",
+                     stats: Optional[dict] = None) -> List[SequenceSegment]:
     """``_segment_sequence`` as a function; the four parameters default to the reference's __init__ defaults.  Frame similarities
     come from the GPU (``PathScorer``).  Without ``audio_track`` an audio-only call needs no GPU (the audio scan is host numpy,
-    as in the reference); with the video's ``AudioTrack`` the scan reads the resident track (see ``walk_segments``)."""
+    as in the reference); with the video's ``AudioTrack`` the scan reads the resident track (see ``walk_segments``).
+
+    ``walk="device"`` (opt-in; "host" is the default and is the route above, untouched) takes the control loop to the device as
+    well: every adjacent pair is scored into one device array (``PathScorer.score_adjacent``), ``hmm_segment_walk`` walks it and
+    the resident track, and the segment list is the one read-back -- the same segments: times equal as floats, the same frame
+    lists, the same audio slices (times come back as Python floats; the frames of a segment are taken as one index range, which
+    is what the reference's comprehension selects when the times are sorted).  It needs the video's ``audio_track`` when there
+    is audio (``ValueError``).  It scores every pair, the host route only the consulted ones: with frames that are not in the
+    cache yet it decodes them all.  A pair that cannot be scored raises its error only if the walk consults it, as on the host
+    route.  Calls it does not take go the host route and say why in ``stats["reason"]``: unsorted or non-float frame_times, NaN
+    parameters, min_segment_duration <= 0, a track that was not float32 / float64 at its source, more steps than
+    MAX_DEVICE_STEPS, a walk that did not finish within its step bound.  Measured on one MI355X with every input resident (600
+    cached 1080p frames, a 600 s float64 track at 16 kHz, 80 segments; profiles/segment_walk.json): 9.4 ms
+    against 31.3 ms for the host walk, 1 read-back against 226; uncached frames and other inputs were not measured.
+
+    ``stats``: a dict that receives ``route`` ("host" / "device") and, from the device walk, ``steps``, ``launches``,
+    ``read_backs``, ``pairs_scored``, ``pairs_consulted``, ``windows_consulted``; ``reason`` when a device call went to the host."""
+    if walk not in ("host", "device"):
+        raise ValueError(f"walk must be 'host' or 'device', got {walk!r}")
+    stats = {} if stats is None else stats
     if video_frames and frame_times and scorer is None:
         scorer = PathScorer()
+    if walk == "device":
+        done = _device_walk(video_frames, frame_times, audio_data, audio_sample_rate, max_segment_duration, min_segment_duration,
+                            frame_similarity_threshold, audio_silence_threshold, scorer, audio_track, stats)
+        if not isinstance(done, str):
+            stats["route"] = "device"
+            return done
+        stats["reason"] = done
+    stats["route"] = "host"
     score_window = _window_scorer(video_frames, scorer) if scorer is not None else None
     return walk_segments(video_frames, frame_times, audio_data, audio_sample_rate, score_window,
                          max_segment_duration, min_segment_duration, frame_similarity_threshold, audio_silence_threshold,
@@ -696,13 +904,15 @@ def _segment_sequence(self, video_frames: Optional[List[str]] = None, frame_time
                       audio_track=None) -> List[SequenceSegment]:
     """Drop-in for ``HippocampalMemory._segment_sequence`` (assign it on the class): reads self.max_segment_duration,
     self.min_segment_duration, self.frame_similarity_threshold and self.audio_silence_threshold.  The video's ``AudioTrack``,
-    given as the ``audio_track`` argument or set as ``self.audio_track``, moves the audio-level scan to the device."""
+    given as the ``audio_track`` argument or set as ``self.audio_track``, moves the audio-level scan to the device;
+    ``self.segment_walk = "device"`` moves the walk itself there (``segment_sequence``'s ``walk``; "host" when not set)."""
     if audio_track is None:
         audio_track = getattr(self, "audio_track", None)
     return segment_sequence(video_frames, frame_times, audio_data, audio_sample_rate,
                             max_segment_duration=self.max_segment_duration, min_segment_duration=self.min_segment_duration,
                             frame_similarity_threshold=self.frame_similarity_threshold,
-                            audio_silence_threshold=self.audio_silence_threshold, audio_track=audio_track)
+                            audio_silence_threshold=self.audio_silence_threshold, audio_track=audio_track,
+                            walk=getattr(self, "segment_walk", "host"))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

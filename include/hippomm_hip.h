@@ -617,6 +617,77 @@ int    hmm_extract_walk(const uint8_t* gray_slots_dev, int n_slots, int H, int W
 int    hmm_extract_carry(uint8_t* gray_slots_dev, int n_slots, int H, int W, hmm_extract_state* state_dev, hmm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The window walk of _segment_sequence (hippomm/core/hippocampal_memory.py:1002-1114) with its control loop on the device: the
+ * adjacent-pair SSIM scores, the frame times and the audio track are resident, the segment list is the only thing read back.
+ *
+ * hmm_segment_walk: scores_dev fp64 [n_frames - 1], scores_dev[i] = SSIM(frame i + 1, frame i) (hmm_ssim_pairs, the later frame in
+ *   skimage's im1 role); flags_dev int32 [n_frames - 1], non-zero where pair i could not be scored (its score is then never read);
+ *   times_dev fp64 [n_frames] with the HOST copy times_host, validated finite and non-decreasing.  n_frames == 0: no video (the three
+ *   device pointers and times_host may be null; so may scores_dev and flags_dev when n_frames == 1).  track_dev null: no audio; otherwise
+ *   the track of hmm_audio_window_sums (track_dtype 0 fp32 / 1 fp64, track_len samples, 16-byte aligned) at the integer sample_rate,
+ *   with window = (int64)(0.5 * sample_rate) >= 1.  All arithmetic on times is fp64, operation by operation what the Python floats of
+ *   the reference do.  From current_start = 0.0, while current_start < total_duration, one step:
+ *     1. current_end = min(current_start + max_segment_duration, total_duration); optimal_end = current_end.
+ *     2. the frames with current_start <= t <= current_end are a contiguous index range [first, last].
+ *     3. for k = last down to first + 1, pair k - 1: flagged -> the walk stops (status HMM_SEGMENT_WALK_FLAGGED, flagged_pair = k - 1,
+ *        no record for this step); scores_dev[k - 1] < frame_similarity_threshold -> optimal_end = t[k], stop reading.  NaN never cuts.
+ *     4. S = (int64)(current_start * sample_rate), E = (int64)(current_end * sample_rate); for off = E - S - window, E - S - 2 window,
+ *        ... > 0 the window [lo, lo + window), lo = S + off, clipped to the track as a numpy slice would be (n samples, maybe 0):
+ *        sum of squares in the track's dtype T by the kernel of hmm_audio_window_sums; mean = T(sum / n) (the division in fp64,
+ *        rounded to fp32 for an fp32 track; 0 / 0 = NaN); rms = sqrt(mean) in T, correctly rounded;
+ *        silent = rms > 0 ? rms < rms_cut : silent_without_rms.  The first silent window sets optimal_end = lo / sample_rate (it
+ *        overrides step 3's) and ends the scan.  rms_cut is the caller's: the least value of T whose level 20 log10(rms) is not
+ *        below the silence threshold under the caller's own log10; silent_without_rms is (-100 < threshold).
+ *     5. optimal_end - current_start < min_segment_duration -> optimal_end = min(current_start + min_segment_duration, total_duration).
+ *     6. records_out_dev[n_segments++] = the step; current_start = optimal_end.
+ *   state_out_dev is written by the call (no need to initialise it): status HMM_SEGMENT_WALK_DONE when the loop condition failed,
+ *   _FLAGGED as above, _BOUND when max_steps steps did not finish (or a step had more than max_windows windows): the records
+ *   written so far are valid and current_start is where the walk stood.  Only records_out_dev[0 .. n_segments) and the state are
+ *   written.  Launches, all on `stream`, which must execute in order; no host synchronisation, no workgroup waits for another:
+ *   without audio one launch for the whole walk; with audio one planning launch (the window table of step 0, in the workspace), then
+ *   per step one launch of the window sums over max_windows table rows and one decide launch that also writes the next step's
+ *   table -- all lengths 0 once the walk has ended, so the remaining launches return at once.  2 max_steps + 1 launches.  Every
+ *   index formed from device memory (frame indices out of times_dev, n_segments) is clamped to its array before use; the inputs are
+ *   not written.
+ *   HMM_E_INVALID before anything is launched (no GPU needed): a null pointer; n_frames < 0; times_host not finite or decreasing;
+ *   a parameter that is NaN or not finite; min_segment_duration <= 0; max_steps < 1 or max_windows < 0; with audio track_dtype not 0 / 1,
+ *   sample_rate < 2, track_len < 0, max_windows < 1, or total_duration * sample_rate at or above 2^52; records / state / workspace /
+ *   scores / times not 8-byte aligned, flags not 4-byte aligned, the track not 16-byte aligned.  HMM_E_WORKSPACE: workspace_bytes below
+ *   hmm_segment_walk_workspace_bytes(max_windows, max_steps) (0 without audio: max_windows == 0, and workspace_dev may then be null).
+ * ---------------------------------------------------------------------------------------- */
+#define HMM_SEGMENT_WALK_RUNNING  0            /* never left behind by a call */
+#define HMM_SEGMENT_WALK_DONE     1
+#define HMM_SEGMENT_WALK_FLAGGED  2
+#define HMM_SEGMENT_WALK_BOUND    3
+
+typedef struct {
+    double  start_time;
+    double  end_time;
+    int32_t first_frame;            /* frames first_frame .. last_frame have start_time <= t <= end_time; none: last_frame = first_frame - 1 */
+    int32_t last_frame;
+    int32_t cut_pair;               /* the pair whose score cut the window in step 3 (even if step 4 or 5 then moved the end), or -1 */
+    int32_t cut_window;             /* the window of step 4 that was silent, counted from the end of the step (0: the last), or -1 */
+    int32_t pairs_consulted;
+    int32_t windows_consulted;
+} hmm_segment_record;
+
+typedef struct {
+    int32_t n_segments;
+    int32_t status;                 /* HMM_SEGMENT_WALK_* */
+    int32_t flagged_pair;           /* the pair that stopped the walk (status _FLAGGED), else -1 */
+    int32_t steps;                  /* steps taken, the unfinished one of a _FLAGGED walk included */
+    double  current_start;
+} hmm_segment_walk_state;
+
+size_t hmm_segment_walk_workspace_bytes(int max_windows, int max_steps);
+int    hmm_segment_walk(const double* scores_dev, const int32_t* flags_dev, const double* times_dev, const double* times_host,
+                        int n_frames, const void* track_dev, int track_dtype, int64_t track_len, int sample_rate,
+                        double total_duration, double max_segment_duration, double min_segment_duration,
+                        double frame_similarity_threshold, double rms_cut, int silent_without_rms, int max_windows, int max_steps,
+                        hmm_segment_record* records_out_dev, hmm_segment_walk_state* state_out_dev, void* workspace_dev,
+                        size_t workspace_bytes, hmm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * cv2.resize of 8-bit frames to a target no larger than the source, as the reference shrinks every recalled frame
  * (hippomm/core/hippocampal_memory.py:2232, :2795: cv2.resize(frame, (320, 180))).  The arithmetic is OpenCV's 8-bit INTER_LINEAR,
  * restated from its published source (imgproc/src/resize.cpp); a build that routes 8-bit resize through another back end may differ.

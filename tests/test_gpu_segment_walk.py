@@ -1,0 +1,199 @@
+"""GPU: segment_sequence(walk="device") -- every adjacent pair scored into one device array, hmm_segment_walk over it and the resident
+track, one read-back -- gives the segments of walk="host": times bit for bit, the same frame lists, the same audio slices.
+
+One video of 48 gray-replicated 24 x 32 PNG frames at 1 fps, written once: scene A frames 0-9, B 10-16, C 17-35, two flat frames
+36-37, D 38-47.  With the defaults (10 s / 5 s / 0.95) the walk meets, in order: a cut at the window's last pair (10, 9); a cut deep
+in a window (17, 16); a window without a cut; a window whose last pair is two flat frames -- a NaN score, consulted, never cutting:
+the scan goes on to (36, 35), flat against scene, which scores 0.0 and cuts; a cut after 2 s that the minimum duration clamps to 5 s;
+a last partial segment.  Tracks are at most 64 000 samples at 1 kHz (500-sample windows), one at 20 kHz (10 000-sample windows: past
+numpy's 8192-element chunk)."""
+import re
+import struct
+import sys
+import types
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parent / "golden"))
+import segmentation_recipes as R  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+H, W, N = 24, 32, 48
+SCENES = [(0, 10, 901), (10, 17, 902), (17, 36, 903), (36, 38, None), (38, 48, 904)]
+VIDEO_ENDS = [10.0, 17.0, 27.0, 36.0, 41.0, 47.0]
+
+
+def _bits(x) -> bytes:
+    return struct.pack("<d", float(x))
+
+
+@pytest.fixture(scope="module")
+def video(tmp_path_factory):
+    from PIL import Image
+    from hippomm_amd.segmentation import FrameCache, PathScorer
+    folder = tmp_path_factory.mktemp("segment_walk")
+    paths = []
+    for lo, hi, scene in SCENES:
+        for i in range(lo, hi):
+            gray = np.full((H, W), 128, np.uint8) if scene is None else R.gray_frame(scene, i, H, W, noise=0.3, shift=0)
+            paths.append(str(folder / R.frame_name(i)))
+            Image.fromarray(R.bgr(gray)).save(paths[-1])
+    bad = str(folder / "unreadable.png")
+    Path(bad).write_bytes(b"not an image")
+    return types.SimpleNamespace(paths=paths, times=[float(i) for i in range(N)], bad=bad, scorer=PathScorer(FrameCache()))
+
+
+def _track_for(x, sr):
+    from hippomm_amd.audio_track import AudioTrack
+    return None if x is None else AudioTrack(x, sr)
+
+
+def both_routes(video, paths, times, audio=None, sr=None, **kw):
+    """-> (host segments, device segments, device stats), the two routes on the same scorer, cache and track."""
+    from hippomm_amd.segmentation import segment_sequence
+    track = _track_for(audio, sr)
+    scorer = video.scorer if paths else None
+    host = segment_sequence(paths, times, audio, sr, scorer=scorer, audio_track=track, walk="host", **kw)
+    stats = {}
+    dev = segment_sequence(paths, times, audio, sr, scorer=scorer, audio_track=track, walk="device", stats=stats, **kw)
+    return host, dev, stats
+
+
+def assert_same_segments(host, dev):
+    assert len(host) == len(dev) and len(host) > 0
+    for a, b in zip(host, dev):
+        assert _bits(a.start_time) == _bits(b.start_time) and _bits(a.end_time) == _bits(b.end_time), (a.start_time, a.end_time,
+                                                                                                         b.start_time, b.end_time)
+        assert a.frames == b.frames and a.frame_times == b.frame_times
+        assert (a.audio_data is None) == (b.audio_data is None)
+        if a.audio_data is not None:
+            assert a.audio_data.dtype == b.audio_data.dtype and a.audio_data.shape == b.audio_data.shape
+            assert a.audio_data.tobytes() == b.audio_data.tobytes()
+
+
+def loud(n, dtype, seed=3, amp=0.3):
+    return (amp * np.random.default_rng(seed).standard_normal(n)).astype(dtype)
+
+
+def test_scores_stay_on_the_device_and_are_the_hosts(video):
+    scores, problems = video.scorer.score_adjacent(video.paths, chunk=7)          # chunks that split scenes, 7 launches
+    assert scores.is_cuda and scores.dtype == torch.float64 and scores.shape == (N - 1,) and problems == [None] * (N - 1)
+    whole, _ = video.scorer.score_adjacent(video.paths)
+    want = np.array(list(video.scorer.score([(video.paths[i + 1], video.paths[i]) for i in range(N - 1)])))
+    got = scores.cpu().numpy()
+    assert got.tobytes() == want.tobytes() == whole.cpu().numpy().tobytes()
+    cuts = {9, 16, 35, 37}                                                         # (10, 9), (17, 16), (36, 35), (38, 37): new scenes
+    nan = {36}                                                                     # (37, 36): both frames flat, 0 / 0
+    for i, s in enumerate(got):
+        assert (np.isnan(s) if i in nan else s < 0.5 if i in cuts else s > 0.97), (i, s)
+
+
+def test_video_walk_meets_every_planted_window(video):
+    host, dev, stats = both_routes(video, video.paths, video.times)
+    assert_same_segments(host, dev)
+    assert [s.end_time for s in dev] == VIDEO_ENDS and [s.start_time for s in dev] == [0.0] + VIDEO_ENDS[:-1]
+    assert dev[0].frames == video.paths[0:11] and dev[3].frames == video.paths[27:37] and dev[5].frames == video.paths[41:48]
+    assert stats["route"] == "device" and stats["launches"] == 1 and stats["read_backs"] == 1 and stats["steps"] == 6
+    #                           (10,9)  20..17  27..18  37, 36  46..38  47..42
+    assert stats["pairs_consulted"] == 1 + 4 + 10 + 2 + 9 + 6 and stats["windows_consulted"] == 0
+    assert stats["pairs_scored"] == N - 1
+
+
+def test_method_form_reads_segment_walk(video):
+    from hippomm_amd.segmentation import _segment_sequence
+    me = types.SimpleNamespace(max_segment_duration=10.0, min_segment_duration=5.0, frame_similarity_threshold=0.95,
+                               audio_silence_threshold=-40, segment_walk="device")
+    assert [s.end_time for s in _segment_sequence(me, video.paths, video.times)] == VIDEO_ENDS
+    me.segment_walk = "host"
+    assert [s.end_time for s in _segment_sequence(me, video.paths, video.times)] == VIDEO_ENDS
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+def test_audio_overrides_video_and_short_tracks_give_empty_windows(video, dtype):
+    x = loud(47_000, dtype)
+    x[15_500:16_000] = 0.0                                         # silence at 15.5 s: overrides the video's cut at 17.0
+    host, dev, stats = both_routes(video, video.paths, video.times, x, 1000)
+    assert_same_segments(host, dev)
+    assert dev[1].start_time == 10.0 and dev[1].end_time == 15.5 and stats["windows_consulted"] > 19
+    assert stats["launches"] == 2 * (10 + 2) + 1 and stats["read_backs"] == 1
+    short = x[:30_200].copy()                                      # the track ends at 30.2 s: later windows are clipped or empty
+    short[21_234] = np.nan                                         # and one window holds a NaN: level -100, it cuts
+    host, dev, _ = both_routes(video, video.paths, video.times, short, 1000)
+    assert_same_segments(host, dev)
+    assert any(s.end_time == 21.0 for s in dev) and dev[-1].end_time == 47.0
+    host, dev, _ = both_routes(video, video.paths, video.times, short[:, None], 1000)      # (n, 1), as np.load of audio.npy gives it
+    assert_same_segments(host, dev)
+    fast = loud(64_000, dtype, seed=4)                             # 4 s at 16 kHz under the 47 s video: 8000-sample windows, 160 000
+    fast[24_000:32_000] = 0.0                                      # samples per step (the route's limits count windows, not samples)
+    host, dev, stats = both_routes(video, video.paths, video.times, fast, 16_000)
+    assert_same_segments(host, dev)
+    assert stats["route"] == "device" and dev[0].end_time == 9.5    # the window at 9.5 s lies past the track's end: empty, -100 dB
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+def test_a_level_equal_to_the_threshold_does_not_cut_and_one_just_below_does(dtype):
+    threshold = 20 * np.log10(2.0 ** -7)
+    x = np.full(30_000, 2.0 ** -7, dtype)                          # every window's level is the threshold exactly
+    host, dev, stats = both_routes(None, None, None, x, 1000, audio_silence_threshold=threshold)
+    assert_same_segments(host, dev)
+    if dtype is np.float64:
+        assert [s.end_time for s in dev] == [10.0, 20.0, 30.0]
+    assert stats["route"] == "device" and stats["pairs_consulted"] == 0
+    x[16_000:16_500] = 2.0 ** -7 * (1 - 2.0 ** -19)                # 1.7e-5 dB below it
+    host, dev, _ = both_routes(None, None, None, x, 1000, audio_silence_threshold=threshold)
+    assert_same_segments(host, dev)
+    if dtype is np.float64:                                        # (in float32 the host's own level at 2^-7 is libm's to round)
+        assert [s.end_time for s in dev] == [10.0, 16.0, 26.0, 30.0]
+
+
+def test_windows_longer_than_a_summation_chunk():
+    x = loud(64_000, np.float32, seed=8)                           # 3.2 s at 20 kHz
+    x[20_000:30_000] *= 0.01                                       # -50 dB from 1.0 s to 1.5 s
+    kw = dict(max_segment_duration=2.0, min_segment_duration=0.5)
+    host, dev, stats = both_routes(None, None, None, x, 20_000, **kw)
+    assert_same_segments(host, dev)
+    assert dev[0].end_time == 1.0 and dev[-1].end_time == 3.2 and stats["route"] == "device"
+    host, dev, _ = both_routes(None, None, None, x.astype(np.float64), 20_000, **kw)
+    assert_same_segments(host, dev)
+
+
+def test_unreadable_files_raise_only_where_consulted(video):
+    from hippomm_amd.segmentation import segment_sequence
+    paths = list(video.paths)
+    paths[13] = video.bad                                          # pairs (13, 12) and (14, 13): the walk cuts at (17, 16) first
+    host, dev, stats = both_routes(video, paths, video.times)
+    assert_same_segments(host, dev)
+    assert [s.end_time for s in dev] == VIDEO_ENDS and stats["pairs_scored"] == N - 3
+    paths = list(video.paths)
+    paths[19] = video.bad                                          # pair (20, 19) is the first one of the second window
+    errors = []
+    for walk in ("host", "device"):
+        with pytest.raises(OSError, match="unreadable.png") as info:
+            segment_sequence(paths, video.times, scorer=video.scorer, walk=walk)
+        errors.append(re.sub(r"0x[0-9a-f]+", "0x", str(info.value)))           # Pillow names its buffer object by address
+    assert errors[0] == errors[1] and video.bad in errors[0]
+
+
+def test_calls_the_device_does_not_take_go_the_host_route(video):
+    from hippomm_amd.segmentation import segment_sequence
+    times = list(video.times)
+    times[20], times[21] = times[21], times[20]
+    for kw, reason in ((dict(frame_times=times), "unsorted"), (dict(frame_times=video.times, min_segment_duration=0.0), "min_segment"),
+                       (dict(frame_times=video.times, max_segment_duration=float("nan")), "NaN")):
+        stats = {}
+        try:
+            dev = segment_sequence(video.paths, scorer=video.scorer, walk="device", stats=stats, **kw)
+            host = segment_sequence(video.paths, scorer=video.scorer, **kw)
+            assert_same_segments(host, dev)
+        except ValueError as exc:                                  # min_segment_duration = 0: the host route's own refusal
+            assert "no progress" in str(exc) and reason == "min_segment"
+        assert stats["route"] == "host" and reason in stats["reason"], stats
+    ints = np.zeros(20_000, np.int16)                              # a track that was not float at its source
+    stats = {}
+    from hippomm_amd.audio_track import AudioTrack
+    with pytest.raises(TypeError, match="float32 or float64 at its source"):
+        segment_sequence(None, None, ints, 1000, audio_track=AudioTrack(ints, 1000), walk="device", stats=stats)
+    assert stats["route"] == "host" and "source" in stats["reason"]
