@@ -77,6 +77,9 @@ _SIGNATURES = {
     "hmm_audio_gather_clips": (C.c_int, [c_ptr, C.c_int, C.c_int64, c_ptr, c_ptr, C.c_int, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, c_ptr, c_ptr, c_ptr]),
     "hmm_audio_window_sums": (C.c_int, [c_ptr, C.c_int, C.c_int64, c_ptr, c_ptr, C.c_int, c_ptr, c_ptr]),
+    "hmm_audio_pcm16_gather_clips": (C.c_int, [c_ptr, C.c_int64, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr,
+                                               c_ptr]),
+    "hmm_audio_pcm16_window_sums": (C.c_int, [c_ptr, C.c_int64, c_ptr, c_ptr, C.c_int, c_ptr, c_ptr]),
     "hmm_gray_u8": (C.c_int, [c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr, c_ptr]),
     "hmm_ssim_pairs_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "hmm_ssim_pairs": (C.c_int, [c_ptr, C.c_int, C.c_int, C.c_int, c_ptr, C.c_int, C.c_double, c_ptr, c_ptr, c_ptr,
@@ -89,6 +92,9 @@ _SIGNATURES = {
     "hmm_segment_walk": (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, c_ptr, C.c_int, C.c_int64, C.c_int, C.c_double, C.c_double,
                                    C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr, c_ptr, C.c_size_t,
                                    c_ptr]),
+    "hmm_segment_walk_pcm16": (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, c_ptr, C.c_int64, C.c_int, C.c_double, C.c_double,
+                                         C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr, c_ptr, C.c_size_t,
+                                         c_ptr]),
     "hmm_resize_linear_u8": (C.c_int, [c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr, C.c_int, C.c_int, c_ptr, c_ptr, c_ptr, c_ptr,
                                        C.c_int, c_ptr]),
     "hmm_jpeg_parse": (C.c_int, [c_ptr, C.c_size_t, c_ptr]),

@@ -21,6 +21,16 @@ comes before the spans exist: ``AudioTrack.window_levels`` takes the 500 ms wind
 
 and one read-back, and forms the levels on the host with numpy scalars of that dtype (``levels_from_sums``): the bits of the
 reference's expression on the host slices (tests/test_cpu_audio_levels_model.py, tests/test_gpu_audio_levels.py).
+
+``AudioTrack.from_wav`` / ``from_pcm16`` keep the 16-bit samples of the WAV the reference's extraction step wrote
+(batch_process.py:280-339) resident as they are, 2 bytes per sample instead of the 8 of ``np.load(audio.npy)``, and give every
+output above the bits of the float64 track ``x / 32768.0`` through three entry points of their own:
+
+    hmm_audio_pcm16_gather_clips   the gather with the loader (float)x * 2^-15 and without peaks (|x / 32768| <= 1: never scaled)
+    hmm_audio_pcm16_window_sums    the exact sum of (x / 32768)^2 of a window of at most 2^22 samples, which any order gives
+    hmm_segment_walk_pcm16         the device walk of segmentation.py over such a track
+
+(tests/test_cpu_audio_pcm.py, tests/test_gpu_audio_pcm.py).
 """
 from __future__ import annotations
 
@@ -121,6 +131,63 @@ def levels_from_sums(sums: np.ndarray, counts: Sequence[int]) -> list:
     return out
 
 
+PCM_WINDOW_MAX = 1 << 22                            # the longest window whose sum of squares is exact on a 16-bit track
+_PCM_SUBFORMAT_TAIL = bytes.fromhex("000000001000800000aa00389b71")           # KSDATAFORMAT_SUBTYPE_*: the GUID behind the tag
+
+
+def read_wav_pcm16(path) -> Tuple[int, np.ndarray]:
+    """A 16-bit PCM WAV file -> (sample_rate, samples): an int16 ``np.memmap`` of shape (n_frames, channels) over the file's
+    ``data`` chunk (a plain empty int16 array when it holds no frame: nothing can be mapped).  Pure host.
+
+    Its own RIFF walker: chunks it does not need (ffmpeg writes a ``LIST`` chunk before ``data``) are skipped, with the pad byte
+    after a chunk of odd size.  Format tag 1, or WAVE_FORMAT_EXTENSIBLE with the PCM sub-format, at 16 bits.  A ``data`` size of
+    0xFFFFFFFF (a streamed file) or one that reaches past the end of the file means "to the end of the file", whole frames only.
+    Everything else raises ``ValueError`` naming what was found: RF64, another sample width or format tag, a block align other
+    than 2 * channels, ``data`` before ``fmt ``, a file without ``data``."""
+    import struct
+    path = str(path)
+    with open(path, "rb") as f:
+        head = f.read(12)
+        size = f.seek(0, 2)
+        if len(head) < 12 or head[:4] not in (b"RIFF", b"RF64") or head[8:12] != b"WAVE":
+            raise ValueError(f"{path}: not a RIFF/WAVE file (it starts with {head[:12]!r})")
+        if head[:4] == b"RF64":
+            raise ValueError(f"{path}: RF64 files are not supported")
+        fmt, at = None, 12
+        while at + 8 <= size:
+            f.seek(at)
+            tag, n = struct.unpack("<4sI", f.read(8))
+            body = at + 8
+            if tag == b"fmt ":
+                raw = f.read(min(n, 40))
+                if n < 16 or len(raw) < 16:
+                    raise ValueError(f"{path}: a fmt chunk of {n} bytes")
+                code, channels, rate, _, align, bits = struct.unpack("<HHIIHH", raw[:16])
+                if code == 0xFFFE:                                            # WAVE_FORMAT_EXTENSIBLE: the tag is in the sub-format
+                    if len(raw) < 40 or raw[26:40] != _PCM_SUBFORMAT_TAIL:
+                        raise ValueError(f"{path}: WAVE_FORMAT_EXTENSIBLE with a fmt chunk of {n} bytes or an unknown sub-format")
+                    code = struct.unpack("<H", raw[24:26])[0]
+                fmt = (code, channels, rate, align, bits)
+            elif tag == b"data":
+                if fmt is None:
+                    raise ValueError(f"{path}: the data chunk comes before any fmt chunk")
+                code, channels, rate, align, bits = fmt
+                if code != 1:
+                    raise ValueError(f"{path}: format tag {code}" + (" (IEEE float)" if code == 3 else "") + ", only PCM (1) is supported")
+                if bits != 16:
+                    raise ValueError(f"{path}: {bits}-bit samples, only 16-bit PCM is supported")
+                if channels < 1 or align != 2 * channels:
+                    raise ValueError(f"{path}: block align {align} with {channels} channels, 16-bit PCM has 2 * channels")
+                if n == 0xFFFFFFFF or n > size - body:
+                    n = size - body                                           # to the end of the file
+                frames = n // align                                           # whole frames only
+                if frames == 0:
+                    return rate, np.empty((0, channels), dtype=np.int16)
+                return rate, np.memmap(path, dtype="<i2", mode="r", offset=body, shape=(frames, channels))
+            at = body + n + (n & 1)
+    raise ValueError(f"{path}: no data chunk" + ("" if fmt else " and no fmt chunk"))
+
+
 def _taps_device(orig: int, new: int, dev: torch.device) -> Tuple[torch.Tensor, int]:
     key = (orig, new, str(dev))
     if key not in _taps:
@@ -133,16 +200,15 @@ class AudioTrack:
     """A video's waveform on the device.  audio_data: what np.load of the reference's audio.npy yields -- float64 (n, 1) -- or
     (n,) / (n, C), float32 or float64 (any other dtype is cast with astype(np.float32) first).  C > 1 is mixed down once on the
     host with the reference's own expression, audio_data.mean(axis=1) (:1206; row-wise, so the whole track at once equals segment
-    by segment).  The track is uploaded in chunks through the package's pinned staging; the caller's array is not pinned."""
+    by segment).  The track is uploaded in chunks through the package's pinned staging; the caller's array is not pinned.
+
+    ``from_wav`` / ``from_pcm16`` build the track from the 16-bit samples of the extracted WAV instead and keep them resident as
+    int16 (``pcm`` is True): every method then answers with the bits of the float64 track ``x / 32768.0``."""
+
+    pcm = False                                     # True on a track of 16-bit samples (from_pcm16 / from_wav)
 
     def __init__(self, audio_data, sample_rate: int, device=None):
-        if device is not None and torch.device(device).type != "cuda":
-            raise ValueError(f"AudioTrack lives on a GPU, got device {device}")
-        self.device = _lib.require_gpu()
-        if device is not None and torch.device(device).index is not None:
-            self.device = torch.device(device)
-        self.sample_rate = int(sample_rate)
-        self.orig, self.new = rate_ratio(self.sample_rate)
+        self._open(sample_rate, device)
         if isinstance(audio_data, torch.Tensor):
             audio_data = audio_data.detach().cpu().numpy()
         x = np.asarray(audio_data)
@@ -156,10 +222,61 @@ class AudioTrack:
             raise ValueError(f"audio_data must be (n,) or (n, channels), got shape {x.shape}")
         self.n_samples = int(x.shape[0])
         self.dtype_code = 1 if x.dtype == np.float64 else 0
-        self.samples = self._upload(np.ascontiguousarray(x))
+        self.samples = self._upload(np.ascontiguousarray(x), torch.float64 if self.dtype_code else torch.float32)
 
-    def _upload(self, x: np.ndarray) -> torch.Tensor:
-        dev_track = torch.empty(x.shape[0], dtype=torch.float64 if self.dtype_code else torch.float32, device=self.device)
+    def _open(self, sample_rate: int, device) -> None:
+        if device is not None and torch.device(device).type != "cuda":
+            raise ValueError(f"AudioTrack lives on a GPU, got device {device}")
+        self.device = _lib.require_gpu()
+        if device is not None and torch.device(device).index is not None:
+            self.device = torch.device(device)
+        self.sample_rate = int(sample_rate)
+        self.orig, self.new = rate_ratio(self.sample_rate)
+
+    @classmethod
+    def from_pcm16(cls, samples, sample_rate: int, device=None) -> "AudioTrack":
+        """The track of 16-bit PCM samples x -- int16 (n,) or (n, 1); any other dtype raises ``TypeError`` -- with the values
+        sf.read gives them, x / 32768: in every output bit the track ``AudioTrack(x.astype(np.float64).reshape(-1, 1) / 32768.0,
+        sample_rate)``, what the reference's extraction step makes of its 16-bit WAV (batch_process.py:280-339), but resident as
+        int16: 2 bytes per sample read, staged and held instead of 8.  ``pcm`` is True, ``samples`` the int16 device tensor;
+        ``source_dtype`` / ``source_shape`` / ``dtype_code`` are those of the float64 (n, 1) array it stands for, and
+        ``as_float64`` returns slices of that array.  Why the bits agree: csrc/audio_track.hip, DESIGN.md section 14.
+
+        (n, C > 1): ``samples.astype(np.float64) / 32768.0`` goes to the ordinary constructor, which mixes it down on the host --
+        the same semantics without the compact layout (``pcm`` is False)."""
+        x = np.asarray(samples.detach().cpu().numpy() if isinstance(samples, torch.Tensor) else samples)
+        if x.dtype != np.int16:
+            raise TypeError(f"from_pcm16 takes int16 samples, got {x.dtype} (a float array goes to AudioTrack(...))")
+        if x.ndim not in (1, 2):
+            raise ValueError(f"samples must be (n,) or (n, channels), got shape {x.shape}")
+        if x.ndim == 2 and x.shape[1] != 1:
+            return cls(x.astype(np.float64) / 32768.0, sample_rate, device)
+        self = cls.__new__(cls)
+        self._open(sample_rate, device)
+        self.pcm = True
+        self.n_samples = int(x.shape[0])
+        self.source_dtype = np.dtype(np.float64)
+        self.source_shape = (self.n_samples, 1)
+        self.dtype_code = 1
+        self.samples = self._upload(np.ascontiguousarray(x.reshape(-1)), torch.int16)    # a memmap stays one: chunks are read as they go up
+        return self
+
+    @classmethod
+    def from_wav(cls, path, device=None) -> "AudioTrack":
+        """``from_pcm16`` of a 16-bit PCM WAV file (``read_wav_pcm16``) at the file's own rate: the file is mapped and goes up chunk
+        by chunk, without a full copy on the host."""
+        rate, samples = read_wav_pcm16(path)
+        return cls.from_pcm16(samples, rate, device)
+
+    def as_float64(self, start: int = 0, stop=None) -> np.ndarray:
+        """The host slice [start:stop] of the float64 (n, 1) array a PCM track stands for (a read-back and numpy's x / 32768.0),
+        for callers that still need a segment's ``audio_data``."""
+        if not self.pcm:
+            raise TypeError("as_float64 is for a track of 16-bit samples (from_pcm16 / from_wav)")
+        return self.samples[start:stop].cpu().numpy().astype(np.float64).reshape(-1, 1) / 32768.0
+
+    def _upload(self, x: np.ndarray, dtype: torch.dtype) -> torch.Tensor:
+        dev_track = torch.empty(x.shape[0], dtype=dtype, device=self.device)
         src, dst = x.view(np.uint8), dev_track.view(torch.uint8)
         with torch.cuda.device(self.device):
             for k, lo in enumerate(range(0, src.shape[0], UPLOAD_CHUNK_BYTES)):
@@ -182,6 +299,12 @@ class AudioTrack:
             return np.empty(0, dtype=np_dtype)
         with torch.cuda.device(self.device):
             table_dev = torch.from_numpy(table).to(self.device)
+            if self.pcm:                             # fp64 sums of (x / 32768)^2, exact: the float64 track's bits (a window above 2^22 is refused)
+                sums = torch.empty(table.shape[0], dtype=torch.float64, device=self.device)
+                _lib.check(lib.hmm_audio_pcm16_window_sums(self.samples.data_ptr(), self.n_samples, table.ctypes.data,
+                                                           table_dev.data_ptr(), table.shape[0], sums.data_ptr(), _lib.stream_ptr()),
+                           "hmm_audio_pcm16_window_sums")
+                return sums.cpu().numpy()
             sums = torch.empty(table.shape[0], dtype=self.samples.dtype, device=self.device)
             _lib.check(lib.hmm_audio_window_sums(self.samples.data_ptr(), self.dtype_code, self.n_samples, table.ctypes.data,
                                                  table_dev.data_ptr(), table.shape[0], sums.data_ptr(), _lib.stream_ptr()),
@@ -204,9 +327,15 @@ class AudioTrack:
 
     # ---- clips ------------------------------------------------------------------------------------------------------------
     def span_peaks(self, spans: np.ndarray) -> torch.Tensor:
-        """Clipped spans (S, 2) int64 -> (S,) fp32 on the device: max |x| of each span's narrowed samples (NaN if it holds one)."""
+        """Clipped spans (S, 2) int64 -> (S,) fp32 on the device: max |x| of each span's narrowed samples (NaN if it holds one).
+        On a 16-bit track: max |x / 32768|, at most 1.0."""
         lib = _lib.load()
         spans = np.ascontiguousarray(spans, dtype=np.int64)
+        if self.pcm:                                 # never above 1.0, so no clip needs it: plain torch on the slices, off every hot path
+            with torch.cuda.device(self.device):
+                peaks = [self.samples[a:b].to(torch.int32).abs().max().to(torch.float32) * 2.0 ** -15 if b > a
+                         else torch.zeros((), dtype=torch.float32, device=self.device) for a, b in spans.tolist()]
+                return torch.stack(peaks) if peaks else torch.empty(0, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             spans_dev = torch.from_numpy(spans).to(self.device)
             peaks = torch.empty(spans.shape[0], dtype=torch.float32, device=self.device)
@@ -222,13 +351,20 @@ class AudioTrack:
         clipped = clip_spans(spans, self.n_samples)
         if clipped.shape[0] == 0:
             return []
-        peaks = self.span_peaks(clipped)
+        peaks = None if self.pcm else self.span_peaks(clipped)                # a 16-bit track is never scaled: no peak pass
         out = []
         with torch.cuda.device(self.device):
             taps, width = (None, 0) if self.orig == self.new else _taps_device(self.orig, self.new, self.device)
             for length, (positions, table) in clip_tables(clipped, self.orig, self.new).items():
                 table_dev = torch.from_numpy(table).to(self.device)
                 clips = torch.empty(table.shape[0], length, dtype=torch.float32, device=self.device)
+                if self.pcm:
+                    _lib.check(lib.hmm_audio_pcm16_gather_clips(self.samples.data_ptr(), self.n_samples, table.ctypes.data,
+                                                                table_dev.data_ptr(), table.shape[0], length, self.orig, self.new,
+                                                                width, None if taps is None else taps.data_ptr(), clips.data_ptr(),
+                                                                _lib.stream_ptr()), "hmm_audio_pcm16_gather_clips")
+                    out.append((positions, clips))
+                    continue
                 _lib.check(lib.hmm_audio_gather_clips(self.samples.data_ptr(), self.dtype_code, self.n_samples, table.ctypes.data,
                                                       table_dev.data_ptr(), table.shape[0], peaks.data_ptr(), clipped.shape[0],
                                                       length, self.orig, self.new, width,

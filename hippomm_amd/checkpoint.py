@@ -264,7 +264,9 @@ def _waveform_piece(a, track, span, device, counts):
     resident = _resident_span(a, track, span)
     dev = track.device if resident else _device_of(a, device)
     with torch.cuda.device(dev), _device_lock:
-        if resident:
+        if resident and getattr(track, "pcm", False):                # int16 samples: x * 2^-15 in float64 is the array's value, exactly
+            m = track.samples[resident[0]:resident[1]].to(torch.float64).mul_(2.0 ** -15).view(-1, 1)
+        elif resident:
             m = track.samples[resident[0]:resident[1]].view(-1, 1)
         elif _cuda_tensor(a):
             m = a.detach().contiguous()

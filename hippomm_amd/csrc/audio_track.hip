@@ -32,7 +32,12 @@
 //            64 consecutive bytes, and no byte outside the window is read.  The order is a function of the window's length
 //            alone: not of the grid, the batch or the run.
 //
-// All three read their span / clip / window tables from the device and clamp what they find there to the track, so a device table
+//   16-bit   a track may also hold the int16 samples x of the extracted WAV, with the values sf.read gives them, x / 32768
+//            (hmm_audio_pcm16_gather_clips, hmm_audio_pcm16_window_sums; hmm_segment_walk_pcm16 in segment_walk.hip).  The gather
+//            gets a third loader, (float)x * 2^-15, and no peaks; the sums get a kernel of their own without the tree.  Both give
+//            the bits of the fp64 track of x / 32768.0: the arguments stand at gather_clips_kernel and pcm16_window_sums_kernel.
+//
+// All of them read their span / clip / window tables from the device and clamp what they find there to the track, so a device table
 // that disagrees with the host copy the entry point has checked reads and writes less, never elsewhere.  No scratch, vector stores
 // only.
 #include "audio_levels.h"
@@ -41,15 +46,22 @@ namespace hmm {
 
 typedef float at_f32x4 __attribute__((ext_vector_type(4)));
 typedef double at_f64x2 __attribute__((ext_vector_type(2)));
+typedef int16_t at_i16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kClipBlock = 256;                                               // output samples (= threads) per workgroup of the gather
+constexpr int kPcmCopyBlock = 8 * kClipBlock;                                 // ... of the copy from a 16-bit track: eight per thread
 
 __device__ __forceinline__ uint32_t abs_bits(float x) { return __float_as_uint(x) & 0x7FFFFFFFu; }
 __device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
+__device__ __forceinline__ float pcm16_float(int16_t x) { return (float)x * 0x1p-15f; }     // exact: sf.read's x / 32768, narrowed
 
-template <bool F64>
+// What a track holds: kF32 and kF64 are track_dtype 0 and 1 of the C ABI; kPcm16 is the layout of the hmm_audio_pcm16_* entry points.
+constexpr int kF32 = 0, kF64 = 1, kPcm16 = 2;
+
+template <int SRC>
 __device__ __forceinline__ float load_narrow(const void* __restrict__ track, int64_t i) {
-    if constexpr (F64) return (float)static_cast<const double*>(track)[i];    // v_cvt_f32_f64: round to nearest even
+    if constexpr (SRC == kF64) return (float)static_cast<const double*>(track)[i];      // v_cvt_f32_f64: round to nearest even
+    else if constexpr (SRC == kPcm16) return pcm16_float(static_cast<const int16_t*>(track)[i]);
     else return static_cast<const float*>(track)[i];
 }
 
@@ -94,25 +106,52 @@ __global__ __launch_bounds__(256) void span_peaks_kernel(const void* __restrict_
 }
 
 // clips: per clip (span start, span length, first output sample of the clip in the span's 16 kHz signal, span index).
-template <bool F64, bool RESAMPLE>
+// A 16-bit track (SRC == kPcm16) has no peaks: |x / 32768| <= 1 always (-32768 gives exactly 1.0, and 1.0f > 1.0f is false), so no
+// span is ever scaled; peaks is null, the span index of a clip row is not looked at, and the samples are (float)x * 2^-15 -- exact,
+// the float the fp64 track of x / 32768.0 narrows to -- so both instantiations give that track's bits.  Its copy case moves
+// kPcmCopyBlock samples per workgroup: the 16-byte groups of eight samples that lie whole inside the block's part of the clip
+// (the track is 16-byte aligned, a clip starts at any sample), elements before the first and behind the last of them, through
+// LDS, from where the floats leave in order.  Nothing outside [start + first, start + first + clip_len) is read.
+template <int SRC, bool RESAMPLE>
 __global__ __launch_bounds__(kClipBlock) void gather_clips_kernel(const void* __restrict__ track, int64_t track_len,
                                                                   const int64_t* __restrict__ clips, const float* __restrict__ peaks,
                                                                   int n_spans, int clip_len, int blocks_per_clip, int orig, int new_,
                                                                   int width, const float* __restrict__ taps, float* __restrict__ out) {
     extern __shared__ float window[];
+    constexpr bool PCM = SRC == kPcm16;
     const int tid = threadIdx.x;
-    const int c = blockIdx.x / blocks_per_clip, i0 = (blockIdx.x % blocks_per_clip) * kClipBlock;
+    const int c = blockIdx.x / blocks_per_clip, i0 = (blockIdx.x % blocks_per_clip) * (PCM && !RESAMPLE ? kPcmCopyBlock : kClipBlock);
     int64_t start = clips[4 * c], len = clips[4 * c + 1];
-    const int64_t first = clips[4 * c + 2], span = clips[4 * c + 3];
-    if (start < 0 || start > track_len || len < 0 || first < 0 || span < 0 || span >= n_spans) return;       // workgroup-uniform
+    const int64_t first = clips[4 * c + 2], span = PCM ? 0 : clips[4 * c + 3];
+    if (start < 0 || start > track_len || len < 0 || first < 0 || span < 0 || (!PCM && span >= n_spans)) return;   // workgroup-uniform
     if (len > track_len - start) len = track_len - start;
-    const float p = peaks[span];
+    float p = 0.0f;
+    if constexpr (!PCM) p = peaks[span];
     const bool scale = p > 1.0f;                                              // false for p == 1 and for a NaN peak
     const int i = i0 + tid;                                                   // sample of the clip
     float* dst = out + (int64_t)c * clip_len;
-    if constexpr (!RESAMPLE) {
+    if constexpr (!RESAMPLE && PCM) {
+        int64_t n = len - first;                                              // samples of the clip the span holds
+        if (n > clip_len) n = clip_len;
+        if (n <= i0) return;                                                  // workgroup-uniform
+        const int i1 = i0 + (int)(n - i0 < kPcmCopyBlock ? n - i0 : kPcmCopyBlock);                 // this workgroup: clip samples [i0, i1)
+        const int16_t* __restrict__ src = static_cast<const int16_t*>(track) + start + first;       // clip sample 0
+        int head = i1 - i0 < 8 ? i1 : i0 + (int)((8 - ((start + first + i0) & 7)) & 7);             // the first clip sample at a 16-byte boundary
+        if (head > i1) head = i1;
+        const int n_vec = (i1 - head) >> 3;                                   // at most kPcmCopyBlock / 8 = one per thread
+        const int tail = head + 8 * n_vec;
+        if (i0 + tid < head) window[tid] = pcm16_float(src[i0 + tid]);
+        if (tid < n_vec) {
+            const at_i16x8 v = reinterpret_cast<const at_i16x8*>(src + head)[tid];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) window[head - i0 + 8 * tid + k] = pcm16_float(v[k]);
+        }
+        if (tail + tid < i1) window[tail - i0 + tid] = pcm16_float(src[tail + tid]);
+        __syncthreads();
+        for (int k = tid; k < i1 - i0; k += kClipBlock) dst[i0 + k] = window[k];
+    } else if constexpr (!RESAMPLE) {
         if (i < clip_len && first + i < len) {
-            const float x = load_narrow<F64>(track, start + first + i);
+            const float x = load_narrow<SRC>(track, start + first + i);
             dst[i] = scale ? __fdiv_rn(x, p) : x;
         }
     } else {
@@ -125,7 +164,7 @@ __global__ __launch_bounds__(kClipBlock) void gather_clips_kernel(const void* __
             const int64_t xi = x0 + k;
             float x = 0.0f;                                                   // outside the span: zero, whatever the track holds there
             if (xi >= 0 && xi < len) {
-                x = load_narrow<F64>(track, start + xi);
+                x = load_narrow<SRC>(track, start + xi);
                 if (scale) x = __fdiv_rn(x, p);
             }
             window[k] = x;
@@ -243,6 +282,68 @@ void launch_window_sums(const void* track_dev, int track_dtype, int64_t track_le
                                                                   static_cast<float*>(sums_dev));
 }
 
+// The sums of a 16-bit track: sums[w] = the fp64 sum of (x / 32768)^2 over the window, the bits window_sums_kernel<double> gives on
+// the fp64 track of x / 32768.0 -- without its tree.  Why any order will do: x / 32768 is exact in fp64, and its square is the
+// integer x^2 <= 2^30 times 2^-30, exact as well.  Over a window of at most kPcmWindowMax = 2^22 samples every partial sum of such
+// squares, in any order, is an integer <= 2^52 times 2^-30: exactly representable, so no addition of numpy's pairwise sum ever
+// rounds, and its result is the exact sum.  Here that sum is taken in integers -- two squares fit 32 bits unsigned, the rest is
+// 64-bit -- and scaled by 2^-30 once: one rounding-free conversion.  One workgroup per window: 16-byte loads of eight samples over
+// the part of the window that is 16-byte aligned, element loads for the head and the tail (no byte outside the window is read), a
+// butterfly over the wave, four wave sums through LDS, one vector store.  A device table is clamped to the track and to 2^22.
+__device__ __forceinline__ uint64_t squares8(const int16_t* __restrict__ body, int64_t v) {
+    const at_i16x8 x = reinterpret_cast<const at_i16x8*>(body)[v];
+    uint64_t s = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k += 2) {
+        const int32_t a = x[k], b = x[k + 1];
+        s += (uint32_t)(a * a) + (uint32_t)(b * b);                           // at most 2^31: no carry is lost
+    }
+    return s;
+}
+
+__global__ __launch_bounds__(256) void pcm16_window_sums_kernel(const int16_t* __restrict__ track, int64_t track_len,
+                                                                const int64_t* __restrict__ windows, double* __restrict__ sums) {
+    __shared__ uint64_t part[4];
+    const int tid = threadIdx.x;
+    int64_t a = windows[2 * blockIdx.x], n = windows[2 * blockIdx.x + 1];
+    a = a < 0 ? 0 : (a > track_len ? track_len : a);
+    n = n < 0 ? 0 : (n > track_len - a ? track_len - a : n);
+    if (n > kPcmWindowMax) n = kPcmWindowMax;
+    const int64_t b = a + n;
+    int64_t body = (a + 7) / 8 * 8;                                           // the track is 16-byte aligned: so is element `body`
+    if (body > b) body = b;
+    const int64_t n_vec = (b - body) / 8;
+    uint64_t s = 0;
+    for (int64_t i = a + tid; i < body; i += 256) {
+        const int32_t x = track[i];
+        s += (uint32_t)(x * x);
+    }
+    int64_t v = tid;
+    for (; v + 768 < n_vec; v += 1024) {                                      // four loads in flight per lane
+        const uint64_t s0 = squares8(track + body, v), s1 = squares8(track + body, v + 256);
+        const uint64_t s2 = squares8(track + body, v + 512), s3 = squares8(track + body, v + 768);
+        s += (s0 + s1) + (s2 + s3);
+    }
+    for (; v < n_vec; v += 256) s += squares8(track + body, v);
+    for (int64_t i = body + n_vec * 8 + tid; i < b; i += 256) {
+        const int32_t x = track[i];
+        s += (uint32_t)(x * x);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)s, off, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(s >> 32), off, 64);
+        s += ((uint64_t)hi << 32) | lo;
+    }
+    if ((tid & 63) == 0) part[tid >> 6] = s;
+    __syncthreads();
+    if (tid == 0) sums[blockIdx.x] = (double)((part[0] + part[1]) + (part[2] + part[3])) * 0x1p-30;
+}
+
+void launch_pcm16_window_sums(const void* track_dev, int64_t track_len, const int64_t* windows_dev, int n_windows, double* sums_dev,
+                              hipStream_t stream) {
+    pcm16_window_sums_kernel<<<n_windows, 256, 0, stream>>>(static_cast<const int16_t*>(track_dev), track_len, windows_dev, sums_dev);
+}
+
 static bool track_overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
     const uint64_t x = (uint64_t)(uintptr_t)a, y = (uint64_t)(uintptr_t)b;
     return a_bytes != 0 && b_bytes != 0 && x < y + b_bytes && y < x + a_bytes;
@@ -320,15 +421,87 @@ extern "C" int hmm_audio_gather_clips(const void* track_dev, int track_dtype, in
     const unsigned grid = (unsigned)(blocks_per_clip * n_clips);
     const size_t lds = (size_t)win * 4;
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define HMM_GATHER(F64, RS)                                                                                                          \
-    gather_clips_kernel<F64, RS><<<grid, kClipBlock, lds, st>>>(track_dev, track_len, clips_dev, peaks_dev, n_spans, clip_len,       \
+#define HMM_GATHER(SRC, RS)                                                                                                          \
+    gather_clips_kernel<SRC, RS><<<grid, kClipBlock, lds, st>>>(track_dev, track_len, clips_dev, peaks_dev, n_spans, clip_len,       \
                                                                 blocks_per_clip, orig, new_, width, taps_dev, clips_out_dev)
     if (orig == new_) {
-        if (track_dtype == 1) HMM_GATHER(true, false); else HMM_GATHER(false, false);
+        if (track_dtype == 1) HMM_GATHER(kF64, false); else HMM_GATHER(kF32, false);
     } else {
-        if (track_dtype == 1) HMM_GATHER(true, true); else HMM_GATHER(false, true);
+        if (track_dtype == 1) HMM_GATHER(kF64, true); else HMM_GATHER(kF32, true);
     }
 #undef HMM_GATHER
+    HMM_LAUNCH_CHECK();
+    return HMM_OK;
+}
+
+extern "C" int hmm_audio_pcm16_gather_clips(const void* track_dev, int64_t track_len, const int64_t* clips_host, const int64_t* clips_dev,
+                                            int n_clips, int clip_len, int orig, int new_, int width, const float* taps_dev,
+                                            float* clips_out_dev, hmm_stream_t stream) {
+    HMM_REQUIRE(track_len >= 0 && n_clips >= 0 && clip_len >= 0 && width >= 0, HMM_E_INVALID,
+                "audio_pcm16_gather_clips: negative count (track_len=%lld, n_clips=%d, clip_len=%d, width=%d)", (long long)track_len,
+                n_clips, clip_len, width);
+    HMM_REQUIRE(orig >= 1 && new_ >= 1, HMM_E_INVALID, "audio_pcm16_gather_clips: orig and new must be at least 1, got %d and %d", orig,
+                new_);
+    if (n_clips == 0 || clip_len == 0) return HMM_OK;                         // nothing to write: no pointer is looked at
+    HMM_REQUIRE(track_dev && clips_host && clips_dev && clips_out_dev, HMM_E_INVALID, "audio_pcm16_gather_clips: null pointer");
+    HMM_REQUIRE(orig == new_ || taps_dev != nullptr, HMM_E_INVALID,
+                "audio_pcm16_gather_clips: taps must be given when orig != new (%d -> %d): null pointer", orig, new_);
+    HMM_REQUIRE(((uintptr_t)track_dev & 15) == 0 && ((uintptr_t)clips_dev & 7) == 0 && ((uintptr_t)taps_dev & 3) == 0 &&
+                    ((uintptr_t)clips_out_dev & 3) == 0, HMM_E_INVALID,
+                "audio_pcm16_gather_clips: the track must be 16-byte aligned, table, taps and clips aligned to their element size");
+    const int64_t win = orig == new_ ? kPcmCopyBlock : ((int64_t)((kClipBlock - 1) / new_ + 1) * orig + 2 * (int64_t)width + orig);
+    HMM_REQUIRE(win * 4 <= 65536, HMM_E_INVALID,
+                "audio_pcm16_gather_clips: resampling %d -> %d with width %d needs a window of %lld samples per workgroup, 16384 fit",
+                orig, new_, width, (long long)win);
+    for (int c = 0; c < n_clips; ++c) {
+        const int64_t a = clips_host[4 * c], len = clips_host[4 * c + 1], first = clips_host[4 * c + 2];
+        HMM_REQUIRE(a >= 0 && len >= 0 && a <= track_len && len <= track_len - a, HMM_E_INVALID,
+                    "audio_pcm16_gather_clips: clip %d: span [%lld, %lld + %lld) lies outside the track [0, %lld]", c, (long long)a,
+                    (long long)a, (long long)len, (long long)track_len);
+        const int64_t n_out = orig == new_ ? len : (len / orig * new_ + (len % orig * new_ + orig - 1) / orig);      // ceil(new len / orig)
+        HMM_REQUIRE(first >= 0 && first <= n_out && clip_len <= n_out - first, HMM_E_INVALID,
+                    "audio_pcm16_gather_clips: clip %d: samples [%lld, %lld + %d) reach past the span's output length %lld", c,
+                    (long long)first, (long long)first, clip_len, (long long)n_out);
+    }
+    HMM_REQUIRE(!track_overlap(track_dev, (uint64_t)track_len * 2, clips_out_dev, (uint64_t)n_clips * (uint64_t)clip_len * 4),
+                HMM_E_INVALID, "audio_pcm16_gather_clips: the output overlaps the track");
+    const int per_block = orig == new_ ? kPcmCopyBlock : kClipBlock;
+    const int blocks_per_clip = (int)(((int64_t)clip_len + per_block - 1) / per_block);
+    HMM_REQUIRE((int64_t)blocks_per_clip * n_clips <= 0x7FFFFFFF, HMM_E_INVALID,
+                "audio_pcm16_gather_clips: %d clips of %d samples exceed one launch", n_clips, clip_len);
+    const unsigned grid = (unsigned)(blocks_per_clip * n_clips);
+    const size_t lds = (size_t)win * 4;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (orig == new_)
+        gather_clips_kernel<kPcm16, false><<<grid, kClipBlock, lds, st>>>(track_dev, track_len, clips_dev, nullptr, 0, clip_len,
+                                                                           blocks_per_clip, orig, new_, width, taps_dev, clips_out_dev);
+    else
+        gather_clips_kernel<kPcm16, true><<<grid, kClipBlock, lds, st>>>(track_dev, track_len, clips_dev, nullptr, 0, clip_len,
+                                                                          blocks_per_clip, orig, new_, width, taps_dev, clips_out_dev);
+    HMM_LAUNCH_CHECK();
+    return HMM_OK;
+}
+
+extern "C" int hmm_audio_pcm16_window_sums(const void* track_dev, int64_t track_len, const int64_t* windows_host,
+                                           const int64_t* windows_dev, int n_windows, double* sums_out_dev, hmm_stream_t stream) {
+    HMM_REQUIRE(track_len >= 0 && n_windows >= 0, HMM_E_INVALID, "audio_pcm16_window_sums: negative count (track_len=%lld, n_windows=%d)",
+                (long long)track_len, n_windows);
+    if (n_windows == 0) return HMM_OK;                                        // nothing to write: no pointer is looked at
+    HMM_REQUIRE(track_dev && windows_host && windows_dev && sums_out_dev, HMM_E_INVALID, "audio_pcm16_window_sums: null pointer");
+    HMM_REQUIRE(((uintptr_t)track_dev & 15) == 0 && ((uintptr_t)windows_dev & 7) == 0 && ((uintptr_t)sums_out_dev & 7) == 0, HMM_E_INVALID,
+                "audio_pcm16_window_sums: the track must be 16-byte aligned, the table and the sums aligned to their element size");
+    for (int w = 0; w < n_windows; ++w) {
+        const int64_t a = windows_host[2 * w], len = windows_host[2 * w + 1];
+        HMM_REQUIRE(a >= 0 && len >= 0 && a <= track_len && len <= track_len - a, HMM_E_INVALID,
+                    "audio_pcm16_window_sums: window %d = [%lld, %lld + %lld) lies outside the track [0, %lld]", w, (long long)a,
+                    (long long)a, (long long)len, (long long)track_len);
+        HMM_REQUIRE(len <= kPcmWindowMax, HMM_E_INVALID,
+                    "audio_pcm16_window_sums: window %d is %lld samples long, above 4194304 (2^22) the sum is no longer exact", w,
+                    (long long)len);
+    }
+    HMM_REQUIRE(!track_overlap(track_dev, (uint64_t)track_len * 2, sums_out_dev, (uint64_t)n_windows * 8), HMM_E_INVALID,
+                "audio_pcm16_window_sums: the output overlaps the track");
+    launch_pcm16_window_sums(track_dev, track_len, windows_dev, n_windows, sums_out_dev, static_cast<hipStream_t>(stream));
     HMM_LAUNCH_CHECK();
     return HMM_OK;
 }

@@ -10,6 +10,8 @@
 //                memory.  So: one planning launch writes the table of step 0; then per step one launch of that kernel over
 //                max_windows table rows and one decide launch, which takes the step and writes the table of the next one.  Rows
 //                past the step's windows, and every row once the walk has ended, have length 0: such a workgroup reads nothing.
+//                A track of int16 samples (hmm_segment_walk_pcm16) takes pcm16_window_sums_kernel there instead: fp64 sums, exact,
+//                the bits the fp64 track of x / 32768.0 gives, so everything behind the sums is the fp64 walk unchanged.
 // The arithmetic on times is fp64, operation by operation the reference's Python floats (contraction is off in this file).  The level
 // of a window never becomes dB here: the caller passes rms_cut, the least rms whose level under the caller's own log10 is not below
 // the silence threshold, and the comparison is made on the rms.  Frame indices come from device memory (times_dev) by binary
@@ -231,47 +233,64 @@ extern "C" size_t hmm_segment_walk_workspace_bytes(int max_windows, int max_step
     return walk_table_bytes(max_windows) + align_up((size_t)max_windows * sizeof(double), 256);
 }
 
-extern "C" int hmm_segment_walk(const double* scores_dev, const int32_t* flags_dev, const double* times_dev, const double* times_host,
-                                int n_frames, const void* track_dev, int track_dtype, int64_t track_len, int sample_rate,
-                                double total_duration, double max_segment_duration, double min_segment_duration,
-                                double frame_similarity_threshold, double rms_cut, int silent_without_rms, int max_windows,
-                                int max_steps, hmm_segment_record* records_out_dev, hmm_segment_walk_state* state_out_dev,
-                                void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream) {
+// Both entry points.  who: the name the refusals carry.  pcm16: the track holds int16 samples (track_dtype is then not looked at); its
+// sums are fp64 -- exact, the bits of the fp64 track of x / 32768.0 (audio_track.hip) -- so mean and rms are formed as for fp64.
+#define WALK_REQUIRE(cond, code, fmt, ...) HMM_REQUIRE(cond, code, "%s: " fmt, who, ##__VA_ARGS__)
+
+static int segment_walk(const char* who, bool pcm16, const double* scores_dev, const int32_t* flags_dev, const double* times_dev,
+                        const double* times_host, int n_frames, const void* track_dev, int track_dtype, int64_t track_len,
+                        int sample_rate, double total_duration, double max_segment_duration, double min_segment_duration,
+                        double frame_similarity_threshold, double rms_cut, int silent_without_rms, int max_windows, int max_steps,
+                        hmm_segment_record* records_out_dev, hmm_segment_walk_state* state_out_dev, void* workspace_dev,
+                        size_t workspace_bytes, hmm_stream_t stream) {
     const bool has_audio = track_dev != nullptr;
-    HMM_REQUIRE(records_out_dev && state_out_dev, HMM_E_INVALID, "segment_walk: null pointer (records or state)");
-    HMM_REQUIRE(n_frames >= 0, HMM_E_INVALID, "segment_walk: n_frames=%d is negative", n_frames);
-    HMM_REQUIRE(n_frames == 0 || (times_dev && times_host), HMM_E_INVALID, "segment_walk: null pointer (times of %d frames)", n_frames);
-    HMM_REQUIRE(n_frames <= 1 || (scores_dev && flags_dev), HMM_E_INVALID, "segment_walk: null pointer (scores or flags of %d pairs)",
+    WALK_REQUIRE(records_out_dev && state_out_dev, HMM_E_INVALID, "null pointer (records or state)");
+    WALK_REQUIRE(n_frames >= 0, HMM_E_INVALID, "n_frames=%d is negative", n_frames);
+    WALK_REQUIRE(n_frames == 0 || (times_dev && times_host), HMM_E_INVALID, "null pointer (times of %d frames)", n_frames);
+    WALK_REQUIRE(n_frames <= 1 || (scores_dev && flags_dev), HMM_E_INVALID, "null pointer (scores or flags of %d pairs)",
                 n_frames - 1);
-    HMM_REQUIRE(!has_audio || workspace_dev, HMM_E_INVALID, "segment_walk: null pointer (workspace of a walk with audio)");
-    HMM_REQUIRE(std::isfinite(total_duration) && std::isfinite(max_segment_duration) && std::isfinite(min_segment_duration),
-                HMM_E_INVALID, "segment_walk: total_duration, max_segment_duration or min_segment_duration is not finite");
-    HMM_REQUIRE(frame_similarity_threshold == frame_similarity_threshold && rms_cut == rms_cut, HMM_E_INVALID,
-                "segment_walk: frame_similarity_threshold or rms_cut is NaN");
-    HMM_REQUIRE(min_segment_duration > 0.0, HMM_E_INVALID, "segment_walk: min_segment_duration=%g must be positive (the walk would not end)",
+    WALK_REQUIRE(!has_audio || workspace_dev, HMM_E_INVALID, "null pointer (workspace of a walk with audio)");
+    WALK_REQUIRE(std::isfinite(total_duration) && std::isfinite(max_segment_duration) && std::isfinite(min_segment_duration),
+                HMM_E_INVALID, "total_duration, max_segment_duration or min_segment_duration is not finite");
+    WALK_REQUIRE(frame_similarity_threshold == frame_similarity_threshold && rms_cut == rms_cut, HMM_E_INVALID,
+                "frame_similarity_threshold or rms_cut is NaN");
+    WALK_REQUIRE(min_segment_duration > 0.0, HMM_E_INVALID, "min_segment_duration=%g must be positive (the walk would not end)",
                 min_segment_duration);
-    HMM_REQUIRE(max_steps >= 1 && max_windows >= 0, HMM_E_INVALID, "segment_walk: max_steps=%d, max_windows=%d: need max_steps >= 1 and "
+    WALK_REQUIRE(max_steps >= 1 && max_windows >= 0, HMM_E_INVALID, "max_steps=%d, max_windows=%d: need max_steps >= 1 and "
                 "max_windows >= 0", max_steps, max_windows);
     for (int i = 0; i < n_frames; ++i) {
-        HMM_REQUIRE(std::isfinite(times_host[i]), HMM_E_INVALID, "segment_walk: time of frame %d is not finite", i);
-        HMM_REQUIRE(i == 0 || times_host[i - 1] <= times_host[i], HMM_E_INVALID,
-                    "segment_walk: frame times are unsorted: frame %d at %.17g follows %.17g", i, times_host[i], times_host[i - 1]);
+        WALK_REQUIRE(std::isfinite(times_host[i]), HMM_E_INVALID, "time of frame %d is not finite", i);
+        WALK_REQUIRE(i == 0 || times_host[i - 1] <= times_host[i], HMM_E_INVALID,
+                    "frame times are unsorted: frame %d at %.17g follows %.17g", i, times_host[i], times_host[i - 1]);
     }
     if (has_audio) {
-        HMM_REQUIRE(track_dtype == 0 || track_dtype == 1, HMM_E_INVALID, "segment_walk: track_dtype must be 0 (fp32) or 1 (fp64), got %d",
-                    track_dtype);
-        HMM_REQUIRE(track_len >= 0 && sample_rate >= 2 && max_windows >= 1, HMM_E_INVALID,
-                    "segment_walk: audio needs track_len >= 0, sample_rate >= 2 and max_windows >= 1 (track_len=%lld, sample_rate=%d, "
+        WALK_REQUIRE(pcm16 || track_dtype == 0 || track_dtype == 1, HMM_E_INVALID, "track_dtype must be 0 (fp32) or 1 (fp64), got %d",
+                     track_dtype);
+        WALK_REQUIRE(!pcm16 || (int64_t)(0.5 * (double)sample_rate) <= kPcmWindowMax, HMM_E_INVALID,
+                     "a window of 0.5 * sample_rate = %lld samples is above 4194304 (2^22): its sum is no longer exact",
+                     (long long)(0.5 * (double)sample_rate));
+        WALK_REQUIRE(track_len >= 0 && sample_rate >= 2 && max_windows >= 1, HMM_E_INVALID,
+                    "audio needs track_len >= 0, sample_rate >= 2 and max_windows >= 1 (track_len=%lld, sample_rate=%d, "
                     "max_windows=%d)", (long long)track_len, sample_rate, max_windows);
-        HMM_REQUIRE(total_duration * (double)sample_rate < 4503599627370496.0, HMM_E_INVALID,
-                    "segment_walk: total_duration * sample_rate = %g does not stay below 2^52 samples", total_duration * (double)sample_rate);
+        WALK_REQUIRE(total_duration * (double)sample_rate < 4503599627370496.0, HMM_E_INVALID,
+                    "total_duration * sample_rate = %g does not stay below 2^52 samples", total_duration * (double)sample_rate);
     }
-    HMM_REQUIRE(((uintptr_t)records_out_dev & 7) == 0 && ((uintptr_t)state_out_dev & 7) == 0 && ((uintptr_t)workspace_dev & 7) == 0 &&
+    WALK_REQUIRE(((uintptr_t)records_out_dev & 7) == 0 && ((uintptr_t)state_out_dev & 7) == 0 && ((uintptr_t)workspace_dev & 7) == 0 &&
                     ((uintptr_t)scores_dev & 7) == 0 && ((uintptr_t)times_dev & 7) == 0 && ((uintptr_t)flags_dev & 3) == 0 &&
                     ((uintptr_t)track_dev & 15) == 0, HMM_E_INVALID,
-                "segment_walk: misaligned pointer (records, state, workspace, scores and times 8-byte aligned, flags 4, the track 16)");
+                "misaligned pointer (records, state, workspace, scores and times 8-byte aligned, flags 4, the track 16)");
     const size_t need = has_audio ? hmm_segment_walk_workspace_bytes(max_windows, max_steps) : 0;
-    HMM_REQUIRE(workspace_bytes >= need, HMM_E_WORKSPACE, "segment_walk: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    WALK_REQUIRE(workspace_bytes >= need, HMM_E_WORKSPACE, "workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    if (pcm16 && has_audio) {                                                // what the call writes may not lie in the track's bytes
+        const uint64_t t0 = (uint64_t)(uintptr_t)track_dev, t1 = t0 + (uint64_t)track_len * 2;
+        const auto inside = [&](const void* p, uint64_t bytes) {
+            const uint64_t q = (uint64_t)(uintptr_t)p;
+            return bytes != 0 && t1 > t0 && q < t1 && t0 < q + bytes;
+        };
+        WALK_REQUIRE(!inside(records_out_dev, (uint64_t)max_steps * sizeof(hmm_segment_record)) &&
+                         !inside(state_out_dev, sizeof(hmm_segment_walk_state)) && !inside(workspace_dev, need),
+                     HMM_E_INVALID, "the records, the state or the workspace overlaps the track");
+    }
 
     WalkArgs a;
     a.scores = scores_dev;
@@ -279,7 +298,7 @@ extern "C" int hmm_segment_walk(const double* scores_dev, const int32_t* flags_d
     a.times = times_dev;
     a.n_frames = n_frames;
     a.has_audio = has_audio ? 1 : 0;
-    a.track_f64 = track_dtype == 1;
+    a.track_f64 = pcm16 || track_dtype == 1;
     a.track_len = track_len;
     a.sample_rate = sample_rate;
     a.window = (int64_t)(0.5 * (double)sample_rate);                         // int(0.5 * audio_sample_rate)
@@ -302,10 +321,34 @@ extern "C" int hmm_segment_walk(const double* scores_dev, const int32_t* flags_d
     segment_walk_plan_kernel<<<1, kWalkThreads, 0, st>>>(a, state_out_dev, table);
     HMM_LAUNCH_CHECK();
     for (int step = 0; step < max_steps; ++step) {
-        launch_window_sums(track_dev, track_dtype, track_len, table, max_windows, sums, st);
+        if (pcm16) launch_pcm16_window_sums(track_dev, track_len, table, max_windows, static_cast<double*>(sums), st);
+        else launch_window_sums(track_dev, track_dtype, track_len, table, max_windows, sums, st);
         HMM_LAUNCH_CHECK();
         segment_walk_decide_kernel<<<1, kWalkThreads, 0, st>>>(a, state_out_dev, records_out_dev, table, sums, step == max_steps - 1);
         HMM_LAUNCH_CHECK();
     }
     return HMM_OK;
+}
+#undef WALK_REQUIRE
+
+extern "C" int hmm_segment_walk(const double* scores_dev, const int32_t* flags_dev, const double* times_dev, const double* times_host,
+                                int n_frames, const void* track_dev, int track_dtype, int64_t track_len, int sample_rate,
+                                double total_duration, double max_segment_duration, double min_segment_duration,
+                                double frame_similarity_threshold, double rms_cut, int silent_without_rms, int max_windows,
+                                int max_steps, hmm_segment_record* records_out_dev, hmm_segment_walk_state* state_out_dev,
+                                void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream) {
+    return segment_walk("segment_walk", false, scores_dev, flags_dev, times_dev, times_host, n_frames, track_dev, track_dtype, track_len,
+                        sample_rate, total_duration, max_segment_duration, min_segment_duration, frame_similarity_threshold, rms_cut,
+                        silent_without_rms, max_windows, max_steps, records_out_dev, state_out_dev, workspace_dev, workspace_bytes, stream);
+}
+
+extern "C" int hmm_segment_walk_pcm16(const double* scores_dev, const int32_t* flags_dev, const double* times_dev,
+                                      const double* times_host, int n_frames, const void* track_dev, int64_t track_len, int sample_rate,
+                                      double total_duration, double max_segment_duration, double min_segment_duration,
+                                      double frame_similarity_threshold, double rms_cut, int silent_without_rms, int max_windows,
+                                      int max_steps, hmm_segment_record* records_out_dev, hmm_segment_walk_state* state_out_dev,
+                                      void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream) {
+    return segment_walk("segment_walk_pcm16", true, scores_dev, flags_dev, times_dev, times_host, n_frames, track_dev, 1, track_len,
+                        sample_rate, total_duration, max_segment_duration, min_segment_duration, frame_similarity_threshold, rms_cut,
+                        silent_without_rms, max_windows, max_steps, records_out_dev, state_out_dev, workspace_dev, workspace_bytes, stream);
 }

@@ -803,6 +803,8 @@ def _device_walk(video_frames, frame_times, audio_data, audio_sample_rate, max_s
         return "duration out of range"
     span = min(max_segment_duration, max(total, 0.0))                          # no step is longer, up to rounding
     window = int(0.5 * rate)
+    if has_audio and getattr(audio_track, "pcm", False) and window > (1 << 22):
+        return "a window above 2^22 samples on a 16-bit track"
     if not total / min_segment_duration < MAX_DEVICE_STEPS or (has_audio and not span * rate / window < MAX_DEVICE_WINDOWS):
         return "more steps or windows than the device route launches"
     max_steps = max(int(np.ceil(total / min_segment_duration)), 0) + 2         # a clamped step advances by min, or reaches the end
@@ -823,13 +825,15 @@ def _device_walk(video_frames, frame_times, audio_data, audio_sample_rate, max_s
         ws = torch.empty(max(lib.hmm_segment_walk_workspace_bytes(max_windows, max_steps), 256), dtype=torch.uint8, device=dev)
         out = torch.empty(max_steps * SEGMENT_RECORD.itemsize + SEGMENT_STATE.itemsize, dtype=torch.uint8, device=dev)
         ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None   # noqa: E731
-        _lib.check(lib.hmm_segment_walk(ptr(scores), ptr(flags), ptr(times_dev), times.ctypes.data if has_video else None,
-                                        len(times), audio_track.samples.data_ptr() if has_audio else None,
-                                        audio_track.dtype_code if has_audio else 0, audio_track.n_samples if has_audio else 0, rate,
-                                        float(total), float(max_segment_duration), float(min_segment_duration),
-                                        float(frame_similarity_threshold), rms_cut, int(silent_without_rms), max_windows, max_steps,
-                                        out.data_ptr(), out.data_ptr() + max_steps * SEGMENT_RECORD.itemsize, ws.data_ptr(),
-                                        ws.numel(), _lib.stream_ptr()), "hmm_segment_walk")
+        head = (ptr(scores), ptr(flags), ptr(times_dev), times.ctypes.data if has_video else None, len(times),
+                audio_track.samples.data_ptr() if has_audio else None)
+        rest = (audio_track.n_samples if has_audio else 0, rate, float(total), float(max_segment_duration), float(min_segment_duration),
+                float(frame_similarity_threshold), rms_cut, int(silent_without_rms), max_windows, max_steps, out.data_ptr(),
+                out.data_ptr() + max_steps * SEGMENT_RECORD.itemsize, ws.data_ptr(), ws.numel(), _lib.stream_ptr())
+        if has_audio and getattr(audio_track, "pcm", False):                   # int16 samples: the entry point without a track_dtype
+            _lib.check(lib.hmm_segment_walk_pcm16(*head, *rest), "hmm_segment_walk_pcm16")
+        else:
+            _lib.check(lib.hmm_segment_walk(*head, audio_track.dtype_code if has_audio else 0, *rest), "hmm_segment_walk")
         host = out.cpu().numpy()                                               # the one read-back
     state = host[max_steps * SEGMENT_RECORD.itemsize:].view(SEGMENT_STATE)[0]
     records = host[:int(state["n_segments"]) * SEGMENT_RECORD.itemsize].view(SEGMENT_RECORD)
@@ -873,7 +877,8 @@ def segment_sequence(video_frames: Optional[List[str]] = None, frame_times: Opti
     is audio (``ValueError``).  It scores every pair, the host route only the consulted ones: with frames that are not in the
     cache yet it decodes them all.  A pair that cannot be scored raises its error only if the walk consults it, as on the host
     route.  Calls it does not take go the host route and say why in ``stats["reason"]``: unsorted or non-float frame_times, NaN
-    parameters, min_segment_duration <= 0, a track that was not float32 / float64 at its source, more steps than
+    parameters, min_segment_duration <= 0, a track that was not float32 / float64 at its source (a 16-bit track of
+    ``AudioTrack.from_wav`` / ``from_pcm16`` stands for a float64 array and is walked by ``hmm_segment_walk_pcm16``), more steps than
     MAX_DEVICE_STEPS, a walk that did not finish within its step bound.  Measured on one MI355X with every input resident (600
     cached 1080p frames, a 600 s float64 track at 16 kHz, 80 segments; profiles/segment_walk.json): 9.4 ms
     against 31.3 ms for the host walk, 1 read-back against 226; uncached frames and other inputs were not measured.

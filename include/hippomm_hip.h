@@ -535,6 +535,33 @@ int hmm_audio_window_sums(const void* track_dev, int track_dtype, int64_t track_
                           const int64_t* windows_dev, int n_windows, void* sums_out_dev, hmm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The same track as the 16-bit samples of the extracted WAV (ffmpeg's 16 kHz mono pcm_s16le file, hippomm/core/batch_process.py:280-339):
+ * track_dev holds track_len int16 samples, 16-byte aligned, 2 bytes per sample where the fp64 track of np.load(audio.npy) holds 8.
+ * The value of sample x is x / 32768 -- what sf.read makes of such a file (libsndfile pcm.c, default normalisation) -- and every
+ * output below carries, bit for bit, what the entry point above gives on the fp64 track (double)x / 32768.0 (track_dtype 1):
+ *   - x / 32768 is exact in fp64 and has at most 16 significant bits, so narrowing it to fp32 is exact too: (float)x * 2^-15;
+ *   - |x / 32768| <= 1 (-32768 gives exactly 1.0 and 1.0f > 1.0f is false): no span is ever scaled, there is no peak pass;
+ *   - a square is an integer <= 2^30 times 2^-30, so over a window of at most 2^22 samples every partial sum, in any order, is an
+ *     integer <= 2^52 times 2^-30 -- exactly representable: numpy's pairwise sum never rounds, and any order gives its bits.
+ * Tables are given twice as above (host copy checked, device copy read by the kernel and clamped to the track).
+ *
+ * hmm_audio_pcm16_gather_clips: hmm_audio_gather_clips without peaks.  clips: n_clips x (span start, span length, first output
+ *   sample, span index) int64 -- the same table; the span index is not looked at.  orig == new: clips_out_dev[c][i] = sample
+ *   first + i of the span as (float)x * 2^-15; 16-byte loads of eight samples where the clip's samples fill an aligned group,
+ *   element loads before and behind; nothing outside the clip's samples is read.  Otherwise the resampling above on those floats:
+ *   the same window, the same order of fused multiply-adds, the same bits.  The same refusals (no track_dtype, no peaks); the
+ *   output may not overlap the track's 2 * track_len bytes.
+ * hmm_audio_pcm16_window_sums: sums_out_dev[w] fp64 = sum of (x / 32768)^2 over window w, exact (accumulated in integers, scaled by
+ *   2^-30 once); 0 for an empty window.  A host window longer than 2^22 samples is HMM_E_INVALID before anything is launched; the
+ *   device copy is clamped to that length as well.  Otherwise the refusals of hmm_audio_window_sums.
+ * ---------------------------------------------------------------------------------------- */
+int hmm_audio_pcm16_gather_clips(const void* track_dev, int64_t track_len, const int64_t* clips_host, const int64_t* clips_dev,
+                                 int n_clips, int clip_len, int orig, int new_, int width, const float* taps_dev,
+                                 float* clips_out_dev, hmm_stream_t stream);
+int hmm_audio_pcm16_window_sums(const void* track_dev, int64_t track_len, const int64_t* windows_host, const int64_t* windows_dev,
+                                int n_windows, double* sums_out_dev, hmm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Frame SSIM (structural similarity) for sequence segmentation and frame differences.  Replaces skimage 0.18.3
  * structural_similarity as hippomm/core/hippocampal_memory.py:980-991 (_compute_frame_similarity, consulted by
  * _segment_sequence :1002-1114) and hippomm/core/batch_process.py:32-69 (compute_frame_difference) call it on gray frames.
@@ -686,6 +713,16 @@ int    hmm_segment_walk(const double* scores_dev, const int32_t* flags_dev, cons
                         double frame_similarity_threshold, double rms_cut, int silent_without_rms, int max_windows, int max_steps,
                         hmm_segment_record* records_out_dev, hmm_segment_walk_state* state_out_dev, void* workspace_dev,
                         size_t workspace_bytes, hmm_stream_t stream);
+/* hmm_segment_walk_pcm16: hmm_segment_walk over the 16-bit track of hmm_audio_pcm16_window_sums (track_dev int16, no track_dtype): the
+ *   same walk, one implementation; a window's sum is that entry point's (fp64, exact), mean and rms are formed as for an fp64 track, so
+ *   rms_cut is the fp64 one.  The same workspace size, launches and refusals, and two more: window = (int64)(0.5 * sample_rate)
+ *   above 2^22, and records, state or workspace overlapping the track's bytes. */
+int    hmm_segment_walk_pcm16(const double* scores_dev, const int32_t* flags_dev, const double* times_dev, const double* times_host,
+                              int n_frames, const void* track_dev, int64_t track_len, int sample_rate, double total_duration,
+                              double max_segment_duration, double min_segment_duration, double frame_similarity_threshold,
+                              double rms_cut, int silent_without_rms, int max_windows, int max_steps,
+                              hmm_segment_record* records_out_dev, hmm_segment_walk_state* state_out_dev, void* workspace_dev,
+                              size_t workspace_bytes, hmm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * cv2.resize of 8-bit frames to a target no larger than the source, as the reference shrinks every recalled frame
