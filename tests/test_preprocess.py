@@ -309,3 +309,66 @@ def test_decode_workers_share_the_quota_among_the_ranks_of_a_node(monkeypatch):
     assert pp.decode_workers() == 2
     monkeypatch.setenv("LOCAL_WORLD_SIZE", "2")
     assert pp.decode_workers() == 6
+
+
+# ---- frames on which clip8 is not the identity where the resize shrinks -----------------------------------------------------------
+BLOCK_SIZES = [(1080, 1920), (2160, 3840)]                         # 21 and 41 taps a side
+
+
+def _block_frame(h, w, phase=0):
+    """A 0 / 255 checkerboard of square blocks of about 2.5 output pixels (12 source pixels at 1080p, 24 at 2160p): every edge
+    makes the bicubic taps over- and undershoot, in the horizontal pass and again in the vertical pass over its clipped rows."""
+    blk = int(2.5 * h / 224)
+    yy, xx = np.mgrid[:h, :w]
+    board = ((((yy + phase) // blk + (xx + 2 * phase) // blk) & 1) * 255).astype(np.uint8)
+    return np.ascontiguousarray(np.repeat(board[..., None], 3, -1))
+
+
+def _two_pass_clip_counts(img, kh, bh, kv, bv, r0, r1):
+    """_numpy_two_pass, counting what np.clip changes: (below 0, above 255) in the horizontal pass, then in the vertical pass."""
+    P = pp.PRECISION_BITS
+    counts = []
+    tmp = np.zeros((r1 - r0, 224, 3), np.int64)
+    for xx in range(224):
+        xmin, xmax = bh[xx]
+        tmp[:, xx] = ((img[r0:r1, xmin:xmin + xmax].astype(np.int64) * kh[xx, :xmax, None].astype(np.int64)).sum(1) + (1 << (P - 1))) >> P
+    counts += [int((tmp < 0).sum()), int((tmp > 255).sum())]
+    tmp = np.clip(tmp, 0, 255)
+    out = np.zeros((224, 224, 3), np.int64)
+    for yy in range(224):
+        ymin, ymax = bv[yy]
+        out[yy] = ((tmp[ymin - r0:ymin - r0 + ymax] * kv[yy, :ymax, None, None].astype(np.int64)).sum(0) + (1 << (P - 1))) >> P
+    counts += [int((out < 0).sum()), int((out > 255).sum())]
+    return counts, np.clip(out, 0, 255).astype(np.uint8)
+
+
+@pytest.mark.parametrize("h,w", BLOCK_SIZES)
+def test_block_frames_clip_both_ways_in_both_passes_and_equal_pillow(h, w):
+    """The random and ramp frames above never leave 0..255 in either pass at a shrinking size, so clip8 runs there as the identity.
+    These frames clip below 0 and above 255 in both passes -- the condition the GPU case below rests on -- and the tables still
+    reproduce Pillow bit for bit."""
+    img = _block_frame(h, w)
+    plan = pp._plan(h, w)
+    assert plan[0].shape[1] == {1080: 21, 2160: 41}[h] == plan[2].shape[1]
+    counts, clipped = _two_pass_clip_counts(img, *plan)
+    assert all(c > 0 for c in counts), counts
+    if h == 1080:
+        assert counts == [162000, 162000, 17568, 17568]
+    got = _numpy_two_pass(img, *plan)
+    assert np.array_equal(got, clipped)
+    nh, nw = pp.resized_shape(h, w)
+    ref = Image.fromarray(img).resize((nw, nh), Image.BICUBIC)
+    left, top = int(round((nw - 224) / 2.0)), int(round((nh - 224) / 2.0))
+    assert np.array_equal(got, np.asarray(ref.crop((left, top, left + 224, top + 224))))
+    rnd = np.random.default_rng(h * 7 + w).integers(0, 256, (h, w, 3), dtype=np.uint8)          # the frame of the table test above
+    assert _two_pass_clip_counts(rnd, *plan)[0] == [0, 0, 0, 0]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("h,w", BLOCK_SIZES)
+def test_device_preprocess_clips_like_pillow_where_it_shrinks(h, w):
+    frames = np.stack([_block_frame(h, w), 255 - _block_frame(h, w), _block_frame(h, w, phase=5)])
+    got = pp.preprocess_frames_device(torch.from_numpy(frames).cuda()).cpu().numpy()
+    for i in range(3):
+        want = _pil_pipeline(frames[i])
+        assert np.array_equal(got[i], want), f"frame {i}: max diff {np.abs(got[i] - want).max()}"
