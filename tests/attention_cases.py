@@ -63,7 +63,7 @@ def _route_tag(r):
 # ---- reference ------------------------------------------------------------------------------------------------------------
 def attention_ref(qkv, B, T, H, dh, bias_k=None, bias_v=None, causal=False, *, keys=None, use_bias=True, use_bias_v=True,
                   round_bias_k=True, dup_edges=(), causal_shift=0, reverse_samples=False, head_shift=0, last_query_from=None,
-                  scale_dh=None):
+                  scale_dh=None, drop_keys=(), repeat_key=None):
     """softmax(q k^T / sqrt(dh)) v per (sample, head) in float64 on the bf16 operands of the packed [B*T][q | k | v] matrix
     (each part H heads of dh).  bias_k / bias_v (fp32, H*dh) are rounded to bf16, as the kernel rounds them when it writes them
     into its K and V images, and appended as key T of every sample.  causal: query i sees keys 0..i.
@@ -74,7 +74,8 @@ def attention_ref(qkv, B, T, H, dh, bias_k=None, bias_v=None, causal=False, *, k
     only the first so many keys; ``use_bias`` False drops the bias position, ``use_bias_v`` False appends zeros for bias_v,
     ``round_bias_k`` False appends bias_k unrounded; ``dup_edges`` copies key e over key e-1 for each e given; ``causal_shift``
     s makes key j visible iff j <= i + s; ``reverse_samples`` answers sample b with sample B-1-b; ``head_shift`` answers head h
-    with head h + shift; ``last_query_from`` r answers query T-1 with query r's row; ``scale_dh`` takes 1/sqrt of another dh."""
+    with head h + shift; ``last_query_from`` r answers query T-1 with query r's row; ``scale_dh`` takes 1/sqrt of another dh;
+    ``drop_keys`` leaves out the keys given; ``repeat_key`` (j, count) appends count copies of key j behind the last key."""
     D = H * dh
     q, k, v = qkv.to(F64).reshape(B, T, 3, H, dh).unbind(2)                           # (B, T, H, dh)
     if bias_k is not None and use_bias:
@@ -85,6 +86,12 @@ def attention_ref(qkv, B, T, H, dh, bias_k=None, bias_v=None, causal=False, *, k
         k, v = k.clone(), v.clone()
         for e in dup_edges:
             k[:, e - 1], v[:, e - 1] = k[:, e], v[:, e]
+    if repeat_key is not None:
+        j, count = repeat_key
+        k, v = (torch.cat([t, t[:, j:j + 1].expand(-1, count, -1, -1)], 1) for t in (k, v))
+    if drop_keys:
+        kept = [j for j in range(k.shape[1]) if j not in drop_keys]
+        k, v = k[:, kept], v[:, kept]
     if keys is not None:
         k, v = k[:, :keys], v[:, :keys]
     Lk = k.shape[1]
