@@ -16,7 +16,8 @@ void set_error(const char* fmt, ...) {
 // 6: hmm_host_rgbx_to_rgb, hmm_host_arrow_rgbx_to_rgb; 7: hmm_rank_segment_hits.  Added within 7 (backward compatible, no bump):
 // hmm_gray_u8, hmm_ssim_pairs_workspace_bytes, hmm_ssim_pairs; hmm_jpeg_parse, hmm_jpeg_slot_bytes, hmm_jpeg_decode_coefs,
 // hmm_jpeg_workspace_bytes, hmm_jpeg_reconstruct; hmm_jpeg_entropy_slot_bytes, hmm_jpeg_prepare_entropy,
-// hmm_jpeg_entropy_workspace_bytes, hmm_jpeg_decode_coefs_device; hmm_rank_segment_hits_filtered, hmm_rank_segment_hits_filtered_multi.
+// hmm_jpeg_entropy_workspace_bytes, hmm_jpeg_decode_coefs_device; hmm_rank_segment_hits_filtered, hmm_rank_segment_hits_filtered_multi;
+// hmm_cosine_topk_f64, hmm_cosine_topk_segmented_f64 (and their _workspace_bytes), hmm_rows_f64_are_f32.
 extern "C" int hmm_abi_version(void) { return 7; }
 extern "C" const char* hmm_last_error(void) { return hmm::g_err; }
 

@@ -11,8 +11,13 @@ hits plus the deferred events with their own hits.  The LLM block stays the inte
 returns that event's ``[(similarity, [segments])]`` entries.  The merge runs on the host over at most ``keep`` device hits and the
 callables' entries; a feature hit among the final ``keep`` is among the best ``keep`` feature hits, so nothing is lost.
 
-Limits: where NaN similarities sort is this library's rule (first), not Python's; a store converted from fp64 holds fp32
-similarities widened, so a 0.4 decision within 2e-6 of the threshold can differ from the reference.
+Limits: where NaN similarities sort is this library's rule (first), not Python's.  By default the similarities are fp32 results,
+so on a store converted from float64 a 0.4 decision within 2e-6 of the threshold, and the order of hits whose cosines differ by
+less than fp32 accumulation noise, can differ from the reference, which computes them in float64.  ``exact64=True`` takes the
+float64 route for a store whose float64 source held fp32 values (a reloaded event does): similarities within 2^-42 of the exact
+quotient in a fixed, documented summation order, the query's norm numpy's own, the two rules and the stable sort on doubles on the
+host.  What stays this library's then: the order inside exact ties, and the last fp32 bit of the norm of a query that lives on the
+device (include/hippomm_hip.h).  The default is unchanged.
 
 ``recall_window_frames`` is the step the reference takes next (:2210-2251 in ``_process_video_query``, :2773-2815 in
 ``_process_multimodal_query``, the same text): the frames of a +-1 s window around every frame_time of the segments found are
@@ -81,7 +86,7 @@ def merge_entries(entries, keep: int) -> List[SequenceSegment]:
 
 
 def _find(modality: str, events: Sequence, query_features, store: Optional[EventStore], deferred: Optional[Callable], k: int,
-          keep: int, min_similarity: float, prefilter: bool) -> List[SequenceSegment]:
+          keep: int, min_similarity: float, prefilter: bool, exact64: bool = False) -> List[SequenceSegment]:
     global _warned_no_callable
     what = f"find_relevant_{'video' if modality == 'vision' else 'audio'}_segments"
     query = query_features.detach().cpu().numpy() if isinstance(query_features, torch.Tensor) else np.asarray(query_features)
@@ -100,7 +105,7 @@ def _find(modality: str, events: Sequence, query_features, store: Optional[Event
     row_limits = [len(_kept_times(event, modality)) for event in having]
     defer = [bool(getattr(event, _MODALITIES[modality], None)) for event in having]
     hits, handed_back = store.relevant_hits(query, k, keep, row_limits=row_limits, defer=defer, min_similarity=min_similarity,
-                                            prefilter=prefilter)
+                                            prefilter=prefilter, exact64=exact64)
     entries = [(similarity, e, order, [_segment(having[e], row, modality)]) for order, (e, row, similarity) in enumerate(hits)]
     for e, idx, sims in handed_back:
         if deferred is None:
@@ -116,22 +121,24 @@ def _find(modality: str, events: Sequence, query_features, store: Optional[Event
 
 
 def find_relevant_video_segments(events, query_features, *, store: Optional[EventStore] = None, deferred: Optional[Callable] = None,
-                                 k: int = 5, keep: int = 5, min_similarity: float = 0.4, prefilter: bool = False
-                                 ) -> List[SequenceSegment]:
+                                 k: int = 5, keep: int = 5, min_similarity: float = 0.4, prefilter: bool = False,
+                                 exact64: bool = False) -> List[SequenceSegment]:
     """``_find_relevant_video_segments`` (:3127-3279) over ``events`` (the long-term store).  ``store``: an ``EventStore`` over the
     vision matrices of the events that have one, in order (built once when not given -- keep it between questions).
     ``deferred(event, idx, sims)``: the LLM block for an event below the threshold that has captions; it returns the event's
     ``[(similarity, [segments])]`` entries (``feature_entries`` is what its error branch returns, and what stands in when no
-    callable is given).  A query whose size is not 1024 returns [] (:3135-3137)."""
-    return _find("vision", events, query_features, store, deferred, k, keep, min_similarity, prefilter)
+    callable is given).  A query whose size is not 1024 returns [] (:3135-3137).  ``exact64=True``: similarities, the threshold
+    decision and the ranking in float64 (``EventStore.relevant_hits``); ValueError with ``prefilter`` or on a store that is not
+    eligible."""
+    return _find("vision", events, query_features, store, deferred, k, keep, min_similarity, prefilter, exact64)
 
 
 def find_relevant_audio_segments(events, query_features, *, store: Optional[EventStore] = None, deferred: Optional[Callable] = None,
-                                 k: int = 5, keep: int = 5, min_similarity: float = 0.4, prefilter: bool = False
-                                 ) -> List[SequenceSegment]:
+                                 k: int = 5, keep: int = 5, min_similarity: float = 0.4, prefilter: bool = False,
+                                 exact64: bool = False) -> List[SequenceSegment]:
     """``_find_relevant_audio_segments`` (:3281-3383); see ``find_relevant_video_segments`` (the store holds the audio matrices,
     the row limit is ``len(event.feature_times['audio_times'])``, the flag is ``holistic_audio_transcription``)."""
-    return _find("audio", events, query_features, store, deferred, k, keep, min_similarity, prefilter)
+    return _find("audio", events, query_features, store, deferred, k, keep, min_similarity, prefilter, exact64)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@ call, which is correct but PCIe-bound.
 from __future__ import annotations
 
 import functools
+import logging
 import math
 import threading
 import weakref
@@ -27,6 +28,8 @@ import numpy as np
 import torch
 
 from . import _lib
+
+logger = logging.getLogger(__name__)
 
 FEATURE_DIM = 1024
 
@@ -48,7 +51,15 @@ _ROUTES = {
 }
 
 
+# The float64 route (exact64=True; include/hippomm_hip.h, "float64-origin stores") has its own entry points and argument order:
+#   store, n, dim, query, query dtype, query norm, [seg_offsets, E,] k, outputs..., workspace, workspace bytes, stream
+_F64_ROUTES = {
+    "flat": ("hmm_cosine_topk_f64", "hmm_cosine_topk_f64_workspace_bytes"),
+    "segmented": ("hmm_cosine_topk_segmented_f64", "hmm_cosine_topk_segmented_f64_workspace_bytes"),
+}
+
 _I64, _F32, _I32 = (torch.int64, np.int64, 8), (torch.float32, np.float32, 4), (torch.int32, np.int32, 4)
+_F64 = (torch.float64, np.float64, 8)
 
 
 class _Packed:
@@ -77,6 +88,12 @@ class _Packed:
 def _hits_layout(*shape):
     """idx | sims | counts of a segmented scan; shape = (E, k) or (Q, E, k)."""
     return _Packed((_I64, shape), (_F32, shape), (_I32, shape[:-1]))
+
+
+@functools.lru_cache(maxsize=64)
+def _hits_layout_f64(*shape):
+    """idx | sims (float64) | counts of a segmented float64 scan; shape = (E, k).  Both 8-byte fields come first."""
+    return _Packed((_I64, shape), (_F64, shape), (_I32, shape[:-1]))
 
 
 @functools.lru_cache(maxsize=64)
@@ -110,27 +127,122 @@ def _queries_2d(queries, device=None) -> torch.Tensor:
     return q if device is None else q.detach().to(device=device, dtype=torch.float32).contiguous()
 
 
+# ---- the float64 route: opt-in ---------------------------------------------------------------------------------------------------
+# load_theta_event hands the reference float64 matrices, so its scans run in float64 (hippocampal_memory.py:387-395,
+# vector_ops.py:178-186).  Such a matrix holds the repr digits of fp32 tower outputs: every value is an fp32 value, the resident
+# fp32 rows lose nothing, and only the arithmetic differs.  With ``exact64=True`` (or, for the unchanged reference loop, after
+# ``enable_exact64()``) a scan widens the rows in registers and accumulates in fp64 (hmm_cosine_topk_f64): similarities within
+# 2^-42 of the exact quotient, float64 out.  OFF by default: every call then returns today's bits through today's kernels.
+_EXACT64 = False
+_warned_not_exact = False
+EXACT64_TOL = 2.0 ** -42
+
+
+def enable_exact64():
+    """Let ``top_k_cosine_similarity`` take the float64 route wherever its result is float64 anyway (a float64 store or a float64
+    query) and the store is eligible (every source value an fp32 value).  A float64 store that is not eligible logs one warning
+    and keeps today's route.  For the unchanged reference loop, which cannot pass ``exact64=True``."""
+    global _EXACT64
+    _EXACT64 = True
+
+
+def disable_exact64():
+    global _EXACT64
+    _EXACT64 = False
+
+
+def first_not_f32(a: np.ndarray):
+    """The flat offset of the first value of a float64 array whose bits differ from ``(double)(float)v``'s, or None when every
+    value is an fp32 value (a NaN whose payload narrows exactly and an fp32 subnormal are).  What hmm_rows_f64_are_f32 reports."""
+    flat = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+    with np.errstate(over="ignore", invalid="ignore"):
+        back = flat.astype(np.float32).astype(np.float64)
+    bad = np.flatnonzero(back.view(np.uint64) != flat.view(np.uint64))
+    return int(bad[0]) if bad.size else None
+
+
+def _exact64_query(a, dev):
+    """(buffer, query address, dtype code, norm address or None) for the float64 entry points.  A host query keeps its dtype
+    (float32 or float64; anything else becomes float32) and travels with ``np.linalg.norm(a)`` evaluated by numpy in that dtype --
+    the reference's own ``a_norm`` -- as one double in the same upload.  A device tensor is used where it lies and the kernel
+    forms the norm (include/hippomm_hip.h: the last fp32 bit of an fp32 query's norm may then differ from numpy's)."""
+    if isinstance(a, torch.Tensor) and a.is_cuda:
+        q = a.detach().reshape(-1)
+        if q.dtype not in (torch.float32, torch.float64):
+            q = q.to(torch.float32)
+        q = q.to(dev).contiguous()
+        if q.numel() != FEATURE_DIM:
+            raise ValueError(f"query must have {FEATURE_DIM} elements, got {q.numel()}")
+        if q.data_ptr() % 16:
+            q = q.clone()
+        return q, q.data_ptr(), int(q.dtype == torch.float64), None
+    host = a.detach().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    host = np.ascontiguousarray(host.reshape(-1), dtype=host.dtype if host.dtype in (np.float32, np.float64) else np.float32)
+    if host.size != FEATURE_DIM:
+        raise ValueError(f"query must have {FEATURE_DIM} elements, got {host.size}")
+    norm = np.array([np.linalg.norm(host)], dtype=np.float64)            # in the query's dtype, widened
+    # 8 unused bytes | norm | query: the query starts 16 bytes into the (256-byte aligned) allocation
+    buf = torch.from_numpy(np.concatenate([np.zeros(8, np.uint8), norm.view(np.uint8), host.view(np.uint8)])).to(dev)
+    return buf, buf.data_ptr() + 16, int(host.dtype == np.float64), buf.data_ptr() + 8
+
+
+def rank_hits_exact64(idx, sims, counts, keep: int, row_limits=None, defer=None, min_similarity: float = 0.4):
+    """The reference's two per-event rules and its stable descending sort on the (E, k) float64 hits of a segmented scan, in numpy
+    on the host -- the reference's own operations: ``sims[e, 0] < float(min_similarity)`` on doubles (a NaN never defers), the row
+    rule ``idx < row_limits[e]``, then Python's stable sort by similarity (NaN first, the library's rule).  -> (hits, deferred)
+    as ``EventStore.relevant_hits`` returns them, similarities float64."""
+    idx, sims, counts = np.asarray(idx), np.asarray(sims, dtype=np.float64), np.asarray(counts)
+    E, k = idx.shape
+    threshold = float(min_similarity)
+    deferred = [e for e in range(E) if defer is not None and defer[e] and counts[e] > 0 and sims[e, 0] < threshold]
+    valid = np.arange(k)[None, :] < counts[:, None]
+    if deferred:
+        valid[deferred] = False
+    if row_limits is not None:
+        valid &= idx < np.asarray(row_limits, dtype=np.int64)[:, None]
+    key = np.where(np.isnan(sims), np.inf, sims)
+    cells = np.flatnonzero(valid.reshape(-1))                             # event order, then slot order
+    down = -key.reshape(-1)[cells]
+    if cells.size > 4 * keep:                                             # only cells at or above the keep-th key can be kept (ties included)
+        at_least = down <= np.partition(down, keep - 1)[keep - 1]
+        cells, down = cells[at_least], down[at_least]
+    order = cells[np.argsort(down, kind="stable")][:keep]
+    hits = [(int(c // k), int(idx.reshape(-1)[c]), float(sims.reshape(-1)[c])) for c in order]
+    return hits, [(int(e), idx[e, :counts[e]].astype(np.int64), sims[e, :counts[e]].copy()) for e in deferred]
+
+
 class FeatureStore:
     """(N,1024) fp32 feature matrix resident in HBM (the ``memory_store`` vision/audio matrix
-    of one event, or many events concatenated), plus the scan workspace."""
+    of one event, or many events concatenated), plus the scan workspace.
+
+    ``f64_exact``: None for an fp32 source; for a float64 source True when every value was an fp32 value (narrowing lost nothing:
+    the store is eligible for the float64 route) and False otherwise.  Conservative: once False it stays False until the store
+    is rebuilt."""
 
     def __init__(self, rows: Union[np.ndarray, torch.Tensor], device=None, shadow: bool = False):
         """``shadow=True`` also builds the bf16 shadow (+2048 B per row) and lets ``search`` / ``search_device`` -- and therefore
         ``top_k_cosine_similarity(q, store, k)`` -- go through it: the same results, bit for bit, for half the bytes streamed.
         The rows must stay unchanged while a shadow exists (see ``build_shadow``)."""
         dev = device or _lib.require_gpu()
+        source64 = None                                  # a float64 source, as it was handed in: checked once the state exists
         if isinstance(rows, np.ndarray):
             source_dtype = rows.dtype
             host = np.ascontiguousarray(rows.reshape(1, -1) if rows.ndim == 1 else rows, dtype=np.float32)
             t = torch.from_numpy(host).to(dev)
+            if source_dtype == np.float64:
+                source64 = rows
         else:
             source_dtype = np.dtype(str(rows.dtype).replace("torch.", "")) if rows.dtype in (
                 torch.float32, torch.float64) else np.dtype(np.float32)
             t = rows.reshape(1, -1) if rows.dim() == 1 else rows
+            if rows.dtype == torch.float64:
+                source64 = t
             t = t.to(device=dev, dtype=torch.float32).contiguous()
         if t.dim() != 2 or t.shape[1] != FEATURE_DIM:
             raise ValueError(f"store must be (N,{FEATURE_DIM}), got {tuple(t.shape)}")
         self._init_state(t, source_dtype)
+        if source64 is not None:
+            self._note_f64_source(source64, 0)
         if shadow and t.shape[0] > 0:
             self.build_shadow()
             self.use_shadow = True
@@ -144,9 +256,77 @@ class FeatureStore:
         self._buf, self._shadow_buf = None, None         # the capacity-sized buffers of a store that has grown (EventStore)
         self._pinned = None                              # the read-back staging buffer (EventStore._read_back)
         self._pinned_rules = None                        # the upload staging buffer of row_limits | defer (EventStore._upload_rules)
+        self._f64_exact = None                           # see the f64_exact property
+        self._f64_first_bad = None                       # (row in the store at ingest, column) of the first value that is no fp32 value
+        self._f64_pending = []                           # [(device report int64[2], first row)] of checks not read back yet
 
     def __len__(self):
         return self.rows.shape[0]
+
+    # ---- eligibility for the float64 route ------------------------------------------------------------------------------------
+    def _note_f64_source(self, source, first_row: int):
+        """AND one float64 source (rows ``first_row`` .. of the store) into ``f64_exact``: a host array is checked with numpy here,
+        a device tensor by hmm_rows_f64_are_f32 on the current stream, beside the ingest; its report is read when somebody asks."""
+        if isinstance(source, torch.Tensor) and source.is_cuda:
+            src = source.detach().contiguous().reshape(-1, FEATURE_DIM)
+            report = torch.empty(2, dtype=torch.int64, device=src.device)
+            _lib.check(_lib.load().hmm_rows_f64_are_f32(src.data_ptr() if src.shape[0] else None, src.shape[0], FEATURE_DIM,
+                                                        report.data_ptr(), _lib.stream_ptr()), "hmm_rows_f64_are_f32")
+            self._f64_pending.append((report, int(first_row)))
+            return
+        at = first_not_f32(source.detach().numpy() if isinstance(source, torch.Tensor) else source)
+        self._and_f64(at is None, None if at is None else (int(first_row) + at // FEATURE_DIM, at % FEATURE_DIM))
+
+    def _and_f64(self, clean: bool, first_bad):
+        if not clean and self._f64_exact is not False:
+            self._f64_first_bad = first_bad
+        self._f64_exact = bool(clean) if self._f64_exact is None else (self._f64_exact and bool(clean))
+
+    @property
+    def f64_exact(self):
+        """None: only fp32 sources so far.  True: float64 sources, every value an fp32 value.  False: some float64 value was
+        narrowed with a rounding; it stays False until the store is rebuilt (also after the event is removed).  Reading it brings
+        back the reports of device-side checks still in flight (one small copy each)."""
+        pending, self._f64_pending = self._f64_pending, []
+        for report, first_row in pending:
+            count, at = (int(v) for v in report.cpu().numpy())
+            self._and_f64(count == 0, None if count == 0 else (first_row + at // FEATURE_DIM, at % FEATURE_DIM))
+        return self._f64_exact
+
+    def _use_exact64(self, exact64: bool, what: str, prefilter: bool = False) -> bool:
+        """The explicit request: refused (ValueError) together with the bf16 shadow route and on a store that is not eligible."""
+        if not exact64:
+            return False
+        if prefilter:
+            raise ValueError(f"{what}: exact64=True does not go through the bf16 shadow (prefilter=True)")
+        if self.f64_exact is False:
+            row, col = self._f64_first_bad
+            raise ValueError(f"{what}: exact64=True needs a store whose float64 source held fp32 values only; the value at "
+                             f"(row {row}, column {col}) was not one")
+        return True
+
+    def _scan_f64(self, shape: str, query, k: int, outputs, seg_offsets: torch.Tensor = None):
+        """One launch of the float64 route ``shape`` of _F64_ROUTES into ``outputs``; does not synchronise."""
+        name, size_name = _F64_ROUTES[shape]
+        lib = _lib.load()
+        keepalive, q_ptr, q_dtype, norm_ptr = _exact64_query(query, self.rows.device)
+        n = len(self)
+        segments = () if seg_offsets is None else (seg_offsets.data_ptr(), seg_offsets.numel() - 1)
+        ws = self._scratch(getattr(lib, size_name)(n, *segments[1:], k))
+        _lib.check(getattr(lib, name)(self.rows.data_ptr(), n, FEATURE_DIM, q_ptr, q_dtype, norm_ptr, *segments, k,
+                                      *[t.data_ptr() for t in outputs], ws.data_ptr(), ws.numel(), _lib.stream_ptr()), name)
+        return keepalive
+
+    def _search_flat_f64(self, query, k: int):
+        if k < 1:
+            raise ValueError("k must be >= 1")
+        dev, k_out = self.rows.device, min(k, len(self))
+        idx = torch.empty(k_out, dtype=torch.int64, device=dev)
+        sims = torch.empty(k_out, dtype=torch.float64, device=dev)
+        n_out = torch.empty(1, dtype=torch.int32, device=dev)
+        if k_out > 0:
+            self._scan_f64("flat", query, k, (idx, sims, n_out))
+        return idx, sims
 
     def _scratch(self, need_bytes: int) -> torch.Tensor:
         """The workspace, reallocated only when it is too small.  No route reads what an earlier call left in it."""
@@ -181,9 +361,12 @@ class FeatureStore:
         self._scan("flat", prefilter, query, k, (idx, sims, n_out), stats=stats)
         return idx, sims
 
-    def search_device(self, query: torch.Tensor, k: int):
+    def search_device(self, query: torch.Tensor, k: int, exact64: bool = False):
         """query: (1024,) fp32 CUDA tensor.  Returns CUDA tensors (idx int64[k'], sims fp32[k'])
-        without synchronising (k' = min(k, N))."""
+        without synchronising (k' = min(k, N)).  ``exact64=True``: the float64 route (hmm_cosine_topk_f64) -- the query may be
+        fp32 or fp64, on the host or the device, sims are float64 within 2^-42 of the exact quotient; never through the shadow."""
+        if self._use_exact64(exact64, "search_device"):
+            return self._search_flat_f64(query, k)
         if self.use_shadow:
             return self.search_prefiltered_device(query, k)
         return self._search_flat(query, k, False)
@@ -250,12 +433,27 @@ class FeatureStore:
         self._scan("keys", False, query, k, (keys,))
         return keys
 
-    def search_segments_device(self, query: torch.Tensor, seg_offsets: torch.Tensor, k: int, prefilter: bool = False):
+    def search_segments_device(self, query: torch.Tensor, seg_offsets: torch.Tensor, k: int, prefilter: bool = False,
+                               exact64: bool = False):
         """Per-event top-k in one pass.  seg_offsets: int64 CUDA tensor (E+1,), row offsets of the events inside
         this store.  Returns CUDA tensors idx (E,k) int64 rows within each event (-1 padded), sims (E,k) fp32,
         counts (E,) int32 = min(k, n_e).  ``prefilter``: stream the bf16 shadow (built on first use) and re-score each event's
-        candidates on the fp32 rows -- the same outputs, bit for bit, for half the bytes (hmm_cosine_topk_segmented_prefilter)."""
+        candidates on the fp32 rows -- the same outputs, bit for bit, for half the bytes (hmm_cosine_topk_segmented_prefilter).
+        ``exact64=True``: the float64 route (hmm_cosine_topk_segmented_f64): sims (E,k) float64, every event's slice what the flat
+        float64 call gives on its rows, bit for bit; not together with ``prefilter``."""
+        if self._use_exact64(exact64, "search_segments_device", prefilter):
+            return self._search_segments_packed_f64(query, seg_offsets, k)[1:]
         return self._search_segments_packed(query, seg_offsets, k, prefilter)[1:]
+
+    def _search_segments_packed_f64(self, query, seg_offsets: torch.Tensor, k: int):
+        """The float64 route of _search_segments_packed: (packed, idx, sims float64, counts), one buffer (_hits_layout_f64)."""
+        if int(k) < 1:
+            raise ValueError("k must be >= 1")
+        layout = _hits_layout_f64(seg_offsets.numel() - 1, int(k))
+        packed = torch.empty(layout.nbytes, dtype=torch.uint8, device=self.rows.device)
+        outputs = layout.device_views(packed)
+        self._scan_f64("segmented", query, int(k), outputs, seg_offsets=seg_offsets)
+        return (packed, *outputs)
 
     def _search_segments_packed(self, query: torch.Tensor, seg_offsets: torch.Tensor, k: int, prefilter: bool = False):
         """search_segments_device, returning (packed, idx, sims, counts): the three outputs are views of ONE buffer
@@ -320,9 +518,13 @@ class FeatureStore:
         idx, sims = idx.cpu().numpy(), sims.cpu().numpy()
         return [(idx[i], sims[i]) for i in range(idx.shape[0])]
 
-    def search(self, query, k: int) -> Tuple[np.ndarray, np.ndarray]:
-        q = _query_to_device(query, self.rows.device)
-        idx, sims = self.search_device(q, k)
+    def search(self, query, k: int, exact64: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """``search_device`` with the results on the host.  ``exact64=True``: float64 similarities from the float64 route; a
+        host query is sent with numpy's own ``np.linalg.norm`` of it, the reference's ``a_norm``."""
+        if self._use_exact64(exact64, "search"):
+            idx, sims = self._search_flat_f64(query, k)
+        else:
+            idx, sims = self.search_device(_query_to_device(query, self.rows.device), k)
         return idx.cpu().numpy(), sims.cpu().numpy()
 
 
@@ -431,6 +633,7 @@ def top_k_cosine_similarity(
     a: Union[np.ndarray, torch.Tensor],
     b: Union[np.ndarray, torch.Tensor, FeatureStore],
     k: int,
+    exact64: bool = False,
 ) -> Tuple[np.ndarray, np.ndarray]:
     """Top-k cosine similarities between one vector and many (reference vector_ops.py:151-188).
 
@@ -441,6 +644,13 @@ def top_k_cosine_similarity(
     float64 (numpy's promotion at :182) and float32 otherwise.  Ties: higher row index first; a zero-norm
     row yields NaN and ranks first, as in the reference.  (The reference leaves the order INSIDE a tie group to numpy's
     unstable argsort; this total order is the library's own rule, include/hippomm_hip.h.)
+
+    By default a float64 result holds fp32 arithmetic widened.  ``exact64=True`` takes the float64 route instead: the resident
+    fp32 rows widened in registers, sums in fp64, ``a_norm`` numpy's own for a host query -- similarities within 2^-42 of the exact
+    quotient and float64 whatever the inputs' dtypes, hence the reference's ranking of near-ties.  It needs a store whose float64
+    source held fp32 values only (``FeatureStore.f64_exact``; a reloaded event does): otherwise ValueError naming the first
+    offending (row, column).  ``enable_exact64()`` makes the same choice for every call whose result is float64 anyway, falling
+    back to today's route, with one logged warning, for a store that is not eligible.
     """
     a_is64 = (isinstance(a, np.ndarray) and a.dtype == np.float64) or (
         isinstance(a, torch.Tensor) and a.dtype == torch.float64)
@@ -457,9 +667,20 @@ def top_k_cosine_similarity(
     # the reference slices argsort(sims)[-k:][::-1] (:185): k = 0 keeps everything ([-0:]), k < 0 the best N - |k| rows
     k = int(k)
     k_eff = n if k == 0 else (max(n + k, 0) if k < 0 else min(k, n))
-    out_dtype = np.float64 if (a_is64 or b_is64) else np.float32
+    out_dtype = np.float64 if (a_is64 or b_is64 or exact64) else np.float32
     if k_eff == 0:
         return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=out_dtype)
+    if not exact64 and _EXACT64 and out_dtype == np.float64:     # the module-wide switch: only where the result is float64 anyway
+        exact64 = store.f64_exact is not False
+        if not exact64:
+            global _warned_not_exact
+            if not _warned_not_exact:
+                _warned_not_exact = True
+                logger.warning("top_k_cosine_similarity: a float64 store holds values that are not fp32 values (first at row %d, "
+                               "column %d); it keeps the fp32 route", *store._f64_first_bad)
+    if exact64:
+        idx, sims = store.search(a, k_eff, exact64=True)
+        return idx.astype(np.int64, copy=False), sims.astype(np.float64, copy=False)
     idx, sims = store.search(a, k_eff)
     return idx.astype(np.int64, copy=False), sims.astype(out_dtype, copy=False)
 
@@ -477,10 +698,16 @@ class EventStore(FeatureStore):
     ``QARecallSystem._find_relevant_*_segments`` iterates over (hippocampal_memory.py:3143, :3294)."""
 
     def __init__(self, event_features, device=None):
-        mats = [np.ascontiguousarray(np.asarray(f).reshape(-1, FEATURE_DIM), dtype=np.float32) for f in event_features]
+        event_features = list(event_features)
+        mats =[np.ascontiguousarray(np.asarray(f).reshape(-1, FEATURE_DIM), dtype=np.float32) for f in event_features]
         lengths = [m.shape[0] for m in mats]
         super().__init__(np.concatenate(mats, axis=0) if sum(lengths) else np.zeros((0, FEATURE_DIM), np.float32), device)
         self._set_events(lengths)
+        at = 0
+        for f, n in zip(event_features, lengths):                # the float64 events, as they were handed in (host arrays: numpy)
+            if getattr(f, "dtype", None) in (np.float64, torch.float64) and n > 0:
+                self._note_f64_source(f.detach().cpu() if isinstance(f, torch.Tensor) else np.asarray(f), at)
+            at += n
 
     @classmethod
     def from_device_rows(cls, rows: torch.Tensor, lengths) -> "EventStore":
@@ -500,14 +727,29 @@ class EventStore(FeatureStore):
         self.lengths = lengths
         self.offsets = torch.tensor(np.concatenate([[0], np.cumsum(lengths)]), dtype=torch.int64, device=self.rows.device)
 
-    def top_hits(self, query, k: int = 5, keep: int = 5, prefilter: bool = False):
+    def _hits_exact64(self, query, k: int):
+        """The per-event float64 top-k on the device and ONE packed read-back -> host (idx (E,k) int64, sims (E,k) float64,
+        counts (E,) int32), copies."""
+        packed, idx, _, _ = self._search_segments_packed_f64(query, self.offsets, int(k))
+        idx_h, sims_h, counts_h = _hits_layout_f64(*idx.shape).host_views(self._read_back(packed))
+        return idx_h.copy(), sims_h.copy(), counts_h.copy()
+
+    def top_hits(self, query, k: int = 5, keep: int = 5, prefilter: bool = False, exact64: bool = False):
         """The caller's whole step in one go (hippocampal_memory.py:3143-3153 + :3275-3277): top-k per event, then every hit of
         every event ranked by similarity and the best `keep` returned as [(event index, row inside the event, similarity)].
         The ranking runs on the device (a stable descending sort of the (E, k) similarities in event order, i.e. what Python's
         stable ``sorted(..., reverse=True)`` does to the list the reference builds event by event); only `keep` hits are read
         back.  NaN similarities (zero-norm rows) rank first, as they do per event.  This IS the reference's answer only on a store
         where every row of every event is a kept row and no event has captions / a transcription: the reference drops hits of
-        rows that were not kept and defers low-similarity events to the LLM BEFORE its sort -- ``relevant_hits`` applies both."""
+        rows that were not kept and defers low-similarity events to the LLM BEFORE its sort -- ``relevant_hits`` applies both.
+
+        ``exact64=True``: the per-event top-k runs on the device in float64 (hmm_cosine_topk_segmented_f64), one packed read-back
+        brings (idx, sims float64, counts), and the stable descending sort runs on the host in numpy (``rank_hits_exact64``) --
+        the reference's own operation on doubles.  Ranking doubles on the device is a follow-up, not part of this route."""
+        if self._use_exact64(exact64, "top_hits", prefilter):
+            if not self.lengths or int(keep) < 1:
+                return []
+            return rank_hits_exact64(*self._hits_exact64(query, k), int(keep))[0]
         q = _query_to_device(query, self.rows.device)
         idx, sims, counts = self.search_segments_device(q, self.offsets, int(k), prefilter)
         E, keep = idx.shape[0], int(keep)
@@ -531,9 +773,15 @@ class EventStore(FeatureStore):
         ev_h, row_h, val_h, n = layout.host_views(packed.cpu().numpy())
         return [(int(ev_h[t]), int(row_h[t]), float(val_h[t])) for t in range(int(n[0]))]
 
-    def top_k_per_event(self, query, k: int = 5, prefilter: bool = False):
+    def top_k_per_event(self, query, k: int = 5, prefilter: bool = False, exact64: bool = False):
         """[(indices int64[k_e], sims float32[k_e]) for every event], each exactly what
-        ``top_k_cosine_similarity(query, event_features, k)`` returns for that event."""
+        ``top_k_cosine_similarity(query, event_features, k)`` returns for that event.  ``exact64=True``: sims float64, what
+        ``top_k_cosine_similarity(query, event_features, k, exact64=True)`` returns for it, bit for bit."""
+        if self._use_exact64(exact64, "top_k_per_event", prefilter):
+            if not self.lengths:
+                return []
+            idx_h, sims_h, counts_h = self._hits_exact64(query, k)
+            return [(idx_h[e, :counts_h[e]], sims_h[e, :counts_h[e]]) for e in range(len(self.lengths))]
         q = _query_to_device(query, self.rows.device)
         packed, idx, _, _ = self._search_segments_packed(q, self.offsets, int(k), prefilter)
         E, k = idx.shape
@@ -605,15 +853,25 @@ class EventStore(FeatureStore):
     # (hmm_rank_segment_hits_filtered[_multi]) and hand the deferred events back with their own hits.
 
     def relevant_hits(self, query, k: int = 5, keep: int = 5, *, row_limits=None, defer=None, min_similarity: float = 0.4,
-                      prefilter: bool = False):
+                      prefilter: bool = False, exact64: bool = False):
         """(hits, deferred).  hits: [(event, row inside the event, similarity)], best first, the best `keep` of the hits that
         pass the row rule (``row < row_limits[event]``) in events that are not deferred.  deferred: [(event, idx int64[k_e],
         sims float32[k_e])] in event order -- the events with ``defer[event]`` set whose best similarity is below
         ``np.float32(min_similarity)``, each with exactly what ``top_k_per_event`` returns for it.  ``row_limits`` / ``defer``: one
         entry per event, or None (no row rule / nothing deferred).  Same order rules as ``top_hits`` (stable, NaN first; a NaN best
         similarity never defers, as ``max(...) < 0.4`` is False).  keep <= 1024.  One scan, one ranking launch, one packed read-back,
-        and -- only when events were deferred -- a second one of their hits alone."""
+        and -- only when events were deferred -- a second one of their hits alone.
+
+        ``exact64=True`` (a store whose float64 source held fp32 values; not with ``prefilter``): the per-event top-k runs on the
+        device in float64, one packed read-back brings (idx, sims float64, counts), and the two rules and the stable descending
+        sort run on the host in numpy (``rank_hits_exact64``): the reference's own operations, ``<`` on doubles against
+        ``float(min_similarity)``.  Similarities (hits and deferred) are float64.  Ranking doubles on the device is a follow-up,
+        not part of this route."""
         rules = self._relevance_rules("relevant_hits", k, keep, row_limits, defer, min_similarity)
+        if self._use_exact64(exact64, "relevant_hits", prefilter):
+            if not self.lengths:
+                return [], []
+            return rank_hits_exact64(*self._hits_exact64(query, k), int(keep), rules[0], rules[1], min_similarity)
         q = _query_to_device(query, self.rows.device)
         if not self.lengths:
             return [], []
@@ -815,6 +1073,16 @@ class EventStore(FeatureStore):
                                                      self._buf.data_ptr(), self._shadow_buf.data_ptr() if shadow else None,
                                                      self._buf.shape[0], at, _lib.stream_ptr()), "hmm_store_ingest_rows")
 
+    def _note_ingested(self, features, src: torch.Tensor, at: int):
+        """AND a float64 event that was just ingested at row ``at`` into ``f64_exact``: a host source is checked with numpy, a
+        device tensor by hmm_rows_f64_are_f32 beside the ingest."""
+        if src.dtype != torch.float64 or src.shape[0] == 0:
+            return
+        if isinstance(features, torch.Tensor):
+            self._note_f64_source(src if features.is_cuda else features.detach(), at)
+        else:
+            self._note_f64_source(np.asarray(features), at)
+
     def append_event(self, features) -> int:
         """Append one event and return its index.  ``features``: numpy or torch, host or device, (n,1024), a 1-D (1024,) row or
         an empty matrix, float32 or float64 (another dtype is converted to float32 first; another width is a ValueError).  A
@@ -828,6 +1096,7 @@ class EventStore(FeatureStore):
     def extend(self, list_of_features):
         """``append_event`` for several events: at most one move, one ingest launch per event, one offsets update.  Returns the
         new events' indices."""
+        list_of_features = list(list_of_features)
         srcs = [self._source_rows(f) for f in list_of_features]
         first = len(self.lengths)
         if not srcs:
@@ -838,8 +1107,9 @@ class EventStore(FeatureStore):
         if self._buf is None or needed > self._buf.shape[0]:
             self._move_to(self._grown(needed), shadow)
         at = n
-        for s in srcs:
+        for f, s in zip(list_of_features, srcs):
             self._ingest(s, at, shadow)
+            self._note_ingested(f, s, at)
             at += s.shape[0]
         self.lengths = list(self.lengths) + [int(s.shape[0]) for s in srcs]
         self.offsets = self._upload_tables(self.lengths)[0]
@@ -896,4 +1166,5 @@ class EventStore(FeatureStore):
         lengths[j] = int(src.shape[0])
         self._regather([-1 if e == j else e for e in range(E)], lengths)
         self._ingest(src, int(sum(lengths[:j])), self._shadow is not None)
+        self._note_ingested(features, src, int(sum(lengths[:j])))
         return self

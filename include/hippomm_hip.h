@@ -281,8 +281,13 @@ int    hmm_rank_segment_hits_multi(const int64_t* idx_dev, const float* sims_dev
  *   deferred_idx_out int64[n_segments*k], deferred_sim_out float[n_segments*k], deferred_count_out int32[n_segments]: for the j-th
  *   deferred event its own (idx, sims, count) slice, copied unchanged, at [j*k ..] / [j].  Entries at and after n_d*k (counts: n_d)
  *   are NOT WRITTEN: they keep whatever the caller left there.
- * One workgroup, no workspace.  For stores converted from fp64 the similarities are fp32 results: a decision within 2e-6 of the
- * threshold can differ from the reference's fp64 comparison. */
+ * One workgroup, no workspace.  The similarities this call ranks are fp32 results.  For a store whose source was float64 the
+ * reference computes them in float64, so by DEFAULT a decision within 2e-6 of the threshold, and the order of hits whose cosines
+ * differ by less than fp32 accumulation noise, are this library's, not the reference's.  The opt-in float64 route below
+ * (hmm_cosine_topk_segmented_f64; exact64=True in Python) removes that for stores whose float64 source held fp32 values: its
+ * similarities are within 2^-42 of the exact quotient, and the two rules and the stable sort are then applied to doubles on the
+ * host.  What stays this library's own in that mode: the order inside EXACT ties, and, for a query that lives on the device, the
+ * last fp32 bit of the query's norm (see there).  The default of every call is unchanged. */
 int    hmm_rank_segment_hits_filtered(const int64_t* idx_dev, const float* sims_dev, const int32_t* counts_dev, int n_segments, int k,
                                       int keep, const int64_t* row_limits_dev /* nullable */, const uint8_t* defer_dev /* nullable */,
                                       float min_similarity,
@@ -303,6 +308,62 @@ int    hmm_rank_segment_hits_filtered_multi(const int64_t* idx_dev, const float*
                                             int32_t* deferred_event_out_dev, int32_t* n_deferred_out_dev,
                                             int64_t* deferred_idx_out_dev, float* deferred_sim_out_dev,
                                             int32_t* deferred_count_out_dev, hmm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Float64-origin stores: similarities and ranking in float64 (opt-in; no other call changes).
+ *
+ * load_theta_event hands the reference float64 matrices (hippocampal_memory.py:387-395), so its top_k_cosine_similarity runs
+ * np.dot(b, a) / (b_norms * a_norm) in float64 (vector_ops.py:178-186).  A reloaded event holds the repr digits of fp32 tower
+ * outputs: every float64 value of such a store is an fp32 value, narrowing it loses nothing, and only the ARITHMETIC differs.
+ * These calls keep the resident fp32 rows and do the arithmetic in fp64.
+ *
+ * Inputs.  store_dev (n_rows, 1024) fp32, each value equal to its float64 source (hmm_rows_f64_are_f32 checks a source).
+ *   query_dev 1024 values, fp32 (query_dtype 0) or fp64 (1), widened to double.  16-byte aligned both.
+ * Similarity.  sim_r = D_r / (sqrt(S_r) * A), D_r = sum x_ri a_i, S_r = sum x_ri^2, accumulated in fp64 with explicit fma on
+ *   exactly widened operands (the product of two fp32-origin doubles is exact in fp64: only the sums round).  Operation order as
+ *   in the reference: the norms multiplied first, then one division; sqrt and / correctly rounded (no fast-math).
+ * Fixed summation order.  One wave per row.  Lane l (0..63) owns columns 4 (64 j + l) + c, j = 0..3, c = 0..3.  Two chains per
+ *   sum, both starting at +0.0: chain 0 takes j = 0 then j = 1, chain 1 takes j = 2 then j = 3, inside a j in the order c = 0, 1,
+ *   2, 3.  Lane value = chain 0 + chain 1.  Wave reduction: v += v[lane ^ off] for off = 32, 16, 8, 4, 2, 1.  A row's similarity
+ *   bits depend on the row, the query and A alone: not on n_rows, the grid, k, or which of the two entry points computed them.
+ * A is the query's norm in the query's own dtype, widened.  query_norm_dev != null: that double is A -- the Python shim passes
+ *   np.linalg.norm(a) of a host query, evaluated by numpy itself: the reference's own expression on the same host, hence its
+ *   bits.  query_norm_dev == null (a query that lives on the device): the kernel accumulates sum a_i^2 in fp64 in the fixed order
+ *   above and takes the square root; for an fp32 query it rounds the root to fp32 and widens it again.  numpy's fp32 dot may differ
+ *   from that in the last fp32 bit.  A is a factor common to all rows: it cannot change a ranking, only a threshold decision within
+ *   about 6e-8 relative.
+ * Error bound (derived, u = 2^-53).  Either sum of 1024 exact products is, in any order, within 1023 u sum|terms| to first order,
+ *   and sum|x_i a_i| <= ||x|| ||a||: the dot contributes at most 1.14e-13 relative to ||x|| ||a||; the root of S_r half of that plus
+ *   u; the product and the division 3 u.  Total < 1.8e-13 < 2^-42 (2.27e-13), absolute on a cosine (for a device query: relative
+ *   to the value computed with the same A).
+ * Total order.  NaN first (a zero-norm row gives 0/0, as in the reference, where argsort puts NaN last before the reversal), then
+ *   similarity descending, -0.0 == +0.0; exact ties: higher row index first, the library's rule everywhere.  Selection compares
+ *   an order-preserving 64-bit transform of the double with the 32-bit position as second word; it is exact, so the flat call's
+ *   result does not depend on how many workgroups share its first level.
+ *
+ * hmm_cosine_topk_f64: idx_out_dev int64[k'], sim_out_dev fp64[k'], k' = min(k, n_rows), best first; n_out_dev (nullable)
+ *   int32[1] = k'.  n_rows >= 1; any k >= 1 (k' > 1024 sorts all rows).
+ * hmm_cosine_topk_segmented_f64: layout, clamping, padding (-1 / 0) and counts of hmm_cosine_topk_segmented, with sim_out_dev fp64;
+ *   every event's slice equals hmm_cosine_topk_f64 on that event's rows, bit for bit.  k <= 1024.  n_rows >= 0.
+ * The workspace holds one double per row (plus, for the flat call, the first level's candidates) and needs no initialisation.
+ * hmm_rows_f64_are_f32: report_dev int64[2] <- { number of values v of the float64 matrix src_dev (n_rows, 1024) whose bits differ
+ *   from (double)(float)v's -- a NaN whose payload narrows exactly passes, a subnormal fp32 value passes --, the lowest flat
+ *   offset (row * 1024 + column) of one, or -1 }.  Runs beside hmm_store_ingest_rows, not inside it.  n_rows == 0 writes { 0, -1 }.
+ * All: every launch goes on `stream`; nothing is allocated, copied or synchronised; no workgroup waits for another.  HMM_E_INVALID
+ *   before anything is launched (no GPU needed) for a null or misaligned pointer, dim != 1024, an unknown query_dtype, k < 1,
+ *   n_rows out of range; HMM_E_WORKSPACE for a workspace below the *_workspace_bytes answer.
+ * ---------------------------------------------------------------------------------------- */
+size_t hmm_cosine_topk_f64_workspace_bytes(int64_t n_rows, int k);
+int    hmm_cosine_topk_f64(const float* store_dev, int64_t n_rows, int dim, const void* query_dev, int query_dtype,
+                           const double* query_norm_dev /* nullable */, int k,
+                           int64_t* idx_out_dev, double* sim_out_dev, int32_t* n_out_dev /* nullable */,
+                           void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
+size_t hmm_cosine_topk_segmented_f64_workspace_bytes(int64_t n_rows, int n_segments, int k);
+int    hmm_cosine_topk_segmented_f64(const float* store_dev, int64_t n_rows, int dim, const void* query_dev, int query_dtype,
+                                     const double* query_norm_dev /* nullable */, const int64_t* seg_offsets_dev, int n_segments,
+                                     int k, int64_t* idx_out_dev, double* sim_out_dev, int32_t* n_out_dev,
+                                     void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
+int    hmm_rows_f64_are_f32(const double* src_dev, int64_t n_rows, int dim, int64_t* report_dev /* [2] */, hmm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Consolidation similarity.  Replaces HippocampalMemory._select_key_frames(features, times,
