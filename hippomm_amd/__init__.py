@@ -8,9 +8,11 @@ through the C ABI in include/hippomm_hip.h:
     hippomm_amd.consolidation.KeyFrameSelector       the same selection grown batch by batch (live path, :1290-1365)
     hippomm_amd.vector_ops.top_k_cosine_similarity   <- hippomm/utils/vector_ops.py:151-188
 
-and the two SSIM call sites of the formation path (frame SSIM in hippomm_amd/csrc/ssim.hip):
+and the two SSIM call sites of the formation path (frame SSIM in hippomm_amd/csrc/ssim.hip; a module per stage of the frame path
+-- ssim, resize, frame_cache, frame_extraction, segmentation -- and every public name of theirs still imports from
+hippomm_amd.segmentation, where all of them used to live):
 
-    hippomm_amd.segmentation.compute_frame_difference   <- hippomm/core/batch_process.py:32-69
+    hippomm_amd.ssim.compute_frame_difference           <- hippomm/core/batch_process.py:32-69
     hippomm_amd.segmentation._compute_frame_similarity  <- hippomm/core/hippocampal_memory.py:980-991
     hippomm_amd.segmentation._segment_sequence          <- hippomm/core/hippocampal_memory.py:1002-1114
     hippomm_amd.sharding                             one-process-per-GPU sharding (RCCL all-gather)
@@ -26,7 +28,7 @@ and a baseline JPEG decoder with the pixel work on the GPU, bit-exact with Pillo
 and its counterpart, a baseline JPEG encoder on the GPU, byte for byte Pillow's file (hippomm_amd/csrc/jpeg_encode.hip):
 
     hippomm_amd.encode_jpeg                          <- Image.fromarray(rgb).save(buf, "JPEG", quality=q, subsampling=s)
-    hippomm_amd.segmentation.save_frame, save_frames <- hippomm/core/batch_process.py:73-114 (cv2.imwrite)
+    hippomm_amd.frame_extraction.save_frame, save_frames <- hippomm/core/batch_process.py:73-114 (cv2.imwrite)
 
 and, opt-in, the decoded pixels of the frames just saved kept on the device for the two reads that follow (hmm_jpeg_encoded_pixels):
 
@@ -42,7 +44,7 @@ INTER_LINEAR for targets no larger than the source (hippomm_amd/csrc/resize.hip)
 a file round-trip (video decoding stays with the caller; the time of a question is the caller's seeks and the captioner, not this):
 
     hippomm_amd.recall_window_frames                 <- hippomm/core/hippocampal_memory.py:2226-2249, :2789-2812
-    hippomm_amd.segmentation.resize_frames           <- cv2.resize(frame, (320, 180))
+    hippomm_amd.resize.resize_frames                 <- cv2.resize(frame, (320, 180))
 
 and, opt-in, the feature matrices of an event file written as JSON text on the device, byte for byte json.dump's (hippomm_amd/csrc/event_json.hip):
 
@@ -67,12 +69,13 @@ nothing read back but the kept list, and a result that can stay a device tensor:
 and, opt-in, the window walk of sequence segmentation itself on the device over resident pair scores, frame times and the audio
 track, the segment list the one read-back (hippomm_amd/csrc/segment_walk.hip):
 
-    hippomm_amd.segmentation.segment_sequence(..., walk="device"), PathScorer.score_adjacent  <- hippomm/core/hippocampal_memory.py:1002-1114
+    hippomm_amd.segmentation.segment_sequence(..., walk="device"), frame_cache.PathScorer.score_adjacent  <- hippomm/core/hippocampal_memory.py:1002-1114
 """
 __version__ = "0.1.0"
 
 from .consolidation import consolidate_short_term_memory  # noqa: E402,F401
 from .jpeg import decode_jpeg, encode_jpeg  # noqa: E402,F401
-from .segmentation import FrameExtractor, extract_frames, extraction_records  # noqa: E402,F401
+from .frame_extraction import FrameExtractor, extract_frames, extraction_records  # noqa: E402,F401
+from . import segmentation  # noqa: E402,F401  (before retrieval: it re-exports retrieval's recall walk, which needs its SequenceSegment)
 from .retrieval import (feature_entries, find_relevant_audio_segments, find_relevant_video_segments,  # noqa: E402,F401
                         recall_window_frames)

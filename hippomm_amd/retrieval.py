@@ -37,8 +37,11 @@ import numpy as np
 import torch
 
 from . import _lib, jpeg
-from .segmentation import (RECALL_SIMILARITY_CUT, RECALL_SIZE, SAVE_QUALITY, SAVE_SUBSAMPLING, WIN, FrameCache, SequenceSegment,
-                           _ssim_launch, _upload_frames, gray_frames, resize_frames, resize_mode, walk_recall_window)
+from .frame_cache import FrameCache
+from .frame_extraction import SAVE_QUALITY, SAVE_SUBSAMPLING
+from .resize import resize_frames, resize_mode
+from .segmentation import SequenceSegment
+from .ssim import WIN, gray_frames, ssim_launch, upload_frames
 from .vector_ops import FEATURE_DIM, EventStore
 
 logger = logging.getLogger(__name__)
@@ -145,6 +148,22 @@ def find_relevant_audio_segments(events, query_features, *, store: Optional[Even
 # the recall frame windows: shrink, JPEG and SSIM dedup of the frames read around every frame_time of the relevant segments
 # ---------------------------------------------------------------------------------------------------------------------------------
 MAX_WINDOW_FRAMES = 8                      # the reference's +-1 s windows at 1 fps hold at most 3
+RECALL_SIZE = (320, 180)                   # (width, height) of cv2.resize at hippocampal_memory.py:2232, :2795
+RECALL_SIMILARITY_CUT = 0.3                # :2238, :2801
+
+
+def walk_recall_window(scores, similarity_cut: float = RECALL_SIMILARITY_CUT) -> List[int]:
+    """The dedup walk of one recall window (hippocampal_memory.py:2223-2249, :2786-2812) as a host function of the scores:
+    ``scores[i][j]``, i < j, is the SSIM of frames i and j of the window with i in the im1 role; only those entries are read, and
+    only the ones the walk consults.  -> the kept indices.  Frame 0 is kept; frame j is dropped iff
+    ``scores[last kept][j] > similarity_cut`` -- a NaN score (a flat earlier frame) keeps the frame, as Python's comparison does
+    -- and a dropped frame does not become the comparison base."""
+    m = len(scores)
+    kept = [0] if m else []
+    for j in range(1, m):
+        if not scores[kept[-1]][j] > similarity_cut:
+            kept.append(j)
+    return kept
 
 
 @dataclass
@@ -169,10 +188,10 @@ def recall_window_frames(windows, size: Tuple[int, int] = RECALL_SIZE, similarit
     with the caller.  At most ``MAX_WINDOW_FRAMES`` frames per window (``ValueError``).
 
     Per call: one pinned upload and one resize launch per source geometry (``cv2.resize(frame, size)``, ``size`` = (width,
-    height): ``segmentation.resize_frames``); one ``encode_jpeg(..., "BGR", return_decoded=True)`` at ``quality`` and 4:2:0 (the
+    height): ``resize.resize_frames``); one ``encode_jpeg(..., "BGR", return_decoded=True)`` at ``quality`` and 4:2:0 (the
     files of ``cv2.imwrite``'s defaults, and their decoded pixels without a file round-trip); one gray pass with min / max; one
     ``hmm_ssim_pairs`` over all (i < j) pairs inside each window, the earlier frame in the im1 role (data_range = max - min of
-    it, as ``_compute_frame_similarity`` passes); one read-back of the scores; then ``segmentation.walk_recall_window`` per window
+    it, as ``_compute_frame_similarity`` passes); one read-back of the scores; then ``walk_recall_window`` per window
     on the host: frame 0 is kept, a frame is dropped iff its SSIM with the last kept frame is ``> similarity_cut``.
 
     ``paths``: one path per frame, nested as ``windows``; the kept frames' files are written there (parents are created), dropped
@@ -211,7 +230,7 @@ def recall_window_frames(windows, size: Tuple[int, int] = RECALL_SIZE, similarit
         dev = _lib.require_gpu()
         small = None
         for members in groups.values():
-            shrunk = resize_frames(_upload_frames([flat[i] for i in members], dev), (dw, dh))
+            shrunk = resize_frames(upload_frames([flat[i] for i in members], dev), (dw, dh))
             if len(groups) == 1:
                 small = shrunk
             else:
@@ -222,7 +241,7 @@ def recall_window_frames(windows, size: Tuple[int, int] = RECALL_SIZE, similarit
                                           return_decoded=True)
         if pairs:
             gray, minmax = gray_frames(decoded, "RGB", return_minmax=True)
-            scores = _ssim_launch(gray, np.array(pairs, dtype=np.int32), -1.0, minmax).cpu().numpy()
+            scores = ssim_launch(gray, np.array(pairs, dtype=np.int32), -1.0, minmax).cpu().numpy()
     out = RecallWindowFrames([], [], [], [], [], None if paths is None else [])
     at = 0
     for w, window in enumerate(windows):

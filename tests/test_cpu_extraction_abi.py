@@ -48,7 +48,7 @@ def test_symbols_are_declared_exported_and_bound_with_matching_signatures():
 
 
 def test_struct_layouts_are_the_python_layers():
-    from hippomm_amd import segmentation as seg
+    from hippomm_amd import frame_extraction as seg
     text = _header()
     for struct, dtype in (("hmm_extract_state", seg.EXTRACT_STATE), ("hmm_extract_record", seg.EXTRACT_RECORD)):
         body = re.search(rf"typedef struct \{{([^}}]*)\}}\s*{struct};", text).group(1)

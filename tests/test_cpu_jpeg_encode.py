@@ -274,7 +274,7 @@ def test_encode_jpeg_refuses_other_dtypes_shapes_and_options_before_it_needs_a_g
 
 def test_save_frame_keeps_the_reference_return_rules(tmp_path, monkeypatch, caplog):
     """The encoder stubbed by Pillow (the bytes the device route returns), so the rules are checked without a GPU."""
-    from hippomm_amd import segmentation as seg
+    from hippomm_amd import frame_extraction as seg             # the module that looks _encode_bgr up, and whose logger it is
     calls = []
 
     def stub(frames):

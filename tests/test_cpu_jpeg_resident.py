@@ -153,8 +153,8 @@ def _pillow_stub(calls):
 @pytest.fixture
 def on_cpu(monkeypatch):
     """The two kernels the caches launch, replaced by CPU stand-ins: the bookkeeping is what these tests are about."""
-    from hippomm_amd import preprocess as pp, segmentation as seg
-    monkeypatch.setattr(seg, "_gray_into", _cpu_gray_into)
+    from hippomm_amd import preprocess as pp, ssim
+    monkeypatch.setattr(ssim, "gray_into", _cpu_gray_into)
     seen = []
 
     def preprocess_into(frames, out, full_hw=None):
@@ -166,7 +166,7 @@ def on_cpu(monkeypatch):
 
 
 def test_save_frames_with_the_caches_keeps_the_return_rules_and_puts_only_what_it_wrote(tmp_path, monkeypatch, caplog, on_cpu):
-    from hippomm_amd import preprocess as pp, segmentation as seg
+    from hippomm_amd import frame_extraction as seg, preprocess as pp    # the module that looks _encode_bgr up, and its logger
     calls = []
     monkeypatch.setattr(seg, "_encode_bgr", _pillow_stub(calls))
     frames = [ec.content(k, 40, 24, 3) for k in ("noise", "ramp", "mid")] + [None]

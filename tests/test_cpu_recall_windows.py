@@ -18,7 +18,7 @@ NAN = float("nan")
 
 # ---- tables ------------------------------------------------------------------------------------------------------------------
 def test_1920_to_320_reads_the_two_middle_pixels_of_every_six_with_equal_weights():
-    from hippomm_amd.segmentation import resize_linear_tables
+    from hippomm_amd.resize import resize_linear_tables
     ofs, coef = resize_linear_tables(1920, 320)
     assert ofs.dtype == np.int32 and coef.dtype == np.int16 and ofs.shape == (320,) and coef.shape == (320, 2)
     assert ofs.tolist() == [6 * d + 2 for d in range(320)]
@@ -28,7 +28,7 @@ def test_1920_to_320_reads_the_two_middle_pixels_of_every_six_with_equal_weights
 
 
 def test_1440_to_320_alternates_quarter_and_three_quarter_weights():
-    from hippomm_amd.segmentation import resize_linear_tables
+    from hippomm_amd.resize import resize_linear_tables
     ofs, coef = resize_linear_tables(1440, 320)                          # scale 4.5: f = 4.5 d + 1.75
     assert ofs.tolist() == [int(np.floor(4.5 * d + 1.75)) for d in range(320)]
     assert coef[0::2].tolist() == [[512, 1536]] * 160
@@ -36,7 +36,7 @@ def test_1440_to_320_alternates_quarter_and_three_quarter_weights():
 
 
 def test_identity_takes_every_pixel_whole():
-    from hippomm_amd.segmentation import resize_linear_tables
+    from hippomm_amd.resize import resize_linear_tables
     ofs, coef = resize_linear_tables(180, 180)
     assert ofs.tolist() == list(range(180))
     assert coef.tolist() == [[2048, 0]] * 180
@@ -45,7 +45,7 @@ def test_identity_takes_every_pixel_whole():
 def test_a_product_ending_in_one_half_rounds_to_even():
     """2049 -> 2048: f = (2 d + 1) / 4096 exactly, so f * 2048 = d + 0.5 and (1 - f) * 2048 = 2047 - d + 0.5; rint goes to the even
     neighbour of each (round-half-up would give (2048, 1) at d = 0)."""
-    from hippomm_amd.segmentation import resize_linear_tables
+    from hippomm_amd.resize import resize_linear_tables
     ofs, coef = resize_linear_tables(2049, 2048)
     assert ofs[:6].tolist() == [0, 1, 2, 3, 4, 5]
     assert coef[:6].tolist() == [[2048, 0], [2046, 2], [2046, 2], [2044, 4], [2044, 4], [2042, 6]]
@@ -54,7 +54,7 @@ def test_a_product_ending_in_one_half_rounds_to_even():
 @pytest.mark.parametrize("src,dst", [(1920, 320), (1440, 320), (1080, 180), (1280, 320), (720, 180), (323, 320), (181, 180),
                                      (640, 320), (400, 180), (11, 7), (9, 5), (2049, 2048), (7, 7), (1000, 333), (4097, 1031)])
 def test_tables_equal_the_index_by_index_restatement(src, dst):
-    from hippomm_amd.segmentation import resize_linear_tables
+    from hippomm_amd.resize import resize_linear_tables
     ofs, coef = resize_linear_tables(src, dst)
     want_ofs, want_coef = ro.tables(src, dst)
     assert ofs.tolist() == want_ofs.tolist() and coef.tolist() == want_coef.tolist()
@@ -63,7 +63,7 @@ def test_tables_equal_the_index_by_index_restatement(src, dst):
 
 
 def test_tables_are_cached_and_read_only():
-    from hippomm_amd.segmentation import resize_linear_tables
+    from hippomm_amd.resize import resize_linear_tables
     a, b = resize_linear_tables(720, 180), resize_linear_tables(720, 180)
     assert a[0] is b[0] and a[1] is b[1]
     with pytest.raises(ValueError):
@@ -72,7 +72,7 @@ def test_tables_are_cached_and_read_only():
 
 # ---- mode --------------------------------------------------------------------------------------------------------------------
 def test_mode_is_area_only_when_both_scales_are_two():
-    from hippomm_amd.segmentation import RESIZE_AREA2X, RESIZE_LINEAR, resize_mode
+    from hippomm_amd.resize import RESIZE_AREA2X, RESIZE_LINEAR, resize_mode
     assert resize_mode((360, 640), (180, 320)) == RESIZE_AREA2X
     assert resize_mode((400, 640), (180, 320)) == RESIZE_LINEAR         # only x is 2
     assert resize_mode((360, 641), (180, 320)) == RESIZE_LINEAR
@@ -84,7 +84,7 @@ def test_mode_is_area_only_when_both_scales_are_two():
 
 @pytest.mark.parametrize("src,dst", [((179, 320), (180, 320)), ((180, 319), (180, 320)), ((90, 160), (180, 320)), ((360, 300), (180, 320))])
 def test_an_enlargement_on_either_axis_is_refused(src, dst):
-    from hippomm_amd.segmentation import resize_linear_tables, resize_mode
+    from hippomm_amd.resize import resize_linear_tables, resize_mode
     with pytest.raises(ValueError, match="no larger than the source"):
         resize_mode(src, dst)
     with pytest.raises(ValueError, match="no enlargement"):
@@ -100,14 +100,14 @@ def _scores(m, entries):
 
 
 def test_walk_keeps_frame_zero_and_a_window_of_one():
-    from hippomm_amd.segmentation import walk_recall_window
+    from hippomm_amd.retrieval import walk_recall_window
     assert walk_recall_window([]) == []
     assert walk_recall_window([[NAN]]) == [0]
     assert walk_recall_window(np.zeros((1, 1))) == [0]
 
 
 def test_walk_of_two_drops_above_the_cut_only():
-    from hippomm_amd.segmentation import walk_recall_window
+    from hippomm_amd.retrieval import walk_recall_window
     assert walk_recall_window(_scores(2, {(0, 1): 0.31})) == [0]
     assert walk_recall_window(_scores(2, {(0, 1): 0.29})) == [0, 1]
     assert walk_recall_window(_scores(2, {(0, 1): 0.3})) == [0, 1]       # the reference drops on > 0.3
@@ -116,7 +116,7 @@ def test_walk_of_two_drops_above_the_cut_only():
 
 
 def test_a_dropped_frame_does_not_become_the_base():
-    from hippomm_amd.segmentation import walk_recall_window
+    from hippomm_amd.retrieval import walk_recall_window
     # 1 is dropped against 0; 2 is then compared with 0 (kept), not with 1: (1, 2) says "drop" and must not be consulted
     assert walk_recall_window(_scores(3, {(0, 1): 0.9, (0, 2): 0.1, (1, 2): 0.9})) == [0, 2]
     # 1 is kept and becomes the base: (0, 2) says "keep" and must not be consulted
@@ -126,7 +126,7 @@ def test_a_dropped_frame_does_not_become_the_base():
 
 
 def test_walk_of_eight_follows_the_last_kept_frame():
-    from hippomm_amd.segmentation import walk_recall_window
+    from hippomm_amd.retrieval import walk_recall_window
     consulted = {(0, 1): 0.8, (0, 2): 0.7, (0, 3): 0.2, (3, 4): NAN, (4, 5): 0.6, (4, 6): 0.31, (4, 7): 0.0}
     assert walk_recall_window(_scores(8, consulted)) == [0, 3, 4, 7]
     everything_new = {(i, i + 1): 0.0 for i in range(7)}
@@ -139,7 +139,7 @@ def test_the_gpu_tests_inputs_decide_far_from_the_cut():
     """tests/recall_window_cases.py, the composed oracle route: every score the walk consults is NaN or further than 1e-6 from
     0.3 (the GPU's SSIM differs from the oracle's in the last digits only), and the windows exercise what they are named for."""
     import recall_window_cases as rc
-    from hippomm_amd.segmentation import walk_recall_window
+    from hippomm_amd.retrieval import walk_recall_window
     want = {w["name"]: w for w in rc.expected()}
     for w in want.values():
         for i, j, s in w["consulted"]:

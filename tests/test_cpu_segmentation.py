@@ -115,7 +115,7 @@ def test_ssim_argument_errors_are_reported_without_a_gpu():
 
 
 def test_frame_difference_rejects_other_dtypes():
-    from hippomm_amd.segmentation import compute_frame_difference
+    from hippomm_amd.ssim import compute_frame_difference
     with pytest.raises(TypeError):
         compute_frame_difference(np.zeros((8, 8), np.float32), np.zeros((8, 8), np.float32))
 
@@ -142,3 +142,38 @@ def test_audio_only_segmentation_runs_on_the_host():
     case = R.seg_case("audio_only")
     segs = segment_sequence(None, None, case["audio"], case["sr"])
     assert [[s.start_time, s.end_time] for s in segs] == [[s["start"], s["end"]] for s in entry["segments"]]
+
+
+# the public names of the frame path's other stages, and the module each one lives in now: segmentation re-exports exactly these
+RE_EXPORTS = {
+    "ssim": ["WIN", "gray_frames", "ssim_pairs", "compute_frame_difference"],
+    "resize": ["RESIZE_COEF_SCALE", "RESIZE_LINEAR", "RESIZE_AREA2X", "resize_linear_tables", "resize_mode", "resize_frames"],
+    "retrieval": ["RECALL_SIZE", "RECALL_SIMILARITY_CUT", "walk_recall_window"],
+    "frame_cache": ["CACHE_BYTES", "UPLOAD_FRAMES", "ADJACENT_CHUNK", "FrameCache", "default_cache", "PathScorer"],
+    "frame_extraction": ["SAVE_QUALITY", "SAVE_SUBSAMPLING", "CHECK_INTERVAL", "MAX_DIFF_THRESHOLD", "MIN_SAVE_GAP", "EXTRACT_BATCH",
+                         "EXTRACT_STATE", "EXTRACT_RECORD", "ExtractionState", "save_frame", "save_frames", "extraction_records",
+                         "FrameExtractor", "extract_frames"],
+}
+OWN = ["MAX_SEGMENT_DURATION", "MIN_SEGMENT_DURATION", "FRAME_SIMILARITY_THRESHOLD", "AUDIO_SILENCE_THRESHOLD", "SEGMENT_RECORD",
+       "SEGMENT_STATE", "WALK_DONE", "WALK_FLAGGED", "WALK_BOUND", "MAX_DEVICE_STEPS", "MAX_DEVICE_WINDOWS", "SequenceSegment",
+       "audio_level", "walk_segments", "silence_cut", "segment_sequence"]
+
+
+def test_the_old_import_paths_give_the_objects_of_the_new_home_modules():
+    import importlib
+    import types
+    from hippomm_amd import segmentation
+    for home, names in RE_EXPORTS.items():
+        module = importlib.import_module(f"hippomm_amd.{home}")
+        for name in names:
+            assert getattr(segmentation, name) is getattr(module, name), (home, name)
+    # the list is complete, and nothing private came along: every public name of the module is its own or one of the above
+    public = {name for name, value in vars(segmentation).items()
+              if not name.startswith("_") and not isinstance(value, types.ModuleType)}
+    borrowed = {"annotations", "dataclass", "lru_cache", "Callable", "Iterable", "List", "Optional", "Tuple"}   # its own imports
+    assert public - borrowed == set(OWN) | {name for names in RE_EXPORTS.values() for name in names}
+    for home in RE_EXPORTS:
+        module = importlib.import_module(f"hippomm_amd.{home}")
+        private = {name for name, value in vars(module).items()
+                   if name.startswith("_") and not name.startswith("__") and not isinstance(value, types.ModuleType)}
+        assert not private & set(vars(segmentation)), (home, private & set(vars(segmentation)))

@@ -39,7 +39,7 @@ def _video(name):
 
 def _fail_saves(monkeypatch, failed):
     """save_frames answers False for these frame counts and writes nothing for them: the golden's failing cv2.imwrite calls."""
-    from hippomm_amd import segmentation as seg
+    from hippomm_amd import frame_extraction as seg             # the module whose FrameExtractor looks save_frames up
     real, names = seg.save_frames, {f"frame_{i:06d}.jpg" for i in failed}
 
     def patched(frames, paths, **kw):

@@ -28,7 +28,7 @@ def _frames(h, w, n):
 
 
 def _run(pattern, h, w, planted=None, first=1, count=None):
-    from hippomm_amd import _lib as L, segmentation as seg
+    from hippomm_amd import _lib as L, frame_extraction as seg
     lib = L.load()
     dev = L.require_gpu()
     n = 9

@@ -143,7 +143,7 @@ def test_decode_of_encode_equals_pillows_decode_of_pillows_encode(dev):
 
 def test_save_frame_and_save_frames_write_the_bytes_of_the_call(dev, tmp_path):
     import hippomm_amd
-    from hippomm_amd import segmentation as seg
+    from hippomm_amd import frame_extraction as seg
     frames = [ec.content(kind, 40, 24, 3, seed=4) for kind in ("noise", "ramp", "impulse")]
     want = hippomm_amd.encode_jpeg(frames, 95, "4:2:0", "BGR")
     assert want == [ec.pillow_bytes(f, 95, "4:2:0", "BGR") for f in frames]

@@ -83,7 +83,8 @@ def test_decode_jpeg_raises_the_same_errors_and_reads_the_switch_at_call_time(mo
 
 def test_segment_sequence_is_bitwise_the_same_with_the_device_entropy_pass(tmp_path, monkeypatch):
     from hippomm_amd import jpeg
-    from hippomm_amd.segmentation import FrameCache, PathScorer, segment_sequence
+    from hippomm_amd.frame_cache import FrameCache, PathScorer
+    from hippomm_amd.segmentation import segment_sequence
     paths = _scene_frames(tmp_path, 8, size=(160, 96), seed=5, cut_every=3)
     times = [float(i) for i in range(8)]
     kw = dict(max_segment_duration=4.0, min_segment_duration=1.0, frame_similarity_threshold=0.7)

@@ -91,7 +91,8 @@ def test_segment_sequence_on_jpeg_frames_equals_the_oracle(tmp_path):
     """segment_sequence through the device route: the segments the window walk makes from the SSIM numpy oracle on
     Pillow-decoded gray frames."""
     import ssim_oracle
-    from hippomm_amd.segmentation import default_cache, segment_sequence, walk_segments
+    from hippomm_amd.frame_cache import default_cache
+    from hippomm_amd.segmentation import segment_sequence, walk_segments
     paths = _scene_frames(tmp_path, 48, size=(640, 360), seed=3, cut_every=7)
     times = [float(i) for i in range(48)]
     gray = [ssim_oracle.gray_from_bgr(pillow(open(p, "rb").read())[..., ::-1]) for p in paths]

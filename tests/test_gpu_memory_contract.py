@@ -581,7 +581,7 @@ class Gray(Case):
         return lib.hmm_gray_u8(p["frames"], self.n, self.h, self.w, {"RGB": 0, "BGR": 1}[self.order], p["gray"], p["minmax"], None)
 
     def shim(self):
-        from hippomm_amd.segmentation import gray_frames
+        from hippomm_amd.ssim import gray_frames
         gray, minmax = gray_frames(self.inputs["frames"], self.order, return_minmax=True)
         return {"gray": gray, "minmax": minmax}
 
@@ -600,9 +600,9 @@ class Ssim(Case):
         self.pairs = np.ascontiguousarray(np.random.default_rng(n_pairs).integers(0, self.nf, (n_pairs, 2)), dtype=np.int32)
         self.inputs = {"gray": gray}
         if from_a:
-            from hippomm_amd.segmentation import _gray_into
+            from hippomm_amd.ssim import gray_into
             minmax = torch.empty((self.nf, 2), dtype=torch.int32, device=DEV)
-            _gray_into(gray, 2, None, minmax)
+            gray_into(gray, 2, None, minmax)
             self.inputs["minmax"] = minmax
         self.outs = {"scores": 8 * n_pairs}
         self.need = lib.hmm_ssim_pairs_workspace_bytes(h, w, n_pairs)
@@ -612,7 +612,7 @@ class Ssim(Case):
                                   -1.0 if self.from_a else 255.0, p.get("minmax"), p["scores"], ws, ws_bytes, None)
 
     def shim(self):
-        from hippomm_amd.segmentation import ssim_pairs
+        from hippomm_amd.ssim import ssim_pairs
         return {"scores": ssim_pairs(self.inputs["gray"], self.pairs, None if self.from_a else 255.0)}
 
 

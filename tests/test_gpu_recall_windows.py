@@ -18,7 +18,7 @@ SHAPES = [((1080, 1920), TARGET), ((720, 1280), TARGET), ((1080, 1440), TARGET),
 
 
 def _resize(frames: np.ndarray, size) -> np.ndarray:
-    from hippomm_amd.segmentation import resize_frames
+    from hippomm_amd.resize import resize_frames
     got = resize_frames(torch.from_numpy(frames).cuda(), size)
     assert got.is_cuda and got.dtype == torch.uint8 and got.is_contiguous()
     return got.cpu().numpy()
@@ -46,7 +46,7 @@ def test_the_area_path_is_taken_only_where_both_scales_are_two():
 
 @pytest.mark.parametrize("channels", [1, 3])
 def test_no_frames_and_five_distinct_frames(channels):
-    from hippomm_amd.segmentation import resize_frames
+    from hippomm_amd.resize import resize_frames
     empty = resize_frames(torch.empty((0, 37, 53, channels), dtype=torch.uint8, device="cuda"), (17, 11))
     assert tuple(empty.shape) == (0, 11, 17, channels) and empty.is_cuda
     rng = np.random.default_rng(11 + channels)
@@ -70,7 +70,7 @@ def test_extreme_frames_stay_inside_int32(src, size):
 
 
 def test_bad_input_is_refused_by_the_python_layer():
-    from hippomm_amd.segmentation import resize_frames
+    from hippomm_amd.resize import resize_frames
     frames = torch.zeros((1, 90, 160, 3), dtype=torch.uint8, device="cuda")
     with pytest.raises(ValueError, match="no larger than the source"):
         resize_frames(frames)                                            # (320, 180) would enlarge
@@ -88,7 +88,7 @@ def test_bad_input_is_refused_by_the_python_layer():
 @pytest.mark.parametrize("src,size,channels", [((11, 9), (5, 7), 3), ((14, 12), (6, 7), 3), ((181, 323), TARGET, 1), ((180, 320), TARGET, 3)])
 def test_guards_hold_inputs_stay_and_pixels_do_not_depend_on_the_poison(src, size, channels):
     from hippomm_amd import _lib
-    from hippomm_amd.segmentation import RESIZE_AREA2X, resize_linear_tables, resize_mode
+    from hippomm_amd.resize import RESIZE_AREA2X, resize_linear_tables, resize_mode
     dev = _lib.require_gpu()
     dw, dh = size
     n = 3
@@ -136,7 +136,7 @@ def test_bad_arguments_are_refused_with_nothing_written():
 @pytest.fixture(scope="module")
 def recalled(tmp_path_factory):
     from hippomm_amd import recall_window_frames
-    from hippomm_amd.segmentation import FrameCache
+    from hippomm_amd.frame_cache import FrameCache
     folder = tmp_path_factory.mktemp("recall")
     windows = [w for _, w in rc.windows()]
     paths = [[str(folder / f"w{k}" / f"frame_{int(t * 1000)}.jpg") for t, _ in w] for k, w in enumerate(windows)]
@@ -164,7 +164,7 @@ def test_recalled_windows_equal_the_composed_oracle_route(recalled):
 
 def test_only_the_kept_files_are_written_and_the_cache_holds_them(recalled):
     import os
-    from hippomm_amd.segmentation import PathScorer
+    from hippomm_amd.frame_cache import PathScorer
     import ssim_oracle as so
     _, keyed, paths, cache = recalled
     want = rc.expected()

@@ -33,7 +33,7 @@ def _bits(x) -> bytes:
 @pytest.fixture(scope="module")
 def video(tmp_path_factory):
     from PIL import Image
-    from hippomm_amd.segmentation import FrameCache, PathScorer
+    from hippomm_amd.frame_cache import FrameCache, PathScorer
     folder = tmp_path_factory.mktemp("segment_walk")
     paths = []
     for lo, hi, scene in SCENES:

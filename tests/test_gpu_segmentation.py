@@ -22,7 +22,7 @@ def _close(got, want, tol=1e-9):
 
 
 def test_ssim_pairs_matches_the_golden_in_both_range_modes():
-    from hippomm_amd.segmentation import ssim_pairs
+    from hippomm_amd.ssim import ssim_pairs
     for name in R.PAIR_CASES:
         a, b = R.pair_case(name)
         g = torch.from_numpy(np.stack([a, b])).cuda()
@@ -34,7 +34,7 @@ def test_ssim_pairs_matches_the_golden_in_both_range_modes():
 
 
 def test_consecutive_1080p_pairs_match_the_oracle_and_are_deterministic():
-    from hippomm_amd.segmentation import ssim_pairs
+    from hippomm_amd.ssim import ssim_pairs
     frames = R.consecutive_1080p(17)
     g = torch.from_numpy(frames).cuda()
     pairs = [[i + 1, i] for i in range(16)]
@@ -51,7 +51,7 @@ def test_consecutive_1080p_pairs_match_the_oracle_and_are_deterministic():
 
 
 def test_gray_kernel_is_exact_over_every_colour():
-    from hippomm_amd.segmentation import gray_frames
+    from hippomm_amd.ssim import gray_frames
     c = np.arange(1 << 24, dtype=np.uint32)
     img = np.stack([(c >> 16) & 255, (c >> 8) & 255, c & 255], axis=1).astype(np.uint8).reshape(1, 4096, 4096, 3)
     want = ssim_oracle.gray_from_bgr(img)                       # channel 0 is B
@@ -64,7 +64,7 @@ def test_gray_kernel_is_exact_over_every_colour():
 
 
 def test_compute_frame_difference_matches_the_golden():
-    from hippomm_amd.segmentation import compute_frame_difference
+    from hippomm_amd.ssim import compute_frame_difference
     for name in R.PAIR_CASES:
         a, b = R.pair_case(name)
         entry = GOLDEN["pairs"][name]
@@ -150,7 +150,8 @@ def test_unreadable_frames_raise_only_where_consulted(tmp_path):
 
 def test_jpeg_path_equals_tensor_path_on_the_same_decode(tmp_path):
     from PIL import Image
-    from hippomm_amd.segmentation import _compute_frame_similarity, gray_frames, ssim_pairs
+    from hippomm_amd.segmentation import _compute_frame_similarity
+    from hippomm_amd.ssim import gray_frames, ssim_pairs
     rng = np.random.default_rng(5)
     paths, rgbs = [], []
     for i in range(2):
@@ -164,3 +165,29 @@ def test_jpeg_path_equals_tensor_path_on_the_same_decode(tmp_path):
     gray = gray_frames(torch.from_numpy(np.stack(rgbs)).cuda(), "RGB")
     want = ssim_pairs(gray, [[0, 1]]).cpu().numpy()[0]
     assert np.float64(got).tobytes() == np.float64(want).tobytes()
+
+
+def test_back_to_back_uploads_do_not_overwrite_a_copy_in_flight():
+    """The staging buffer is reused without a host synchronisation after each upload: the second call has to wait for the first
+    call's copy before it rewrites the buffer (``PinnedStage.wait``).  Two uploads of 16 frames of 1080 x 1920 x 3 (about 100 MB
+    each) with different contents, compared on the device after both calls have returned; then a 7 x 7 frame difference straight
+    after a large upload, which shares the buffer, against its value on a quiet stream.  Measured on one MI355X host: the call
+    returns after 4.3 ms with its copy still pending for another 1.8 ms, so the second call does meet a copy in flight."""
+    from hippomm_amd import _lib
+    from hippomm_amd.ssim import compute_frame_difference, upload_frames
+    dev = _lib.require_gpu()
+    rng = np.random.default_rng(1615)
+    first = rng.integers(0, 256, (16, 1080, 1920, 3), dtype=np.uint8)
+    second = rng.integers(0, 256, (16, 1080, 1920, 3), dtype=np.uint8)
+    small = rng.integers(0, 256, (2, 7, 7, 3), dtype=np.uint8)
+    torch.cuda.synchronize()
+    quiet = compute_frame_difference(small[0], small[1])
+    torch.cuda.synchronize()
+    up1 = upload_frames(list(first), dev)
+    up2 = upload_frames(list(second), dev)
+    want1, want2 = torch.from_numpy(first).to(dev), torch.from_numpy(second).to(dev)
+    assert torch.equal(up1, want1) and torch.equal(up2, want2)
+    del want1, want2
+    upload_frames(list(first), dev)
+    busy = compute_frame_difference(small[0], small[1])
+    assert busy == quiet and np.isfinite(quiet)

@@ -81,7 +81,7 @@ def route_b(frames, folder, batch, resident=False):
 def steps_of_b(frames, kept, folder, batch=16):
     """One batch of B, its steps timed apart: upload, gray + walk + read-back, encode + write of the kept ones."""
     import torch
-    from hippomm_amd import segmentation as seg
+    from hippomm_amd import frame_extraction as seg
     from hippomm_amd._pinned import PinnedStage
     n = min(batch, len(frames))
     stage = PinnedStage((n, *frames[0].shape))
@@ -93,7 +93,7 @@ def steps_of_b(frames, kept, folder, batch=16):
 
     def walk():
         walker.fill(up)
-        walker.walk(0, [k * INTERVAL / FPS for k in range(n)], [1] * n, [0] * n, seg.MAX_DIFF_THRESHOLD, seg.MIN_SAVE_GAP)
+        walker.walk(0, [k * INTERVAL for k in range(n)], FPS, INTERVAL, [0] * n, seg.MAX_DIFF_THRESHOLD, seg.MIN_SAVE_GAP)
         return walker.read(n)
     walk_ms, (records, _) = _timed(walk)
     mine = [k for k in range(n) if records["saved"][k]]

@@ -75,7 +75,7 @@ def formation(out_path):
     import tempfile
     import torch
     from bench import write_synthetic_jpegs
-    from hippomm_amd import jpeg, segmentation
+    from hippomm_amd import frame_cache, jpeg, segmentation
     from hippomm_amd.encoder import ImageBind, synthetic_state_dict
     res = {}
     with tempfile.TemporaryDirectory(prefix="hmm_jpeg_probe_") as folder:
@@ -105,13 +105,13 @@ def formation(out_path):
         legs = {}
         for on in (True, False, True, False, True, False):
             jpeg._route["on"] = on
-            segmentation._default_cache = None                   # every leg decodes all its frames
+            frame_cache._default_cache = None                   # every leg decodes all its frames
             t = _median_ms(lambda: segmentation.segment_sequence(paths, times), 1)
             legs.setdefault("device" if on else "host", []).append(t)
             if on:
                 legs["device_decodes"] = segmentation.default_cache().device_decodes
         jpeg._route["on"] = True
-        segmentation._default_cache = None
+        frame_cache._default_cache = None
         row = {"device": min(legs["device"]), "host": min(legs["host"]), "all": legs,
                "jpeg_mean_bytes_1080p": int(mean_bytes)}
         row["host_over_device"] = round(row["host"] / row["device"], 3)

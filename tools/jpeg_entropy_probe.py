@@ -52,7 +52,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_entropy.json"))
     a = ap.parse_args()
     import torch
-    from hippomm_amd import jpeg, preprocess, segmentation
+    from hippomm_amd import frame_cache, jpeg, preprocess, segmentation
     result = {"frames": a.frames, "sizes": {}, "workloads": {}}
     for w, h in ((1280, 720), (1920, 1080)):
         data = frames(w, h, a.frames)
@@ -100,7 +100,7 @@ def main():
         legs = {"device": [], "host": []}
         for mode in ("device", "host") * 3:
             os.environ["HMM_JPEG_ENTROPY"] = mode
-            segmentation._default_cache = None                             # every leg decodes all its frames
+            frame_cache._default_cache = None                             # every leg decodes all its frames
             legs[mode].append(_median_ms(lambda: segmentation.segment_sequence(paths, times), 1))
         result["workloads"]["segment_sequence_600_1080p_ms"] = {m: min(v) for m, v in legs.items()}
     os.environ.pop("HMM_JPEG_ENTROPY", None)

@@ -51,7 +51,7 @@ def main():
     import torch
     from PIL import Image
     from jpeg_encode_probe import frames as synthetic
-    from hippomm_amd import _lib, jpeg, recall_window_frames, segmentation as seg
+    from hippomm_amd import _lib, jpeg, recall_window_frames, segmentation as seg, ssim
     dev = _lib.require_gpu()
     n = a.windows * a.frames
     host = list(synthetic(W, H, n).flip(-1).contiguous().cpu().numpy())      # BGR, on the host
@@ -62,13 +62,13 @@ def main():
     kept = None
     for rep in range(a.reps + 1):
         row = {}
-        row["upload"], up = _timed(lambda: seg._upload_frames(host, dev))
+        row["upload"], up = _timed(lambda: ssim.upload_frames(host, dev))
         row["resize"], small = _timed(lambda: seg.resize_frames(up, seg.RECALL_SIZE))
         row["encode_with_decoded"], (files, decoded) = _timed(
             lambda: jpeg.encode_jpeg(small, quality=seg.SAVE_QUALITY, subsampling=seg.SAVE_SUBSAMPLING, channel_order="BGR",
                                      return_decoded=True))
         row["gray_minmax"], (gray, minmax) = _timed(lambda: seg.gray_frames(decoded, "RGB", return_minmax=True))
-        row["ssim_pairs"], scores = _timed(lambda: seg._ssim_launch(gray, pairs, -1.0, minmax))
+        row["ssim_pairs"], scores = _timed(lambda: ssim.ssim_launch(gray, pairs, -1.0, minmax))
         row["read_back"], scores = _timed(lambda: scores.cpu().numpy())
         per = a.frames * (a.frames - 1) // 2
 

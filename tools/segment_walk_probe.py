@@ -80,10 +80,10 @@ def timed(fn):
 
 def count_host_side(fn):
     """-> (library calls, read-backs) of one host-route call: each hmm_ssim_pairs and hmm_audio_window_sums call is read back."""
-    from hippomm_amd import segmentation as seg
+    from hippomm_amd import ssim as ssim_home                     # PathScorer looks ssim_launch up on this module
     from hippomm_amd.audio_track import AudioTrack
     calls = {"hmm_ssim_pairs": 0, "hmm_audio_window_sums": 0}
-    ssim, sums = seg._ssim_launch, AudioTrack.window_sums
+    ssim, sums = ssim_home.ssim_launch, AudioTrack.window_sums
 
     def counted_ssim(*a, **k):
         calls["hmm_ssim_pairs"] += 1
@@ -92,11 +92,11 @@ def count_host_side(fn):
     def counted_sums(self, table):
         calls["hmm_audio_window_sums"] += int(len(table) > 0)
         return sums(self, table)
-    seg._ssim_launch, AudioTrack.window_sums = counted_ssim, counted_sums
+    ssim_home.ssim_launch, AudioTrack.window_sums = counted_ssim, counted_sums
     try:
         fn()
     finally:
-        seg._ssim_launch, AudioTrack.window_sums = ssim, sums
+        ssim_home.ssim_launch, AudioTrack.window_sums = ssim, sums
     return calls, sum(calls.values())
 
 
@@ -111,7 +111,8 @@ def main():
         raise SystemExit("segment_walk_probe needs a GPU: nothing is measured without one")
     from hippomm_amd import _lib
     from hippomm_amd.audio_track import AudioTrack
-    from hippomm_amd.segmentation import FrameCache, PathScorer, segment_sequence
+    from hippomm_amd.frame_cache import FrameCache, PathScorer
+    from hippomm_amd.segmentation import segment_sequence
     dev = _lib.require_gpu()
     with tempfile.TemporaryDirectory(prefix="hmm_segment_walk_") as folder:
         cache = FrameCache(cache_bytes=(a.frames + 8) * H * W)

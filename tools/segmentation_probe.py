@@ -38,17 +38,17 @@ FLOP_PER_POSITION = 5 + 9 + 3 + 2 + 4 + 2 + 1 + 1 + 1 + 1
 
 def kernels(n_pairs: int):
     import torch
-    from hippomm_amd.segmentation import _gray_into, _ssim_launch
+    from hippomm_amd.ssim import gray_into, ssim_launch
     torch.cuda.set_device(0)
     g = torch.randint(0, 256, (n_pairs + 1, H, W), dtype=torch.uint8, device="cuda", generator=torch.Generator("cuda").manual_seed(1))
     mm = torch.empty((n_pairs + 1, 2), dtype=torch.int32, device="cuda")
-    _gray_into(g, 2, None, mm)
+    gray_into(g, 2, None, mm)
     pairs = np.array([[i + 1, i] for i in range(n_pairs)], np.int32)
     for _ in range(3):
-        _ssim_launch(g, pairs, -1.0, mm)
+        ssim_launch(g, pairs, -1.0, mm)
     torch.cuda.synchronize()
     for _ in range(20):
-        _ssim_launch(g, pairs, -1.0, mm)
+        ssim_launch(g, pairs, -1.0, mm)
     torch.cuda.synchronize()
     print(f"kernels: {n_pairs} pairs x 23 calls")
 
@@ -117,7 +117,7 @@ def _write_video(folder, regime, n=600):
 def calls():
     import torch
     import ssim_oracle
-    from hippomm_amd import segmentation as seg
+    from hippomm_amd import frame_cache, segmentation as seg
     torch.cuda.set_device(0)
     rng = np.random.default_rng(3)
     out = {"frame": [H, W]}
@@ -149,7 +149,7 @@ def calls():
         seg._compute_frame_similarity(None, pa, pb)
         cold, warm = [], []
         for _ in range(10):
-            seg._default_cache = None
+            frame_cache._default_cache = None
             t0 = time.perf_counter()
             seg._compute_frame_similarity(None, pa, pb)
             cold.append(time.perf_counter() - t0)
