@@ -58,6 +58,12 @@ _SIGNATURES = {
     "hmm_cosine_topk_segmented_f64": (C.c_int, [c_ptr, C.c_int64, C.c_int, c_ptr, C.c_int, c_ptr, c_ptr, C.c_int, C.c_int, c_ptr, c_ptr,
                                                 c_ptr, c_ptr, C.c_size_t, c_ptr]),
     "hmm_rows_f64_are_f32": (C.c_int, [c_ptr, C.c_int64, C.c_int, c_ptr, c_ptr]),
+    "hmm_cosine_topk_multi_f64_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    "hmm_cosine_topk_multi_f64": (C.c_int, [c_ptr, C.c_int64, C.c_int, c_ptr, C.c_int, c_ptr, C.c_int, C.c_int, c_ptr, c_ptr, c_ptr,
+                                            c_ptr, C.c_size_t, c_ptr]),
+    "hmm_cosine_topk_segmented_multi_f64_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "hmm_cosine_topk_segmented_multi_f64": (C.c_int, [c_ptr, C.c_int64, C.c_int, c_ptr, C.c_int, c_ptr, C.c_int, c_ptr, C.c_int, C.c_int,
+                                                      c_ptr, c_ptr, c_ptr, c_ptr, C.c_size_t, c_ptr]),
     "hmm_cosine_topk_multi_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "hmm_cosine_topk_multi": (C.c_int, [c_ptr, C.c_int64, C.c_int, c_ptr, C.c_int, C.c_int, c_ptr, c_ptr, c_ptr, c_ptr,
                                         C.c_size_t, c_ptr]),

@@ -5,6 +5,10 @@
 //   scan_sims_f64_kernel     one wave per row, two rows in flight per wave, the load pattern of scan_topk_kernel (lane l reads the
 //                            float4 at columns 4 (64 j + l), j = 0..3: every load instruction of a wave covers 1 KiB contiguous).
 //                            One double per row into an [N] workspace array.  4096 B per row, read once.
+//   scan_sims_f64_multi_kernel  the same pass for up to 16 queries (the batched entry points): the queries wait in LDS, a wave
+//                            holds four rows widened in registers and reads each query fragment once per row block.  One double
+//                            per (query, row) into query-major planes, plane q at sims + q N.  Bit for bit the doubles of
+//                            scan_sims_f64_kernel for that query alone.
 //   select_f64_kernel        top-k of a range of those doubles (or of candidate pairs) under the library's total order, by one
 //                            workgroup: k rounds of a block-wide arg-max (k <= 64; a range of up to 16 pairs per thread is read once
 //                            and kept in registers), or a bitonic sort of (key, index) pairs through 1024-pair LDS chunks (k <= 1024).  Per event: one workgroup per event.  Flat: G workgroups over
@@ -74,6 +78,23 @@ __device__ __forceinline__ void row_sums_f64(const float4 (&x)[4], const double 
     S = wave_sum(s0 + s1);
 }
 
+// The norm of a query that no norm was handed in for: same lane ownership, chains and butterfly as a row's sums.
+template <bool Q64>
+__device__ __forceinline__ double query_norm_f64(const double (&a)[4][4]) {
+    double c0 = 0.0, c1 = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (j < 2) c0 = fma(a[j][c], a[j][c], c0);
+            else       c1 = fma(a[j][c], a[j][c], c1);
+        }
+    }
+    double A = sqrt(wave_sum(c0 + c1));
+    if constexpr (!Q64) A = (double)(float)A;                   // an fp32 query's norm is an fp32 number (numpy's dtype rule)
+    return A;
+}
+
 // Two rows (32 VGPRs of loads) in flight per wave, as scan_topk_kernel keeps them; the query costs 32 VGPRs as doubles.  The
 // arithmetic per row is 2048 fp64 FMAs and 1024 conversions against 4096 bytes: far below the fp64 rate that would hide HBM.
 template <bool Q64>
@@ -95,22 +116,7 @@ __global__ __launch_bounds__(256) void scan_sims_f64_kernel(const float4* __rest
             a[j][0] = (double)q.x; a[j][1] = (double)q.y; a[j][2] = (double)q.z; a[j][3] = (double)q.w;
         }
     }
-    double A;
-    if (query_norm != nullptr) {
-        A = *query_norm;
-    } else {                                                    // the query's own norm, same lane ownership, chains and butterfly
-        double c0 = 0.0, c1 = 0.0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                if (j < 2) c0 = fma(a[j][c], a[j][c], c0);
-                else       c1 = fma(a[j][c], a[j][c], c1);
-            }
-        }
-        A = sqrt(wave_sum(c0 + c1));
-        if constexpr (!Q64) A = (double)(float)A;               // an fp32 query's norm is an fp32 number (numpy's dtype rule)
-    }
+    const double A = query_norm != nullptr ? *query_norm : query_norm_f64<Q64>(a);
 
     const int64_t n_pairs = (n_rows + 1) >> 1;
     for (int64_t p = wave; p < n_pairs; p += n_waves) {
@@ -131,6 +137,183 @@ __global__ __launch_bounds__(256) void scan_sims_f64_kernel(const float4* __rest
         if (lane == 0) {
             sims[r] = v0;
             if (two) sims[r + 1] = v1;
+        }
+    }
+}
+
+// ---- the similarity pass for a batch of queries -----------------------------------------------------------------------------------
+// Up to kF64MultiQ queries per pass.  They wait in LDS in the dtype they came in (fp32: 4 KiB each, widened on read; fp64: 8 KiB),
+// laid out so that lane l reads its fragment j with conflict-free 16-byte reads; behind 16 doubles that hold every query's A.
+// A wave takes blocks of kF64MultiRows consecutive rows: 16 loads of 1 KiB each, all in flight before the first use, widened ONCE
+// into 128 VGPRs, then each query's fragment is read once per block (the next one is fetched while this one is used).
+//
+// The sums keep THE FIXED SUMMATION ORDER per (row, query): the same two fma chains per lane, lane value = chain 0 + chain 1, and
+// the butterfly's operand pairs.  The butterfly is PACKED: at off = 32 lanes 0..31 form v[l] + v[l ^ 32] of rows 0 and 1 only and
+// lanes 32..63 of rows 2 and 3 (v_permlane32_swap hands each half what it needs), at off = 16 the lane's two rows become one, and
+// off = 8, 4, 2, 1 run on that one value.  Lane l ends with the sum of row l >> 4.  Every sum formed is a butterfly sum of the same
+// two operands (IEEE addition is commutative), every sum not formed would have been a bitwise copy of one that is.
+// S and sqrt(S) are formed once per row block; D / (sqrt(S) * A) once per (row, query), by the 16 lanes that hold the row.
+constexpr int kF64MultiQ = 16;
+constexpr int kF64MultiRows = 4;
+constexpr int kF64MultiThreads = 512;                          // 8 waves, two per SIMD: one workgroup per CU at up to 256 VGPRs
+constexpr size_t kF64MultiNormBytes = kF64MultiQ * sizeof(double);
+static size_t multi_lds_bytes(int nq, bool q64) { return kF64MultiNormBytes + (size_t)nq * HMM_FEATURE_DIM * (q64 ? 8 : 4); }
+
+__device__ __forceinline__ double f64_of(uint32_t lo, uint32_t hi) { return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo)); }
+__device__ __forceinline__ uint32_t lo_of(double v) { return (uint32_t)(uint64_t)__double_as_longlong(v); }
+__device__ __forceinline__ uint32_t hi_of(double v) { return (uint32_t)((uint64_t)__double_as_longlong(v) >> 32); }
+
+// Lanes with bit 5 clear: a[l] + a[l ^ 32]; lanes with it set: b[l ^ 32] + b[l].  (swap: upper half of [0] <-> lower half of [1])
+__device__ __forceinline__ double fold32_f64(double a, double b) {
+    const auto lo = __builtin_amdgcn_permlane32_swap(lo_of(a), lo_of(b), false, false);
+    const auto hi = __builtin_amdgcn_permlane32_swap(hi_of(a), hi_of(b), false, false);
+    return f64_of(lo[0], hi[0]) + f64_of(lo[1], hi[1]);
+}
+// Lanes with bit 4 clear: a[l] + a[l ^ 16]; lanes with it set: b[l ^ 16] + b[l].  (swap: odd rows of [0] <-> even rows of [1])
+__device__ __forceinline__ double fold16_f64(double a, double b) {
+    const auto lo = __builtin_amdgcn_permlane16_swap(lo_of(a), lo_of(b), false, false);
+    const auto hi = __builtin_amdgcn_permlane16_swap(hi_of(a), hi_of(b), false, false);
+    return f64_of(lo[0], hi[0]) + f64_of(lo[1], hi[1]);
+}
+template <int J>
+__device__ __forceinline__ double lane_xor_f64(double v) {
+    return f64_of((uint32_t)lane_xor_b32<J>((int)lo_of(v)), (uint32_t)lane_xor_b32<J>((int)hi_of(v)));
+}
+// The four rows' lane values -> in lane l the wave sum of row l >> 4, with the butterfly's operand pairs.
+__device__ __forceinline__ double wave_sum4_f64(const double (&v)[4]) {
+    double u = fold16_f64(fold32_f64(v[0], v[2]), fold32_f64(v[1], v[3]));
+    u += lane_xor_f64<8>(u);
+    u += lane_xor_f64<4>(u);
+    u += lane_xor_f64<2>(u);
+    u += lane_xor_f64<1>(u);
+    return u;
+}
+
+// A query fragment as it lies in LDS, and widened.  fp32: float4 [q][j][lane], the layout of the query itself.  fp64: double2
+// [q][j][h][lane], h = 0 the columns c = 0, 1 and h = 1 the columns c = 2, 3: lane l's 16-byte reads are 16 bytes apart.
+template <bool Q64> struct QueryFrag;
+template <> struct QueryFrag<false> {
+    float4 v[4];
+    __device__ __forceinline__ void load(const unsigned char* lds, int q, int lane) {
+        const float4* p = reinterpret_cast<const float4*>(lds) + q * 256 + lane;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = p[j * 64];
+    }
+    __device__ __forceinline__ void widen(double (&a)[4][4]) const {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { a[j][0] = (double)v[j].x; a[j][1] = (double)v[j].y; a[j][2] = (double)v[j].z; a[j][3] = (double)v[j].w; }
+    }
+};
+template <> struct QueryFrag<true> {
+    double2 v[4][2];
+    __device__ __forceinline__ void load(const unsigned char* lds, int q, int lane) {
+        const double2* p = reinterpret_cast<const double2*>(lds) + q * 512 + lane;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { v[j][0] = p[(2 * j) * 64]; v[j][1] = p[(2 * j + 1) * 64]; }
+    }
+    __device__ __forceinline__ void widen(double (&a)[4][4]) const {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { a[j][0] = v[j][0].x; a[j][1] = v[j][0].y; a[j][2] = v[j][1].x; a[j][3] = v[j][1].y; }
+    }
+};
+
+template <bool Q64>
+__global__ __launch_bounds__(kF64MultiThreads) void scan_sims_f64_multi_kernel(const float4* __restrict__ store, int64_t n_rows,
+                                                                              const void* __restrict__ queries,
+                                                                              const double* __restrict__ query_norms, int nq,
+                                                                              double* __restrict__ sims) {
+    extern __shared__ __align__(16) unsigned char lds_f64_multi[];
+    double* s_norm = reinterpret_cast<double*>(lds_f64_multi);
+    unsigned char* s_query = lds_f64_multi + kF64MultiNormBytes;
+    const int lane = threadIdx.x & 63, wave_in_block = threadIdx.x >> 6;
+
+    // exactly nq queries are read: 16 bytes per thread and step, coalesced
+    if constexpr (Q64) {
+        const double2* src = static_cast<const double2*>(queries);
+        double2* dst = reinterpret_cast<double2*>(s_query);
+        for (int i = threadIdx.x; i < nq * 512; i += kF64MultiThreads) {
+            const int q = i >> 9, e = i & 511;                  // e = 2 (64 j + l) + h
+            dst[q * 512 + ((e >> 7) * 2 + (e & 1)) * 64 + ((e >> 1) & 63)] = src[i];
+        }
+    } else {
+        const float4* src = static_cast<const float4*>(queries);
+        float4* dst = reinterpret_cast<float4*>(s_query);
+        for (int i = threadIdx.x; i < nq * 256; i += kF64MultiThreads) dst[i] = src[i];
+    }
+    __syncthreads();
+    for (int q = wave_in_block; q < nq; q += kF64MultiThreads / 64) {
+        double A;
+        if (query_norms != nullptr) {
+            A = query_norms[q];
+        } else {
+            QueryFrag<Q64> f;
+            double a[4][4];
+            f.load(s_query, q, lane);
+            f.widen(a);
+            A = query_norm_f64<Q64>(a);
+        }
+        if (lane == 0) s_norm[q] = A;
+    }
+    __syncthreads();
+
+    const int64_t wave = (int64_t)blockIdx.x * (kF64MultiThreads / 64) + wave_in_block;
+    const int64_t n_waves = (int64_t)gridDim.x * (kF64MultiThreads / 64);
+    const int64_t n_blocks = (n_rows + kF64MultiRows - 1) / kF64MultiRows;
+    const int mine = lane >> 4;                                 // the row of the block whose sums this lane ends up with
+    for (int64_t b = wave; b < n_blocks; b += n_waves) {
+        const int64_t r0 = b * kF64MultiRows;
+        float4 x[kF64MultiRows][4];
+#pragma unroll
+        for (int i = 0; i < kF64MultiRows; ++i) {
+            const int64_t r = (r0 + i) < n_rows ? (r0 + i) : (n_rows - 1);      // wave-uniform; the last row again, never a row past the end
+            const float4* p = store + r * 256 + lane;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) x[i][j] = ld16<true>(p + j * 64);
+        }
+        __builtin_amdgcn_sched_barrier(0);                      // all sixteen loads in flight before the first use
+        double xd[kF64MultiRows][4][4], s[kF64MultiRows];
+#pragma unroll
+        for (int i = 0; i < kF64MultiRows; ++i) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {                       // v_cvt_f64_f32: exact
+                xd[i][j][0] = (double)x[i][j].x; xd[i][j][1] = (double)x[i][j].y; xd[i][j][2] = (double)x[i][j].z; xd[i][j][3] = (double)x[i][j].w;
+            }
+            double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    if (j < 2) s0 = fma(xd[i][j][c], xd[i][j][c], s0);
+                    else       s1 = fma(xd[i][j][c], xd[i][j][c], s1);
+                }
+            }
+            s[i] = s0 + s1;
+        }
+        const double root = sqrt(wave_sum4_f64(s));             // of row r0 + mine
+        const bool writes = (lane & 15) == 0 && (r0 + mine) < n_rows;
+        double* out = sims + r0 + mine;
+
+        QueryFrag<Q64> next;
+        next.load(s_query, 0, lane);
+        for (int q = 0; q < nq; ++q) {
+            double a[4][4], d[kF64MultiRows];
+            next.widen(a);
+            next.load(s_query, (q + 1) < nq ? (q + 1) : q, lane);
+#pragma unroll
+            for (int i = 0; i < kF64MultiRows; ++i) {
+                double d0 = 0.0, d1 = 0.0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        if (j < 2) d0 = fma(xd[i][j][c], a[j][c], d0);
+                        else       d1 = fma(xd[i][j][c], a[j][c], d1);
+                    }
+                }
+                d[i] = d0 + d1;
+            }
+            const double sim = wave_sum4_f64(d) / (root * s_norm[q]);
+            if (writes) out[(int64_t)q * n_rows] = sim;
         }
     }
 }
@@ -224,11 +407,14 @@ __global__ __launch_bounds__(1024) void select_f64_kernel(const double* __restri
                                                                        const uint32_t* __restrict__ cand_pos, uint32_t n_cand, int k,
                                                                        uint64_t* __restrict__ out_keys, uint32_t* __restrict__ out_pos,
                                                                        int64_t* __restrict__ idx_out, double* __restrict__ sim_out,
-                                                                       int32_t* __restrict__ counts_out, int pad) {
+                                                                       int32_t* __restrict__ counts_out, int pad,
+                                                                       int64_t plane_stride, int64_t cand_stride) {
     __shared__ Pair64 wave_best[16];
     __shared__ uint64_t s_keys[SORT ? 2048 : 1];
     __shared__ uint32_t s_pos[SORT ? 2048 : 1];
     const unsigned g = blockIdx.x;
+    sims += (int64_t)blockIdx.y * plane_stride;                 // the query's plane and candidates (a batched call; else y = 0)
+    if (cand_keys != nullptr) { cand_keys += (int64_t)blockIdx.y * cand_stride; cand_pos += (int64_t)blockIdx.y * cand_stride; }
     SelectIn in{sims, cand_keys, cand_pos, 0, 0u, 0u};
     int64_t sim_base = 0;
     if (cand_keys != nullptr) {
@@ -249,7 +435,7 @@ __global__ __launch_bounds__(1024) void select_f64_kernel(const double* __restri
         in.pos_base = (uint32_t)lo;
         in.n = (uint32_t)(hi - lo);
     }
-    const int64_t out0 = (int64_t)g * k;
+    const int64_t range = (int64_t)blockIdx.y * gridDim.x + g, out0 = range * k;
     int found = 0;                                              // block-uniform
 
     auto emit = [&](int t, const Pair64& p) {                   // one thread writes slot t
@@ -308,7 +494,7 @@ __global__ __launch_bounds__(1024) void select_f64_kernel(const double* __restri
     if constexpr (FINAL) {
         if (pad)
             for (int t = found + threadIdx.x; t < k; t += blockDim.x) { idx_out[out0 + t] = -1; sim_out[out0 + t] = 0.0; }
-        if (counts_out != nullptr && threadIdx.x == 0) counts_out[g] = found;
+        if (counts_out != nullptr && threadIdx.x == 0) counts_out[range] = found;
     } else {
         for (int t = found + threadIdx.x; t < k; t += blockDim.x) { out_keys[out0 + t] = 0ull; out_pos[out0 + t] = kNoPos; }
     }
@@ -430,6 +616,102 @@ static void launch_scan_f64(const float* store, int64_t n, const void* query, in
     else                  scan_sims_f64_kernel<false><<<scan_grid_f64(n), 256, 0, st>>>(s4, n, query, query_norm, sims);
 }
 
+// One pass of the batched scan: nq <= kF64MultiQ queries into nq planes of n doubles.  A pass of one query is the single kernel.
+static int launch_scan_f64_multi(const float* store, int64_t n, const void* queries, int query_dtype, const double* query_norms, int nq,
+                                 double* sims, hipStream_t st) {
+    if (nq == 1) {
+        launch_scan_f64(store, n, queries, query_dtype, query_norms, sims, st);
+        return HMM_OK;
+    }
+    const float4* s4 = reinterpret_cast<const float4*>(store);
+    const int64_t blocks = ((n + kF64MultiRows - 1) / kF64MultiRows + kF64MultiThreads / 64 - 1) / (kF64MultiThreads / 64);
+    const unsigned grid = (unsigned)(blocks < 1 ? 1 : (blocks > kNumCU ? kNumCU : blocks));     // one workgroup per CU: registers and LDS
+    const size_t lds = multi_lds_bytes(nq, query_dtype == 1);
+    if (query_dtype == 1) {
+        HMM_ENSURE_DYN_LDS(scan_sims_f64_multi_kernel<true>, (int)multi_lds_bytes(kF64MultiQ, true));
+        scan_sims_f64_multi_kernel<true><<<grid, kF64MultiThreads, lds, st>>>(s4, n, queries, query_norms, nq, sims);
+    } else {
+        HMM_ENSURE_DYN_LDS(scan_sims_f64_multi_kernel<false>, (int)multi_lds_bytes(kF64MultiQ, false));
+        scan_sims_f64_multi_kernel<false><<<grid, kF64MultiThreads, lds, st>>>(s4, n, queries, query_norms, nq, sims);
+    }
+    return HMM_OK;
+}
+
+// hmm_cosine_topk_f64's selection for nq planes of n doubles (plane q at sims + q n) into rows q of (nq, k_eff) outputs: the same
+// launches with the query as the second grid dimension of the two levels; min(k, n) > 1024 sorts plane after plane through the
+// one pair buffer.
+static void select_flat_multi_f64(const double* sims, int64_t n, const F64Plan& p, int nq, uint64_t* keys, uint32_t* pos, int64_t* idx_out,
+                            double* sim_out, int32_t* n_out, hipStream_t st) {
+    if (p.global_sort) {
+        const int64_t half = p.n_pad / 2;
+        for (int q = 0; q < nq; ++q) {
+            const double* plane = sims + (int64_t)q * n;
+            keys_from_sims_f64_kernel<<<(unsigned)((p.n_pad + 255) / 256), 256, 0, st>>>(plane, n, p.n_pad, keys, pos);
+            for (int64_t size = 2; size <= p.n_pad; size <<= 1)
+                for (int64_t stride = size >> 1; stride > 0; stride >>= 1)
+                    bitonic_global_f64_step_kernel<<<(unsigned)((half + 255) / 256), 256, 0, st>>>(keys, pos, half, stride, size);
+            decode_sorted_f64_kernel<<<(p.k_eff + 255) / 256, 256, 0, st>>>(pos, plane, p.k_eff, idx_out + (int64_t)q * p.k_eff,
+                                                                            sim_out + (int64_t)q * p.k_eff, n_out ? n_out + q : nullptr);
+        }
+        return;
+    }
+    const int64_t per = (n + p.groups - 1) / p.groups, cand = (int64_t)p.groups * p.k_eff;
+    const dim3 first(p.groups, nq), second(1, nq);
+    if (p.k_eff <= kF64ArgmaxK) {
+        select_f64_kernel<false, false><<<first, argmax_threads(per), 0, st>>>(sims, n, nullptr, nullptr, nullptr, 0u, p.k_eff, keys, pos,
+                                                                              nullptr, nullptr, nullptr, 0, n, 0);
+        select_f64_kernel<false, true><<<second, argmax_threads(cand), 0, st>>>(sims, n, nullptr, keys, pos, (uint32_t)cand, p.k_eff, nullptr,
+                                                                               nullptr, idx_out, sim_out, n_out, 0, n, cand);
+    } else {
+        select_f64_kernel<true, false><<<first, 1024, 0, st>>>(sims, n, nullptr, nullptr, nullptr, 0u, p.k_eff, keys, pos, nullptr, nullptr,
+                                                              nullptr, 0, n, 0);
+        select_f64_kernel<true, true><<<second, 1024, 0, st>>>(sims, n, nullptr, keys, pos, (uint32_t)cand, p.k_eff, nullptr, nullptr, idx_out,
+                                                               sim_out, n_out, 0, n, cand);
+    }
+}
+
+// hmm_cosine_topk_segmented_f64's selection for nq planes into (nq, E, k) outputs: one workgroup per (query, event).
+static void select_segments_multi_f64(const double* sims, int64_t n, const int64_t* seg_off, int n_segments, int k, int nq, int64_t* idx_out,
+                                double* sim_out, int32_t* n_out, hipStream_t st) {
+    const dim3 grid(n_segments, nq);
+    if (k <= kF64ArgmaxK)
+        select_f64_kernel<false, true><<<grid, 256, 0, st>>>(sims, n, seg_off, nullptr, nullptr, 0u, k, nullptr, nullptr, idx_out, sim_out,
+                                                             n_out, 1, n, 0);
+    else
+        select_f64_kernel<true, true><<<grid, 1024, 0, st>>>(sims, n, seg_off, nullptr, nullptr, 0u, k, nullptr, nullptr, idx_out, sim_out,
+                                                             n_out, 1, n, 0);
+}
+
+// The batched plan: the flat plan with min(Q, 16) planes and as many candidate lists (one pair buffer for the full sort).
+static F64Plan flat_plan_multi(int64_t n, int n_queries, int k) {
+    F64Plan p = flat_plan(n, k);
+    const size_t planes = (size_t)(n_queries < kF64MultiQ ? n_queries : kF64MultiQ);
+    const size_t pairs = p.global_sort ? (size_t)p.n_pad : planes * (size_t)p.groups * p.k_eff;
+    p.keys_off = align_up(planes * (size_t)n * sizeof(double), 256);
+    p.pos_off = p.keys_off + align_up(pairs * sizeof(uint64_t), 256);
+    p.total = p.pos_off + align_up(pairs * sizeof(uint32_t), 256);
+    return p;
+}
+
+static int check_multi(const char* what, const float* store, int64_t n_rows, int dim, const void* queries, int query_dtype,
+                       const double* query_norms, int n_queries, int k, const int64_t* idx_out, const double* sim_out,
+                       const int32_t* n_out, const void* workspace) {
+    HMM_REQUIRE(dim == HMM_FEATURE_DIM, HMM_E_INVALID, "%s: dim must be %d, got %d", what, HMM_FEATURE_DIM, dim);
+    HMM_REQUIRE(query_dtype == 0 || query_dtype == 1, HMM_E_INVALID, "%s: query_dtype must be 0 (fp32) or 1 (fp64), got %d", what,
+                query_dtype);
+    HMM_REQUIRE(n_queries >= 1, HMM_E_INVALID, "%s: n_queries must be >= 1", what);
+    HMM_REQUIRE(n_rows >= 0 && n_rows < (int64_t)0xFFFFFFFFll, HMM_E_INVALID, "%s: n_rows out of range", what);
+    HMM_REQUIRE(k >= 1, HMM_E_INVALID, "%s: k must be >= 1", what);
+    HMM_REQUIRE(queries != nullptr && idx_out != nullptr && sim_out != nullptr && workspace != nullptr &&
+                    (n_rows == 0 || store != nullptr), HMM_E_INVALID, "%s: null pointer", what);
+    HMM_REQUIRE(((uintptr_t)store & 15) == 0 && ((uintptr_t)queries & 15) == 0 && ((uintptr_t)workspace & 15) == 0, HMM_E_INVALID,
+                "%s: store, queries and workspace must be 16-byte aligned", what);
+    HMM_REQUIRE(((uintptr_t)query_norms & 7) == 0 && ((uintptr_t)idx_out & 7) == 0 && ((uintptr_t)sim_out & 7) == 0 &&
+                    ((uintptr_t)n_out & 3) == 0, HMM_E_INVALID,
+                "%s: query_norms, idx_out and sim_out must be 8-byte aligned, n_out 4-byte aligned", what);
+    return HMM_OK;
+}
+
 }  // namespace hmm
 
 using namespace hmm;
@@ -469,14 +751,14 @@ extern "C" int hmm_cosine_topk_f64(const float* store_dev, int64_t n_rows, int d
     } else if (p.k_eff <= kF64ArgmaxK) {
         const int64_t per = (n_rows + p.groups - 1) / p.groups, cand = (int64_t)p.groups * p.k_eff;
         select_f64_kernel<false, false><<<p.groups, argmax_threads(per), 0, st>>>(sims, n_rows, nullptr, nullptr, nullptr, 0u, p.k_eff, keys,
-                                                                                 pos, nullptr, nullptr, nullptr, 0);
+                                                                                 pos, nullptr, nullptr, nullptr, 0, 0, 0);
         select_f64_kernel<false, true><<<1, argmax_threads(cand), 0, st>>>(sims, n_rows, nullptr, keys, pos, (uint32_t)cand, p.k_eff, nullptr,
-                                                                          nullptr, idx_out_dev, sim_out_dev, n_out_dev, 0);
+                                                                          nullptr, idx_out_dev, sim_out_dev, n_out_dev, 0, 0, 0);
     } else {
         select_f64_kernel<true, false><<<p.groups, 1024, 0, st>>>(sims, n_rows, nullptr, nullptr, nullptr, 0u, p.k_eff, keys, pos, nullptr,
-                                                                 nullptr, nullptr, 0);
+                                                                 nullptr, nullptr, 0, 0, 0);
         select_f64_kernel<true, true><<<1, 1024, 0, st>>>(sims, n_rows, nullptr, keys, pos, (uint32_t)(p.groups * p.k_eff), p.k_eff, nullptr,
-                                                          nullptr, idx_out_dev, sim_out_dev, n_out_dev, 0);
+                                                          nullptr, idx_out_dev, sim_out_dev, n_out_dev, 0, 0, 0);
     }
     HMM_LAUNCH_CHECK();
     return HMM_OK;
@@ -511,10 +793,10 @@ extern "C" int hmm_cosine_topk_segmented_f64(const float* store_dev, int64_t n_r
     }
     if (k <= kF64ArgmaxK)
         select_f64_kernel<false, true><<<n_segments, 256, 0, st>>>(sims, n_rows, seg_offsets_dev, nullptr, nullptr, 0u, k, nullptr, nullptr,
-                                                                   idx_out_dev, sim_out_dev, n_out_dev, 1);
+                                                                   idx_out_dev, sim_out_dev, n_out_dev, 1, 0, 0);
     else
         select_f64_kernel<true, true><<<n_segments, 1024, 0, st>>>(sims, n_rows, seg_offsets_dev, nullptr, nullptr, 0u, k, nullptr, nullptr,
-                                                                   idx_out_dev, sim_out_dev, n_out_dev, 1);
+                                                                   idx_out_dev, sim_out_dev, n_out_dev, 1, 0, 0);
     HMM_LAUNCH_CHECK();
     return HMM_OK;
 }
@@ -534,6 +816,80 @@ extern "C" int hmm_rows_f64_are_f32(const double* src_dev, int64_t n_rows, int d
         const int64_t n_values = n_rows * HMM_FEATURE_DIM;
         const int64_t blocks = (n_values + 256 * 16 - 1) / (256 * 16);
         rows_f64_are_f32_kernel<<<(unsigned)(blocks > kScanBlocks ? kScanBlocks : blocks), 256, 0, st>>>(src_dev, n_values, report);
+        HMM_LAUNCH_CHECK();
+    }
+    return HMM_OK;
+}
+
+// ---- the batched entry points: one pass over the store per 16 queries -------------------------------------------------------------
+extern "C" size_t hmm_cosine_topk_multi_f64_workspace_bytes(int64_t n_rows, int n_queries, int k) {
+    if (n_rows < 1 || n_rows >= (int64_t)0xFFFFFFFFll || n_queries < 1 || k < 1) return 0;
+    return flat_plan_multi(n_rows, n_queries, k).total;
+}
+
+extern "C" int hmm_cosine_topk_multi_f64(const float* store_dev, int64_t n_rows, int dim, const void* queries_dev, int query_dtype,
+                                         const double* query_norms_dev, int n_queries, int k, int64_t* idx_out_dev, double* sim_out_dev,
+                                         int32_t* n_out_dev, void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream) {
+    const char* what = "cosine_topk_multi_f64";
+    int rc = check_multi(what, store_dev, n_rows, dim, queries_dev, query_dtype, query_norms_dev, n_queries, k, idx_out_dev, sim_out_dev,
+                         n_out_dev, workspace_dev);
+    if (rc != HMM_OK) return rc;
+    HMM_REQUIRE(n_rows >= 1, HMM_E_INVALID, "%s: n_rows must be >= 1", what);
+    const F64Plan p = flat_plan_multi(n_rows, n_queries, k);
+    HMM_REQUIRE(workspace_bytes >= p.total, HMM_E_WORKSPACE, "%s: workspace too small (%zu < %zu)", what, workspace_bytes, p.total);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace_dev);
+    double* sims = reinterpret_cast<double*>(ws + p.sims_off);
+    uint64_t* keys = reinterpret_cast<uint64_t*>(ws + p.keys_off);
+    uint32_t* pos = reinterpret_cast<uint32_t*>(ws + p.pos_off);
+    const size_t q_bytes = (size_t)HMM_FEATURE_DIM * (query_dtype == 1 ? 8 : 4);
+    for (int q0 = 0; q0 < n_queries; q0 += kF64MultiQ) {       // the passes follow each other on the stream and share the workspace
+        const int nq = n_queries - q0 < kF64MultiQ ? n_queries - q0 : kF64MultiQ;
+        rc = launch_scan_f64_multi(store_dev, n_rows, static_cast<const char*>(queries_dev) + q0 * q_bytes, query_dtype,
+                                   query_norms_dev ? query_norms_dev + q0 : nullptr, nq, sims, st);
+        if (rc != HMM_OK) return rc;
+        HMM_LAUNCH_CHECK();
+        select_flat_multi_f64(sims, n_rows, p, nq, keys, pos, idx_out_dev + (int64_t)q0 * p.k_eff, sim_out_dev + (int64_t)q0 * p.k_eff,
+                        n_out_dev ? n_out_dev + q0 : nullptr, st);
+        HMM_LAUNCH_CHECK();
+    }
+    return HMM_OK;
+}
+
+extern "C" size_t hmm_cosine_topk_segmented_multi_f64_workspace_bytes(int64_t n_rows, int n_segments, int n_queries, int k) {
+    if (n_rows < 0 || n_rows >= (int64_t)0xFFFFFFFFll || n_segments < 1 || n_queries < 1 || k < 1) return 0;
+    const size_t planes = (size_t)(n_queries < kF64MultiQ ? n_queries : kF64MultiQ);
+    return align_up(planes * (size_t)(n_rows > 0 ? n_rows : 1) * sizeof(double), 256);
+}
+
+extern "C" int hmm_cosine_topk_segmented_multi_f64(const float* store_dev, int64_t n_rows, int dim, const void* queries_dev,
+                                                   int query_dtype, const double* query_norms_dev, int n_queries,
+                                                   const int64_t* seg_offsets_dev, int n_segments, int k, int64_t* idx_out_dev,
+                                                   double* sim_out_dev, int32_t* n_out_dev, void* workspace_dev, size_t workspace_bytes,
+                                                   hmm_stream_t stream) {
+    const char* what = "cosine_topk_segmented_multi_f64";
+    int rc = check_multi(what, store_dev, n_rows, dim, queries_dev, query_dtype, query_norms_dev, n_queries, k, idx_out_dev, sim_out_dev,
+                         n_out_dev, workspace_dev);
+    if (rc != HMM_OK) return rc;
+    HMM_REQUIRE(n_segments >= 1 && k <= kF64MaxK, HMM_E_INVALID, "%s: need n_segments >= 1 and 1 <= k <= %d", what, kF64MaxK);
+    HMM_REQUIRE(seg_offsets_dev != nullptr && n_out_dev != nullptr, HMM_E_INVALID, "%s: null pointer", what);
+    HMM_REQUIRE(((uintptr_t)seg_offsets_dev & 7) == 0, HMM_E_INVALID, "%s: seg_offsets must be 8-byte aligned", what);
+    HMM_REQUIRE(workspace_bytes >= hmm_cosine_topk_segmented_multi_f64_workspace_bytes(n_rows, n_segments, n_queries, k), HMM_E_WORKSPACE,
+                "%s: workspace too small", what);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    double* sims = static_cast<double*>(workspace_dev);
+    const size_t q_bytes = (size_t)HMM_FEATURE_DIM * (query_dtype == 1 ? 8 : 4);
+    const int64_t cells = (int64_t)n_segments * k;
+    for (int q0 = 0; q0 < n_queries; q0 += kF64MultiQ) {
+        const int nq = n_queries - q0 < kF64MultiQ ? n_queries - q0 : kF64MultiQ;
+        if (n_rows > 0) {
+            rc = launch_scan_f64_multi(store_dev, n_rows, static_cast<const char*>(queries_dev) + q0 * q_bytes, query_dtype,
+                                       query_norms_dev ? query_norms_dev + q0 : nullptr, nq, sims, st);
+            if (rc != HMM_OK) return rc;
+            HMM_LAUNCH_CHECK();
+        }
+        select_segments_multi_f64(sims, n_rows, seg_offsets_dev, n_segments, k, nq, idx_out_dev + q0 * cells, sim_out_dev + q0 * cells,
+                            n_out_dev + (int64_t)q0 * n_segments, st);
         HMM_LAUNCH_CHECK();
     }
     return HMM_OK;

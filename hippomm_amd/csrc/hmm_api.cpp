@@ -17,7 +17,8 @@ void set_error(const char* fmt, ...) {
 // hmm_gray_u8, hmm_ssim_pairs_workspace_bytes, hmm_ssim_pairs; hmm_jpeg_parse, hmm_jpeg_slot_bytes, hmm_jpeg_decode_coefs,
 // hmm_jpeg_workspace_bytes, hmm_jpeg_reconstruct; hmm_jpeg_entropy_slot_bytes, hmm_jpeg_prepare_entropy,
 // hmm_jpeg_entropy_workspace_bytes, hmm_jpeg_decode_coefs_device; hmm_rank_segment_hits_filtered, hmm_rank_segment_hits_filtered_multi;
-// hmm_cosine_topk_f64, hmm_cosine_topk_segmented_f64 (and their _workspace_bytes), hmm_rows_f64_are_f32.
+// hmm_cosine_topk_f64, hmm_cosine_topk_segmented_f64 (and their _workspace_bytes), hmm_rows_f64_are_f32;
+// hmm_cosine_topk_multi_f64, hmm_cosine_topk_segmented_multi_f64 (and their _workspace_bytes).
 extern "C" int hmm_abi_version(void) { return 7; }
 extern "C" const char* hmm_last_error(void) { return hmm::g_err; }
 

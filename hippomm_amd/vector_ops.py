@@ -58,6 +58,13 @@ _F64_ROUTES = {
     "segmented": ("hmm_cosine_topk_segmented_f64", "hmm_cosine_topk_segmented_f64_workspace_bytes"),
 }
 
+# The batched float64 routes: the same, with a (Q,1024) batch, one norm per question and Q after the norms:
+#   store, n, dim, queries, query dtype, query norms, Q, [seg_offsets, E,] k, outputs..., workspace, workspace bytes, stream
+_F64_MULTI_ROUTES = {
+    "flat": ("hmm_cosine_topk_multi_f64", "hmm_cosine_topk_multi_f64_workspace_bytes"),
+    "segmented": ("hmm_cosine_topk_segmented_multi_f64", "hmm_cosine_topk_segmented_multi_f64_workspace_bytes"),
+}
+
 _I64, _F32, _I32 = (torch.int64, np.int64, 8), (torch.float32, np.float32, 4), (torch.int32, np.int32, 4)
 _F64 = (torch.float64, np.float64, 8)
 
@@ -92,7 +99,7 @@ def _hits_layout(*shape):
 
 @functools.lru_cache(maxsize=64)
 def _hits_layout_f64(*shape):
-    """idx | sims (float64) | counts of a segmented float64 scan; shape = (E, k).  Both 8-byte fields come first."""
+    """idx | sims (float64) | counts of a segmented float64 scan; shape = (E, k) or (Q, E, k).  Both 8-byte fields come first."""
     return _Packed((_I64, shape), (_F64, shape), (_I32, shape[:-1]))
 
 
@@ -184,6 +191,42 @@ def _exact64_query(a, dev):
     # 8 unused bytes | norm | query: the query starts 16 bytes into the (256-byte aligned) allocation
     buf = torch.from_numpy(np.concatenate([np.zeros(8, np.uint8), norm.view(np.uint8), host.view(np.uint8)])).to(dev)
     return buf, buf.data_ptr() + 16, int(host.dtype == np.float64), buf.data_ptr() + 8
+
+
+def _exact64_queries(queries, dev):
+    """The batch form of ``_exact64_query``: (buffer, address of the (Q,1024) batch, dtype code, address of the Q norms or None, Q).
+    A host batch keeps its dtype (float32 or float64; anything else becomes float32) and travels with one norm per question in the
+    same upload, each ``np.linalg.norm(row)`` of the contiguous 1-D row -- the call the single route and the reference make;
+    ``norm(q, axis=1)`` sums along another path and need not give its bits.  A device batch is used where it lies and the kernel
+    forms the norms.  The batch starts at a 16-byte boundary either way."""
+    if isinstance(queries, torch.Tensor) and queries.is_cuda:
+        q = queries.detach()
+        if q.dim() != 2 or q.shape[1] != FEATURE_DIM:
+            raise ValueError(f"queries must be (Q,{FEATURE_DIM}), got {tuple(q.shape)}")
+        if q.shape[0] == 0:
+            raise ValueError("no queries")
+        if q.dtype not in (torch.float32, torch.float64):
+            q = q.to(torch.float32)
+        q = q.to(dev).contiguous()
+        if q.data_ptr() % 16:
+            q = q.clone()
+        return q, q.data_ptr(), int(q.dtype == torch.float64), None, q.shape[0]
+    host = queries.detach().numpy() if isinstance(queries, torch.Tensor) else np.asarray(queries)
+    if host.ndim != 2 or host.shape[1] != FEATURE_DIM:
+        raise ValueError(f"queries must be (Q,{FEATURE_DIM}), got {tuple(host.shape)}")
+    if host.shape[0] == 0:
+        raise ValueError("no queries")
+    host = np.ascontiguousarray(host, dtype=host.dtype if host.dtype in (np.float32, np.float64) else np.float32)
+    Q = host.shape[0]
+    norms = np.zeros(Q + (Q & 1), dtype=np.float64)                       # an even number of doubles: the batch behind them stays 16-byte aligned
+    norms[:Q] = [np.linalg.norm(row) for row in host]                     # each in the query's dtype, widened
+    buf = torch.from_numpy(np.concatenate([norms.view(np.uint8), host.reshape(-1).view(np.uint8)])).to(dev)
+    if buf.data_ptr() % 16:                                               # a host buffer (no GPU in the process) may lie anywhere
+        spare = torch.empty(buf.numel() + 16, dtype=torch.uint8, device=buf.device)
+        skew = (-spare.data_ptr()) % 16
+        spare[skew: skew + buf.numel()].copy_(buf)
+        buf = spare[skew: skew + buf.numel()]
+    return buf, buf.data_ptr() + norms.nbytes, int(host.dtype == np.float64), buf.data_ptr(), Q
 
 
 def rank_hits_exact64(idx, sims, counts, keep: int, row_limits=None, defer=None, min_similarity: float = 0.4):
@@ -328,6 +371,49 @@ class FeatureStore:
             self._scan_f64("flat", query, k, (idx, sims, n_out))
         return idx, sims
 
+    def _scan_f64_multi(self, shape: str, queries, k: int, outputs, seg_offsets: torch.Tensor = None):
+        """One call of the batched float64 route ``shape`` of _F64_MULTI_ROUTES into ``outputs`` (one pass over the store per 16
+        questions inside it); ``queries`` is what _exact64_queries returned.  Does not synchronise."""
+        name, size_name = _F64_MULTI_ROUTES[shape]
+        lib = _lib.load()
+        _, q_ptr, q_dtype, norms_ptr, Q = queries
+        n = len(self)
+        segments = () if seg_offsets is None else (seg_offsets.data_ptr(), seg_offsets.numel() - 1)
+        ws = self._scratch(getattr(lib, size_name)(n, *segments[1:], Q, k))
+        _lib.check(getattr(lib, name)(self.rows.data_ptr(), n, FEATURE_DIM, q_ptr, q_dtype, norms_ptr, Q, *segments, k,
+                                      *[t.data_ptr() for t in outputs], ws.data_ptr(), ws.numel(), _lib.stream_ptr()), name)
+
+    def _search_multi_f64(self, queries, k: int):
+        """The float64 route of search_multi_device: (idx (Q,k') int64, sims (Q,k') float64), k' = min(k, N)."""
+        if int(k) < 1:
+            raise ValueError("k must be >= 1")
+        batch = _exact64_queries(queries, self.rows.device)
+        dev, Q, k_out = self.rows.device, batch[-1], min(int(k), len(self))
+        idx = torch.empty(Q, k_out, dtype=torch.int64, device=dev)
+        sims = torch.empty(Q, k_out, dtype=torch.float64, device=dev)
+        n_out = torch.empty(Q, dtype=torch.int32, device=dev)
+        if k_out > 0:
+            self._scan_f64_multi("flat", batch, int(k), (idx, sims, n_out))
+        return idx, sims
+
+    def _search_segments_multi_packed_f64(self, queries, seg_offsets: torch.Tensor, k: int):
+        """The float64 route of _search_segments_multi_packed: (packed, idx (Q,E,k), sims float64, counts (Q,E)), one buffer
+        (_hits_layout_f64)."""
+        if int(k) < 1:
+            raise ValueError("k must be >= 1")
+        batch = _exact64_queries(queries, self.rows.device)
+        Q, E, k = batch[-1], seg_offsets.numel() - 1, int(k)
+        layout = _hits_layout_f64(Q, E, k)
+        packed = torch.empty(layout.nbytes, dtype=torch.uint8, device=self.rows.device)
+        idx, sims, counts = layout.device_views(packed)
+        if E > 0 and len(self) == 0:                             # events without a row: the padding is the answer
+            idx.fill_(-1)
+            sims.zero_()
+            counts.zero_()
+        elif E > 0:
+            self._scan_f64_multi("segmented", batch, k, (idx, sims, counts), seg_offsets=seg_offsets)
+        return packed, idx, sims, counts
+
     def _scratch(self, need_bytes: int) -> torch.Tensor:
         """The workspace, reallocated only when it is too small.  No route reads what an earlier call left in it."""
         if self._ws is None or self._ws.numel() < need_bytes:
@@ -465,14 +551,18 @@ class FeatureStore:
         return (packed, *outputs)
 
     def search_segments_multi_device(self, queries, seg_offsets: torch.Tensor, k: int, prefilter: bool = False,
-                                     stats: torch.Tensor = None):
+                                     stats: torch.Tensor = None, exact64: bool = False):
         """``search_segments_device`` for a batch of questions in one pass over the store per 16 of them
         (hmm_cosine_topk_segmented_multi).  queries: (Q,1024) numpy or torch, any device, fp32 or fp64.  Returns CUDA tensors
         idx (Q,E,k) int64 rows within each event (-1 padded), sims (Q,E,k) fp32, counts (Q,E) int32 = min(k, n_e), without
         synchronising.  ``prefilter``: stream the bf16 shadow (built on first use) and re-score each event's candidates on the
         fp32 rows -- the same outputs, bit for bit (hmm_cosine_topk_segmented_multi_prefilter); ``stats``: optional int32[2]
         CUDA tensor receiving ((event, question) pairs that re-scored the whole event, rows re-scored), -1 / -1 when the exact
-        function was the whole call."""
+        function was the whole call.  ``exact64=True``: the float64 route for the batch (hmm_cosine_topk_segmented_multi_f64): sims
+        (Q,E,k) float64, slice q what ``search_segments_device(queries[q], ..., exact64=True)`` returns, bit for bit; the batch is
+        all fp32 or all fp64; not together with ``prefilter``."""
+        if self._use_exact64(exact64, "search_segments_multi_device", bool(prefilter)):
+            return self._search_segments_multi_packed_f64(queries, seg_offsets, k)[1:]
         return self._search_segments_multi_packed(queries, seg_offsets, k, prefilter, stats)[1:]
 
     def _search_segments_multi_packed(self, queries, seg_offsets: torch.Tensor, k: int, prefilter: bool = False,
@@ -493,13 +583,19 @@ class FeatureStore:
             self._scan("segmented_multi", bool(prefilter), q, k, (idx, sims, counts), Q=Q, seg_offsets=seg_offsets, stats=stats)
         return packed, idx, sims, counts
 
-    def search_multi_device(self, queries: torch.Tensor, k: int, prefilter: bool = None, stats: torch.Tensor = None):
+    def search_multi_device(self, queries: torch.Tensor, k: int, prefilter: bool = None, stats: torch.Tensor = None,
+                            exact64: bool = False):
         """queries (Q,1024) fp32 on the store's device -> (idx (Q,k') int64, sims (Q,k') fp32) device tensors,
         k' = min(k, N).  One pass over the store per 16 queries (hmm_cosine_topk_multi).  ``prefilter=True``: one pass over the
         bf16 shadow instead, candidates re-scored on the fp32 rows -- the same outputs, bit for bit
         (hmm_cosine_topk_multi_prefilter).  ``None`` is the exact pass even on a store built with ``shadow=True``: the shadow
         route has not been timed against it yet, and the results are the same either way; ``stats``: optional int32 (Q,2) CUDA tensor receiving per
-        question (candidates re-scored, saturated lists), -1 / -1 when the exact function was the whole call."""
+        question (candidates re-scored, saturated lists), -1 / -1 when the exact function was the whole call.
+        ``exact64=True``: the float64 route for the batch (hmm_cosine_topk_multi_f64), one pass per 16 queries: sims (Q,k') float64,
+        row q what ``search_device(queries[q], k, exact64=True)`` returns, bit for bit; the batch may be fp32 or fp64, on the host
+        or the device; not together with ``prefilter``."""
+        if self._use_exact64(exact64, "search_multi_device", bool(prefilter)):
+            return self._search_multi_f64(queries, k)
         queries = _queries_2d(queries, self.rows.device)
         nq, n, dev = queries.shape[0], len(self), self.rows.device
         idx = torch.empty(nq, k, dtype=torch.int64, device=dev)
@@ -510,9 +606,13 @@ class FeatureStore:
         kk = min(k, n)
         return idx[:, :kk], sims[:, :kk]
 
-    def search_multi(self, queries, k: int, prefilter: bool = None) -> List[Tuple[np.ndarray, np.ndarray]]:
+    def search_multi(self, queries, k: int, prefilter: bool = None, exact64: bool = False) -> List[Tuple[np.ndarray, np.ndarray]]:
         """Per query the (indices int64, similarities) pair top_k_cosine_similarity would return.  ``prefilter``: see
-        ``search_multi_device``."""
+        ``search_multi_device``.  ``exact64=True``: per query what ``search(query, k, exact64=True)`` returns, float64, from one
+        pass over the store per 16 queries; a host batch is sent with numpy's own norm of every row."""
+        if self._use_exact64(exact64, "search_multi", bool(prefilter)):
+            idx, sims = (t.cpu().numpy() for t in self._search_multi_f64(queries, k))
+            return [(idx[i], sims[i]) for i in range(idx.shape[0])]
         q = queries if isinstance(queries, torch.Tensor) else torch.from_numpy(np.asarray(queries, dtype=np.float32))
         idx, sims = self.search_multi_device(q.reshape(-1, FEATURE_DIM), k, prefilter)
         idx, sims = idx.cpu().numpy(), sims.cpu().numpy()
@@ -734,6 +834,12 @@ class EventStore(FeatureStore):
         idx_h, sims_h, counts_h = _hits_layout_f64(*idx.shape).host_views(self._read_back(packed))
         return idx_h.copy(), sims_h.copy(), counts_h.copy()
 
+    def _hits_exact64_multi(self, queries, k: int):
+        """_hits_exact64 for a batch: ONE packed read-back -> host (idx (Q,E,k) int64, sims (Q,E,k) float64, counts (Q,E) int32)."""
+        packed, idx, _, _ = self._search_segments_multi_packed_f64(queries, self.offsets, int(k))
+        idx_h, sims_h, counts_h = _hits_layout_f64(*idx.shape).host_views(self._read_back(packed))
+        return idx_h.copy(), sims_h.copy(), counts_h.copy()
+
     def top_hits(self, query, k: int = 5, keep: int = 5, prefilter: bool = False, exact64: bool = False):
         """The caller's whole step in one go (hippocampal_memory.py:3143-3153 + :3275-3277): top-k per event, then every hit of
         every event ranked by similarity and the best `keep` returned as [(event index, row inside the event, similarity)].
@@ -810,12 +916,18 @@ class EventStore(FeatureStore):
             torch.cuda.current_stream(packed.device).synchronize()
         return host.numpy()
 
-    def top_k_per_event_multi(self, queries, k: int = 5, prefilter: bool = False):
+    def top_k_per_event_multi(self, queries, k: int = 5, prefilter: bool = False, exact64: bool = False):
         """``top_k_per_event`` for a batch of questions: per query the list that ``top_k_per_event(query, k)`` returns, from one
         pass over the store per 16 questions and one read-back.  ``prefilter``: through the bf16 shadow, the same results
-        (``search_segments_multi_device``)."""
+        (``search_segments_multi_device``).  ``exact64=True``: per query what ``top_k_per_event(query, k, exact64=True)`` returns,
+        sims float64, bit for bit."""
         q = _queries_2d(queries)
         Q, E, k = q.shape[0], len(self.lengths), int(k)
+        if self._use_exact64(exact64, "top_k_per_event_multi", prefilter):
+            if E == 0 or len(self) == 0:
+                return [[(np.zeros(0, np.int64), np.zeros(0, np.float64)) for _ in range(E)] for _ in range(Q)]
+            idx_h, sims_h, counts_h = self._hits_exact64_multi(queries, k)
+            return [[(idx_h[qi, e, :counts_h[qi, e]], sims_h[qi, e, :counts_h[qi, e]]) for e in range(E)] for qi in range(Q)]
         if E == 0 or len(self) == 0:
             return [[(np.zeros(0, np.int64), np.zeros(0, np.float32)) for _ in range(E)] for _ in range(Q)]
         packed = self._search_segments_multi_packed(q, self.offsets, k, prefilter)[0]
@@ -825,15 +937,21 @@ class EventStore(FeatureStore):
             return [list(zip(idx_h[qi], sims_h[qi])) for qi in range(Q)]
         return [[(idx_h[qi, e, :counts_h[e]], sims_h[qi, e, :counts_h[e]]) for e in range(E)] for qi in range(Q)]
 
-    def top_hits_multi(self, queries, k: int = 5, keep: int = 5, prefilter: bool = False):
+    def top_hits_multi(self, queries, k: int = 5, keep: int = 5, prefilter: bool = False, exact64: bool = False):
         """``top_hits`` for a batch of questions: per query the list that ``top_hits(query, k, keep)`` returns.  One pass over the
         store per 16 questions, one ranking launch for all of them (hmm_rank_segment_hits_multi), one read-back of Q x `keep`
         hits.  keep > 64 is served by ``top_hits`` per query.  ``prefilter``: the pass streams the bf16 shadow, the same results
-        (``search_segments_multi_device``)."""
+        (``search_segments_multi_device``).  ``exact64=True``: per query what ``top_hits(query, k, keep, exact64=True)`` returns:
+        the float64 per-event top-k of the whole batch, one packed read-back of (idx, sims float64, counts), and
+        ``rank_hits_exact64`` per question on the host."""
         q = _queries_2d(queries)
         Q, E, k, keep = q.shape[0], len(self.lengths), int(k), int(keep)
+        exact64 = self._use_exact64(exact64, "top_hits_multi", prefilter)
         if E == 0 or len(self) == 0 or keep < 1:
             return [[] for _ in range(Q)]
+        if exact64:
+            idx_h, sims_h, counts_h = self._hits_exact64_multi(queries, k)
+            return [rank_hits_exact64(idx_h[qi], sims_h[qi], counts_h[qi], keep)[0] for qi in range(Q)]
         if keep > 64:
             return [self.top_hits(q[qi], k, keep, prefilter) for qi in range(Q)]
         idx, sims, counts = self.search_segments_multi_device(q, self.offsets, k, prefilter)
@@ -879,14 +997,21 @@ class EventStore(FeatureStore):
         return self._rank_relevant(packed[1:], None, int(keep), rules)[0]
 
     def relevant_hits_multi(self, queries, k: int = 5, keep: int = 5, *, row_limits=None, defer=None, min_similarity: float = 0.4,
-                            prefilter: bool = False):
+                            prefilter: bool = False, exact64: bool = False):
         """``relevant_hits`` for a batch of questions: per query the (hits, deferred) pair, from one pass over the store per 16
         questions, one ranking launch for all of them (hmm_rank_segment_hits_filtered_multi) and the same one or two read-backs.
-        The similarities are those of ``top_k_per_event_multi``."""
+        The similarities are those of ``top_k_per_event_multi``.  ``exact64=True``: per query what ``relevant_hits(query, ...,
+        exact64=True)`` returns: the float64 per-event top-k of the whole batch, one packed read-back, then both rules and the
+        stable sort per question on the host (``rank_hits_exact64``)."""
         rules = self._relevance_rules("relevant_hits_multi", k, keep, row_limits, defer, min_similarity)
         q = _queries_2d(queries)
+        exact64 = self._use_exact64(exact64, "relevant_hits_multi", prefilter)
         if not self.lengths:
             return [([], []) for _ in range(q.shape[0])]
+        if exact64:
+            idx_h, sims_h, counts_h = self._hits_exact64_multi(queries, k)
+            return [rank_hits_exact64(idx_h[qi], sims_h[qi], counts_h[qi], int(keep), rules[0], rules[1], min_similarity)
+                    for qi in range(q.shape[0])]
         packed = self._search_segments_multi_packed(q, self.offsets, int(k), prefilter)
         return self._rank_relevant(packed[1:], q.shape[0], int(keep), rules)
 

@@ -365,6 +365,43 @@ int    hmm_cosine_topk_segmented_f64(const float* store_dev, int64_t n_rows, int
                                      void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
 int    hmm_rows_f64_are_f32(const double* src_dev, int64_t n_rows, int dim, int64_t* report_dev /* [2] */, hmm_stream_t stream);
 
+/* Float64-origin stores, batched: one pass over the store per 16 queries, the same bits.
+ *
+ * queries_dev (n_queries, 1024), all fp32 (query_dtype 0) or all fp64 (1), 16-byte aligned; query_norms_dev null, or one double per
+ *   query, each used as hmm_cosine_topk_f64 uses its query_norm_dev (null: the kernel forms every norm by that call's rule,
+ *   (double)(float) for an fp32 query included).  Any n_queries >= 1: served in passes of 16 inside the call.
+ * Bit contract.  The fixed summation order above holds per (row, query), unchanged: lane ownership, the two fma chains from +0.0,
+ *   lane value = chain 0 + chain 1, the operand pairs of the butterfly 32, 16, 8, 4, 2, 1, sim = D / (sqrt(S) * A).  S does not
+ *   depend on the query and is formed once per row.  The pass forms each butterfly sum in the lanes that go on to use it (several
+ *   (row, query) values packed per step) instead of in all 64: the same two operands are added, IEEE addition is commutative, and
+ *   a sum that is not formed would have been a bitwise copy of one that is.  No matrix cores: fp64 MFMA has its own accumulation
+ *   order.  Hence the similarity of row r to query q has the bits that hmm_cosine_topk_f64 computes for query q alone, whatever
+ *   the entry point, n_queries, the query's position in the batch, its batch-mates, n_rows or k.
+ * Selection.  The single calls' kernels and total order with the query as a second grid dimension: per event one workgroup per
+ *   (query, event); flat, two exact levels per query; flat with min(k, n_rows) > 1024, the single call's full sort, query after query.
+ * hmm_cosine_topk_multi_f64: idx_out_dev int64 (n_queries, k'), sim_out_dev fp64 (n_queries, k'), k' = min(k, n_rows): row q is what
+ *   hmm_cosine_topk_f64 writes for query q, bit for bit; n_out_dev (nullable) int32[n_queries] = k'.  n_rows >= 1.
+ * hmm_cosine_topk_segmented_multi_f64: idx_out_dev (n_queries, n_segments, k) int64, -1 padded, sim_out_dev the same shape fp64, 0.0
+ *   padded, n_out_dev (n_queries, n_segments) int32: slice q is what hmm_cosine_topk_segmented_f64 writes for query q.  k <= 1024.
+ * The workspace holds ONE pass: min(n_queries, 16) planes of n_rows doubles (plane q of a pass at its start + q n_rows doubles),
+ *   plus the flat call's candidate pairs; it does not grow with n_queries beyond 16 and needs no initialisation.
+ * Every launch goes on `stream`; nothing is allocated, copied or synchronised; no workgroup waits for another.  Before anything is
+ *   launched (no GPU needed): HMM_E_INVALID for a null pointer, dim != 1024, an unknown query_dtype, n_queries < 1, k < 1, the
+ *   segmented call's k > 1024, a store, query or workspace address that is not 16-byte aligned, a norm or output address that is
+ *   not 8-byte aligned; HMM_E_WORKSPACE for a workspace below the *_workspace_bytes answer. */
+size_t hmm_cosine_topk_multi_f64_workspace_bytes(int64_t n_rows, int n_queries, int k);
+int    hmm_cosine_topk_multi_f64(const float* store_dev, int64_t n_rows, int dim, const void* queries_dev,
+                                 int query_dtype /* 0 fp32, 1 fp64: one per call */,
+                                 const double* query_norms_dev /* nullable, [n_queries] */, int n_queries, int k,
+                                 int64_t* idx_out_dev, double* sim_out_dev, int32_t* n_out_dev /* nullable, [n_queries] */,
+                                 void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
+size_t hmm_cosine_topk_segmented_multi_f64_workspace_bytes(int64_t n_rows, int n_segments, int n_queries, int k);
+int    hmm_cosine_topk_segmented_multi_f64(const float* store_dev, int64_t n_rows, int dim, const void* queries_dev, int query_dtype,
+                                           const double* query_norms_dev /* nullable, [n_queries] */, int n_queries,
+                                           const int64_t* seg_offsets_dev, int n_segments, int k,
+                                           int64_t* idx_out_dev, double* sim_out_dev, int32_t* n_out_dev,
+                                           void* workspace_dev, size_t workspace_bytes, hmm_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Consolidation similarity.  Replaces HippocampalMemory._select_key_frames(features, times,
  * similarity_threshold=0.9) (hippomm/core/hippocampal_memory.py:944-967; caller :855).
