@@ -1,11 +1,13 @@
 // feature_search in float64 for stores whose float64 source held fp32 values only (include/hippomm_hip.h, "float64-origin
 // stores").  The resident rows stay fp32 -- narrowing such a source lost nothing -- and this route widens them in registers and
-// accumulates in fp64, so the only roundings are those of the sums.  Opt-in; its own small pipeline beside the fp32 scans:
+// accumulates in fp64, so the only roundings are those of the sums.  Opt-in; its own small pipeline beside the fp32 scans.  ONE host
+// path: a call is passes of up to 16 queries, each a scan into query-major planes and a selection with the query as the grid's second
+// dimension; the single-query entry points are batches of one (scan_flat_f64 / scan_segments_f64 behind every entry's own checks).
 //
 //   scan_sims_f64_kernel     one wave per row, two rows in flight per wave, the load pattern of scan_topk_kernel (lane l reads the
 //                            float4 at columns 4 (64 j + l), j = 0..3: every load instruction of a wave covers 1 KiB contiguous).
-//                            One double per row into an [N] workspace array.  4096 B per row, read once.
-//   scan_sims_f64_multi_kernel  the same pass for up to 16 queries (the batched entry points): the queries wait in LDS, a wave
+//                            One double per row into an [N] workspace array.  4096 B per row, read once.  A pass of one query.
+//   scan_sims_f64_multi_kernel  the same pass for 2 to 16 queries: the queries wait in LDS, a wave
 //                            holds four rows widened in registers and reads each query fragment once per row block.  One double
 //                            per (query, row) into query-major planes, plane q at sims + q N.  Bit for bit the doubles of
 //                            scan_sims_f64_kernel for that query alone.
@@ -564,11 +566,15 @@ struct F64Plan {
     bool global_sort;    // k_eff > 1024
     int groups;          // first-level workgroups of the two-level selection
     int64_t n_pad;       // pairs of the global sort
-    size_t sims_off, keys_off, pos_off, total;
+    size_t keys_off, pos_off, total;      // the planes lie at offset 0
 };
 static int64_t next_pow2_i64(int64_t x) { int64_t p = 1; while (p < x) p <<= 1; return p; }
 
-static F64Plan flat_plan(int64_t n, int k) {
+static int planes_of(int n_queries) { return n_queries < kF64MultiQ ? n_queries : kF64MultiQ; }      // of one pass: min(Q, 16)
+
+// The flat call's workspace: `planes` planes of n doubles, then as many candidate lists (one pair buffer for the full sort, which
+// takes plane after plane through it).
+static F64Plan flat_plan(int64_t n, int planes, int k) {
     F64Plan p{};
     p.k_eff = (int)(k < n ? k : n);
     p.global_sort = p.k_eff > kF64MaxK;
@@ -576,13 +582,15 @@ static F64Plan flat_plan(int64_t n, int k) {
     const int cap = p.k_eff <= kF64ArgmaxK ? kF64MaxGroups : kF64MaxGroupsSort;
     p.groups = (int)(by_slice < 1 ? 1 : (by_slice > cap ? cap : by_slice));
     p.n_pad = p.global_sort ? next_pow2_i64(n) : 0;
-    const size_t pairs = p.global_sort ? (size_t)p.n_pad : (size_t)p.groups * p.k_eff;
-    p.sims_off = 0;
-    p.keys_off = align_up((size_t)n * sizeof(double), 256);
+    const size_t pairs = p.global_sort ? (size_t)p.n_pad : (size_t)planes * p.groups * p.k_eff;
+    p.keys_off = align_up((size_t)planes * n * sizeof(double), 256);
     p.pos_off = p.keys_off + align_up(pairs * sizeof(uint64_t), 256);
     p.total = p.pos_off + align_up(pairs * sizeof(uint32_t), 256);
     return p;
 }
+
+// The per-event call's workspace: the planes alone (an empty store still gets a non-empty one).
+static size_t segmented_workspace(int64_t n, int planes) { return align_up((size_t)planes * (size_t)(n > 0 ? n : 1) * sizeof(double), 256); }
 
 // Threads of an arg-max workgroup over `n` pairs: 256 while they fit its registers, 1024 beyond.
 static unsigned argmax_threads(int64_t n) { return n <= 256 * kF64Held ? 256u : 1024u; }
@@ -609,21 +617,15 @@ static int check_common(const char* what, const float* store, int64_t n_rows, in
     return HMM_OK;
 }
 
-static void launch_scan_f64(const float* store, int64_t n, const void* query, int query_dtype, const double* query_norm, double* sims,
-                            hipStream_t st) {
-    const float4* s4 = reinterpret_cast<const float4*>(store);
-    if (query_dtype == 1) scan_sims_f64_kernel<true><<<scan_grid_f64(n), 256, 0, st>>>(s4, n, query, query_norm, sims);
-    else                  scan_sims_f64_kernel<false><<<scan_grid_f64(n), 256, 0, st>>>(s4, n, query, query_norm, sims);
-}
-
-// One pass of the batched scan: nq <= kF64MultiQ queries into nq planes of n doubles.  A pass of one query is the single kernel.
+// One pass of the scan: nq <= kF64MultiQ queries into nq planes of n doubles.  A pass of one query is the single-query kernel.
 static int launch_scan_f64_multi(const float* store, int64_t n, const void* queries, int query_dtype, const double* query_norms, int nq,
                                  double* sims, hipStream_t st) {
+    const float4* s4 = reinterpret_cast<const float4*>(store);
     if (nq == 1) {
-        launch_scan_f64(store, n, queries, query_dtype, query_norms, sims, st);
+        if (query_dtype == 1) scan_sims_f64_kernel<true><<<scan_grid_f64(n), 256, 0, st>>>(s4, n, queries, query_norms, sims);
+        else                  scan_sims_f64_kernel<false><<<scan_grid_f64(n), 256, 0, st>>>(s4, n, queries, query_norms, sims);
         return HMM_OK;
     }
-    const float4* s4 = reinterpret_cast<const float4*>(store);
     const int64_t blocks = ((n + kF64MultiRows - 1) / kF64MultiRows + kF64MultiThreads / 64 - 1) / (kF64MultiThreads / 64);
     const unsigned grid = (unsigned)(blocks < 1 ? 1 : (blocks > kNumCU ? kNumCU : blocks));     // one workgroup per CU: registers and LDS
     const size_t lds = multi_lds_bytes(nq, query_dtype == 1);
@@ -637,60 +639,124 @@ static int launch_scan_f64_multi(const float* store, int64_t n, const void* quer
     return HMM_OK;
 }
 
-// hmm_cosine_topk_f64's selection for nq planes of n doubles (plane q at sims + q n) into rows q of (nq, k_eff) outputs: the same
-// launches with the query as the second grid dimension of the two levels; min(k, n) > 1024 sorts plane after plane through the
-// one pair buffer.
-static void select_flat_multi_f64(const double* sims, int64_t n, const F64Plan& p, int nq, uint64_t* keys, uint32_t* pos, int64_t* idx_out,
-                            double* sim_out, int32_t* n_out, hipStream_t st) {
-    if (p.global_sort) {
-        const int64_t half = p.n_pad / 2;
-        for (int q = 0; q < nq; ++q) {
-            const double* plane = sims + (int64_t)q * n;
-            keys_from_sims_f64_kernel<<<(unsigned)((p.n_pad + 255) / 256), 256, 0, st>>>(plane, n, p.n_pad, keys, pos);
-            for (int64_t size = 2; size <= p.n_pad; size <<= 1)
-                for (int64_t stride = size >> 1; stride > 0; stride >>= 1)
-                    bitonic_global_f64_step_kernel<<<(unsigned)((half + 255) / 256), 256, 0, st>>>(keys, pos, half, stride, size);
-            decode_sorted_f64_kernel<<<(p.k_eff + 255) / 256, 256, 0, st>>>(pos, plane, p.k_eff, idx_out + (int64_t)q * p.k_eff,
-                                                                            sim_out + (int64_t)q * p.k_eff, n_out ? n_out + q : nullptr);
-        }
-        return;
+// ---- selection launches -----------------------------------------------------------------------------------------------------------
+// One select_f64_kernel launch: what its workgroups select from and where they write, built in one of three named ways;
+// launch_select unpacks it into the kernel's arguments.  The kernel multiplies blockIdx.y by a plane stride and a candidate stride:
+// they are n_rows and n_cand, the distances between two queries' planes and candidate lists.  A call with one query passes the same
+// values as a batch -- its grid has y == 1, so they are multiplied by blockIdx.y == 0.
+struct SelectLaunch {
+    const double* sims; int64_t n_rows; int k;                               // the planes: plane y at sims + y n_rows
+    const int64_t* seg_off;                                                  // events()
+    const uint64_t* cand_keys; const uint32_t* cand_pos; uint32_t n_cand;    // candidates(): list y at cand_keys + y n_cand
+    uint64_t* out_keys; uint32_t* out_pos;                                   // !FINAL: candidate lists, key 0 padded
+    int64_t* idx_out; double* sim_out; int32_t* counts_out; int pad;         // FINAL: the hits, -1 / 0 padded to k when pad
+
+    // range g = slice g of ceil(n / gridDim.x) rows of the plane -> its k candidates (the flat call's first level)
+    static SelectLaunch slices(const double* sims, int64_t n, int k, uint64_t* out_keys, uint32_t* out_pos) {
+        SelectLaunch s{}; s.sims = sims; s.n_rows = n; s.k = k; s.out_keys = out_keys; s.out_pos = out_pos; return s;
     }
+    // range e = the rows of event e of the offset table -> its hits, padded (the per-event call)
+    static SelectLaunch events(const double* sims, int64_t n, int k, const int64_t* seg_off, int64_t* idx, double* sim, int32_t* counts) {
+        SelectLaunch s = slices(sims, n, k, nullptr, nullptr);
+        s.seg_off = seg_off; s.idx_out = idx; s.sim_out = sim; s.counts_out = counts; s.pad = 1;
+        return s;
+    }
+    // one range: the query's n_cand candidate pairs -> its hits (the flat call's second level)
+    static SelectLaunch candidates(const double* sims, int64_t n, int k, const uint64_t* keys, const uint32_t* pos, uint32_t n_cand,
+                                   int64_t* idx, double* sim, int32_t* counts) {
+        SelectLaunch s = events(sims, n, k, nullptr, idx, sim, counts);
+        s.cand_keys = keys; s.cand_pos = pos; s.n_cand = n_cand; s.pad = 0;
+        return s;
+    }
+};
+
+template <bool SORT, bool FINAL>
+static void launch_select(dim3 grid, unsigned threads, hipStream_t st, const SelectLaunch& s) {
+    select_f64_kernel<SORT, FINAL><<<grid, threads, 0, st>>>(s.sims, s.n_rows, s.seg_off, s.cand_keys, s.cand_pos, s.n_cand, s.k, s.out_keys,
+                                                             s.out_pos, s.idx_out, s.sim_out, s.counts_out, s.pad, s.n_rows, (int64_t)s.n_cand);
+}
+
+// min(k, n) > 1024: a full sort of one plane's (key, index) pairs through the pair buffer.
+static void sort_plane_f64(const double* plane, int64_t n, const F64Plan& p, uint64_t* keys, uint32_t* pos, int64_t* idx_out,
+                           double* sim_out, int32_t* n_out, hipStream_t st) {
+    const int64_t half = p.n_pad / 2;
+    keys_from_sims_f64_kernel<<<(unsigned)((p.n_pad + 255) / 256), 256, 0, st>>>(plane, n, p.n_pad, keys, pos);
+    for (int64_t size = 2; size <= p.n_pad; size <<= 1)
+        for (int64_t stride = size >> 1; stride > 0; stride >>= 1)
+            bitonic_global_f64_step_kernel<<<(unsigned)((half + 255) / 256), 256, 0, st>>>(keys, pos, half, stride, size);
+    decode_sorted_f64_kernel<<<(p.k_eff + 255) / 256, 256, 0, st>>>(pos, plane, p.k_eff, idx_out, sim_out, n_out);
+}
+
+// The flat selection for nq planes of n doubles into rows q of (nq, k_eff) outputs: two levels with the query as the second grid
+// dimension, or plane after plane through the full sort.
+static void select_flat_f64(const double* sims, int64_t n, const F64Plan& p, int nq, uint64_t* keys, uint32_t* pos, int64_t* idx_out,
+                            double* sim_out, int32_t* n_out, hipStream_t st) {
     const int64_t per = (n + p.groups - 1) / p.groups, cand = (int64_t)p.groups * p.k_eff;
     const dim3 first(p.groups, nq), second(1, nq);
-    if (p.k_eff <= kF64ArgmaxK) {
-        select_f64_kernel<false, false><<<first, argmax_threads(per), 0, st>>>(sims, n, nullptr, nullptr, nullptr, 0u, p.k_eff, keys, pos,
-                                                                              nullptr, nullptr, nullptr, 0, n, 0);
-        select_f64_kernel<false, true><<<second, argmax_threads(cand), 0, st>>>(sims, n, nullptr, keys, pos, (uint32_t)cand, p.k_eff, nullptr,
-                                                                               nullptr, idx_out, sim_out, n_out, 0, n, cand);
+    const SelectLaunch level1 = SelectLaunch::slices(sims, n, p.k_eff, keys, pos);
+    const SelectLaunch level2 = SelectLaunch::candidates(sims, n, p.k_eff, keys, pos, (uint32_t)cand, idx_out, sim_out, n_out);
+    if (p.global_sort) {
+        for (int q = 0; q < nq; ++q)
+            sort_plane_f64(sims + (int64_t)q * n, n, p, keys, pos, idx_out + (int64_t)q * p.k_eff, sim_out + (int64_t)q * p.k_eff,
+                           n_out ? n_out + q : nullptr, st);
+    } else if (p.k_eff <= kF64ArgmaxK) {
+        launch_select<false, false>(first, argmax_threads(per), st, level1);
+        launch_select<false, true>(second, argmax_threads(cand), st, level2);
     } else {
-        select_f64_kernel<true, false><<<first, 1024, 0, st>>>(sims, n, nullptr, nullptr, nullptr, 0u, p.k_eff, keys, pos, nullptr, nullptr,
-                                                              nullptr, 0, n, 0);
-        select_f64_kernel<true, true><<<second, 1024, 0, st>>>(sims, n, nullptr, keys, pos, (uint32_t)cand, p.k_eff, nullptr, nullptr, idx_out,
-                                                               sim_out, n_out, 0, n, cand);
+        launch_select<true, false>(first, 1024, st, level1);
+        launch_select<true, true>(second, 1024, st, level2);
     }
 }
 
-// hmm_cosine_topk_segmented_f64's selection for nq planes into (nq, E, k) outputs: one workgroup per (query, event).
-static void select_segments_multi_f64(const double* sims, int64_t n, const int64_t* seg_off, int n_segments, int k, int nq, int64_t* idx_out,
+// The per-event selection for nq planes into (nq, E, k) outputs: one workgroup per (query, event).
+static void select_segments_f64(const double* sims, int64_t n, const int64_t* seg_off, int n_segments, int k, int nq, int64_t* idx_out,
                                 double* sim_out, int32_t* n_out, hipStream_t st) {
     const dim3 grid(n_segments, nq);
-    if (k <= kF64ArgmaxK)
-        select_f64_kernel<false, true><<<grid, 256, 0, st>>>(sims, n, seg_off, nullptr, nullptr, 0u, k, nullptr, nullptr, idx_out, sim_out,
-                                                             n_out, 1, n, 0);
-    else
-        select_f64_kernel<true, true><<<grid, 1024, 0, st>>>(sims, n, seg_off, nullptr, nullptr, 0u, k, nullptr, nullptr, idx_out, sim_out,
-                                                             n_out, 1, n, 0);
+    const SelectLaunch events = SelectLaunch::events(sims, n, k, seg_off, idx_out, sim_out, n_out);
+    if (k <= kF64ArgmaxK) launch_select<false, true>(grid, 256, st, events);
+    else                  launch_select<true, true>(grid, 1024, st, events);
 }
 
-// The batched plan: the flat plan with min(Q, 16) planes and as many candidate lists (one pair buffer for the full sort).
-static F64Plan flat_plan_multi(int64_t n, int n_queries, int k) {
-    F64Plan p = flat_plan(n, k);
-    const size_t planes = (size_t)(n_queries < kF64MultiQ ? n_queries : kF64MultiQ);
-    const size_t pairs = p.global_sort ? (size_t)p.n_pad : planes * (size_t)p.groups * p.k_eff;
-    p.keys_off = align_up(planes * (size_t)n * sizeof(double), 256);
-    p.pos_off = p.keys_off + align_up(pairs * sizeof(uint64_t), 256);
-    p.total = p.pos_off + align_up(pairs * sizeof(uint32_t), 256);
-    return p;
+// ---- the two cores: everything behind an entry point's own argument checks ---------------------------------------------------------
+// A call of Q queries is ceil(Q / 16) passes that follow each other on the stream and share the workspace; a single query is a batch
+// of one (launch_scan_f64_multi gives it scan_sims_f64_kernel).
+static int scan_flat_f64(const float* store, int64_t n, const void* queries, int query_dtype, const double* query_norms, int n_queries,
+                         const F64Plan& p, int64_t* idx_out, double* sim_out, int32_t* n_out, void* workspace, hipStream_t st) {
+    double* sims = static_cast<double*>(workspace);
+    uint64_t* keys = reinterpret_cast<uint64_t*>(static_cast<char*>(workspace) + p.keys_off);
+    uint32_t* pos = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + p.pos_off);
+    const size_t q_bytes = (size_t)HMM_FEATURE_DIM * (query_dtype == 1 ? 8 : 4);
+    for (int q0 = 0; q0 < n_queries; q0 += kF64MultiQ) {
+        const int nq = planes_of(n_queries - q0);
+        if (int rc = launch_scan_f64_multi(store, n, static_cast<const char*>(queries) + q0 * q_bytes, query_dtype,
+                                           query_norms ? query_norms + q0 : nullptr, nq, sims, st); rc != HMM_OK) return rc;
+        HMM_LAUNCH_CHECK();
+        select_flat_f64(sims, n, p, nq, keys, pos, idx_out + (int64_t)q0 * p.k_eff, sim_out + (int64_t)q0 * p.k_eff,
+                        n_out ? n_out + q0 : nullptr, st);
+        HMM_LAUNCH_CHECK();
+    }
+    return HMM_OK;
+}
+
+// The per-event form.  Without rows no scan is launched and every event gets its padding.
+static int scan_segments_f64(const float* store, int64_t n, const void* queries, int query_dtype, const double* query_norms,
+                             int n_queries, const int64_t* seg_off, int n_segments, int k, int64_t* idx_out, double* sim_out,
+                             int32_t* n_out, void* workspace, hipStream_t st) {
+    double* sims = static_cast<double*>(workspace);
+    const size_t q_bytes = (size_t)HMM_FEATURE_DIM * (query_dtype == 1 ? 8 : 4);
+    const int64_t cells = (int64_t)n_segments * k;
+    for (int q0 = 0; q0 < n_queries; q0 += kF64MultiQ) {
+        const int nq = planes_of(n_queries - q0);
+        if (n > 0) {
+            if (int rc = launch_scan_f64_multi(store, n, static_cast<const char*>(queries) + q0 * q_bytes, query_dtype,
+                                               query_norms ? query_norms + q0 : nullptr, nq, sims, st); rc != HMM_OK) return rc;
+            HMM_LAUNCH_CHECK();
+        }
+        select_segments_f64(sims, n, seg_off, n_segments, k, nq, idx_out + q0 * cells, sim_out + q0 * cells,
+                            n_out + (int64_t)q0 * n_segments, st);
+        HMM_LAUNCH_CHECK();
+    }
+    return HMM_OK;
 }
 
 static int check_multi(const char* what, const float* store, int64_t n_rows, int dim, const void* queries, int query_dtype,
@@ -718,7 +784,7 @@ using namespace hmm;
 
 extern "C" size_t hmm_cosine_topk_f64_workspace_bytes(int64_t n_rows, int k) {
     if (n_rows < 1 || n_rows >= (int64_t)0xFFFFFFFFll || k < 1) return 0;
-    return flat_plan(n_rows, k).total;
+    return flat_plan(n_rows, 1, k).total;
 }
 
 extern "C" int hmm_cosine_topk_f64(const float* store_dev, int64_t n_rows, int dim, const void* query_dev, int query_dtype,
@@ -732,41 +798,15 @@ extern "C" int hmm_cosine_topk_f64(const float* store_dev, int64_t n_rows, int d
                 "cosine_topk_f64: workspace must be given and 16-byte aligned");
     HMM_REQUIRE(((uintptr_t)idx_out_dev & 7) == 0 && ((uintptr_t)sim_out_dev & 7) == 0 && ((uintptr_t)n_out_dev & 3) == 0, HMM_E_INVALID,
                 "cosine_topk_f64: outputs must be aligned to their element size");
-    const F64Plan p = flat_plan(n_rows, k);
+    const F64Plan p = flat_plan(n_rows, 1, k);
     HMM_REQUIRE(workspace_bytes >= p.total, HMM_E_WORKSPACE, "cosine_topk_f64: workspace too small (%zu < %zu)", workspace_bytes, p.total);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace_dev);
-    double* sims = reinterpret_cast<double*>(ws + p.sims_off);
-    uint64_t* keys = reinterpret_cast<uint64_t*>(ws + p.keys_off);
-    uint32_t* pos = reinterpret_cast<uint32_t*>(ws + p.pos_off);
-    launch_scan_f64(store_dev, n_rows, query_dev, query_dtype, query_norm_dev, sims, st);
-    HMM_LAUNCH_CHECK();
-    if (p.global_sort) {
-        keys_from_sims_f64_kernel<<<(unsigned)((p.n_pad + 255) / 256), 256, 0, st>>>(sims, n_rows, p.n_pad, keys, pos);
-        const int64_t half = p.n_pad / 2;
-        for (int64_t size = 2; size <= p.n_pad; size <<= 1)
-            for (int64_t stride = size >> 1; stride > 0; stride >>= 1)
-                bitonic_global_f64_step_kernel<<<(unsigned)((half + 255) / 256), 256, 0, st>>>(keys, pos, half, stride, size);
-        decode_sorted_f64_kernel<<<(p.k_eff + 255) / 256, 256, 0, st>>>(pos, sims, p.k_eff, idx_out_dev, sim_out_dev, n_out_dev);
-    } else if (p.k_eff <= kF64ArgmaxK) {
-        const int64_t per = (n_rows + p.groups - 1) / p.groups, cand = (int64_t)p.groups * p.k_eff;
-        select_f64_kernel<false, false><<<p.groups, argmax_threads(per), 0, st>>>(sims, n_rows, nullptr, nullptr, nullptr, 0u, p.k_eff, keys,
-                                                                                 pos, nullptr, nullptr, nullptr, 0, 0, 0);
-        select_f64_kernel<false, true><<<1, argmax_threads(cand), 0, st>>>(sims, n_rows, nullptr, keys, pos, (uint32_t)cand, p.k_eff, nullptr,
-                                                                          nullptr, idx_out_dev, sim_out_dev, n_out_dev, 0, 0, 0);
-    } else {
-        select_f64_kernel<true, false><<<p.groups, 1024, 0, st>>>(sims, n_rows, nullptr, nullptr, nullptr, 0u, p.k_eff, keys, pos, nullptr,
-                                                                 nullptr, nullptr, 0, 0, 0);
-        select_f64_kernel<true, true><<<1, 1024, 0, st>>>(sims, n_rows, nullptr, keys, pos, (uint32_t)(p.groups * p.k_eff), p.k_eff, nullptr,
-                                                          nullptr, idx_out_dev, sim_out_dev, n_out_dev, 0, 0, 0);
-    }
-    HMM_LAUNCH_CHECK();
-    return HMM_OK;
+    return scan_flat_f64(store_dev, n_rows, query_dev, query_dtype, query_norm_dev, 1, p, idx_out_dev, sim_out_dev, n_out_dev,
+                         workspace_dev, static_cast<hipStream_t>(stream));
 }
 
 extern "C" size_t hmm_cosine_topk_segmented_f64_workspace_bytes(int64_t n_rows, int n_segments, int k) {
     if (n_rows < 0 || n_rows >= (int64_t)0xFFFFFFFFll || n_segments < 1 || k < 1) return 0;
-    return align_up((size_t)(n_rows > 0 ? n_rows : 1) * sizeof(double), 256);
+    return segmented_workspace(n_rows, 1);
 }
 
 extern "C" int hmm_cosine_topk_segmented_f64(const float* store_dev, int64_t n_rows, int dim, const void* query_dev, int query_dtype,
@@ -785,20 +825,8 @@ extern "C" int hmm_cosine_topk_segmented_f64(const float* store_dev, int64_t n_r
                 "cosine_topk_segmented_f64: offsets / outputs must be aligned to their element size");
     HMM_REQUIRE(workspace_bytes >= hmm_cosine_topk_segmented_f64_workspace_bytes(n_rows, n_segments, k), HMM_E_WORKSPACE,
                 "cosine_topk_segmented_f64: workspace too small");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    double* sims = static_cast<double*>(workspace_dev);
-    if (n_rows > 0) {
-        launch_scan_f64(store_dev, n_rows, query_dev, query_dtype, query_norm_dev, sims, st);
-        HMM_LAUNCH_CHECK();
-    }
-    if (k <= kF64ArgmaxK)
-        select_f64_kernel<false, true><<<n_segments, 256, 0, st>>>(sims, n_rows, seg_offsets_dev, nullptr, nullptr, 0u, k, nullptr, nullptr,
-                                                                   idx_out_dev, sim_out_dev, n_out_dev, 1, 0, 0);
-    else
-        select_f64_kernel<true, true><<<n_segments, 1024, 0, st>>>(sims, n_rows, seg_offsets_dev, nullptr, nullptr, 0u, k, nullptr, nullptr,
-                                                                   idx_out_dev, sim_out_dev, n_out_dev, 1, 0, 0);
-    HMM_LAUNCH_CHECK();
-    return HMM_OK;
+    return scan_segments_f64(store_dev, n_rows, query_dev, query_dtype, query_norm_dev, 1, seg_offsets_dev, n_segments, k, idx_out_dev,
+                             sim_out_dev, n_out_dev, workspace_dev, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int hmm_rows_f64_are_f32(const double* src_dev, int64_t n_rows, int dim, int64_t* report_dev, hmm_stream_t stream) {
@@ -821,10 +849,9 @@ extern "C" int hmm_rows_f64_are_f32(const double* src_dev, int64_t n_rows, int d
     return HMM_OK;
 }
 
-// ---- the batched entry points: one pass over the store per 16 queries -------------------------------------------------------------
 extern "C" size_t hmm_cosine_topk_multi_f64_workspace_bytes(int64_t n_rows, int n_queries, int k) {
     if (n_rows < 1 || n_rows >= (int64_t)0xFFFFFFFFll || n_queries < 1 || k < 1) return 0;
-    return flat_plan_multi(n_rows, n_queries, k).total;
+    return flat_plan(n_rows, planes_of(n_queries), k).total;
 }
 
 extern "C" int hmm_cosine_topk_multi_f64(const float* store_dev, int64_t n_rows, int dim, const void* queries_dev, int query_dtype,
@@ -835,31 +862,15 @@ extern "C" int hmm_cosine_topk_multi_f64(const float* store_dev, int64_t n_rows,
                          n_out_dev, workspace_dev);
     if (rc != HMM_OK) return rc;
     HMM_REQUIRE(n_rows >= 1, HMM_E_INVALID, "%s: n_rows must be >= 1", what);
-    const F64Plan p = flat_plan_multi(n_rows, n_queries, k);
+    const F64Plan p = flat_plan(n_rows, planes_of(n_queries), k);
     HMM_REQUIRE(workspace_bytes >= p.total, HMM_E_WORKSPACE, "%s: workspace too small (%zu < %zu)", what, workspace_bytes, p.total);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace_dev);
-    double* sims = reinterpret_cast<double*>(ws + p.sims_off);
-    uint64_t* keys = reinterpret_cast<uint64_t*>(ws + p.keys_off);
-    uint32_t* pos = reinterpret_cast<uint32_t*>(ws + p.pos_off);
-    const size_t q_bytes = (size_t)HMM_FEATURE_DIM * (query_dtype == 1 ? 8 : 4);
-    for (int q0 = 0; q0 < n_queries; q0 += kF64MultiQ) {       // the passes follow each other on the stream and share the workspace
-        const int nq = n_queries - q0 < kF64MultiQ ? n_queries - q0 : kF64MultiQ;
-        rc = launch_scan_f64_multi(store_dev, n_rows, static_cast<const char*>(queries_dev) + q0 * q_bytes, query_dtype,
-                                   query_norms_dev ? query_norms_dev + q0 : nullptr, nq, sims, st);
-        if (rc != HMM_OK) return rc;
-        HMM_LAUNCH_CHECK();
-        select_flat_multi_f64(sims, n_rows, p, nq, keys, pos, idx_out_dev + (int64_t)q0 * p.k_eff, sim_out_dev + (int64_t)q0 * p.k_eff,
-                        n_out_dev ? n_out_dev + q0 : nullptr, st);
-        HMM_LAUNCH_CHECK();
-    }
-    return HMM_OK;
+    return scan_flat_f64(store_dev, n_rows, queries_dev, query_dtype, query_norms_dev, n_queries, p, idx_out_dev, sim_out_dev, n_out_dev,
+                         workspace_dev, static_cast<hipStream_t>(stream));
 }
 
 extern "C" size_t hmm_cosine_topk_segmented_multi_f64_workspace_bytes(int64_t n_rows, int n_segments, int n_queries, int k) {
     if (n_rows < 0 || n_rows >= (int64_t)0xFFFFFFFFll || n_segments < 1 || n_queries < 1 || k < 1) return 0;
-    const size_t planes = (size_t)(n_queries < kF64MultiQ ? n_queries : kF64MultiQ);
-    return align_up(planes * (size_t)(n_rows > 0 ? n_rows : 1) * sizeof(double), 256);
+    return segmented_workspace(n_rows, planes_of(n_queries));
 }
 
 extern "C" int hmm_cosine_topk_segmented_multi_f64(const float* store_dev, int64_t n_rows, int dim, const void* queries_dev,
@@ -876,21 +887,6 @@ extern "C" int hmm_cosine_topk_segmented_multi_f64(const float* store_dev, int64
     HMM_REQUIRE(((uintptr_t)seg_offsets_dev & 7) == 0, HMM_E_INVALID, "%s: seg_offsets must be 8-byte aligned", what);
     HMM_REQUIRE(workspace_bytes >= hmm_cosine_topk_segmented_multi_f64_workspace_bytes(n_rows, n_segments, n_queries, k), HMM_E_WORKSPACE,
                 "%s: workspace too small", what);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    double* sims = static_cast<double*>(workspace_dev);
-    const size_t q_bytes = (size_t)HMM_FEATURE_DIM * (query_dtype == 1 ? 8 : 4);
-    const int64_t cells = (int64_t)n_segments * k;
-    for (int q0 = 0; q0 < n_queries; q0 += kF64MultiQ) {
-        const int nq = n_queries - q0 < kF64MultiQ ? n_queries - q0 : kF64MultiQ;
-        if (n_rows > 0) {
-            rc = launch_scan_f64_multi(store_dev, n_rows, static_cast<const char*>(queries_dev) + q0 * q_bytes, query_dtype,
-                                       query_norms_dev ? query_norms_dev + q0 : nullptr, nq, sims, st);
-            if (rc != HMM_OK) return rc;
-            HMM_LAUNCH_CHECK();
-        }
-        select_segments_multi_f64(sims, n_rows, seg_offsets_dev, n_segments, k, nq, idx_out_dev + q0 * cells, sim_out_dev + q0 * cells,
-                            n_out_dev + (int64_t)q0 * n_segments, st);
-        HMM_LAUNCH_CHECK();
-    }
-    return HMM_OK;
+    return scan_segments_f64(store_dev, n_rows, queries_dev, query_dtype, query_norms_dev, n_queries, seg_offsets_dev, n_segments, k,
+                             idx_out_dev, sim_out_dev, n_out_dev, workspace_dev, static_cast<hipStream_t>(stream));
 }

@@ -52,14 +52,13 @@ _ROUTES = {
 
 
 # The float64 route (exact64=True; include/hippomm_hip.h, "float64-origin stores") has its own entry points and argument order:
-#   store, n, dim, query, query dtype, query norm, [seg_offsets, E,] k, outputs..., workspace, workspace bytes, stream
+#   store, n, dim, queries, query dtype, query norms, [Q,] [seg_offsets, E,] k, outputs..., workspace, workspace bytes, stream
+# and sizes the workspace with (n, [E,] [Q,] k).  One host path, FeatureStore._scan_f64, serves both tables: a single query is a
+# (1,1024) batch with one norm, sent to the entry points that take no Q; a batch goes to those that take it.
 _F64_ROUTES = {
     "flat": ("hmm_cosine_topk_f64", "hmm_cosine_topk_f64_workspace_bytes"),
     "segmented": ("hmm_cosine_topk_segmented_f64", "hmm_cosine_topk_segmented_f64_workspace_bytes"),
 }
-
-# The batched float64 routes: the same, with a (Q,1024) batch, one norm per question and Q after the norms:
-#   store, n, dim, queries, query dtype, query norms, Q, [seg_offsets, E,] k, outputs..., workspace, workspace bytes, stream
 _F64_MULTI_ROUTES = {
     "flat": ("hmm_cosine_topk_multi_f64", "hmm_cosine_topk_multi_f64_workspace_bytes"),
     "segmented": ("hmm_cosine_topk_segmented_multi_f64", "hmm_cosine_topk_segmented_multi_f64_workspace_bytes"),
@@ -92,15 +91,14 @@ class _Packed:
 
 
 @functools.lru_cache(maxsize=64)                                 # a caller's shapes repeat from call to call
-def _hits_layout(*shape):
-    """idx | sims | counts of a segmented scan; shape = (E, k) or (Q, E, k)."""
-    return _Packed((_I64, shape), (_F32, shape), (_I32, shape[:-1]))
+def _hits_layout(*shape, sims=_F32):
+    """idx | sims | counts of a segmented scan; shape = (E, k) or (Q, E, k).  The 8-byte fields come first."""
+    return _Packed((_I64, shape), (sims, shape), (_I32, shape[:-1]))
 
 
-@functools.lru_cache(maxsize=64)
 def _hits_layout_f64(*shape):
-    """idx | sims (float64) | counts of a segmented float64 scan; shape = (E, k) or (Q, E, k).  Both 8-byte fields come first."""
-    return _Packed((_I64, shape), (_F64, shape), (_I32, shape[:-1]))
+    """_hits_layout of a segmented float64 scan: sims float64."""
+    return _hits_layout(*shape, sims=_F64)
 
 
 @functools.lru_cache(maxsize=64)
@@ -169,36 +167,20 @@ def first_not_f32(a: np.ndarray):
 
 
 def _exact64_query(a, dev):
-    """(buffer, query address, dtype code, norm address or None) for the float64 entry points.  A host query keeps its dtype
-    (float32 or float64; anything else becomes float32) and travels with ``np.linalg.norm(a)`` evaluated by numpy in that dtype --
-    the reference's own ``a_norm`` -- as one double in the same upload.  A device tensor is used where it lies and the kernel
-    forms the norm (include/hippomm_hip.h: the last fp32 bit of an fp32 query's norm may then differ from numpy's)."""
-    if isinstance(a, torch.Tensor) and a.is_cuda:
-        q = a.detach().reshape(-1)
-        if q.dtype not in (torch.float32, torch.float64):
-            q = q.to(torch.float32)
-        q = q.to(dev).contiguous()
-        if q.numel() != FEATURE_DIM:
-            raise ValueError(f"query must have {FEATURE_DIM} elements, got {q.numel()}")
-        if q.data_ptr() % 16:
-            q = q.clone()
-        return q, q.data_ptr(), int(q.dtype == torch.float64), None
-    host = a.detach().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-    host = np.ascontiguousarray(host.reshape(-1), dtype=host.dtype if host.dtype in (np.float32, np.float64) else np.float32)
-    if host.size != FEATURE_DIM:
-        raise ValueError(f"query must have {FEATURE_DIM} elements, got {host.size}")
-    norm = np.array([np.linalg.norm(host)], dtype=np.float64)            # in the query's dtype, widened
-    # 8 unused bytes | norm | query: the query starts 16 bytes into the (256-byte aligned) allocation
-    buf = torch.from_numpy(np.concatenate([np.zeros(8, np.uint8), norm.view(np.uint8), host.view(np.uint8)])).to(dev)
-    return buf, buf.data_ptr() + 16, int(host.dtype == np.float64), buf.data_ptr() + 8
+    """One query of any shape with 1024 elements as a batch of one: what ``_exact64_queries`` returns for its (1,1024) view."""
+    a = a if isinstance(a, torch.Tensor) else np.asarray(a)
+    if math.prod(a.shape) != FEATURE_DIM:
+        raise ValueError(f"query must have {FEATURE_DIM} elements, got {math.prod(a.shape)}")
+    return _exact64_queries(a.reshape(1, FEATURE_DIM), dev)
 
 
 def _exact64_queries(queries, dev):
-    """The batch form of ``_exact64_query``: (buffer, address of the (Q,1024) batch, dtype code, address of the Q norms or None, Q).
+    """(buffer, address of the (Q,1024) batch, dtype code, address of the Q norms or None, Q) for the float64 entry points.
     A host batch keeps its dtype (float32 or float64; anything else becomes float32) and travels with one norm per question in the
-    same upload, each ``np.linalg.norm(row)`` of the contiguous 1-D row -- the call the single route and the reference make;
-    ``norm(q, axis=1)`` sums along another path and need not give its bits.  A device batch is used where it lies and the kernel
-    forms the norms.  The batch starts at a 16-byte boundary either way."""
+    same upload, each ``np.linalg.norm(row)`` of the contiguous 1-D row evaluated by numpy in that dtype -- the reference's own
+    ``a_norm``; ``norm(q, axis=1)`` sums along another path and need not give its bits.  A device batch is used where it lies and
+    the kernel forms the norms (include/hippomm_hip.h: the last fp32 bit of an fp32 query's norm may then differ from numpy's).
+    The batch starts at a 16-byte boundary either way."""
     if isinstance(queries, torch.Tensor) and queries.is_cuda:
         q = queries.detach()
         if q.dim() != 2 or q.shape[1] != FEATURE_DIM:
@@ -348,71 +330,33 @@ class FeatureStore:
                              f"(row {row}, column {col}) was not one")
         return True
 
-    def _scan_f64(self, shape: str, query, k: int, outputs, seg_offsets: torch.Tensor = None):
-        """One launch of the float64 route ``shape`` of _F64_ROUTES into ``outputs``; does not synchronise."""
-        name, size_name = _F64_ROUTES[shape]
+    def _scan_f64(self, shape: str, batch, k: int, outputs, seg_offsets: torch.Tensor = None, single: bool = False):
+        """One call of the float64 route ``shape`` into ``outputs`` (inside it one pass over the store per 16 questions);
+        ``batch`` is what _exact64_queries returned.  ``single``: the single-query entry point of _F64_ROUTES, which takes no Q,
+        instead of the batched one of _F64_MULTI_ROUTES.  Does not synchronise."""
+        name, size_name = (_F64_ROUTES if single else _F64_MULTI_ROUTES)[shape]
         lib = _lib.load()
-        keepalive, q_ptr, q_dtype, norm_ptr = _exact64_query(query, self.rows.device)
-        n = len(self)
+        _, q_ptr, q_dtype, norms_ptr, Q = batch
+        n, count = len(self), () if single else (Q,)
         segments = () if seg_offsets is None else (seg_offsets.data_ptr(), seg_offsets.numel() - 1)
-        ws = self._scratch(getattr(lib, size_name)(n, *segments[1:], k))
-        _lib.check(getattr(lib, name)(self.rows.data_ptr(), n, FEATURE_DIM, q_ptr, q_dtype, norm_ptr, *segments, k,
-                                      *[t.data_ptr() for t in outputs], ws.data_ptr(), ws.numel(), _lib.stream_ptr()), name)
-        return keepalive
-
-    def _search_flat_f64(self, query, k: int):
-        if k < 1:
-            raise ValueError("k must be >= 1")
-        dev, k_out = self.rows.device, min(k, len(self))
-        idx = torch.empty(k_out, dtype=torch.int64, device=dev)
-        sims = torch.empty(k_out, dtype=torch.float64, device=dev)
-        n_out = torch.empty(1, dtype=torch.int32, device=dev)
-        if k_out > 0:
-            self._scan_f64("flat", query, k, (idx, sims, n_out))
-        return idx, sims
-
-    def _scan_f64_multi(self, shape: str, queries, k: int, outputs, seg_offsets: torch.Tensor = None):
-        """One call of the batched float64 route ``shape`` of _F64_MULTI_ROUTES into ``outputs`` (one pass over the store per 16
-        questions inside it); ``queries`` is what _exact64_queries returned.  Does not synchronise."""
-        name, size_name = _F64_MULTI_ROUTES[shape]
-        lib = _lib.load()
-        _, q_ptr, q_dtype, norms_ptr, Q = queries
-        n = len(self)
-        segments = () if seg_offsets is None else (seg_offsets.data_ptr(), seg_offsets.numel() - 1)
-        ws = self._scratch(getattr(lib, size_name)(n, *segments[1:], Q, k))
-        _lib.check(getattr(lib, name)(self.rows.data_ptr(), n, FEATURE_DIM, q_ptr, q_dtype, norms_ptr, Q, *segments, k,
+        ws = self._scratch(getattr(lib, size_name)(n, *segments[1:], *count, k))
+        _lib.check(getattr(lib, name)(self.rows.data_ptr(), n, FEATURE_DIM, q_ptr, q_dtype, norms_ptr, *count, *segments, k,
                                       *[t.data_ptr() for t in outputs], ws.data_ptr(), ws.numel(), _lib.stream_ptr()), name)
 
-    def _search_multi_f64(self, queries, k: int):
-        """The float64 route of search_multi_device: (idx (Q,k') int64, sims (Q,k') float64), k' = min(k, N)."""
+    def _search_flat_f64(self, queries, k: int, single: bool = False):
+        """The float64 route of search_multi_device: (idx (Q,k') int64, sims (Q,k') float64), k' = min(k, N); ``single``: of
+        search_device, without the leading Q.  An empty store launches nothing (and a single query is then not looked at)."""
         if int(k) < 1:
             raise ValueError("k must be >= 1")
-        batch = _exact64_queries(queries, self.rows.device)
-        dev, Q, k_out = self.rows.device, batch[-1], min(int(k), len(self))
-        idx = torch.empty(Q, k_out, dtype=torch.int64, device=dev)
-        sims = torch.empty(Q, k_out, dtype=torch.float64, device=dev)
-        n_out = torch.empty(Q, dtype=torch.int32, device=dev)
+        dev, k_out = self.rows.device, min(int(k), len(self))
+        batch = None if single and k_out == 0 else (_exact64_query if single else _exact64_queries)(queries, dev)
+        lead = () if single else (batch[-1],)
+        idx = torch.empty(*lead, k_out, dtype=torch.int64, device=dev)
+        sims = torch.empty(*lead, k_out, dtype=torch.float64, device=dev)
+        n_out = torch.empty(*lead or (1,), dtype=torch.int32, device=dev)
         if k_out > 0:
-            self._scan_f64_multi("flat", batch, int(k), (idx, sims, n_out))
+            self._scan_f64("flat", batch, int(k), (idx, sims, n_out), single=single)
         return idx, sims
-
-    def _search_segments_multi_packed_f64(self, queries, seg_offsets: torch.Tensor, k: int):
-        """The float64 route of _search_segments_multi_packed: (packed, idx (Q,E,k), sims float64, counts (Q,E)), one buffer
-        (_hits_layout_f64)."""
-        if int(k) < 1:
-            raise ValueError("k must be >= 1")
-        batch = _exact64_queries(queries, self.rows.device)
-        Q, E, k = batch[-1], seg_offsets.numel() - 1, int(k)
-        layout = _hits_layout_f64(Q, E, k)
-        packed = torch.empty(layout.nbytes, dtype=torch.uint8, device=self.rows.device)
-        idx, sims, counts = layout.device_views(packed)
-        if E > 0 and len(self) == 0:                             # events without a row: the padding is the answer
-            idx.fill_(-1)
-            sims.zero_()
-            counts.zero_()
-        elif E > 0:
-            self._scan_f64_multi("segmented", batch, k, (idx, sims, counts), seg_offsets=seg_offsets)
-        return packed, idx, sims, counts
 
     def _scratch(self, need_bytes: int) -> torch.Tensor:
         """The workspace, reallocated only when it is too small.  No route reads what an earlier call left in it."""
@@ -452,7 +396,7 @@ class FeatureStore:
         without synchronising (k' = min(k, N)).  ``exact64=True``: the float64 route (hmm_cosine_topk_f64) -- the query may be
         fp32 or fp64, on the host or the device, sims are float64 within 2^-42 of the exact quotient; never through the shadow."""
         if self._use_exact64(exact64, "search_device"):
-            return self._search_flat_f64(query, k)
+            return self._search_flat_f64(query, k, single=True)
         if self.use_shadow:
             return self.search_prefiltered_device(query, k)
         return self._search_flat(query, k, False)
@@ -527,28 +471,37 @@ class FeatureStore:
         candidates on the fp32 rows -- the same outputs, bit for bit, for half the bytes (hmm_cosine_topk_segmented_prefilter).
         ``exact64=True``: the float64 route (hmm_cosine_topk_segmented_f64): sims (E,k) float64, every event's slice what the flat
         float64 call gives on its rows, bit for bit; not together with ``prefilter``."""
-        if self._use_exact64(exact64, "search_segments_device", prefilter):
-            return self._search_segments_packed_f64(query, seg_offsets, k)[1:]
-        return self._search_segments_packed(query, seg_offsets, k, prefilter)[1:]
+        exact64 = self._use_exact64(exact64, "search_segments_device", prefilter)
+        return self._search_segments_packed(query, seg_offsets, k, prefilter, single=True, exact64=exact64)[1:]
 
-    def _search_segments_packed_f64(self, query, seg_offsets: torch.Tensor, k: int):
-        """The float64 route of _search_segments_packed: (packed, idx, sims float64, counts), one buffer (_hits_layout_f64)."""
-        if int(k) < 1:
+    def _search_segments_packed(self, queries, seg_offsets: torch.Tensor, k: int, prefilter: bool = False, stats: torch.Tensor = None,
+                                single: bool = False, exact64: bool = False):
+        """search_segments_multi_device -- or, ``single``, search_segments_device for one query -- returning (packed, idx, sims,
+        counts): the three outputs are views of ONE buffer (_hits_layout), so that a caller who wants them on the host reads them
+        back with one copy.  Through the fp32 rows, the bf16 shadow (``prefilter``) or the float64 route (``exact64``: sims float64;
+        the queries as _exact64_queries takes them, otherwise fp32 on the device for ``single``).  A batch without events or
+        without rows launches nothing: the padding is the answer.  A single query always goes to its entry point, which refuses
+        E == 0 and k < 1 itself (on the fp32 routes) and pads the events of a store without rows."""
+        k, dev, E = int(k), self.rows.device, seg_offsets.numel() - 1
+        batch = queries if single or exact64 else _queries_2d(queries, dev)
+        if k < 1 and (exact64 or not single):
             raise ValueError("k must be >= 1")
-        layout = _hits_layout_f64(seg_offsets.numel() - 1, int(k))
-        packed = torch.empty(layout.nbytes, dtype=torch.uint8, device=self.rows.device)
-        outputs = layout.device_views(packed)
-        self._scan_f64("segmented", query, int(k), outputs, seg_offsets=seg_offsets)
-        return (packed, *outputs)
-
-    def _search_segments_packed(self, query: torch.Tensor, seg_offsets: torch.Tensor, k: int, prefilter: bool = False):
-        """search_segments_device, returning (packed, idx, sims, counts): the three outputs are views of ONE buffer
-        (_hits_layout), so that a caller who wants them on the host reads them back with one copy (top_k_per_event)."""
-        layout = _hits_layout(seg_offsets.numel() - 1, k)
-        packed = torch.empty(layout.nbytes, dtype=torch.uint8, device=self.rows.device)
-        outputs = layout.device_views(packed)
-        self._scan("segmented", bool(prefilter and len(self) > 0), query, k, outputs, seg_offsets=seg_offsets)
-        return (packed, *outputs)
+        if exact64:
+            batch = (_exact64_query if single else _exact64_queries)(queries, dev)
+        Q = None if single else (batch[-1] if exact64 else batch.shape[0])
+        layout = _hits_layout(*(() if single else (Q,)), E, k, sims=_F64 if exact64 else _F32)
+        packed = torch.empty(layout.nbytes, dtype=torch.uint8, device=dev)
+        idx, sims, counts = layout.device_views(packed)
+        if not single and (E == 0 or len(self) == 0):
+            idx.fill_(-1)
+            sims.zero_()
+            counts.zero_()
+        elif exact64:
+            self._scan_f64("segmented", batch, k, (idx, sims, counts), seg_offsets=seg_offsets, single=single)
+        else:
+            self._scan("segmented" if single else "segmented_multi", bool(prefilter and len(self) > 0), batch, k, (idx, sims, counts),
+                       Q=Q, seg_offsets=seg_offsets, stats=stats)
+        return packed, idx, sims, counts
 
     def search_segments_multi_device(self, queries, seg_offsets: torch.Tensor, k: int, prefilter: bool = False,
                                      stats: torch.Tensor = None, exact64: bool = False):
@@ -561,27 +514,8 @@ class FeatureStore:
         function was the whole call.  ``exact64=True``: the float64 route for the batch (hmm_cosine_topk_segmented_multi_f64): sims
         (Q,E,k) float64, slice q what ``search_segments_device(queries[q], ..., exact64=True)`` returns, bit for bit; the batch is
         all fp32 or all fp64; not together with ``prefilter``."""
-        if self._use_exact64(exact64, "search_segments_multi_device", bool(prefilter)):
-            return self._search_segments_multi_packed_f64(queries, seg_offsets, k)[1:]
-        return self._search_segments_multi_packed(queries, seg_offsets, k, prefilter, stats)[1:]
-
-    def _search_segments_multi_packed(self, queries, seg_offsets: torch.Tensor, k: int, prefilter: bool = False,
-                                      stats: torch.Tensor = None):
-        """search_segments_multi_device, returning (packed, idx, sims, counts): the three outputs are views of `packed`."""
-        q = _queries_2d(queries, self.rows.device)
-        Q, E, k = q.shape[0], seg_offsets.numel() - 1, int(k)
-        if k < 1:
-            raise ValueError("k must be >= 1")
-        layout = _hits_layout(Q, E, k)
-        packed = torch.empty(layout.nbytes, dtype=torch.uint8, device=self.rows.device)
-        idx, sims, counts = layout.device_views(packed)
-        if E > 0 and len(self) == 0:                             # events without a row: nothing to scan, the padding is the answer
-            idx.fill_(-1)
-            sims.zero_()
-            counts.zero_()
-        elif E > 0:
-            self._scan("segmented_multi", bool(prefilter), q, k, (idx, sims, counts), Q=Q, seg_offsets=seg_offsets, stats=stats)
-        return packed, idx, sims, counts
+        exact64 = self._use_exact64(exact64, "search_segments_multi_device", bool(prefilter))
+        return self._search_segments_packed(queries, seg_offsets, k, prefilter, stats, exact64=exact64)[1:]
 
     def search_multi_device(self, queries: torch.Tensor, k: int, prefilter: bool = None, stats: torch.Tensor = None,
                             exact64: bool = False):
@@ -595,7 +529,7 @@ class FeatureStore:
         row q what ``search_device(queries[q], k, exact64=True)`` returns, bit for bit; the batch may be fp32 or fp64, on the host
         or the device; not together with ``prefilter``."""
         if self._use_exact64(exact64, "search_multi_device", bool(prefilter)):
-            return self._search_multi_f64(queries, k)
+            return self._search_flat_f64(queries, k)
         queries = _queries_2d(queries, self.rows.device)
         nq, n, dev = queries.shape[0], len(self), self.rows.device
         idx = torch.empty(nq, k, dtype=torch.int64, device=dev)
@@ -611,7 +545,7 @@ class FeatureStore:
         ``search_multi_device``.  ``exact64=True``: per query what ``search(query, k, exact64=True)`` returns, float64, from one
         pass over the store per 16 queries; a host batch is sent with numpy's own norm of every row."""
         if self._use_exact64(exact64, "search_multi", bool(prefilter)):
-            idx, sims = (t.cpu().numpy() for t in self._search_multi_f64(queries, k))
+            idx, sims = (t.cpu().numpy() for t in self._search_flat_f64(queries, k))
             return [(idx[i], sims[i]) for i in range(idx.shape[0])]
         q = queries if isinstance(queries, torch.Tensor) else torch.from_numpy(np.asarray(queries, dtype=np.float32))
         idx, sims = self.search_multi_device(q.reshape(-1, FEATURE_DIM), k, prefilter)
@@ -622,7 +556,7 @@ class FeatureStore:
         """``search_device`` with the results on the host.  ``exact64=True``: float64 similarities from the float64 route; a
         host query is sent with numpy's own ``np.linalg.norm`` of it, the reference's ``a_norm``."""
         if self._use_exact64(exact64, "search"):
-            idx, sims = self._search_flat_f64(query, k)
+            idx, sims = self._search_flat_f64(query, k, single=True)
         else:
             idx, sims = self.search_device(_query_to_device(query, self.rows.device), k)
         return idx.cpu().numpy(), sims.cpu().numpy()
@@ -827,16 +761,10 @@ class EventStore(FeatureStore):
         self.lengths = lengths
         self.offsets = torch.tensor(np.concatenate([[0], np.cumsum(lengths)]), dtype=torch.int64, device=self.rows.device)
 
-    def _hits_exact64(self, query, k: int):
-        """The per-event float64 top-k on the device and ONE packed read-back -> host (idx (E,k) int64, sims (E,k) float64,
-        counts (E,) int32), copies."""
-        packed, idx, _, _ = self._search_segments_packed_f64(query, self.offsets, int(k))
-        idx_h, sims_h, counts_h = _hits_layout_f64(*idx.shape).host_views(self._read_back(packed))
-        return idx_h.copy(), sims_h.copy(), counts_h.copy()
-
-    def _hits_exact64_multi(self, queries, k: int):
-        """_hits_exact64 for a batch: ONE packed read-back -> host (idx (Q,E,k) int64, sims (Q,E,k) float64, counts (Q,E) int32)."""
-        packed, idx, _, _ = self._search_segments_multi_packed_f64(queries, self.offsets, int(k))
+    def _hits_exact64(self, queries, k: int, single: bool = False):
+        """The per-event float64 top-k on the device and ONE packed read-back -> host (idx (Q,E,k) int64, sims (Q,E,k) float64,
+        counts (Q,E) int32), copies; ``single``: of one query, without the leading Q."""
+        packed, idx, _, _ = self._search_segments_packed(queries, self.offsets, k, single=single, exact64=True)
         idx_h, sims_h, counts_h = _hits_layout_f64(*idx.shape).host_views(self._read_back(packed))
         return idx_h.copy(), sims_h.copy(), counts_h.copy()
 
@@ -855,7 +783,7 @@ class EventStore(FeatureStore):
         if self._use_exact64(exact64, "top_hits", prefilter):
             if not self.lengths or int(keep) < 1:
                 return []
-            return rank_hits_exact64(*self._hits_exact64(query, k), int(keep))[0]
+            return rank_hits_exact64(*self._hits_exact64(query, k, single=True), int(keep))[0]
         q = _query_to_device(query, self.rows.device)
         idx, sims, counts = self.search_segments_device(q, self.offsets, int(k), prefilter)
         E, keep = idx.shape[0], int(keep)
@@ -886,10 +814,10 @@ class EventStore(FeatureStore):
         if self._use_exact64(exact64, "top_k_per_event", prefilter):
             if not self.lengths:
                 return []
-            idx_h, sims_h, counts_h = self._hits_exact64(query, k)
+            idx_h, sims_h, counts_h = self._hits_exact64(query, k, single=True)
             return [(idx_h[e, :counts_h[e]], sims_h[e, :counts_h[e]]) for e in range(len(self.lengths))]
         q = _query_to_device(query, self.rows.device)
-        packed, idx, _, _ = self._search_segments_packed(q, self.offsets, int(k), prefilter)
+        packed, idx, _, _ = self._search_segments_packed(q, self.offsets, k, prefilter, single=True)
         E, k = idx.shape
         if E == 0:
             return []
@@ -926,11 +854,11 @@ class EventStore(FeatureStore):
         if self._use_exact64(exact64, "top_k_per_event_multi", prefilter):
             if E == 0 or len(self) == 0:
                 return [[(np.zeros(0, np.int64), np.zeros(0, np.float64)) for _ in range(E)] for _ in range(Q)]
-            idx_h, sims_h, counts_h = self._hits_exact64_multi(queries, k)
+            idx_h, sims_h, counts_h = self._hits_exact64(queries, k)
             return [[(idx_h[qi, e, :counts_h[qi, e]], sims_h[qi, e, :counts_h[qi, e]]) for e in range(E)] for qi in range(Q)]
         if E == 0 or len(self) == 0:
             return [[(np.zeros(0, np.int64), np.zeros(0, np.float32)) for _ in range(E)] for _ in range(Q)]
-        packed = self._search_segments_multi_packed(q, self.offsets, k, prefilter)[0]
+        packed = self._search_segments_packed(q, self.offsets, k, prefilter)[0]
         idx_h, sims_h, counts_h = _hits_layout(Q, E, k).host_views(self._read_back(packed))
         idx_h, sims_h, counts_h = idx_h.copy(), sims_h.copy(), counts_h[0].copy()      # counts = min(k, n_e): the same for every query
         if int(counts_h.min()) == k:
@@ -950,7 +878,7 @@ class EventStore(FeatureStore):
         if E == 0 or len(self) == 0 or keep < 1:
             return [[] for _ in range(Q)]
         if exact64:
-            idx_h, sims_h, counts_h = self._hits_exact64_multi(queries, k)
+            idx_h, sims_h, counts_h = self._hits_exact64(queries, k)
             return [rank_hits_exact64(idx_h[qi], sims_h[qi], counts_h[qi], keep)[0] for qi in range(Q)]
         if keep > 64:
             return [self.top_hits(q[qi], k, keep, prefilter) for qi in range(Q)]
@@ -989,11 +917,11 @@ class EventStore(FeatureStore):
         if self._use_exact64(exact64, "relevant_hits", prefilter):
             if not self.lengths:
                 return [], []
-            return rank_hits_exact64(*self._hits_exact64(query, k), int(keep), rules[0], rules[1], min_similarity)
+            return rank_hits_exact64(*self._hits_exact64(query, k, single=True), int(keep), rules[0], rules[1], min_similarity)
         q = _query_to_device(query, self.rows.device)
         if not self.lengths:
             return [], []
-        packed = self._search_segments_packed(q, self.offsets, int(k), prefilter)
+        packed = self._search_segments_packed(q, self.offsets, k, prefilter, single=True)
         return self._rank_relevant(packed[1:], None, int(keep), rules)[0]
 
     def relevant_hits_multi(self, queries, k: int = 5, keep: int = 5, *, row_limits=None, defer=None, min_similarity: float = 0.4,
@@ -1009,10 +937,10 @@ class EventStore(FeatureStore):
         if not self.lengths:
             return [([], []) for _ in range(q.shape[0])]
         if exact64:
-            idx_h, sims_h, counts_h = self._hits_exact64_multi(queries, k)
+            idx_h, sims_h, counts_h = self._hits_exact64(queries, k)
             return [rank_hits_exact64(idx_h[qi], sims_h[qi], counts_h[qi], int(keep), rules[0], rules[1], min_similarity)
                     for qi in range(q.shape[0])]
-        packed = self._search_segments_multi_packed(q, self.offsets, int(k), prefilter)
+        packed = self._search_segments_packed(q, self.offsets, k, prefilter)
         return self._rank_relevant(packed[1:], q.shape[0], int(keep), rules)
 
     def _relevance_rules(self, what: str, k, keep, row_limits, defer, min_similarity):

@@ -92,7 +92,7 @@ def source_constants() -> dict:
                  r"by_slice = \(n \+ kF64Slice - 1\) / kF64Slice;",
                  r"cap = p\.k_eff <= kF64ArgmaxK \? kF64MaxGroups : kF64MaxGroupsSort;",
                  r"p\.n_pad = p\.global_sort \? next_pow2_i64\(n\) : 0;", r"\} else if \(p\.k_eff <= kF64ArgmaxK\) \{",
-                 r"per = \(n_rows \+ gridDim\.x - 1\) / gridDim\.x;", r"if \(k <= kF64ArgmaxK\)\s*select_f64_kernel<false, true><<<n_segments, 256,"):
+                 r"per = \(n_rows \+ gridDim\.x - 1\) / gridDim\.x;", r"if \(k <= kF64ArgmaxK\)\s*launch_select<false, true>\(grid, 256,"):
         assert re.search(line, text), f"{SOURCE}: `{line}` is gone; flat_plan / the dispatch changed its form"
     # the eligibility kernel's grid: 16 values per thread of 256, capped at kScanBlocks
     m = re.search(r"blocks = \(n_values \+ (\d+) \* (\d+) - 1\) / \(\1 \* \2\);", text)

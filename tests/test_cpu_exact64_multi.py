@@ -48,6 +48,16 @@ def test_workspace_answers():
             assert flat(n, 1, k) <= flat(n, 2, k) <= flat(n, 16, k)
 
 
+def test_a_single_query_gets_the_workspace_of_a_batch_of_one():
+    from hippomm_amd import _lib
+    lib = _lib.load()
+    for n in (1, 3, 4096, 4097, 100000):
+        for k in (1, 64, 65, 1024, 1025):
+            assert lib.hmm_cosine_topk_f64_workspace_bytes(n, k) == lib.hmm_cosine_topk_multi_f64_workspace_bytes(n, 1, k) > 0
+            assert (lib.hmm_cosine_topk_segmented_f64_workspace_bytes(n, 7, k)
+                    == lib.hmm_cosine_topk_segmented_multi_f64_workspace_bytes(n, 7, 1, k) > 0)
+
+
 def test_argument_errors_are_reported_without_a_gpu():
     from hippomm_amd import _lib
     lib = _lib.load()

@@ -350,6 +350,63 @@ def _contract_run(pattern, align, shape, dtype):
     return tuple(v.cpu().numpy().tobytes() for v in (idx_v, sim_v, cnt_v))
 
 
+# ---- a single query is a batch of one -----------------------------------------------------------------------------------------------
+ONE_FLAT = ((1, 1), (3, 5), (4097, 64), (4097, 65), (1100, 1100))  # held arg-max, the second level across a slice seam, LDS chunks, full sort
+ONE_EVENTS = [0, 0, 1, 3, 303, 1328]                              # 5 events of 0, 1, 2, 300 and 1025 rows
+
+
+def _single_and_batch_of_one(n, k, dtype, handed_norm, off=None):
+    """The raw single-query entry point and the batched one with Q = 1 on the same guarded inputs -> their (idx, sims, n_out) bytes."""
+    from hippomm_amd import _lib
+    lib = _lib.load()
+    q64 = dtype == "float64"
+    store = torch.from_numpy(multi.store_rows(4100)[:n])
+    query = _pool("host64" if q64 else "host32")[5]
+    norm = np.array([np.linalg.norm(query)], dtype=np.float64)    # in the query's dtype, widened: what a host query travels with
+    E = len(off) - 1 if off else 0
+    sizes_of = ((lib.hmm_cosine_topk_segmented_f64_workspace_bytes(n, E, k), lib.hmm_cosine_topk_segmented_multi_f64_workspace_bytes(n, E, 1, k))
+                if off else (lib.hmm_cosine_topk_f64_workspace_bytes(n, k), lib.hmm_cosine_topk_multi_f64_workspace_bytes(n, 1, k)))
+    assert sizes_of[0] == sizes_of[1] > 0
+    cells, counts = (E * k, E) if off else (min(k, n), 1)
+    ar = A.GuardedArena(A.needed_bytes([store.numel() * 4, query.nbytes, 8, 8 * (E + 1)] + 2 * [8 * cells, 8 * cells, 4 * counts, sizes_of[0]]),
+                        DEV, A.PATTERNS["big"])
+    p = ar.address
+    s, q = p(ar.put(store.to(DEV), "store")), p(ar.put(_dev(query), "query"))
+    norm_ptr = p(ar.put(torch.from_numpy(norm).to(DEV), "norm")) if handed_norm else None
+    off_ptr = p(ar.put(torch.tensor(off or [0], dtype=torch.int64, device=DEV), "offsets"))
+    outs = []
+    for batched in (False, True):
+        views = [ar.carve(8 * cells, "idx"), ar.carve(8 * cells, "sims"), ar.carve(4 * counts, "n_out")]
+        ws = p(ar.carve(sizes_of[0], "workspace"))
+        idx, sim, cnt = (p(v) for v in views)
+        Q = (1,) if batched else ()
+        if off:
+            call = lib.hmm_cosine_topk_segmented_multi_f64 if batched else lib.hmm_cosine_topk_segmented_f64
+            rc = call(s, n, 1024, q, int(q64), norm_ptr, *Q, off_ptr, E, k, idx, sim, cnt, ws, sizes_of[0], _lib.stream_ptr())
+        else:
+            call = lib.hmm_cosine_topk_multi_f64 if batched else lib.hmm_cosine_topk_f64
+            rc = call(s, n, 1024, q, int(q64), norm_ptr, *Q, k, idx, sim, cnt, ws, sizes_of[0], _lib.stream_ptr())
+        assert rc == 0, lib.hmm_last_error()
+        torch.cuda.synchronize()
+        ar.check_guards()
+        outs.append(tuple(v.cpu().numpy().tobytes() for v in views))
+    return outs
+
+
+@pytest.mark.parametrize("handed_norm", [True, False])
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+def test_the_single_entry_points_write_the_bytes_of_a_batch_of_one(dtype, handed_norm):
+    for n, k in ONE_FLAT:
+        single, batch = _single_and_batch_of_one(n, k, dtype, handed_norm)
+        assert np.frombuffer(single[2], np.int32).tolist() == [min(k, n)], (n, k)
+        assert single == batch, f"flat n={n} k={k}"
+    sizes = np.diff(ONE_EVENTS)
+    for k in (5, 65):
+        single, batch = _single_and_batch_of_one(ONE_EVENTS[-1], k, dtype, handed_norm, ONE_EVENTS)
+        assert np.frombuffer(single[2], np.int32).tolist() == np.minimum(sizes, k).tolist(), k
+        assert single == batch, f"per event k={k}"
+
+
 CONTRACT = {"flat argmax": (17, 4100, 5, None), "flat chunks": (17, 4100, 70, None), "flat below one block": (2, 3, 5, None),
             "segmented": (17, 1003, 5, multi.SEGMENT_OFFSETS), "segmented chunks": (17, 1003, 70, multi.SEGMENT_OFFSETS)}
 
